@@ -10,6 +10,12 @@ as ONE launch by default (--rollout scripted: the synthetic transitions are a sc
 the line also carries the figure with one launch per environment step (`stepwise_rollout`, --rollout stepwise), which is
 how the N>1 layouts -- they exchange actions every step -- run.
 
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  Everything else it
+can measure -- the roofline, the CPU baseline, the stepwise / host-buffer / one-learner figures, the rollout / update split --
+runs only with --full.  --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32): per
+learner the updated parameters and Adam moments, the rollout buffer's rows and the update's per-minibatch statistics.  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 Launch: `python bench.py` (N=1), `python bench.py --gpus N` (spawns its own N ranks through torch.distributed.run), or
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
@@ -104,11 +110,60 @@ def parse():
                          "sample).  policy+env: ModularPolicy's -30 logit offset (modular/policies.py:330-333) as well")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to "
                     "exercise the N>1 code path with several ranks on ONE GPU)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need, after the timed region: "
+                    "roofline, cpu_baseline (+ gpu_reference_semantics_E1), iteration_split, stepwise_rollout, "
+                    "host_buffers_pcie_inclusive, one_agent_per_gpu, and the liar line's rollout_ms; the three options below "
+                    "leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the extra figures measured after the timed region "
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the extra figures measured after the timed region "
                     "(stepwise_rollout, one_agent_per_gpu): a kernel trace of the run then holds the headline's launches only")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+# --dump-outputs: at most this many bytes over all ranks; larger rollout buffers are cut to a fixed, seeded sample of rows
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(out_dir: str, models, names, world: int = 1) -> None:
+    """What the timed path hands its caller after the last timed step, per learner: the updated parameters and Adam moments, the
+    rollout buffer's actions / values / log-probabilities / rewards / episode starts / advantages / returns, and the update's
+    per-minibatch statistics (PH_NSTAT columns), as float32 DIR/<learner>_<array>.npy.  The buffer's observations are the seeded
+    synthetic inputs themselves and are left out.  Buffer rows are flattened (n_steps * n_envs, ...); when the whole exceeds this
+    rank's share of DUMP_BUDGET, the same seeded sample of rows (sorted) is written for every buffer array."""
+    th.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    buf_names = ("actions", "values", "log_probs", "rewards", "episode_starts", "advantages", "returns")
+    out = {}
+    for m, name in zip(models, names):
+        pol, rb = m.policy, m.rollout_buffer
+        for k, t in (("params", pol.params), ("adam_m", pol.adam_m), ("adam_v", pol.adam_v)):
+            out[f"{name}_{k}"] = t.detach().float().cpu().numpy()
+        stats = getattr(m, "_stats_dev", None)
+        if stats is not None:
+            out[f"{name}_train_stats"] = stats.detach().float().cpu().numpy()
+        for k in buf_names:
+            t = getattr(rb, k)
+            out[f"{name}_{k}"] = t.detach().float().reshape(rb.buffer_size * rb.n_envs, -1).squeeze(-1).cpu().numpy()
+    budget = DUMP_BUDGET // max(1, world)
+    fixed = sum(v.nbytes for k, v in out.items() if not k.endswith(buf_names))
+    rows = {v.shape[0] for k, v in out.items() if k.endswith(buf_names)}
+    per_row = sum(v.nbytes // v.shape[0] for k, v in out.items() if k.endswith(buf_names))
+    if rows and fixed + per_row * max(rows) > budget:
+        keep = max(1, (budget - fixed) // per_row)
+        for n in rows:
+            idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, keep), replace=False))
+            for k, v in out.items():
+                if k.endswith(buf_names) and v.shape[0] == n:
+                    out[k] = v[idx]
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    log(f"dump-outputs: {len(out)} arrays, {sum(v.nbytes for v in out.values()) / 2**20:.1f} MiB -> {out_dir}")
 
 
 def build_agents(args, device):
@@ -470,6 +525,8 @@ def bench_roundrobin(args, device, rank, world, json_fd, tdist):
         side.run_iteration()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [model], [f"rank{rank}_agent0"], world)
     tmax = th.tensor([dt], dtype=th.float64, device=device if args.backend == "nccl" else "cpu")
     tdist.all_reduce(tmax, op=tdist.ReduceOp.MAX)
     dt = float(tmax.item())
@@ -542,6 +599,8 @@ def bench_liar(args, device, json_fd):
         evs[k + 1].record(g.stream)
     th.cuda.synchronize(device)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, models, ("ego", "partner"))
     per = sorted(evs[k].elapsed_time(evs[k + 1]) for k in range(args.steps))
     rows1, ep1 = partner_rows(), sp.episodes
     ego_steps, alt_steps = E * T * args.steps, rows1 - rows0
@@ -561,7 +620,7 @@ def bench_liar(args, device, json_fd):
                    "rollout_requested": "persistent"},
     }
     # the rollout alone (one launch for n_steps vector steps)
-    if sp.persistent:
+    if args.full and sp.persistent:
         alt_pos = alt.pos.clone()
         th.cuda.synchronize(device)
         t1 = time.perf_counter()
@@ -570,7 +629,7 @@ def bench_liar(args, device, json_fd):
         result["rollout_ms"] = 1e3 * (time.perf_counter() - t1)
         alt.pos.copy_(alt_pos)
         ego.model.rollout_buffer.pos = 0
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         pol, rb, model = models[0].policy, models[0].rollout_buffer, models[0]
         lay, hp, ms = pol.layout, models[0].hyper(), C.c_float(0)
         gm = int(getattr(pol, "gemm_mode", 0))
@@ -596,7 +655,7 @@ def bench_liar(args, device, json_fd):
                          "unit": "TFLOP/s (bf16 dense)", "frac": executed / (ms.value * 1e-3) / 1e12 / 2500.0,
                          "note": "the matrix-pipe work the kernel issues: one-hot X as one bf16 plane (three terms per first-layer "
                                  "block), six terms elsewhere"}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args)
     os.write(json_fd, (json.dumps(result) + "\n").encode())
     return 0
@@ -731,6 +790,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     log(f"timed region {dt:.3f}s")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [a.model for a in agents],
+                     [(f"rank{rank}_" if world > 1 else "") + f"agent{i}" for i in range(len(agents))], world)
     per_iter = [max(marks[i][k].elapsed_time(marks[i + 1][k]) for k in range(len(streams))) for i in range(args.steps)]
     ranks_seen, devices_seen = 1, 1
     if distributed:
@@ -794,7 +856,7 @@ def main():
                          f"first: {exchange.p2p_timeout_record()}")
     if distributed and ranks_seen != args.gpus:
         raise SystemExit(f"bench.py: the collective saw {ranks_seen} ranks, --gpus is {args.gpus}")
-    if mode == "graph" and args.rollout == "scripted" and not distributed:
+    if args.full and mode == "graph" and args.rollout == "scripted" and not distributed:
         # How the iteration divides, measured without a profiler: the learners' one-launch rollouts alone (side by side, as in the
         # iteration), timed over 10 repetitions; the rest of the iteration is the update -- GAE, the gradient pack and n_epochs x
         # minibatches of (gradient launch, reduce, Adam) per learner -- whose gradient launches take turns on the device, so
@@ -826,7 +888,7 @@ def main():
                         "(the gradient kernel alone) and roofline.in_graph (the same kernel under rocprofv3, which serialises the learners)"}
         except Exception as exc:  # noqa: BLE001 -- an extra figure, never fatal
             result["iteration_split"] = {"error": str(exc)}
-    if mode == "graph" and args.rollout == "scripted" and not args.headline_only:
+    if args.full and mode == "graph" and args.rollout == "scripted" and not args.headline_only:
         # the same iteration with one launch per environment step, timed in the same process on the same agents: what the
         # scripted rollout saves is launch boundaries, nothing else (the two walks are bitwise equal)
         sgraphs = [IterationGraph(a, d, s) for a, d, s in zip(agents, datas, streams)]
@@ -845,7 +907,7 @@ def main():
                                       "steps": k2, "note": "one launch per environment step inside the iteration graphs "
                                       "(--rollout stepwise): what an environment that lives on the host or on another node forces; the N>1 layouts of this bench "
                                               "hand actions over in-kernel and launch a rollout once, like the default"}
-    if mode == "graph" and world == 1 and not args.headline_only:
+    if args.full and mode == "graph" and world == 1 and not args.headline_only:
         # The same iteration when the boundary hands over HOST buffers (the owning-handle ABI's situation): every learner's rollout
         # inputs -- observations, rewards, dones of the n_steps x n_envs transitions -- cross PCIe from pinned host memory before its
         # graph runs, its sampled actions cross back after.  Never `value`: that is measured with the inputs resident in HBM.
@@ -881,7 +943,8 @@ def main():
                         "copied back after (async copies on the learner's stream): the rate when the caller owns host arrays; not `value`"}
         except Exception as exc:  # noqa: BLE001 -- an extra figure, never fatal
             result["host_buffers_pcie_inclusive"] = {"error": str(exc)}
-    if mode == "graph" and world == 1 and args.agents_per_gpu != 1 and args.rollout in ("scripted", "stepwise") and not args.headline_only:
+    if (args.full and mode == "graph" and world == 1 and args.agents_per_gpu != 1 and args.rollout in ("scripted", "stepwise")
+            and not args.headline_only):
         # north_star's literal layout -- ONE learner per GPU ("8 agents on 8 GPUs") -- on this GPU: the N = 1 base a scaling curve of
         # `--agents-per-gpu 1` runs is measured against.  Nothing overlaps the learner's reduce / Adam then, so each minibatch's
         # reduce + clip + Adam runs as one launch (ppo_step_kernel) between two gradient launches.
@@ -906,10 +969,10 @@ def main():
         except Exception as exc:  # noqa: BLE001 -- an extra figure, never fatal
             result["one_agent_per_gpu"] = {"error": str(exc)}
     if rank == 0:
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             result["roofline"] = roofline(args, agents[0])
             log("roofline measured")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(args)
             result["gpu_over_cpu"] = value / result["cpu_baseline"]["value"]
             try:

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 V=pantheonrl_amd/csrc/variants
 for rep in $(seq 1 ${REPS:-2}); do
   for so in "$@"; do
-    PANTHEON_HIP_LIB=$PWD/$V/$so.so python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+    PANTHEON_HIP_LIB=$PWD/$V/$so.so python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 one, sw, r = d.get('one_agent_per_gpu', {}), d.get('stepwise_rollout', {}), d['roofline']

@@ -9,7 +9,7 @@ for rep in 1 2; do
 done
 if [ -n "$AB_BENCH" ]; then
   for so in "$@"; do
-    PANTHEON_HIP_LIB=$PWD/$V/$so.so python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$so bench: %.2f M agent-steps/s, %.3f ms/iter, grad %.1f us' % (d['value']/1e6, d['ms_per_step'], d['roofline']['launch_ms']*1e3))"
+    PANTHEON_HIP_LIB=$PWD/$V/$so.so python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$so bench: %.2f M agent-steps/s, %.3f ms/iter, grad %.1f us' % (d['value']/1e6, d['ms_per_step'], d['roofline']['launch_ms']*1e3))"
   done
 fi
 if [ -n "$AB_TEST" ]; then

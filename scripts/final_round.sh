@@ -8,9 +8,9 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1
 grep -E "passed|failed|error" $OUT/gpu_tests.log | tail -2
-timeout 150 python bench.py > $OUT/bench_stdout.json 2> $OUT/bench.log
+timeout 150 python bench.py --full > $OUT/bench_stdout.json 2> $OUT/bench.log
 tail -c 300 $OUT/bench_stdout.json | head -c 0
-timeout 120 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python bench.py --no-cpu-baseline --no-roofline --headline-only > $OUT/bench_under_rocprof.json 2> $OUT/kt.log
+timeout 120 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python bench.py --full --no-cpu-baseline --no-roofline --headline-only > $OUT/bench_under_rocprof.json 2> $OUT/kt.log
 python scripts/rocprof_summary.py $(find $OUT/kt -name "*_results.db" | head -1) > $OUT/bench_graph_kernel_stats.txt 2>&1
 rm -rf $OUT/kt
 python -c "

@@ -1,7 +1,7 @@
 """Pins the integer game fixtures to the REFERENCE's own code (build container only; `/root/reference` never travels).
 
     python tests/golden/check_against_reference.py              # verify both fixtures against the reference's functions
-    python tests/golden/check_against_reference.py --regenerate # rewrite game_traces.npz from the reference's functions
+    python tests/golden/check_against_reference.py --regenerate # rewrite game_traces.npz and game_random_play.npz from them
 
 What runs here is the reference's source, loaded from where it lies (nothing is copied into this repository):
 `pantheonrl/envs/liargym/liar.py` (LiarEnv.player_step / sanitize_action / eval_bluff / getObs / multi_reset, :53-102) and
@@ -16,7 +16,10 @@ Checked / produced:
     and done flag is replayed through the reference's LiarEnv;
   * tests/golden/game_traces.npz -- 192 seeded Liar's Dice tables x 14 steps and 999 RPS rounds: every live step is replayed
     through the reference's LiarEnv / RPSEnv; `--regenerate` writes the file from those replays (same seeds and raw moves as
-    make_game_traces.py, so the product's restatement and the reference must agree bit for bit or the not-gpu test fails).
+    make_game_traces.py, so the product's restatement and the reference must agree bit for bit or the not-gpu test fails);
+  * tests/golden/game_random_play.npz -- 200 more tables of fresh random play (random_play): inputs and the reference's
+    observations, rewards and done flags, which the not-gpu test replays through the product;
+  * the dealt hands of game_traces.npz are the reference's multi_reset under np.random.seed(7).
 With this the integer rows of the oracle are REFERENCE-generated.  The float path (SB3 1.7.0 arithmetic) stays unpinned:
 stable-baselines3 is absent and the reference holds no vectors for it.
 """
@@ -131,6 +134,30 @@ def check_dice(liar_ns) -> None:
         assert t.egohand + t.althand == [int(v) for v in z["liar_hands"][e]], e
 
 
+RANDOM_PLAY = "game_random_play.npz"
+
+
+def random_play(liar_ns, n_games: int = 200, n_steps: int = 14, seed: int = 11) -> dict:
+    """fresh random play beyond the committed traces: n_games tables (random hands, random first mover) x n_steps raw moves drawn
+    from default_rng(seed), every step taken whether or not the game has ended -> the inputs and the reference's outputs"""
+    rng = np.random.default_rng(seed)
+    hands = np.zeros((n_games, 12), np.int64)
+    ego = np.zeros(n_games, np.uint8)
+    raw = np.zeros((n_games, n_steps, 2), np.int64)
+    obs = np.zeros((n_games, n_steps, 30), np.float32)
+    rew = np.zeros((n_games, n_steps, 2), np.float32)
+    done = np.zeros((n_games, n_steps), np.uint8)
+    for g in range(n_games):
+        hands[g] = rng.integers(0, 7, 12)
+        t = _table(liar_ns, hands[g, :6], hands[g, 6:])
+        ego[g] = bool(rng.integers(0, 2))
+        for s in range(n_steps):
+            raw[g, s] = [rng.integers(0, 7), rng.integers(0, 12)]
+            o, r, d, _ = t.player_step(raw[g, s].copy(), bool(ego[g]))
+            obs[g, s], rew[g, s], done[g, s] = np.asarray(o, np.float32), r, d
+    return dict(hands=hands, ego=ego, raw=raw, obs=obs, rew=rew, done=done)
+
+
 def main() -> int:
     if not os.path.isdir(REFERENCE):
         print(f"{REFERENCE} not present: this check runs in the build container only")
@@ -147,8 +174,17 @@ def main() -> int:
     for k, v in out.items():
         assert np.array_equal(v, z[k]), f"game_traces.npz[{k}] differs from the reference's output"
     check_dice(liar_ns)
+    play = random_play(liar_ns)
+    play_path = os.path.join(HERE, RANDOM_PLAY)
+    if "--regenerate" in sys.argv:
+        np.savez_compressed(play_path, **play)
+        print(f"{RANDOM_PLAY} rewritten from the reference's LiarEnv")
+    committed = np.load(play_path)
+    for k, v in play.items():
+        assert np.array_equal(v, committed[k]), f"{RANDOM_PLAY}[{k}] differs from the reference's output"
     print(f"reference check ok: {n_hand} hand-worked steps, {int(out['liar_alive'].sum())} trace steps, "
-          f"{len(out['rps_ego_reward'])} RPS rounds, {z['liar_hands'].shape[0]} dealt tables")
+          f"{len(out['rps_ego_reward'])} RPS rounds, {z['liar_hands'].shape[0]} dealt tables, "
+          f"{play['done'].shape[0]} random games")
     return 0
 
 

@@ -4,7 +4,8 @@ Build container only: `/root/reference` never travels, the fixtures this script 
 
     python tests/golden/make_reference_fixtures.py            # regenerate in memory, compare byte for byte with the committed files
     python tests/golden/make_reference_fixtures.py --write    # (re)write tests/golden/ref_*.json, ref_transitions.npz, ref_adap_context.npz,
-                                                              # ref_ppo_train.npz, ref_modular.npz, ref_bc.npz
+                                                              # ref_ppo_train.npz, ref_modular.npz, ref_bc.npz and
+                                                              # ref_fixtures_sha256.json (their digests, checked by the not-gpu test)
 
 What runs is the reference's source, imported from where it lies (nothing is copied into this repository):
 
@@ -81,6 +82,7 @@ that replay them through pantheonrl_amd.common.
 """
 from __future__ import annotations
 
+import hashlib
 import importlib
 import io
 import json
@@ -1234,12 +1236,24 @@ def generate() -> dict:
     for name, obj in files.items():
         out[name] = (json.dumps(obj, indent=None, separators=(",", ":"), sort_keys=True) + "\n").encode()
     for name, arrays in (("ref_transitions.npz", npy), ("ref_adap_context.npz", adap), ("ref_ppo_train.npz", train),
-                         ("ref_modular.npz", modular), ("ref_bc.npz", bc),
+                         # the ModularPolicy cases' final parameters in a file of their own: each file stays under 1 MiB
+                         ("ref_modular.npz", {k: v for k, v in modular.items() if not k.endswith(".params_final")}),
+                         ("ref_modular_final.npz", {k: v for k, v in modular.items() if k.endswith(".params_final")}),
+                         ("ref_bc.npz", bc),
                          ("ref_action_mask.npz", masks)):
         f = io.BytesIO()
         np.savez(f, **{k: arrays[k] for k in sorted(arrays)})       # uncompressed + sorted: byte-reproducible
         out[name] = f.getvalue()
     return out
+
+
+MANIFEST = "ref_fixtures_sha256.json"
+
+
+def manifest(made: dict) -> bytes:
+    """SHA-256 of every generated fixture's bytes: what the not-gpu test checks the committed files against"""
+    digests = {name: hashlib.sha256(data).hexdigest() for name, data in made.items()}
+    return (json.dumps(digests, indent=1, sort_keys=True) + "\n").encode()
 
 
 def main() -> int:
@@ -1249,7 +1263,7 @@ def main() -> int:
     made = generate()
     write = "--write" in sys.argv
     bad = []
-    for name, data in made.items():
+    for name, data in {**made, MANIFEST: manifest(made)}.items():
         path = os.path.join(HERE, name)
         if write:
             with open(path, "wb") as fh:

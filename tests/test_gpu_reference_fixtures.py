@@ -320,8 +320,8 @@ def test_device_modular_train_matches_the_reference_train_loop(name):
     from pantheonrl_amd.modular import ModularAlgorithm
     from tests.golden.make_reference_fixtures import MODULAR_CASES
     c = MODULAR_CASES[name]
-    z = np.load(os.path.join(GOLDEN, "ref_modular.npz"))
-    g = {k[len(name) + 1:]: z[k] for k in z.files if k.startswith(name + ".")}
+    z = {**np.load(os.path.join(GOLDEN, "ref_modular.npz")), **np.load(os.path.join(GOLDEN, "ref_modular_final.npz"))}
+    g = {k[len(name) + 1:]: z[k] for k in z if k.startswith(name + ".")}
     K, T, E = c["K"], c["T"], c["E"]
     env = type("E", (), dict(observation_space=sp.Box(-np.inf, np.inf, (c["D"],)), action_space=sp.Discrete(c["n_act"]),
                              _is_dummy_space_env=True))()
@@ -360,8 +360,8 @@ def test_device_modular_forward_matches_the_reference_policy_text(name):
     from pantheonrl_amd.modular import ModularPolicy
     from tests.golden.make_reference_fixtures import MODULAR_CASES
     c = MODULAR_CASES[name]
-    z = np.load(os.path.join(GOLDEN, "ref_modular.npz"))
-    g = {k[len(name) + 1:]: z[k] for k in z.files if k.startswith(name + ".")}
+    z = {**np.load(os.path.join(GOLDEN, "ref_modular.npz")), **np.load(os.path.join(GOLDEN, "ref_modular_final.npz"))}
+    g = {k[len(name) + 1:]: z[k] for k in z if k.startswith(name + ".")}
     pol = ModularPolicy(sp.Box(-np.inf, np.inf, (c["D"],)), sp.Discrete(c["n_act"]), device="cuda", seed=0, num_partners=c["K"], **c["kw"])
     assert g["params0"].size == pol.P_total
     pol.set_flat_params(g["params0"])

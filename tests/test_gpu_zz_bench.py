@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +42,7 @@ def _json_line(out: str) -> dict:
 
 
 def test_bench_single_gpu_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--full"], capture_output=True, text=True,
                        timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -55,11 +56,45 @@ def test_bench_single_gpu_contract():
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
 
 
-def test_bench_liar_line_runs_the_device_game():
+def test_bench_plain_run_is_the_headline_alone_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing measured after the timed region; --dump-outputs writes the last
+    timed step's results (float32 .npy per learner), and two runs with the same arguments write the same arrays bit for bit"""
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_json_line(r.stdout))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    for k in ("roofline", "cpu_baseline", "gpu_over_cpu", "gpu_reference_semantics_E1", "iteration_split", "stepwise_rollout",
+              "host_buffers_pcie_inclusive", "one_agent_per_gpu"):
+        assert k not in d, k
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    for i in range(2):
+        for k in ("params", "adam_m", "adam_v", "train_stats", "actions", "values", "log_probs", "advantages", "returns"):
+            assert f"agent{i}_{k}.npy" in names, (i, k)
+    total = 0
+    for name in names:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype == np.float32 and x.size > 0, name
+        assert np.array_equal(x, y, equal_nan=True), name
+        total += x.nbytes
+    assert total <= 64 << 20
+    rows = 96 * 16
+    assert np.load(tmp_path / "a" / "agent0_advantages.npy").shape == (rows,)
+    assert np.any(np.load(tmp_path / "a" / "agent0_params.npy") != np.load(tmp_path / "a" / "agent1_params.npy"))
+
+
+def test_bench_liar_line_runs_the_device_game(tmp_path):
     """`bench.py --workload liar` (BASELINE config 2) plays the game itself on the device -- not synthetic transitions of its shapes --
     and carries the gradient kernel's roofline in both conventions (dense 6 M per row, and the executed matrix-pipe work)"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "liar", "--n-envs", "64", "--n-steps", "32",
-                        "--n-epochs", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True,
+                        "--n-epochs", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True,
                        timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -72,6 +107,9 @@ def test_bench_liar_line_runs_the_device_game():
     rf = d["roofline"]
     assert rf["kernel"].startswith("ppo_grad_split_oh_kernel") and 0 < rf["frac"] < 1 and 0 < rf["executed"]["frac"] < 1
     assert rf["executed"]["flops_per_launch"] > rf["flops_per_launch"] / 6            # bf16 terms: more issued work than the dense f32 count / 6
+    for who in ("ego", "partner"):
+        assert np.load(tmp_path / f"{who}_params.npy").dtype == np.float32
+        assert np.load(tmp_path / f"{who}_returns.npy").shape == (64 * 32,)
 
 
 def test_bench_two_ranks_agent_per_rank_path():
@@ -116,17 +154,20 @@ def test_bench_refuses_more_gpus_than_visible_and_a_mismatched_world():
     assert r.returncode != 0 and "disagrees" in r.stderr
 
 
-def test_bench_round_robin_mode_four_ranks():
+def test_bench_round_robin_mode_four_ranks(tmp_path):
     """BASELINE config 4 as a bench mode: ego + 3 partners, one agent per rank (here sharing the box's GPU over gloo)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--mode", "roundrobin", "--workload", "rps", "--n-envs", "48",
-                        "--n-steps", "8", "--n-epochs", "1", "--steps", "3", "--warmup", "1", "--backend", "gloo"],
+                        "--n-steps", "8", "--n-epochs", "1", "--steps", "3", "--warmup", "1", "--backend", "gloo",
+                        "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 4 and d["value"] > 0 and d["config"]["launch_mode"] == "roundrobin"
     # one-step episodes: every environment changes partner at every step, so each partner's 8-row columns fill after 24 steps
     assert d["config"]["partner_updates"] >= 1
+    for rank in range(4):
+        assert np.load(tmp_path / f"rank{rank}_agent0_params.npy").dtype == np.float32
 
 
 def test_bench_config5_shape_one_agent_per_rank_four_ranks():
