@@ -150,9 +150,11 @@ struct DevGuard {
   DevGuard& operator=(const DevGuard&) = delete;
 };
 
+// grow a workspace array to n elements; never inside graph capture (the captured launches would keep the freed pointer)
 template <typename T>
-int ensure(T*& p, size_t& cap, size_t n) {
+int ensure(const ph_ctx* ctx, T*& p, size_t& cap, size_t n) {
   if (n <= cap) return 0;
+  if (ctx->capturing) return fail("workspace would grow inside graph capture: run the same call once outside capture first");
   if (p) (void)hipFree(p);
   p = nullptr;
   cap = 0;
@@ -314,6 +316,198 @@ int check_rb(const ph_rollout* rb) {
   if ((long long)rb->T * rb->E >= (1ll << 31)) return fail("rollout buffer: T*E must fit in int32");
   return 0;
 }
+
+// a zeroed forward record with the spec resolved and the fields every forward entry point sets
+int fwd_args(ph::FwdArgs& a, ph_ctx* ctx, const ph_spec* spec, bool box_act_ok, const float* params, const float* obs, int n,
+             unsigned long long seed, unsigned long long counter, int* act_i32, float* values, float* logp) {
+  std::memset(&a, 0, sizeof(a));
+  if (resolve(ctx, spec, &a.nd, box_act_ok)) return 1;
+  a.params = params;
+  a.obs = obs;
+  a.n = n;
+  a.seed = seed;
+  a.counter = counter;
+  a.epoch = ctx->rng_epoch;
+  a.act_i32 = act_i32;
+  a.values = values;
+  a.logp = logp;
+  return 0;
+}
+
+// the fused RolloutBuffer.add of a forward record: row `pos` of `rb` (none when rb is null), and pending_reward added to the
+// previous row's rewards (Agent.update folded into the next step's launch); messages name the entry point `who`
+int fwd_bind_row(const char* who, ph::FwdArgs& a, const ph_rollout* rb, int pos, const float* episode_start_in,
+                 const float* pending_reward) {
+  const std::string w(who);
+  if (!rb) return pending_reward ? fail(w + ": pending_reward needs the fused rollout-buffer write") : 0;
+  if (check_rb(rb)) return 1;
+  if (a.n != rb->E) return fail(w + ": fused add needs n == rollout E");
+  if (pos < 0 || pos >= rb->T) return fail(w + ": pos out of range (buffer full?)");
+  if (!episode_start_in) return fail(w + ": fused add needs episode_start_in");
+  const size_t row = (size_t)pos * rb->E;
+  a.rb_obs = rb->observations + row * a.nd.D;
+  a.rb_act = rb->actions + row * a.nd.A;
+  a.rb_rew = rb->rewards + row;
+  a.rb_es = rb->episode_starts + row;
+  a.rb_val = rb->values + row;
+  a.rb_logp = rb->log_probs + row;
+  a.es_in = episode_start_in;
+  if (pending_reward) {
+    if (pos < 1) return fail(w + ": pending_reward needs pos >= 1");
+    a.prev_rew = rb->rewards + (row - rb->E);
+    a.pending_reward = pending_reward;
+  }
+  return 0;
+}
+
+// The advantage-statistics record of n_mb minibatches per epoch walking a permutation of the buffer's N rows: `perms`, or the
+// keyed Feistel order of perm_seed materialised into perm_idx; the order once more as physical rows into perm_phys (the tile
+// walk then has no index arithmetic).  No row records and no stop-flag reset: callers add what their launches read.
+ph::AdvStatArgs adv_args_epochs(const ph_ctx* ctx, const ph_rollout* rb, const int* perms, unsigned long long perm_seed, int batch,
+                                int n_mb) {
+  const int N = rb->T * rb->E;
+  ph::AdvStatArgs aa{};
+  aa.rb_adv = rb->advantages;
+  aa.T = rb->T;
+  aa.E = rb->E;
+  aa.perms = perms;
+  aa.perm_n = (uint32_t)N;
+  aa.perm_hb = ph::feistel_half_bits((uint32_t)N);
+  aa.perm_seed = perm_seed;
+  aa.epoch = ctx->rng_epoch;
+  aa.N = N;
+  aa.batch = batch;
+  aa.n_mb = n_mb;
+  aa.out = ctx->advstats;
+  aa.partial = ctx->advpart;
+  aa.idx_out = perms ? nullptr : ctx->perm_idx;
+  aa.phys_out = ctx->perm_phys;
+  return aa;
+}
+// the same for one minibatch given as indices[0..nb): one "epoch" whose first nb entries are the minibatch
+ph::AdvStatArgs adv_args_minibatch(const ph_ctx* ctx, const ph_rollout* rb, const int* indices, int nb) {
+  ph::AdvStatArgs aa{};
+  aa.rb_adv = rb->advantages;
+  aa.T = rb->T;
+  aa.E = rb->E;
+  aa.perms = indices;
+  aa.perm_hb = 1;
+  aa.N = nb;
+  aa.batch = nb;
+  aa.n_mb = 1;
+  aa.out = ctx->advstats;
+  aa.partial = ctx->advpart;
+  aa.phys_out = ctx->perm_phys;
+  return aa;
+}
+
+// minibatch mbi = ep * n_mb + k of n_mb minibatches per epoch over N rows: positions [start, start + nb) of epoch ep's order,
+// whose indices begin at idx (`perms`, or the order the advantage-statistics launch materialised into perm_idx)
+struct MbWalk {
+  int ep, start, nb;
+  const int* idx;
+};
+MbWalk minibatch_walk(const ph_ctx* ctx, const int* perms, int N, int n_mb, int batch_size, int mbi) {
+  MbWalk w;
+  w.ep = mbi / n_mb;
+  w.start = (mbi - w.ep * n_mb) * batch_size;
+  w.nb = N - w.start < batch_size ? N - w.start : batch_size;
+  w.idx = (perms ? perms : ctx->perm_idx) + (size_t)w.ep * N + w.start;
+  return w;
+}
+
+// The reduce record of one minibatch: nslab gradient slabs of slab_len floats (`map`: slab position -> parameter index, null =
+// canonical order) and 2 * nslab statistics partials -> grad[P] and stats_out.  With `opt` a train() call's KL decision and step
+// counter; without it a plain gradient (no KL stop, no step).
+ph::ReduceArgs reduce_args(const ph_ctx* ctx, const ph_ppo_hyper* hp, const ph_opt_state* opt, int P, int slab_len, const int* map,
+                           int nslab, int nb, float* grad, float* stats_out) {
+  ph::ReduceArgs r;
+  r.slabs = ctx->slabs;
+  r.nslab = nslab;
+  r.nstatpart = 2 * nslab;
+  r.P = P;
+  r.slab_len = slab_len;
+  r.map = map;
+  r.grad = grad;
+  r.blocksq = ctx->blocksq;
+  r.statpart = ctx->statpart;
+  r.stats_out = stats_out;
+  r.nb = nb;
+  r.ent_coef = hp->ent_coef;
+  r.vf_coef = hp->vf_coef;
+  r.target_kl = opt ? hp->target_kl : -1.f;
+  r.stop_flag = ctx->stop_flag;
+  r.step = opt ? opt->step : nullptr;
+  r.scalars = ctx->scalars;
+  return r;
+}
+// the clip + Adam record of a train() call's minibatch, on the gradient the reduction of slab_len-float slabs left in ctx->grad;
+// `wimage`: the split kernel's weight image kept in step with the parameters, or null
+ph::AdamArgs adam_args(const ph_ctx* ctx, const ph_ppo_hyper* hp, const ph_opt_state* opt, int P, int slab_len, float* stats_out,
+                       unsigned short* wimage, const int* wimage_map) {
+  ph::AdamArgs ad;
+  ad.params = opt->params;
+  ad.m = opt->adam_m;
+  ad.v = opt->adam_v;
+  ad.grad = ctx->grad;
+  ad.blocksq = ctx->blocksq;
+  ad.nblk = ph::reduce_blocks(slab_len);
+  ad.P = P;
+  ad.step = opt->step;
+  ad.scalars = ctx->scalars;
+  ad.stop_flag = ctx->stop_flag;
+  ad.lr = hp->learning_rate;
+  ad.beta1 = hp->adam_beta1;
+  ad.beta2 = hp->adam_beta2;
+  ad.eps = hp->adam_eps;
+  ad.max_norm = hp->max_grad_norm;
+  ad.stats_out = stats_out;
+  ad.wimage = wimage;
+  ad.wimage_map = wimage_map;
+  return ad;
+}
+
+// the checks of a train() entry point's optimizer state, hyper-parameters and sizes; messages name the entry point `who`.
+// `aligned`: the caller's kernels need 16-byte aligned parameters.
+int check_train_call(const char* who, const ph_ctx* ctx, const ph_opt_state* opt, const ph_ppo_hyper* hp, int n_epochs,
+                     int batch_size, bool aligned = true) {
+  const std::string w(who);
+  if (!ctx) return fail("null ctx");
+  if (!opt || !opt->params || !opt->adam_m || !opt->adam_v || !opt->step) return fail(w + ": null optimizer state");
+  if (aligned && (uintptr_t)opt->params % 16 != 0) return fail(w + ": params must be 16-byte aligned");
+  if (!hp) return fail(w + ": null hyper-parameters");
+  if (n_epochs <= 0 || batch_size <= 0) return fail(w + ": n_epochs and batch_size must be positive");
+  return 0;
+}
+// the same for a one-minibatch gradient entry point
+int check_minibatch_call(const char* who, const ph_ctx* ctx, const float* params, const ph_rollout* rb, const ph_ppo_hyper* hp,
+                         const int* indices, int nb, const float* grad_out, bool aligned = true) {
+  const std::string w(who);
+  if (!ctx) return fail("null ctx");
+  if (!params || !hp || !indices || !grad_out) return fail(w + ": null argument");
+  if (aligned && (uintptr_t)params % 16 != 0) return fail(w + ": params must be 16-byte aligned");
+  if (check_rb(rb)) return 1;
+  if (nb <= 0) return fail(w + ": nb must be positive");
+  return 0;
+}
+
+// average milliseconds of one fn(i) (0 = success) over reps calls i = 0 .. reps-1, timed by the context's events on its stream
+// after `warm` untimed calls fn(0 .. warm-1)
+template <typename F>
+int time_reps(ph_ctx* ctx, int warm, int reps, F&& fn, float* avg_ms) {
+  for (int i = 0; i < warm; ++i)
+    if (fn(i)) return 1;
+  PH_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int i = 0; i < reps; ++i)
+    if (fn(i)) return 1;
+  PH_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  PH_HIP(hipEventSynchronize(ctx->ev1));
+  float ms = 0.f;
+  PH_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *avg_ms = ms / (float)reps;
+  return 0;
+}
+int hip_rc(hipError_t e, const char* what) { return e == hipSuccess ? 0 : fail_hip(what, e); }
 
 }  // namespace
 
@@ -811,47 +1005,17 @@ int ph_policy_forward(ph_ctx* ctx, const ph_spec* spec, const float* params, con
   if ((uintptr_t)params % 16 != 0) return fail("ph_policy_forward: params must be 16-byte aligned");
   if (n <= 0) return fail("ph_policy_forward: n must be positive");
   ph::FwdArgs a;
-  std::memset(&a, 0, sizeof(a));
-  if (resolve(ctx, spec, &a.nd, true)) return 1;
+  if (fwd_args(a, ctx, spec, true, params, obs, n, seed, counter, actions_i32, values, log_probs)) return 1;
   if (a.nd.gauss && action_mask) return fail("ph_policy_forward: action masks belong to the categorical heads");
-  a.params = params;
-  a.obs = obs;
-  a.n = n;
   a.mask = action_mask;
   a.uniforms = uniforms;
   a.given_actions = given_actions;
-  a.seed = seed;
-  a.counter = counter;
-  a.epoch = ctx->rng_epoch;
   a.prof = ctx->prof;
   a.deterministic = deterministic;
-  a.act_i32 = actions_i32;
   a.act_f32 = actions_f32;
-  a.values = values;
-  a.logp = log_probs;
   a.entropy = entropy;
   a.logits = logits;
-  if (rb) {
-    if (check_rb(rb)) return 1;
-    if (n != rb->E) return fail("ph_policy_forward: fused add needs n == rollout E");
-    if (pos < 0 || pos >= rb->T) return fail("ph_policy_forward: pos out of range (buffer full?)");
-    if (!episode_start_in) return fail("ph_policy_forward: fused add needs episode_start_in");
-    const size_t row = (size_t)pos * rb->E;
-    a.rb_obs = rb->observations + row * a.nd.D;
-    a.rb_act = rb->actions + row * a.nd.A;
-    a.rb_rew = rb->rewards + row;
-    a.rb_es = rb->episode_starts + row;
-    a.rb_val = rb->values + row;
-    a.rb_logp = rb->log_probs + row;
-    a.es_in = episode_start_in;
-    if (pending_reward) {
-      if (pos < 1) return fail("ph_policy_forward: pending_reward needs pos >= 1");
-      a.prev_rew = rb->rewards + (row - rb->E);
-      a.pending_reward = pending_reward;
-    }
-  } else if (pending_reward) {
-    return fail("ph_policy_forward: pending_reward needs the fused rollout-buffer write");
-  }
+  if (fwd_bind_row("ph_policy_forward", a, rb, pos, episode_start_in, pending_reward)) return 1;
   a.host_done = ctx->fwd_host_done;
   a.host_seq = ctx->act_seq;
   PH_HIP(ph::launch_policy_fwd(a, gemm_mode, ctx->stream));
@@ -954,29 +1118,12 @@ int ph_scripted_rollout(ph_ctx* ctx, const ph_spec* spec, const float* params, c
   if (n != rb->E) return fail("ph_scripted_rollout: n must equal the rollout buffer's E");
   if (pos0 < 0 || pos0 + n_steps > rb->T) return fail("ph_scripted_rollout: rows pos0 .. pos0 + n_steps - 1 must lie in the buffer");
   ph::FwdArgs a;
-  std::memset(&a, 0, sizeof(a));
-  if (resolve(ctx, spec, &a.nd)) return 1;
+  if (fwd_args(a, ctx, spec, false, params, obs_seq, n, seed, counter0, actions_i32, values, log_probs)) return 1;
   if (!ph::fwd16_eligible(a.nd, n))
     return fail("ph_scripted_rollout: needs the 16-row forward's shape class (one feature chunk, one Discrete head of <= 8 logits, "
                 "n < 16384); use ph_policy_forward per step");
-  a.params = params;
-  a.obs = obs_seq;
-  a.n = n;
-  a.seed = seed;
-  a.counter = counter0;
-  a.epoch = ctx->rng_epoch;
   a.prof = ctx->prof;
-  a.act_i32 = actions_i32;
-  a.values = values;
-  a.logp = log_probs;
-  const size_t row = (size_t)pos0 * rb->E;
-  a.rb_obs = rb->observations + row * a.nd.D;
-  a.rb_act = rb->actions + row * a.nd.A;
-  a.rb_rew = rb->rewards + row;
-  a.rb_es = rb->episode_starts + row;
-  a.rb_val = rb->values + row;
-  a.rb_logp = rb->log_probs + row;
-  a.es_in = episode_start0;
+  if (fwd_bind_row("ph_scripted_rollout", a, rb, pos0, episode_start0, nullptr)) return 1;   // step 0's row
   ph::ScriptedSteps sc;
   sc.n_steps = n_steps;
   sc.obs_seq = obs_seq;
@@ -1007,19 +1154,11 @@ int step_multi_impl(ph_ctx* ctx, int n_calls, const ph_step_call* calls, const p
     ph::FwdArgs& a = m.a[i];
     if (!c.params || !c.obs || !c.rb || !c.episode_start_in) return fail("ph_policy_step_multi: null argument");
     if ((uintptr_t)c.params % 16 != 0) return fail("ph_policy_step_multi: params must be 16-byte aligned");
-    if (resolve(ctx, c.spec, &a.nd)) return 1;
-    if (check_rb(c.rb)) return 1;
-    if (c.n != c.rb->E) return fail("ph_policy_step_multi: n must equal the rollout E");
-    if (c.pos < 0 || c.pos >= c.rb->T) return fail("ph_policy_step_multi: pos out of range (buffer full?)");
+    if (fwd_args(a, ctx, c.spec, false, c.params, c.obs, c.n, c.seed, c.counter, c.actions_i32, c.values, c.log_probs)) return 1;
+    if (fwd_bind_row("ph_policy_step_multi", a, c.rb, c.pos, c.episode_start_in, c.pending_reward)) return 1;
     if (i > 0 && (c.n != calls[0].n || a.nd.Lp != m.a[0].nd.Lp))
       return fail("ph_policy_step_multi: all calls must share n and the padded logit count");
-    a.params = c.params;
-    a.obs = c.obs;
-    a.n = c.n;
     a.mask = c.action_mask;
-    a.seed = c.seed;
-    a.counter = c.counter;
-    a.epoch = ctx->rng_epoch;
     a.deterministic = c.deterministic & 1;
     if (c.deterministic & (PH_STEP_FIX_ILLEGAL | PH_STEP_MASK_ENV_ONLY)) {
       if (!c.action_mask) return fail("PH_STEP_FIX_ILLEGAL / PH_STEP_MASK_ENV_ONLY need an action mask");
@@ -1028,31 +1167,15 @@ int step_multi_impl(ph_ctx* ctx, int n_calls, const ph_step_call* calls, const p
       a.env_mask = c.action_mask;
       if (c.deterministic & PH_STEP_MASK_ENV_ONLY) a.mask = nullptr;   // the policy never sees the mask (plain PPO partner)
     }
-    a.act_i32 = c.actions_i32;
-    a.values = c.values;
-    a.logp = c.log_probs;
-    const size_t row = (size_t)c.pos * c.rb->E;
-    a.rb_obs = c.rb->observations + row * a.nd.D;
-    a.rb_act = c.rb->actions + row * a.nd.A;
-    a.rb_rew = c.rb->rewards + row;
-    a.rb_es = c.rb->episode_starts + row;
-    a.rb_val = c.rb->values + row;
-    a.rb_logp = c.rb->log_probs + row;
-    a.es_in = c.episode_start_in;
-    if (c.pending_reward) {
-      if (c.pos < 1) return fail("ph_policy_step_multi: pending_reward needs pos >= 1");
-      a.prev_rew = c.rb->rewards + (row - c.rb->E);
-      a.pending_reward = c.pending_reward;
-      if (c.joint_actions) {
-        if (!c.partner_seat || c.n_seats <= 0 || c.seat < 0 || c.seat >= c.n_seats)
-          return fail("ph_policy_step_multi: bad joint-action description");
-        a.joint = c.joint_actions;
-        a.n_seats = c.n_seats;
-        a.seat = c.seat;
-        a.partner_seat = c.partner_seat;
-        a.bonus = c.bonus;
-        a.reward_rule = ctx->joint_reward_rule;
-      }
+    if (c.pending_reward && c.joint_actions) {
+      if (!c.partner_seat || c.n_seats <= 0 || c.seat < 0 || c.seat >= c.n_seats)
+        return fail("ph_policy_step_multi: bad joint-action description");
+      a.joint = c.joint_actions;
+      a.n_seats = c.n_seats;
+      a.seat = c.seat;
+      a.partner_seat = c.partner_seat;
+      a.bonus = c.bonus;
+      a.reward_rule = ctx->joint_reward_rule;
     }
   }
   if (x) {  // exchange fused into the launch (16-row kernel only; the caller checked eligibility)
@@ -1336,7 +1459,7 @@ int ph_selfplay_rollout_persistent(ph_ctx* ctx, int n_calls, const ph_rollout_ca
     if (!c.params || !c.obs_seq || !c.rew_seq || !c.done_seq || !c.rb || !c.episode_start0 || !c.partner_seat)
       return fail("ph_selfplay_rollout_persistent: null argument");
     if ((uintptr_t)c.params % 16 != 0) return fail("ph_selfplay_rollout_persistent: params must be 16-byte aligned");
-    if (resolve(ctx, c.spec, &a.nd)) return 1;
+    if (fwd_args(a, ctx, c.spec, false, c.params, c.obs_seq, c.n, c.seed, c.counter0, c.actions_i32, c.values, c.log_probs)) return 1;
     if (!ph::fwd16_eligible(a.nd, c.n))
       return fail("ph_selfplay_rollout_persistent: needs the 16-row forward's shape class (one feature chunk, one Discrete head "
                   "of <= 8 logits, n < 16384)");
@@ -1344,20 +1467,11 @@ int ph_selfplay_rollout_persistent(ph_ctx* ctx, int n_calls, const ph_rollout_ca
     if (c.n != c.rb->E || c.n != calls[0].n) return fail("ph_selfplay_rollout_persistent: every call's n must equal its rollout E and agree");
     if (c.rb->T < T) return fail("ph_selfplay_rollout_persistent: the rollout buffer has fewer than T rows");
     if (c.n_seats <= 0 || c.seat < 0 || c.seat >= c.n_seats) return fail("ph_selfplay_rollout_persistent: bad seat description");
-    a.params = c.params;
-    a.obs = c.obs_seq;
-    a.n = c.n;
     if (c.mask_mode < 0 || c.mask_mode > 3) return fail("ph_selfplay_rollout_persistent: mask_mode is 0..3");
     sm.sc[i].mask_policy = (c.mask_seq && (c.mask_mode == 0 || c.mask_mode == 1)) ? 1 : 0;
     sm.sc[i].mask_env = (c.mask_seq && (c.mask_mode == 1 || c.mask_mode == 2)) ? 1 : 0;
     a.mask = sm.sc[i].mask_policy ? c.mask_seq : nullptr;
     a.env_mask = sm.sc[i].mask_env ? c.mask_seq : nullptr;
-    a.seed = c.seed;
-    a.counter = c.counter0;
-    a.epoch = ctx->rng_epoch;
-    a.act_i32 = c.actions_i32;
-    a.values = c.values;
-    a.logp = c.log_probs;
     a.rb_obs = c.rb->observations;
     a.rb_act = c.rb->actions;
     a.rb_rew = c.rb->rewards;
@@ -1403,20 +1517,10 @@ int ph_policy_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const float* para
   if ((uintptr_t)params % 16 != 0) return fail("ph_policy_forward_ragged: params must be 16-byte aligned");
   if (check_rb(rb)) return 1;
   ph::FwdArgs a;
-  std::memset(&a, 0, sizeof(a));
-  if (resolve(ctx, spec, &a.nd)) return 1;
-  a.params = params;
-  a.obs = obs;
-  a.n = rb->E;
+  if (fwd_args(a, ctx, spec, false, params, obs, rb->E, seed, counter, actions_i32, values, log_probs)) return 1;
   a.mask = action_mask;
-  a.seed = seed;
-  a.counter = counter;
-  a.epoch = ctx->rng_epoch;
   a.prof = ctx->prof;
   a.deterministic = deterministic;
-  a.act_i32 = actions_i32;
-  a.values = values;
-  a.logp = log_probs;
   a.rb_obs = rb->observations;  // array bases: rows are selected per env
   a.rb_act = rb->actions;
   a.rb_rew = rb->rewards;
@@ -1558,20 +1662,13 @@ int ph_liar_selfplay_rollout(ph_ctx* ctx, const ph_liar_selfplay* sp, int ego_po
        (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
     return fail("ph_liar_selfplay_rollout: hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
   if (((uintptr_t)s.ego_params | (uintptr_t)s.alt_params) % 16) return fail("ph_liar_selfplay_rollout: params must be 16-byte aligned");
+  // exactly the argument records ph_liar_selfplay_step's three forwards build (ph_policy_forward / _ragged); the Philox
+  // counters are the kernel's
   ph::FwdArgs ego, reply, opening;
-  std::memset(&ego, 0, sizeof(ego));
-  if (resolve(ctx, s.spec, &ego.nd)) return 1;
+  if (fwd_args(ego, ctx, s.spec, false, s.ego_params, s.obs_ego, s.n, s.ego_seed, 0, s.ego_actions, s.ego_values, s.ego_log_probs))
+    return 1;
   if (!ph::liar_rollout_eligible(ego.nd, s.n))
     return fail("ph_liar_selfplay_rollout: the spec does not fit the 16-row one-hot forward (use ph_liar_selfplay_step)");
-  // exactly the argument records ph_liar_selfplay_step's three forwards build (ph_policy_forward / _ragged)
-  ego.params = s.ego_params;
-  ego.obs = s.obs_ego;
-  ego.n = s.n;
-  ego.seed = s.ego_seed;
-  ego.epoch = ctx->rng_epoch;
-  ego.act_i32 = s.ego_actions;
-  ego.values = s.ego_values;
-  ego.logp = s.ego_log_probs;
   const size_t row = (size_t)ego_pos * s.n;
   ego.rb_obs = s.ego_rb->observations + row * ego.nd.D;
   ego.rb_act = s.ego_rb->actions + row * ego.nd.A;
@@ -1665,7 +1762,7 @@ int rebuild_weight_image(ph_ctx* ctx, const ph::NetDims& nd, const float* params
   if (!nd.split) return 0;
   if ((size_t)nd.wimage_elems > ctx->wimage_cap) {
     if (ctx->capturing) return fail("first split-kernel use inside graph capture: call it once outside capture first");
-    if (ensure(ctx->wimage, ctx->wimage_cap, (size_t)nd.wimage_elems)) return 1;
+    if (ensure(ctx, ctx->wimage, ctx->wimage_cap, (size_t)nd.wimage_elems)) return 1;
     ctx->wimage_zeroed_for = 0;
   }
   // Elements no parameter backs are written by nobody (weight_image_kernel / ppo_adam_kernel go through the map), so they are
@@ -1688,18 +1785,13 @@ int build_grad_pack(ph_ctx* ctx, const ph::NetDims& nd, const ph_rollout* rb, si
   if (nd.split != 1) return 0;   // the one-hot kernel gathers its rows itself (D integers per row: nothing to split ahead)
   const size_t rows = (size_t)rb->T * rb->E;
   const size_t need_img = (rows + 1) * ph::XIMG_ROW_U4;
-  if (ctx->capturing) {
-    if (need_img > ctx->ximg_cap || n_rec > ctx->rec_cap || 2 * rows > ctx->rowrec_cap)
-      return fail("workspace would grow inside graph capture: run the same call once outside capture first");
-  } else {
-    if (ensure(ctx->ximg, ctx->ximg_cap, need_img)) return 1;
-    if (ensure(ctx->rowrec, ctx->rowrec_cap, 2 * rows)) return 1;
-    if (n_rec > ctx->rec_cap) {
-      size_t c1 = ctx->rec_cap, c2 = ctx->rec_cap;
-      if (ensure(ctx->rec_pi, c1, n_rec)) return 1;
-      if (ensure(ctx->rec_vf, c2, n_rec)) return 1;
-      ctx->rec_cap = n_rec;
-    }
+  if (ensure(ctx, ctx->ximg, ctx->ximg_cap, need_img)) return 1;
+  if (ensure(ctx, ctx->rowrec, ctx->rowrec_cap, 2 * rows)) return 1;
+  if (n_rec > ctx->rec_cap) {
+    size_t c1 = ctx->rec_cap, c2 = ctx->rec_cap;
+    if (ensure(ctx, ctx->rec_pi, c1, n_rec)) return 1;
+    if (ensure(ctx, ctx->rec_vf, c2, n_rec)) return 1;
+    ctx->rec_cap = n_rec;
   }
   PH_HIP(ph::launch_obs_planes(rb->observations, (int)rows, nd.D, nd.F, ph::grad_fast_fold(nd) ? 1 : 0, ctx->ximg, rb->advantages,
                                rb->log_probs, rb->actions, rb->returns, rb->values, ctx->rowrec, ctx->stream));
@@ -1715,6 +1807,7 @@ void fill_adv_records(ph::AdvStatArgs& aa, const ph_ctx* ctx, const ph::NetDims&
   aa.rb_val = rb->values;
 }
 
+
 // gemm_mode 2 (products as six bf16 MFMA terms over three-plane operands, float32 accuracy) applies to the gradient launches
 // of specs ppo_grad_split_kernel takes; everywhere else it means 0.  The split kernel's slabs have their own order.
 void select_gemm(ph::NetDims& nd, int gemm_mode) {
@@ -1726,26 +1819,21 @@ void select_gemm(ph::NetDims& nd, int gemm_mode) {
 int slab_len_of(const ph::NetDims& nd) { return nd.split ? nd.slab_len_split : (nd.slab_map ? 2 * ph::RS_NET : nd.lay.P); }
 
 int ensure_train_ws(ph_ctx* ctx, int P, int slab_len, int nwg_max, int n_mb_total, size_t n_idx = 0, size_t n_phys = 0) {
-  if (ctx->capturing) {
-    if ((size_t)nwg_max * slab_len > ctx->slabs_cap || (size_t)n_mb_total * 2 > ctx->advstats_cap || n_idx > ctx->perm_idx_cap ||
-        n_phys > ctx->perm_phys_cap || (size_t)ph::reduce_blocks(slab_len) + 1 > ctx->step_words_cap || !ctx->step_gen)
-      return fail("workspace would grow inside graph capture: run the same call once outside capture first");
-    return 0;
-  }
-  if (n_phys && ensure(ctx->perm_phys, ctx->perm_phys_cap, n_phys)) return 1;
-  if (ensure(ctx->slabs, ctx->slabs_cap, (size_t)nwg_max * slab_len)) return 1;
-  if (ensure(ctx->statpart, ctx->statpart_cap, (size_t)2 * nwg_max * ph::NSTATP)) return 1;
-  if (ensure(ctx->grad, ctx->grad_cap, (size_t)P)) return 1;
-  if (ensure(ctx->blocksq, ctx->blocksq_cap, (size_t)ph::reduce_blocks(slab_len))) return 1;
-  if (ensure(ctx->advstats, ctx->advstats_cap, (size_t)n_mb_total * 2)) return 1;
-  if (ensure(ctx->advpart, ctx->advpart_cap, (size_t)n_mb_total * 2 * ph::ADV_SPLIT)) return 1;
-  if (n_idx && ensure(ctx->perm_idx, ctx->perm_idx_cap, n_idx)) return 1;
+  if (n_phys && ensure(ctx, ctx->perm_phys, ctx->perm_phys_cap, n_phys)) return 1;
+  if (ensure(ctx, ctx->slabs, ctx->slabs_cap, (size_t)nwg_max * slab_len)) return 1;
+  if (ensure(ctx, ctx->statpart, ctx->statpart_cap, (size_t)2 * nwg_max * ph::NSTATP)) return 1;
+  if (ensure(ctx, ctx->grad, ctx->grad_cap, (size_t)P)) return 1;
+  if (ensure(ctx, ctx->blocksq, ctx->blocksq_cap, (size_t)ph::reduce_blocks(slab_len))) return 1;
+  if (ensure(ctx, ctx->advstats, ctx->advstats_cap, (size_t)n_mb_total * 2)) return 1;
+  if (ensure(ctx, ctx->advpart, ctx->advpart_cap, (size_t)n_mb_total * 2 * ph::ADV_SPLIT)) return 1;
+  if (n_idx && ensure(ctx, ctx->perm_idx, ctx->perm_idx_cap, n_idx)) return 1;
   const size_t n_words = (size_t)ph::reduce_blocks(slab_len) + 1;
   if (n_words > ctx->step_words_cap) {
-    if (ensure(ctx->step_words, ctx->step_words_cap, n_words)) return 1;
+    if (ensure(ctx, ctx->step_words, ctx->step_words_cap, n_words)) return 1;
     PH_HIP(hipMemsetAsync(ctx->step_words, 0, n_words * sizeof(unsigned long long), ctx->stream));
   }
   if (!ctx->step_gen) {
+    if (ctx->capturing) return fail("workspace would grow inside graph capture: run the same call once outside capture first");
     PH_HIP(hipMalloc((void**)&ctx->step_gen, 4 * sizeof(unsigned int)));   // generation, timed-out waits, -, -
     PH_HIP(hipMemsetAsync(ctx->step_gen, 0, 4 * sizeof(unsigned int), ctx->stream));
   }
@@ -1797,13 +1885,8 @@ int adap_check(ph_ctx* ctx, const ph::NetDims& nd, const ph_adap_loss* ad, const
   if (ph::adap_lds_bytes(nd, ad->num_context_samples, ad->context_size) > 160 * 1024)
     return fail(w + ": observation / action space too large for the context kernel's LDS tile");
   const size_t nwg = (size_t)ph::adap_workgroups(ad->num_context_samples, ad->num_state_samples);
-  if (ctx->capturing) {
-    if (nwg * ph::adap_slab_floats(nd.lay) > ctx->adap_extra_cap || nwg > ctx->adap_loss_cap)
-      return fail("workspace would grow inside graph capture: run the same call once outside capture first");
-    return 0;
-  }
-  if (ensure(ctx->adap_extra, ctx->adap_extra_cap, nwg * ph::adap_slab_floats(nd.lay))) return 1;
-  if (ensure(ctx->adap_loss, ctx->adap_loss_cap, nwg)) return 1;
+  if (ensure(ctx, ctx->adap_extra, ctx->adap_extra_cap, nwg * ph::adap_slab_floats(nd.lay))) return 1;
+  if (ensure(ctx, ctx->adap_loss, ctx->adap_loss_cap, nwg)) return 1;
   return 0;
 }
 
@@ -1855,39 +1938,19 @@ int adap_launch(ph_ctx* ctx, const ph::NetDims& nd, const float* params, const p
 
 // the advantage-statistics launch of a train() call: statistics of every minibatch, the minibatch order, the row records
 void train_adv_args(const TrainPlan& t, bool need_idx, ph::AdvStatArgs& aa) {
-  ph_ctx* ctx = t.ctx;
-  aa.clear_flag = ctx->stop_flag;    // the call's KL stop flag starts at 0 (no launch of its own: nothing reads it before the first gradient launch)
-  aa.rb_adv = t.rb->advantages;
-  aa.T = t.rb->T;
-  aa.E = t.rb->E;
-  aa.perms = t.perms;
-  aa.perm_n = (uint32_t)t.N;
-  aa.perm_hb = ph::feistel_half_bits((uint32_t)t.N);
-  aa.perm_seed = t.perm_seed;
-  aa.epoch = ctx->rng_epoch;
-  aa.N = t.N;
-  aa.batch = t.batch_size;
-  aa.n_mb = t.n_mb;
-  aa.out = ctx->advstats;
-  aa.partial = ctx->advpart;
-  aa.idx_out = t.perms ? nullptr : ctx->perm_idx;
-  aa.phys_out = ctx->perm_phys;      // the order once more as physical rows: the tile walk then has no index arithmetic
+  aa = adv_args_epochs(t.ctx, t.rb, t.perms, t.perm_seed, t.batch_size, t.n_mb);
+  aa.clear_flag = t.ctx->stop_flag;  // the call's KL stop flag starts at 0 (no launch of its own: nothing reads it before the first gradient launch)
   // the split kernel reads the row records only: the materialised order (8 of the launch's 40 bytes per element) is written
   // for whoever else walks it -- the other gradient kernels, ADAP's context launch (need_idx)
   if (t.nd.split == 1 && !need_idx) aa.idx_out = aa.phys_out = nullptr;
-  fill_adv_records(aa, ctx, t.nd, t.rb);
+  fill_adv_records(aa, t.ctx, t.nd, t.rb);
 }
 
 // validation, workspace, stop-flag reset and the advantage statistics / minibatch order of every minibatch
-int train_prepare(TrainPlan& t, ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb,
+int train_prepare(const char* who, TrainPlan& t, ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb,
                   const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms, unsigned long long perm_seed,
                   float* stats, int gemm_mode, bool need_idx = false) {
-  if (!ctx) return fail("null ctx");
-  if (!opt || !opt->params || !opt->adam_m || !opt->adam_v || !opt->step) return fail("ph_ppo_train: null optimizer state");
-  if ((uintptr_t)opt->params % 16 != 0) return fail("ph_ppo_train: params must be 16-byte aligned");
-  if (!hp) return fail("ph_ppo_train: null hyper-parameters");
-  if (check_rb(rb)) return 1;
-  if (n_epochs <= 0 || batch_size <= 0) return fail("ph_ppo_train: n_epochs and batch_size must be positive");
+  if (check_train_call(who, ctx, opt, hp, n_epochs, batch_size) || check_rb(rb)) return 1;
   if (resolve(ctx, spec, &t.nd, true)) return 1;
   select_gemm(t.nd, gemm_mode);
   t.ctx = ctx;
@@ -1924,26 +1987,25 @@ constexpr unsigned long long STEP_WAIT_TICKS = 200000000ull;
 // gradient launch of minibatch mbi = ep * n_mb + k
 int train_launch_grad(const TrainPlan& t, int mbi, MbPlan* pl_out) {
   ph_ctx* ctx = t.ctx;
-  const int ep = mbi / t.n_mb, k = mbi - ep * t.n_mb;
-  const int start = k * t.batch_size;
-  const int nb = (t.N - start < t.batch_size) ? t.N - start : t.batch_size;
-  const MbPlan pl = plan_minibatch(ctx, t.nd, nb);
+  const MbWalk w = minibatch_walk(ctx, t.perms, t.N, t.n_mb, t.batch_size, mbi);
+  const size_t pos = (size_t)w.ep * t.N + w.start;   // of the minibatch's first row in the call's (n_epochs, N) order
+  const MbPlan pl = plan_minibatch(ctx, t.nd, w.nb);
   ph::GradArgs g;
   std::memset(&g, 0, sizeof(g));
   fill_grad_args(g, t.nd, t.opt->params, t.rb, t.hp, ctx);
-  g.idx = (t.perms ? t.perms : ctx->perm_idx) + (size_t)ep * t.N + start;
-  g.idx_phys = ctx->perm_phys + (size_t)ep * t.N + start;
+  g.idx = w.idx;
+  g.idx_phys = ctx->perm_phys + pos;
   if (t.nd.split == 1) {
-    g.rec_pi = ctx->rec_pi + (size_t)ep * t.N + start;
-    g.rec_vf = ctx->rec_vf + (size_t)ep * t.N + start;
+    g.rec_pi = ctx->rec_pi + pos;
+    g.rec_vf = ctx->rec_vf + pos;
   }
   g.perm_n = (uint32_t)t.N;
   g.perm_hb = t.hb;
   g.perm_seed = t.perm_seed;
-  g.perm_epoch = ep;
+  g.perm_epoch = w.ep;
   g.epoch = ctx->rng_epoch;
-  g.mb_start = start;
-  g.nb = nb;
+  g.mb_start = w.start;
+  g.nb = w.nb;
   g.advstats = ctx->advstats + 2 * (size_t)mbi;
   g.ntiles = pl.ntiles;
   *pl_out = pl;
@@ -1954,42 +2016,10 @@ int train_launch_grad(const TrainPlan& t, int mbi, MbPlan* pl_out) {
 // the argument records of minibatch mbi's reduce (+ statistics, KL decision) and clip + Adam
 void fill_step_args(const TrainPlan& t, int mbi, const MbPlan& pl, ph::ReduceArgs& r, ph::AdamArgs& ad) {
   ph_ctx* ctx = t.ctx;
-  r.slabs = ctx->slabs;
-  r.nslab = pl.nwg;
-  r.nstatpart = 2 * pl.nwg;
-  r.P = t.P;
-  r.slab_len = slab_len_of(t.nd);
-  r.map = t.nd.slab_map;
-  r.grad = ctx->grad;
-  r.blocksq = ctx->blocksq;
-  r.statpart = ctx->statpart;
-  r.stats_out = t.stats ? t.stats + (size_t)mbi * PH_NSTAT : nullptr;
-  r.nb = pl.nb;
-  r.ent_coef = t.hp->ent_coef;
-  r.vf_coef = t.hp->vf_coef;
-  r.target_kl = t.hp->target_kl;
-  r.stop_flag = ctx->stop_flag;
-  r.step = t.opt->step;
-  r.scalars = ctx->scalars;
+  float* stats_out = t.stats ? t.stats + (size_t)mbi * PH_NSTAT : nullptr;
+  r = reduce_args(ctx, t.hp, t.opt, t.P, slab_len_of(t.nd), t.nd.slab_map, pl.nwg, pl.nb, ctx->grad, stats_out);
   r.wide = t.alone && ctx->exclusive;
-  ad.params = t.opt->params;
-  ad.m = t.opt->adam_m;
-  ad.v = t.opt->adam_v;
-  ad.grad = ctx->grad;
-  ad.blocksq = ctx->blocksq;
-  ad.nblk = ph::reduce_blocks(slab_len_of(t.nd));
-  ad.P = t.P;
-  ad.step = t.opt->step;
-  ad.scalars = ctx->scalars;
-  ad.stop_flag = ctx->stop_flag;
-  ad.lr = t.hp->learning_rate;
-  ad.beta1 = t.hp->adam_beta1;
-  ad.beta2 = t.hp->adam_beta2;
-  ad.eps = t.hp->adam_eps;
-  ad.max_norm = t.hp->max_grad_norm;
-  ad.stats_out = r.stats_out;
-  ad.wimage = t.nd.split ? ctx->wimage : nullptr;
-  ad.wimage_map = t.nd.wimage_map;
+  ad = adam_args(ctx, t.hp, t.opt, t.P, slab_len_of(t.nd), stats_out, t.nd.split ? ctx->wimage : nullptr, t.nd.wimage_map);
 }
 
 // slab reduction + statistics + KL decision, then clip + Adam, of the minibatch whose gradient launch returned `pl`
@@ -2000,9 +2030,8 @@ int train_launch_step(const TrainPlan& t, int mbi, const MbPlan& pl) {
   ph::AdamArgs ad;
   fill_step_args(t, mbi, pl, r, ad);
   if (t.adap) {
-    const int ep = mbi / t.n_mb, start = (mbi - ep * t.n_mb) * t.batch_size;
-    const int* idx = (t.perms ? t.perms : ctx->perm_idx) + (size_t)ep * t.N + start;
-    if (adap_launch(ctx, t.nd, t.opt->params, t.rb, t.adap, idx, pl.nb, mbi, &r)) return 1;
+    const MbWalk w = minibatch_walk(ctx, t.perms, t.N, t.n_mb, t.batch_size, mbi);
+    if (adap_launch(ctx, t.nd, t.opt->params, t.rb, t.adap, w.idx, w.nb, mbi, &r)) return 1;
   }
   const bool fused = step_fused_wanted(ctx, slab_len_of(t.nd), t.alone != 0);
 #ifdef PH_EXPERIMENT_SKIP_STEP   // TIMING EXPERIMENTS ONLY (never in the default build; scripts/build_variants.sh): what the gradient launches
@@ -2023,11 +2052,12 @@ int train_launch_step(const TrainPlan& t, int mbi, const MbPlan& pl) {
 }  // namespace
 
 namespace {
-int train_run(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb, const ph_ppo_hyper* hp,
-              int n_epochs, int batch_size, const int* perms, unsigned long long perm_seed, float* stats, int gemm_mode,
-              const ph_adap_loss* adap) {
+int train_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb,
+              const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms, unsigned long long perm_seed, float* stats,
+              int gemm_mode, const ph_adap_loss* adap) {
   TrainPlan t;
-  if (train_prepare(t, ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, adap != nullptr)) return 1;
+  if (train_prepare(who, t, ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, adap != nullptr))
+    return 1;
   if (adap && t.nd.gauss) return fail("ph_adap_train: the context term is written for the categorical heads");
   if (adap && adap_check(ctx, t.nd, adap, "ph_adap_train")) return 1;
   t.adap = adap;
@@ -2044,7 +2074,7 @@ int ph_ppo_train(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, cons
                  const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms,
                  unsigned long long perm_seed, float* stats, int gemm_mode) {
   DevGuard dev_guard(ctx);
-  return train_run(ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, nullptr);
+  return train_run("ph_ppo_train", ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, nullptr);
 }
 
 int ph_adap_train(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb,
@@ -2052,7 +2082,7 @@ int ph_adap_train(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, con
                   unsigned long long perm_seed, float* stats, int gemm_mode, const ph_adap_loss* adap) {
   DevGuard dev_guard(ctx);
   if (!adap) return fail("ph_adap_train: null context-term description");
-  return train_run(ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, adap);
+  return train_run("ph_adap_train", ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, adap);
 }
 
 int ph_ppo_train_multi(const ph_train_call* calls, int n_calls) {
@@ -2062,8 +2092,8 @@ int ph_ppo_train_multi(const ph_train_call* calls, int n_calls) {
   int total[PH_MAX_TRAIN_CALLS], longest = 0;
   for (int k = 0; k < n_calls; ++k) {
     const ph_train_call& c = calls[k];
-    if (train_prepare(t[k], c.ctx, c.spec, c.opt, c.rb, c.hyper, c.n_epochs, c.batch_size, c.perms, c.perm_seed, c.stats,
-                      c.gemm_mode))
+    if (train_prepare("ph_ppo_train_multi", t[k], c.ctx, c.spec, c.opt, c.rb, c.hyper, c.n_epochs, c.batch_size, c.perms,
+                      c.perm_seed, c.stats, c.gemm_mode))
       return 1;
     t[k].alone = n_calls == 1;
     if (!t[k].ctx->ev_grad) PH_HIP(hipEventCreateWithFlags(&t[k].ctx->ev_grad, hipEventDisableTiming));
@@ -2096,8 +2126,8 @@ int ph_ppo_train_multi(const ph_train_call* calls, int n_calls) {
 }
 
 namespace {
-int minibatch_grad_run(ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb, const ph_ppo_hyper* hp,
-                       const int* indices, int nb, float* grad_out, float* stats_out, int gemm_mode,
+int minibatch_grad_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb,
+                       const ph_ppo_hyper* hp, const int* indices, int nb, float* grad_out, float* stats_out, int gemm_mode,
                        const ph_adap_loss* adap);
 }  // namespace
 
@@ -2105,7 +2135,7 @@ int ph_ppo_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const float* params,
                           const ph_ppo_hyper* hp, const int* indices, int nb, float* grad_out, float* stats_out,
                           int gemm_mode) {
   DevGuard dev_guard(ctx);
-  return minibatch_grad_run(ctx, spec, params, rb, hp, indices, nb, grad_out, stats_out, gemm_mode, nullptr);
+  return minibatch_grad_run("ph_ppo_minibatch_grad", ctx, spec, params, rb, hp, indices, nb, grad_out, stats_out, gemm_mode, nullptr);
 }
 
 int ph_adap_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb,
@@ -2113,18 +2143,14 @@ int ph_adap_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const float* params
                            int gemm_mode, const ph_adap_loss* adap) {
   DevGuard dev_guard(ctx);
   if (!adap) return fail("ph_adap_minibatch_grad: null context-term description");
-  return minibatch_grad_run(ctx, spec, params, rb, hp, indices, nb, grad_out, stats_out, gemm_mode, adap);
+  return minibatch_grad_run("ph_adap_minibatch_grad", ctx, spec, params, rb, hp, indices, nb, grad_out, stats_out, gemm_mode, adap);
 }
 
 namespace {
-int minibatch_grad_run(ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb, const ph_ppo_hyper* hp,
-                       const int* indices, int nb, float* grad_out, float* stats_out, int gemm_mode,
+int minibatch_grad_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb,
+                       const ph_ppo_hyper* hp, const int* indices, int nb, float* grad_out, float* stats_out, int gemm_mode,
                        const ph_adap_loss* adap) {
-  if (!ctx) return fail("null ctx");
-  if (!params || !hp || !indices || !grad_out) return fail("ph_ppo_minibatch_grad: null argument");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_ppo_minibatch_grad: params must be 16-byte aligned");
-  if (check_rb(rb)) return 1;
-  if (nb <= 0) return fail("ph_ppo_minibatch_grad: nb must be positive");
+  if (check_minibatch_call(who, ctx, params, rb, hp, indices, nb, grad_out)) return 1;
   ph::NetDims nd;
   if (resolve(ctx, spec, &nd, adap == nullptr)) return 1;
   select_gemm(nd, gemm_mode);
@@ -2135,22 +2161,7 @@ int minibatch_grad_run(ph_ctx* ctx, const ph_spec* spec, const float* params, co
   PH_HIP(ph::launch_set_int(ctx->stop_flag, 0, s));
   if (rebuild_weight_image(ctx, nd, params)) return 1;
   if (build_grad_pack(ctx, nd, rb, (size_t)nb)) return 1;
-  ph::AdvStatArgs aa;
-  aa.rb_adv = rb->advantages;
-  aa.T = rb->T;
-  aa.E = rb->E;
-  aa.perms = indices;  // one "epoch" whose first nb entries are the minibatch
-  aa.perm_n = 0;
-  aa.perm_hb = 1;
-  aa.perm_seed = 0;
-  aa.epoch = nullptr;
-  aa.N = nb;
-  aa.batch = nb;
-  aa.n_mb = 1;
-  aa.out = ctx->advstats;
-  aa.partial = ctx->advpart;
-  aa.idx_out = nullptr;
-  aa.phys_out = ctx->perm_phys;
+  ph::AdvStatArgs aa = adv_args_minibatch(ctx, rb, indices, nb);
   fill_adv_records(aa, ctx, nd, rb);
   PH_HIP(ph::launch_adv_stats(aa, 1, s));
   ph::GradArgs g;
@@ -2162,26 +2173,9 @@ int minibatch_grad_run(ph_ctx* ctx, const ph_spec* spec, const float* params, co
   g.advstats = ctx->advstats;
   g.ntiles = pl.ntiles;
   PH_HIP(ph::launch_ppo_grad(g, pl.nwg, gemm_mode, s));
-  ph::ReduceArgs r;
-  r.slabs = ctx->slabs;
-  r.nslab = pl.nwg;
-  r.nstatpart = 2 * pl.nwg;
-  r.P = P;
-  r.slab_len = slab_len_of(nd);
-  r.map = nd.slab_map;
-  r.grad = grad_out;
-  r.blocksq = ctx->blocksq;
-  r.statpart = ctx->statpart;
-  r.stats_out = stats_out;
-  r.nb = nb;
-  r.ent_coef = hp->ent_coef;
-  r.vf_coef = hp->vf_coef;
-  r.target_kl = -1.f;
-  r.stop_flag = ctx->stop_flag;
-  r.step = nullptr;
-  r.scalars = ctx->scalars;
+  ph::ReduceArgs r = reduce_args(ctx, hp, nullptr, P, slab_len_of(nd), nd.slab_map, pl.nwg, nb, grad_out, stats_out);
   if (adap) {
-    if (adap_check(ctx, nd, adap, "ph_adap_minibatch_grad")) return 1;
+    if (adap_check(ctx, nd, adap, who)) return 1;
     if (adap_launch(ctx, nd, params, rb, adap, indices, nb, 0, &r)) return 1;
   }
   PH_HIP(ph::launch_ppo_reduce(r, s));
@@ -2232,10 +2226,7 @@ int am_work(ph_ctx* ctx, const ph_adapmult_layout& L, int D, int rows, ph::AmWor
                           R, R, R, R, R};
   size_t total = 0;
   for (size_t n : sizes) total += up(n);
-  if (total > ctx->am_buf_cap) {
-    if (ctx->capturing) return fail("workspace would grow inside graph capture: run the same call once outside capture first");
-    if (ensure(ctx->am_buf, ctx->am_buf_cap, total)) return 1;
-  }
+  if (ensure(ctx, ctx->am_buf, ctx->am_buf_cap, total)) return 1;
   float* p = ctx->am_buf;
   float** fields[] = {&w->x, &w->xa, &w->y, &w->h, &w->z, &w->v, &w->dz, &w->dv, &w->dzh, &w->dy, &w->dza, &w->xg,
                       &w->act, &w->oldlp, &w->adv, &w->ret, &w->oldv};
@@ -2249,8 +2240,9 @@ int am_nslab(int nb) {
   const int n = (nb + 15) / 16;
   return n < 1 ? 1 : (n > 64 ? 64 : n);
 }
-// PPO loss gradient of rows indices[0..nb) into ctx->slabs (nslab slabs of P floats, canonical order) + statistics partials; with
-// `adap` the context term's slabs and loss shares as well (fields of *r).  advstats: {mean, std} of the minibatch's advantages.
+// PPO loss gradient of rows indices[0..nb) into ctx->slabs (am_nslab(nb) slabs of P floats, canonical order) + statistics partials,
+// for the reduce record *r the caller built; with `adap` the context term's slabs and loss shares as well (the extra fields of *r).
+// advstats: {mean, std} of the minibatch's advantages.
 int am_minibatch(ph_ctx* ctx, const ph_adapmult_layout& L, int D, const float* params, const ph_rollout* rb, const ph_ppo_hyper* hp,
                  const int* indices, int nb, const float* advstats, const ph_adap_loss* adap, int mbi, ph::ReduceArgs* r) {
   hipStream_t s = ctx->stream;
@@ -2287,16 +2279,10 @@ int am_minibatch(ph_ctx* ctx, const ph_adapmult_layout& L, int D, const float* p
     PH_HIP(ph::am_backward_net(L, params, net, w.xg, D, nb, w, ctx->slabs, nslab, L.P, net == 0 ? L.act_W : L.val_W,
                                net == 0 ? L.act_b : L.val_b, s));
   }
-  r->slabs = ctx->slabs;
-  r->nslab = nslab;
-  r->nstatpart = 2 * nslab;
-  r->P = L.P;
-  r->slab_len = L.P;
-  r->map = nullptr;
   if (adap) {   // adap/util.py:97-131: n_states sampled states under Cs sampled contexts, policy net only
     const int cs = adap->context_size, extra_len = L.vf_W1 + (L.val_W - L.act_W);
-    if (ensure(ctx->adap_extra, ctx->adap_extra_cap, (size_t)n_states * extra_len)) return 1;
-    if (ensure(ctx->adap_loss, ctx->adap_loss_cap, (size_t)n_states)) return 1;
+    if (ensure(ctx, ctx->adap_extra, ctx->adap_extra_cap, (size_t)n_states * extra_len)) return 1;
+    if (ensure(ctx, ctx->adap_loss, ctx->adap_loss_cap, (size_t)n_states)) return 1;
     ph::AmCtx a;
     std::memset(&a, 0, sizeof(a));
     a.rb_obs = rb->observations;
@@ -2363,38 +2349,15 @@ int ph_adapmult_forward(ph_ctx* ctx, const ph_spec* spec, int context_size, cons
   ph_adapmult_layout L;
   if (ph_adapmult_layout_of(spec, context_size, &L)) return 1;
   ph::FwdArgs a;
-  std::memset(&a, 0, sizeof(a));
-  if (resolve(ctx, spec, &a.nd)) return 1;
-  a.params = params;
-  a.obs = obs;
-  a.n = n;
+  if (fwd_args(a, ctx, spec, false, params, obs, n, seed, counter, actions_i32, values, log_probs)) return 1;
   a.mask = action_mask;
   a.uniforms = uniforms;
   a.given_actions = given_actions;
-  a.seed = seed;
-  a.counter = counter;
-  a.epoch = ctx->rng_epoch;
   a.deterministic = deterministic;
-  a.act_i32 = actions_i32;
   a.act_f32 = actions_f32;
-  a.values = values;
-  a.logp = log_probs;
   a.entropy = entropy;
   a.logits = logits;
-  if (rb) {
-    if (check_rb(rb)) return 1;
-    if (n != rb->E) return fail("ph_adapmult_forward: fused add needs n == rollout E");
-    if (pos < 0 || pos >= rb->T) return fail("ph_adapmult_forward: pos out of range (buffer full?)");
-    if (!episode_start_in) return fail("ph_adapmult_forward: fused add needs episode_start_in");
-    const size_t row = (size_t)pos * rb->E;
-    a.rb_obs = rb->observations + row * a.nd.D;
-    a.rb_act = rb->actions + row * a.nd.A;
-    a.rb_rew = rb->rewards + row;
-    a.rb_es = rb->episode_starts + row;
-    a.rb_val = rb->values + row;
-    a.rb_logp = rb->log_probs + row;
-    a.es_in = episode_start_in;
-  }
+  if (fwd_bind_row("ph_adapmult_forward", a, rb, pos, episode_start_in, nullptr)) return 1;
   ph::AmWork w;
   if (am_work(ctx, L, a.nd.D, n, &w)) return 1;
   PH_HIP(ph::am_forward_net(L, params, 0, obs, a.nd.D, n, w, ctx->stream));
@@ -2407,10 +2370,8 @@ int ph_adapmult_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, int context_siz
                                const ph_ppo_hyper* hp, const int* indices, int nb, float* grad_out, float* stats_out,
                                const ph_adap_loss* adap) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !hp || !indices || !grad_out) return fail("ph_adapmult_minibatch_grad: null argument");
-  if (check_rb(rb)) return 1;
-  if (nb <= 0) return fail("ph_adapmult_minibatch_grad: nb must be positive");
+  // AdapPolicyMult's kernels read the parameters as plain floats: no alignment asked
+  if (check_minibatch_call("ph_adapmult_minibatch_grad", ctx, params, rb, hp, indices, nb, grad_out, false)) return 1;
   ph_adapmult_layout L;
   if (ph_adapmult_layout_of(spec, context_size, &L)) return 1;
   if (adap && am_adap_ok(L, adap, "ph_adapmult_minibatch_grad")) return 1;
@@ -2418,36 +2379,9 @@ int ph_adapmult_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, int context_siz
   if (ensure_train_ws(ctx, L.P, L.P, nslab, 1, 0, (size_t)nb)) return 1;
   hipStream_t s = ctx->stream;
   PH_HIP(ph::launch_set_int(ctx->stop_flag, 0, s));
-  ph::AdvStatArgs aa;
-  aa.rb_adv = rb->advantages;
-  aa.T = rb->T;
-  aa.E = rb->E;
-  aa.perms = indices;  // one "epoch" whose first nb entries are the minibatch
-  aa.perm_n = 0;
-  aa.perm_hb = 1;
-  aa.perm_seed = 0;
-  aa.epoch = nullptr;
-  aa.N = nb;
-  aa.batch = nb;
-  aa.n_mb = 1;
-  aa.out = ctx->advstats;
-  aa.partial = ctx->advpart;
-  aa.idx_out = nullptr;
-  aa.phys_out = ctx->perm_phys;
-  PH_HIP(ph::launch_adv_stats(aa, 1, s));
-  ph::ReduceArgs r;
+  PH_HIP(ph::launch_adv_stats(adv_args_minibatch(ctx, rb, indices, nb), 1, s));   // no row records: the gather kernel reads the rows
+  ph::ReduceArgs r = reduce_args(ctx, hp, nullptr, L.P, L.P, nullptr, nslab, nb, grad_out, stats_out);
   if (am_minibatch(ctx, L, spec->obs.n, params, rb, hp, indices, nb, ctx->advstats, adap, 0, &r)) return 1;
-  r.grad = grad_out;
-  r.blocksq = ctx->blocksq;
-  r.statpart = ctx->statpart;
-  r.stats_out = stats_out;
-  r.nb = nb;
-  r.ent_coef = hp->ent_coef;
-  r.vf_coef = hp->vf_coef;
-  r.target_kl = -1.f;
-  r.stop_flag = ctx->stop_flag;
-  r.step = nullptr;
-  r.scalars = ctx->scalars;
   PH_HIP(ph::launch_ppo_reduce(r, s));
   return 0;
 }
@@ -2456,11 +2390,8 @@ int ph_adapmult_train(ph_ctx* ctx, const ph_spec* spec, int context_size, const 
                       const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms, unsigned long long perm_seed,
                       float* stats, const ph_adap_loss* adap) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!opt || !opt->params || !opt->adam_m || !opt->adam_v || !opt->step) return fail("ph_adapmult_train: null optimizer state");
-  if (!hp || !adap) return fail("ph_adapmult_train: null hyper-parameters / context-term description");
-  if (check_rb(rb)) return 1;
-  if (n_epochs <= 0 || batch_size <= 0) return fail("ph_adapmult_train: n_epochs and batch_size must be positive");
+  if (check_train_call("ph_adapmult_train", ctx, opt, hp, n_epochs, batch_size, false) || check_rb(rb)) return 1;
+  if (!adap) return fail("ph_adapmult_train: null context-term description");
   ph_adapmult_layout L;
   if (ph_adapmult_layout_of(spec, context_size, &L)) return 1;
   if (am_adap_ok(L, adap, "ph_adapmult_train")) return 1;
@@ -2469,63 +2400,16 @@ int ph_adapmult_train(ph_ctx* ctx, const ph_spec* spec, int context_size, const 
   if (ensure_train_ws(ctx, L.P, L.P, am_nslab(nb_max), n_epochs * n_mb, perms ? 0 : (size_t)n_epochs * N, (size_t)n_epochs * N))
     return 1;
   hipStream_t s = ctx->stream;
-  const uint32_t hb = ph::feistel_half_bits((uint32_t)N);
-  ph::AdvStatArgs aa;
-  aa.rb_adv = rb->advantages;
-  aa.T = rb->T;
-  aa.E = rb->E;
-  aa.perms = perms;
-  aa.perm_n = (uint32_t)N;
-  aa.perm_hb = hb;
-  aa.perm_seed = perm_seed;
-  aa.epoch = ctx->rng_epoch;
-  aa.N = N;
-  aa.batch = batch_size;
-  aa.n_mb = n_mb;
-  aa.out = ctx->advstats;
-  aa.partial = ctx->advpart;
-  aa.idx_out = perms ? nullptr : ctx->perm_idx;
-  aa.phys_out = ctx->perm_phys;
+  ph::AdvStatArgs aa = adv_args_epochs(ctx, rb, perms, perm_seed, batch_size, n_mb);   // no row records: the gather kernel reads the rows
   aa.clear_flag = ctx->stop_flag;
   PH_HIP(ph::launch_adv_stats(aa, n_epochs * n_mb, s));
   for (int mbi = 0; mbi < n_epochs * n_mb; ++mbi) {
-    const int ep = mbi / n_mb, k = mbi - ep * n_mb, start = k * batch_size;
-    const int nb = (N - start < batch_size) ? N - start : batch_size;
-    const int* idx = (perms ? perms : ctx->perm_idx) + (size_t)ep * N + start;
-    ph::ReduceArgs r;
-    if (am_minibatch(ctx, L, spec->obs.n, opt->params, rb, hp, idx, nb, ctx->advstats + 2 * (size_t)mbi, adap, mbi, &r)) return 1;
-    r.grad = ctx->grad;
-    r.blocksq = ctx->blocksq;
-    r.statpart = ctx->statpart;
-    r.stats_out = stats ? stats + (size_t)mbi * PH_NSTAT : nullptr;
-    r.nb = nb;
-    r.ent_coef = hp->ent_coef;
-    r.vf_coef = hp->vf_coef;
-    r.target_kl = hp->target_kl;
-    r.stop_flag = ctx->stop_flag;
-    r.step = opt->step;
-    r.scalars = ctx->scalars;
-    PH_HIP(ph::launch_ppo_reduce(r, s));
-    ph::AdamArgs ad;
-    ad.params = opt->params;
-    ad.m = opt->adam_m;
-    ad.v = opt->adam_v;
-    ad.grad = ctx->grad;
-    ad.blocksq = ctx->blocksq;
-    ad.nblk = ph::reduce_blocks(L.P);
-    ad.P = L.P;
-    ad.step = opt->step;
-    ad.scalars = ctx->scalars;
-    ad.stop_flag = ctx->stop_flag;
-    ad.lr = hp->learning_rate;
-    ad.beta1 = hp->adam_beta1;
-    ad.beta2 = hp->adam_beta2;
-    ad.eps = hp->adam_eps;
-    ad.max_norm = hp->max_grad_norm;
-    ad.stats_out = r.stats_out;
-    ad.wimage = nullptr;
-    ad.wimage_map = nullptr;
-    PH_HIP(ph::launch_ppo_adam(ad, s));
+    const MbWalk w = minibatch_walk(ctx, perms, N, n_mb, batch_size, mbi);
+    float* st = stats ? stats + (size_t)mbi * PH_NSTAT : nullptr;
+    ph::ReduceArgs r = reduce_args(ctx, hp, opt, L.P, L.P, nullptr, am_nslab(w.nb), w.nb, ctx->grad, st);
+    if (am_minibatch(ctx, L, spec->obs.n, opt->params, rb, hp, w.idx, w.nb, ctx->advstats + 2 * (size_t)mbi, adap, mbi, &r)) return 1;
+    PH_HIP(ph::launch_ppo_reduce(r, s));   // reduce, then clip + Adam: never the fused step, no weight image
+    PH_HIP(ph::launch_ppo_adam(adam_args(ctx, hp, opt, L.P, L.P, st, nullptr, nullptr), s));
   }
   return 0;
 }
@@ -2549,22 +2433,9 @@ int ph_bench_ppo_grad(ph_ctx* ctx, const ph_spec* spec, const float* params, con
   PH_HIP(ph::launch_set_int(ctx->stop_flag, 0, s));
   if (rebuild_weight_image(ctx, nd, params)) return 1;
   if (build_grad_pack(ctx, nd, rb, (size_t)N)) return 1;
-  ph::AdvStatArgs aa;
-  aa.rb_adv = rb->advantages;
-  aa.T = rb->T;
-  aa.E = rb->E;
-  aa.perms = nullptr;
-  aa.perm_n = (uint32_t)N;
-  aa.perm_hb = ph::feistel_half_bits((uint32_t)N);
-  aa.perm_seed = 12345;
-  aa.epoch = nullptr;
-  aa.N = N;
-  aa.batch = nb;
-  aa.n_mb = n_mb;
-  aa.out = ctx->advstats;
-  aa.partial = ctx->advpart;
-  aa.idx_out = nd.split == 1 ? nullptr : ctx->perm_idx;   // as in ph_ppo_train: the grad launches read the materialised order,
-  aa.phys_out = nd.split == 1 ? nullptr : ctx->perm_phys; // the split kernel the row records
+  ph::AdvStatArgs aa = adv_args_epochs(ctx, rb, nullptr, 12345, nb, n_mb);
+  aa.epoch = nullptr;   // one fixed order, whatever the RNG epoch
+  if (nd.split == 1) aa.idx_out = aa.phys_out = nullptr;   // as in ph_ppo_train: the split kernel reads the row records only
   fill_adv_records(aa, ctx, nd, rb);
   PH_HIP(ph::launch_adv_stats(aa, n_mb, s));
   ph::GradArgs g;
@@ -2575,25 +2446,17 @@ int ph_bench_ppo_grad(ph_ctx* ctx, const ph_spec* spec, const float* params, con
   g.perm_seed = aa.perm_seed;
   g.nb = nb;
   g.ntiles = pl.ntiles;
-  auto launch = [&](int i) -> hipError_t {
-    const size_t start = (size_t)(i % n_mb) * nb;
-    g.idx = ctx->perm_idx + start;
-    g.idx_phys = ctx->perm_phys + start;
-    g.mb_start = (int)start;
-    g.rec_pi = ctx->rec_pi ? ctx->rec_pi + start : nullptr;
-    g.rec_vf = ctx->rec_vf ? ctx->rec_vf + start : nullptr;
+  auto launch = [&](int i) {
+    const MbWalk w = minibatch_walk(ctx, nullptr, N, n_mb, nb, i % n_mb);
+    g.idx = w.idx;
+    g.idx_phys = ctx->perm_phys + w.start;
+    g.mb_start = w.start;
+    g.rec_pi = ctx->rec_pi ? ctx->rec_pi + w.start : nullptr;
+    g.rec_vf = ctx->rec_vf ? ctx->rec_vf + w.start : nullptr;
     g.advstats = ctx->advstats + 2 * (size_t)(i % n_mb);
-    return ph::launch_ppo_grad(g, pl.nwg, gemm_mode, s);
+    return hip_rc(ph::launch_ppo_grad(g, pl.nwg, gemm_mode, s), "ph_bench_ppo_grad: launch_ppo_grad");
   };
-  for (int i = 0; i < n_mb; ++i) PH_HIP(launch(i));  // warm
-  PH_HIP(hipEventRecord(ctx->ev0, s));
-  for (int i = 0; i < reps; ++i) PH_HIP(launch(i));
-  PH_HIP(hipEventRecord(ctx->ev1, s));
-  PH_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  PH_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  *avg_ms_out = ms / (float)reps;
-  return 0;
+  return time_reps(ctx, n_mb, reps, launch, avg_ms_out);   // warm: one pass over the minibatches
 }
 
 int ph_bench_gae(ph_ctx* ctx, const ph_rollout* rb, const float* last_values, const float* dones, double gamma,
@@ -2602,20 +2465,10 @@ int ph_bench_gae(ph_ctx* ctx, const ph_rollout* rb, const float* last_values, co
   if (!ctx || !last_values || !dones || !avg_ms_out) return fail("ph_bench_gae: null argument");
   if (check_rb(rb)) return 1;
   if (reps <= 0 || mode < 0 || mode > 2) return fail("ph_bench_gae: bad arguments");
-  hipStream_t s = ctx->stream;
-  auto once = [&]() {
-    return ph::launch_gae(rb->rewards, rb->values, rb->episode_starts, last_values, dones, rb->advantages, rb->returns,
-                          rb->T, rb->E, gamma, gae_lambda, mode, s);
-  };
-  PH_HIP(once());
-  PH_HIP(hipEventRecord(ctx->ev0, s));
-  for (int i = 0; i < reps; ++i) PH_HIP(once());
-  PH_HIP(hipEventRecord(ctx->ev1, s));
-  PH_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  PH_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  *avg_ms_out = ms / (float)reps;
-  return 0;
+  return time_reps(ctx, 1, reps, [&](int) {
+    return hip_rc(ph::launch_gae(rb->rewards, rb->values, rb->episode_starts, last_values, dones, rb->advantages, rb->returns,
+                                 rb->T, rb->E, gamma, gae_lambda, mode, ctx->stream), "ph_bench_gae: launch_gae");
+  }, avg_ms_out);
 }
 
 int ph_bench_train_kernels(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb,
@@ -2625,47 +2478,38 @@ int ph_bench_train_kernels(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state*
   if (reps <= 0) return fail("ph_bench_train_kernels: reps must be positive");
   for (int i = 0; i < PH_BENCH_NKERN; ++i) us_out[i] = 0.f;
   TrainPlan t;
-  if (train_prepare(t, ctx, spec, opt, rb, hp, n_epochs, batch_size, nullptr, 12345ull, nullptr, gemm_mode)) return 1;
+  if (train_prepare("ph_bench_train_kernels", t, ctx, spec, opt, rb, hp, n_epochs, batch_size, nullptr, 12345ull, nullptr, gemm_mode))
+    return 1;
   hipStream_t s = ctx->stream;
-  int rc = 0;
-  auto timed = [&](int slot, auto&& fn) -> int {
-    if (fn()) return 1;   // warm
-    PH_HIP(hipEventRecord(ctx->ev0, s));
-    for (int i = 0; i < reps; ++i)
-      if (fn()) return 1;
-    PH_HIP(hipEventRecord(ctx->ev1, s));
-    PH_HIP(hipEventSynchronize(ctx->ev1));
+  auto timed = [&](int slot, auto&& fn) -> int {   // microseconds of one fn() (0 = success) into us_out[slot]
     float ms = 0.f;
-    PH_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    us_out[slot] = 1e3f * ms / (float)reps;
+    if (time_reps(ctx, 1, reps, [&](int) { return fn(); }, &ms)) return 1;
+    us_out[slot] = 1e3f * ms;
     return 0;
   };
-  auto hip = [&](hipError_t e) -> int {
-    if (e != hipSuccess) { rc = fail(std::string("ph_bench_train_kernels: ") + hipGetErrorString(e)); return 1; }
-    return 0;
-  };
+  auto hip = [](hipError_t e) { return hip_rc(e, "ph_bench_train_kernels"); };
   if (t.nd.split) {
     if (timed(PH_BENCH_WEIGHT_IMAGE, [&] { return rebuild_weight_image(ctx, t.nd, opt->params); })) return 1;
     if (timed(PH_BENCH_OBS_PLANES, [&] { return build_grad_pack(ctx, t.nd, rb, (size_t)n_epochs * t.N); })) return 1;
   }
   ph::AdvStatArgs aa;
   train_adv_args(t, false, aa);
-  if (timed(PH_BENCH_ADV_STATS, [&] { return hip(ph::launch_adv_stats(aa, n_epochs * t.n_mb, s)); })) return rc ? rc : 1;
+  if (timed(PH_BENCH_ADV_STATS, [&] { return hip(ph::launch_adv_stats(aa, n_epochs * t.n_mb, s)); })) return 1;
   MbPlan pl;
   if (train_launch_grad(t, 0, &pl)) return 1;   // slabs and partial statistics of minibatch 0 for the reduction to read
   ph::ReduceArgs r;
   ph::AdamArgs ad;
   fill_step_args(t, 0, pl, r, ad);
   r.wide = 0;
-  if (timed(PH_BENCH_REDUCE, [&] { return hip(ph::launch_ppo_reduce(r, s)); })) return rc ? rc : 1;
+  if (timed(PH_BENCH_REDUCE, [&] { return hip(ph::launch_ppo_reduce(r, s)); })) return 1;
   r.wide = 1;
-  if (timed(PH_BENCH_REDUCE_WIDE, [&] { return hip(ph::launch_ppo_reduce(r, s)); })) return rc ? rc : 1;
-  if (timed(PH_BENCH_ADAM, [&] { return hip(ph::launch_ppo_adam(ad, s)); })) return rc ? rc : 1;
+  if (timed(PH_BENCH_REDUCE_WIDE, [&] { return hip(ph::launch_ppo_reduce(r, s)); })) return 1;
+  if (timed(PH_BENCH_ADAM, [&] { return hip(ph::launch_ppo_adam(ad, s)); })) return 1;
   if (ctx->step_words && ctx->step_gen && ph::step_fused_fits(ph::reduce_blocks(slab_len_of(t.nd)), slab_len_of(t.nd), ctx->num_cu)) {
     if (timed(PH_BENCH_STEP_FUSED, [&] {
           return hip(ph::launch_ppo_step(r, ad, ctx->step_words, ctx->step_gen, ctx->step_gen + 1, STEP_WAIT_TICKS, s));
         }))
-      return rc ? rc : 1;
+      return 1;
   }
   if (rb->T >= 2) {   // RolloutBuffer.add of one step (row 1 <- row 0): buffer_add_kernel
     const size_t E = (size_t)rb->E;
@@ -2674,7 +2518,7 @@ int ph_bench_train_kernels(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state*
                                            rb->episode_starts + E, rb->values + E, rb->log_probs + E, rb->observations,
                                            rb->actions, rb->episode_starts, rb->values, rb->log_probs, rb->E, t.nd.D, t.nd.A, s));
         }))
-      return rc ? rc : 1;
+      return 1;
   }
   us_out[PH_BENCH_SLAB_FLOATS] = (float)((double)pl.nwg * slab_len_of(t.nd));
   return 0;
@@ -2726,14 +2570,7 @@ struct ModBufs {
 int mod_buffers(ph_ctx* ctx, int nb, int n_mod, ModBufs* b) {
   const size_t rows = ((size_t)nb + 63) / 64 * 64;
   const size_t need = rows * (64 * 3 + 8 * 2 + 8 * 2 * (size_t)n_mod + 3);
-  if (need > ctx->mw.act_cap) {
-    if (ctx->capturing) return fail("workspace would grow inside graph capture: run the same call once outside capture first");
-    if (ctx->mw.act) (void)hipFree(ctx->mw.act);
-    ctx->mw.act = nullptr;
-    ctx->mw.act_cap = 0;
-    PH_HIP(hipMalloc((void**)&ctx->mw.act, need * sizeof(float)));
-    ctx->mw.act_cap = need;
-  }
+  if (ensure(ctx, ctx->mw.act, ctx->mw.act_cap, need)) return 1;
   if (!ctx->mw.kl_sum) {
     if (ctx->capturing) return fail("first ModularPolicy call inside graph capture: call it once outside capture first");
     PH_HIP(hipMalloc((void**)&ctx->mw.kl_sum, sizeof(float)));
@@ -2958,25 +2795,32 @@ int mod_minibatch(ph_ctx* ctx, const ph_spec* spec, const ph_modular* mod, const
   L.t[1].slab_stride = NS * ph::RS_NET;
   PH_HIP(ph::launch_tower(L, nwg, 2, gemm_mode, s));
 
-  ph::ReduceArgs r;
-  r.slabs = slabs;
-  r.nslab = nwg;
-  r.nstatpart = 0;
-  r.P = nd.lay.P + M * ml.P;
-  r.slab_len = NS * ph::RS_NET;
-  r.map = ctx->mw.maps + (size_t)mb.k_mod * NS * ph::RS_NET;
-  r.grad = grad;
-  r.blocksq = ctx->blocksq;
-  r.statpart = ctx->statpart;
-  r.stats_out = nullptr;
-  r.nb = nb;
-  r.ent_coef = 0.f;
-  r.vf_coef = 0.f;
-  r.target_kl = -1.f;
-  r.stop_flag = ctx->stop_flag;
-  r.step = nullptr;
-  r.scalars = ctx->scalars;
+  ph::ReduceArgs r = reduce_args(ctx, hp, nullptr, nd.lay.P + M * ml.P, NS * ph::RS_NET,
+                                 ctx->mw.maps + (size_t)mb.k_mod * NS * ph::RS_NET, nwg, nb, grad, nullptr);
+  r.nstatpart = 0;              // the gradient only: the loss statistics are the finalize launch's
+  r.ent_coef = r.vf_coef = 0.f;
   PH_HIP(ph::launch_ppo_reduce(r, s));
+  return 0;
+}
+
+// the finalize launch of a minibatch: its loss statistics from the loss kernel's partials, the epoch's KL sum, the step counter
+int mod_finalize(ph_ctx* ctx, const ph_ppo_hyper* hp, int nb, int* step, int* mod_first, int k_mod, float* stats_out,
+                 float reg_coef) {
+  ph::ModFinalizeArgs fa;
+  std::memset(&fa, 0, sizeof(fa));
+  fa.statpart = ctx->statpart;
+  fa.nstatpart = (nb + 255) / 256;
+  fa.nb = nb;
+  fa.step = step;
+  fa.mod_first = mod_first;
+  fa.k_mod = k_mod;
+  fa.kl_sum = ctx->mw.kl_sum;
+  fa.stats_out = stats_out;
+  fa.ent_coef = hp->ent_coef;
+  fa.vf_coef = hp->vf_coef;
+  fa.reg_coef = reg_coef;
+  fa.stop_flag = ctx->stop_flag;
+  PH_HIP(ph::launch_modular_finalize(fa, ctx->stream));
   return 0;
 }
 
@@ -2984,7 +2828,7 @@ int mod_workspace(ph_ctx* ctx, const ph_modular* mod, int P_total, int nb_max, i
   const int ntiles = (nb_max + 63) / 64, nwg = ntiles < ctx->num_cu ? ntiles : ctx->num_cu;
   const int loss_blocks = (nb_max + 255) / 256;
   if (ensure_train_ws(ctx, P_total, mod_slots(mod) * ph::RS_NET, nwg, n_mb_total, n_idx)) return 1;
-  if (!ctx->capturing && ensure(ctx->statpart, ctx->statpart_cap, (size_t)(loss_blocks > 2 * nwg ? loss_blocks : 2 * nwg) * ph::NSTATP))
+  if (ensure(ctx, ctx->statpart, ctx->statpart_cap, (size_t)(loss_blocks > 2 * nwg ? loss_blocks : 2 * nwg) * ph::NSTATP))
     return 1;
   return 0;
 }
@@ -3014,8 +2858,7 @@ int ph_modular_forward(ph_ctx* ctx, const ph_spec* spec, const ph_modular* mod, 
   if ((uintptr_t)params % 16 != 0) return fail("ph_modular_forward: params must be 16-byte aligned");
   if (n <= 0) return fail("ph_modular_forward: n must be positive");
   ph::FwdArgs a;
-  std::memset(&a, 0, sizeof(a));
-  if (resolve(ctx, spec, &a.nd)) return 1;
+  if (fwd_args(a, ctx, spec, false, params, obs, n, seed, counter, actions_i32, values, log_probs)) return 1;
   if (check_modular(mod, a.nd, "ph_modular_forward")) return 1;
   if (partner_idx < 0 || partner_idx >= mod->num_partners) return fail("ph_modular_forward: partner_idx out of range");
   ph_layout ml;
@@ -3026,42 +2869,13 @@ int ph_modular_forward(ph_ctx* ctx, const ph_spec* spec, const ph_modular* mod, 
   if (mod_forward_towers(ctx, a.nd, ml, params, obs, a.nd.D, nullptr, 0, 0, n, b, mod->n_modules, k_mod, false, gemm_mode,
                          nullptr))
     return 1;
-  a.params = params;
-  a.obs = obs;
-  a.n = n;
   a.mask = action_mask;
   a.uniforms = uniforms;
   a.given_actions = given_actions;
-  a.seed = seed;
-  a.counter = counter;
-  a.epoch = ctx->rng_epoch;
   a.deterministic = deterministic;
-  a.act_i32 = actions_i32;
   a.act_f32 = actions_f32;
-  a.values = values;
-  a.logp = log_probs;
   a.entropy = entropy;
-  if (rb) {
-    if (check_rb(rb)) return 1;
-    if (n != rb->E) return fail("ph_modular_forward: fused add needs n == rollout E");
-    if (pos < 0 || pos >= rb->T) return fail("ph_modular_forward: pos out of range (buffer full?)");
-    if (!episode_start_in) return fail("ph_modular_forward: fused add needs episode_start_in");
-    const size_t row = (size_t)pos * rb->E;
-    a.rb_obs = rb->observations + row * a.nd.D;
-    a.rb_act = rb->actions + row * a.nd.A;
-    a.rb_rew = rb->rewards + row;
-    a.rb_es = rb->episode_starts + row;
-    a.rb_val = rb->values + row;
-    a.rb_logp = rb->log_probs + row;
-    a.es_in = episode_start_in;
-    if (pending_reward) {
-      if (pos < 1) return fail("ph_modular_forward: pending_reward needs pos >= 1");
-      a.prev_rew = rb->rewards + (row - rb->E);
-      a.pending_reward = pending_reward;
-    }
-  } else if (pending_reward) {
-    return fail("ph_modular_forward: pending_reward needs the fused rollout-buffer write");
-  }
+  if (fwd_bind_row("ph_modular_forward", a, rb, pos, episode_start_in, pending_reward)) return 1;
   PH_HIP(ph::launch_modular_act(a, b.zm, b.zmod + (size_t)k_mod * n * 8, b.vm, b.vk, mod->nomain, logits_main, logits_partner,
                                 ctx->stream));
   return 0;
@@ -3071,11 +2885,7 @@ int ph_modular_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const ph_modular
                               const ph_rollout* rb, const ph_ppo_hyper* hp, const int* indices, int nb, float marginal_reg_coef,
                               float* grad_out, float* stats_out, int gemm_mode) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !hp || !indices || !grad_out) return fail("ph_modular_minibatch_grad: null argument");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_modular_minibatch_grad: params must be 16-byte aligned");
-  if (check_rb(rb)) return 1;
-  if (nb <= 0) return fail("ph_modular_minibatch_grad: nb must be positive");
+  if (check_minibatch_call("ph_modular_minibatch_grad", ctx, params, rb, hp, indices, nb, grad_out)) return 1;
   ph::NetDims nd;
   if (resolve(ctx, spec, &nd)) return 1;
   if (check_modular(mod, nd, "ph_modular_minibatch_grad")) return 1;
@@ -3087,50 +2897,15 @@ int ph_modular_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const ph_modular
   if (mod_maps(ctx, spec, mod, nd.lay, ml)) return 1;
   hipStream_t s = ctx->stream;
   PH_HIP(ph::launch_set_int(ctx->stop_flag, 0, s));
-  ph::AdvStatArgs aa;
-  aa.rb_adv = rb->advantages;
-  aa.T = rb->T;
-  aa.E = rb->E;
-  aa.perms = indices;
-  aa.perm_n = 0;
-  aa.perm_hb = 1;
-  aa.perm_seed = 0;
-  aa.epoch = nullptr;
-  aa.N = nb;
-  aa.batch = nb;
-  aa.n_mb = 1;
-  aa.out = ctx->advstats;
-  aa.partial = ctx->advpart;
-  aa.idx_out = nullptr;
-  aa.phys_out = nullptr;
+  ph::AdvStatArgs aa = adv_args_minibatch(ctx, rb, indices, nb);
+  aa.phys_out = nullptr;   // the towers gather their rows through the env-major indices
   PH_HIP(ph::launch_adv_stats(aa, 1, s));
   PH_HIP(hipMemsetAsync(grad_out, 0, (size_t)P_total * sizeof(float), s));
-  ModMinibatch mb;
-  mb.rb = rb;
-  mb.idx = indices;
-  mb.nb = nb;
-  mb.advstats = ctx->advstats;
-  mb.k_mod = mod->module_of[partner_idx];
-  mb.reg_coef = marginal_reg_coef;
-  mb.stats_out = stats_out;
+  const ModMinibatch mb{rb, indices, nb, ctx->advstats, mod->module_of[partner_idx], marginal_reg_coef, stats_out};
   if (mod_minibatch(ctx, spec, mod, nd, ml, params, hp, mb, grad_out, gemm_mode)) return 1;
   if (stats_out) {   // statistics without touching any optimizer state: a scratch step counter / first-use table
     PH_HIP(hipMemsetAsync(ctx->mw.scratch, 0, (2 + PH_MOD_MAX) * sizeof(int), s));
-    ph::ModFinalizeArgs fa;
-    std::memset(&fa, 0, sizeof(fa));
-    fa.statpart = ctx->statpart;
-    fa.nstatpart = (nb + 255) / 256;
-    fa.nb = nb;
-    fa.step = ctx->mw.scratch;
-    fa.mod_first = ctx->mw.scratch + 1;
-    fa.k_mod = 0;
-    fa.kl_sum = ctx->mw.kl_sum;
-    fa.stats_out = stats_out;
-    fa.ent_coef = hp->ent_coef;
-    fa.vf_coef = hp->vf_coef;
-    fa.reg_coef = marginal_reg_coef;
-    fa.stop_flag = ctx->stop_flag;
-    PH_HIP(ph::launch_modular_finalize(fa, s));
+    if (mod_finalize(ctx, hp, nb, ctx->mw.scratch, ctx->mw.scratch + 1, 0, stats_out, marginal_reg_coef)) return 1;
   }
   return 0;
 }
@@ -3139,12 +2914,9 @@ int ph_modular_train(ph_ctx* ctx, const ph_spec* spec, const ph_modular* mod, co
                      const ph_rollout* rbs, const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms,
                      unsigned long long perm_seed, float* stats, float marginal_reg_coef, int gemm_mode) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!opt || !opt->params || !opt->adam_m || !opt->adam_v || !opt->step || !mod_first)
-    return fail("ph_modular_train: null optimizer state");
-  if ((uintptr_t)opt->params % 16 != 0) return fail("ph_modular_train: params must be 16-byte aligned");
-  if (!hp || !rbs) return fail("ph_modular_train: null argument");
-  if (n_epochs <= 0 || batch_size <= 0) return fail("ph_modular_train: n_epochs and batch_size must be positive");
+  if (check_train_call("ph_modular_train", ctx, opt, hp, n_epochs, batch_size)) return 1;
+  if (!mod_first) return fail("ph_modular_train: null optimizer state");
+  if (!rbs) return fail("ph_modular_train: null argument");
   ph::NetDims nd;
   if (resolve(ctx, spec, &nd)) return 1;
   if (check_modular(mod, nd, "ph_modular_train")) return 1;
@@ -3165,59 +2937,24 @@ int ph_modular_train(ph_ctx* ctx, const ph_spec* spec, const ph_modular* mod, co
     if (mod_buffers(ctx, nb_max, M, &probe)) return 1;
   }
   hipStream_t s = ctx->stream;
-  const uint32_t hb = ph::feistel_half_bits((uint32_t)N);
   for (int k = 0; k < mod->num_partners; ++k) {
     const ph_rollout* rb = &rbs[k];
     const int k_mod = mod->module_of[k];
     PH_HIP(ph::launch_set_int(ctx->stop_flag, 0, s));
     PH_HIP(hipMemsetAsync(ctx->mw.kl_sum, 0, sizeof(float), s));
     const int* perms_k = perms ? perms + (size_t)k * n_epochs * N : nullptr;
-    ph::AdvStatArgs aa;
-    aa.rb_adv = rb->advantages;
-    aa.T = rb->T;
-    aa.E = rb->E;
-    aa.perms = perms_k;
-    aa.perm_n = (uint32_t)N;
-    aa.perm_hb = hb;
-    aa.perm_seed = perm_seed + (unsigned long long)k * 0x9E3779B97F4A7C15ull;
-    aa.epoch = ctx->rng_epoch;
-    aa.N = N;
-    aa.batch = batch_size;
-    aa.n_mb = n_mb;
-    aa.out = ctx->advstats;
-    aa.partial = ctx->advpart;
-    aa.idx_out = perms_k ? nullptr : ctx->perm_idx;
-    aa.phys_out = nullptr;
+    const unsigned long long seed_k = perm_seed + (unsigned long long)k * 0x9E3779B97F4A7C15ull;   // an order per partner
+    ph::AdvStatArgs aa = adv_args_epochs(ctx, rb, perms_k, seed_k, batch_size, n_mb);
+    aa.phys_out = nullptr;   // the towers gather their rows through the env-major indices
     PH_HIP(ph::launch_adv_stats(aa, n_epochs * n_mb, s));
     for (int ep = 0; ep < n_epochs; ++ep) {
       for (int j = 0; j < n_mb; ++j) {
-        const int mbi = ep * n_mb + j, start = j * batch_size;
-        const int nb = (N - start < batch_size) ? N - start : batch_size;
+        const int mbi = ep * n_mb + j;
+        const MbWalk w = minibatch_walk(ctx, perms_k, N, n_mb, batch_size, mbi);
         float* st = stats ? stats + ((size_t)k * n_epochs * n_mb + mbi) * PH_NSTAT : nullptr;
-        ModMinibatch mb;
-        mb.rb = rb;
-        mb.idx = (perms_k ? perms_k : ctx->perm_idx) + (size_t)ep * N + start;
-        mb.nb = nb;
-        mb.advstats = ctx->advstats + 2 * (size_t)mbi;
-        mb.k_mod = k_mod;
-        mb.reg_coef = marginal_reg_coef;
-        mb.stats_out = st;
+        const ModMinibatch mb{rb, w.idx, w.nb, ctx->advstats + 2 * (size_t)mbi, k_mod, marginal_reg_coef, st};
         if (mod_minibatch(ctx, spec, mod, nd, ml, opt->params, hp, mb, ctx->grad, gemm_mode)) return 1;
-        ph::ModFinalizeArgs fa;
-        std::memset(&fa, 0, sizeof(fa));
-        fa.statpart = ctx->statpart;
-        fa.nstatpart = (nb + 255) / 256;
-        fa.nb = nb;
-        fa.step = opt->step;
-        fa.mod_first = mod_first;
-        fa.k_mod = k_mod;
-        fa.kl_sum = ctx->mw.kl_sum;
-        fa.stats_out = st;
-        fa.ent_coef = hp->ent_coef;
-        fa.vf_coef = hp->vf_coef;
-        fa.reg_coef = marginal_reg_coef;
-        fa.stop_flag = ctx->stop_flag;
-        PH_HIP(ph::launch_modular_finalize(fa, s));
+        if (mod_finalize(ctx, hp, w.nb, opt->step, mod_first, k_mod, st, marginal_reg_coef)) return 1;
         ph::ModAdamArgs ad;
         std::memset(&ad, 0, sizeof(ad));
         ad.params = opt->params;
