@@ -303,8 +303,7 @@ int ph_policy_forward(ph_ctx *ctx, const ph_spec *spec, const float *params, con
  * actions are bitwise those of ph_policy_forward with the same (seed, counter).  A launch of one 16-row tile (n <= 16, the
  * 16-row forward's shape class) signals its end through two words in the same pinned memory, stored by the policy and the value
  * workgroup after their last output, and the call polls those (bounded: 50 ms, then the stream wait) instead of synchronising
- * the stream; PH_ACT_HOST_WAIT=stream in the environment selects the stream wait for every launch.  Either way every write of the
- * launch, the rollout-buffer row included, is complete when the call returns.
+ * the stream.  Either way every write of the launch, the rollout-buffer row included, is complete when the call returns.
  *   obs_host (n, D) f32; episode_start_host (n) f32 or NULL (required with rb); actions_host (n, A) i32; values_host (n);
  *   log_probs_host (n) -- any output may be NULL. */
 int ph_policy_act_host(ph_ctx *ctx, const ph_spec *spec, const float *params, const float *obs_host, int n,
@@ -702,8 +701,7 @@ int ph_adapmult_train(ph_ctx *ctx, const ph_spec *spec, int context_size, const 
  * times between two HIP events on the ctx stream; *avg_ms_out = mean launch duration.  Launch i takes minibatch
  * i mod ceil(T*E / batch) of one in-kernel permutation of the buffer (size min(batch_size, T*E)), as the launches of an epoch do:
  * consecutive launches read DIFFERENT rows, so the figure does not flatter the kernel with rows the previous launch left in
- * the L2 (with PH_BENCH_GRAD_SAME_ROWS=1 every launch repeats the first minibatch -- the round-1..3 behaviour).
- * Optimizer state is not touched.  Synchronises. */
+ * the L2.  Optimizer state is not touched.  Synchronises. */
 int ph_bench_ppo_grad(ph_ctx *ctx, const ph_spec *spec, const float *params, const ph_rollout *rb,
                       const ph_ppo_hyper *hyper /* host */, int batch_size, int reps, int gemm_mode,
                       float *avg_ms_out /* host */);

@@ -4,15 +4,69 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "ph_launch.h"
+
+namespace ph {
+
+namespace {
+// (kernel, device) pairs granted more than 64 KiB of dynamic LDS: a list that only grows at its head, under the mutex; readers walk
+// it without the lock (a node's kernel and device never change, its grant only grows)
+struct LdsGrant {
+  const void* kernel;
+  int device;
+  std::atomic<size_t> bytes;
+  LdsGrant* next;
+};
+std::atomic<LdsGrant*> lds_grants{nullptr};
+std::mutex lds_grant_mutex;
+
+LdsGrant* find_lds_grant(const void* kernel, int device) {
+  for (LdsGrant* g = lds_grants.load(std::memory_order_acquire); g; g = g->next)
+    if (g->kernel == kernel && g->device == device) return g;
+  return nullptr;
+}
+}  // namespace
+
+hipError_t allow_dynamic_lds(const void* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return hipSuccess;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  LdsGrant* g = find_lds_grant(kernel, dev);
+  if (g && g->bytes.load(std::memory_order_acquire) >= bytes) return hipSuccess;
+  std::lock_guard<std::mutex> lock(lds_grant_mutex);
+  if (!g && !(g = find_lds_grant(kernel, dev))) {
+    g = new LdsGrant{kernel, dev, {0}, lds_grants.load(std::memory_order_relaxed)};
+    lds_grants.store(g, std::memory_order_release);
+  }
+  if (g->bytes.load(std::memory_order_relaxed) >= bytes) return hipSuccess;   // granted by another caller meanwhile
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) g->bytes.store(bytes, std::memory_order_release);
+  return e;
+}
+
+int device_cu_count() {
+  static std::atomic<int> cached[64];   // per device index; 0 = not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  const bool slot = dev >= 0 && dev < 64;
+  int cu = slot ? cached[dev].load(std::memory_order_relaxed) : 0;
+  if (cu > 0) return cu;
+  if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) return 0;
+  if (slot) cached[dev].store(cu, std::memory_order_relaxed);
+  return cu;
+}
+
+}  // namespace ph
 
 namespace {
 
@@ -1022,17 +1076,6 @@ int ph_policy_forward(ph_ctx* ctx, const ph_spec* spec, const float* params, con
   return 0;
 }
 
-// How ph_policy_act_host waits for a one-tile launch: 1 = on the launch's two completion words in host memory, 0 = on the stream.
-// PH_ACT_HOST_WAIT=stream selects the latter (the A/B switch of the measurement in DESIGN.md section 3.1).
-static bool act_host_waits_on_words() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("PH_ACT_HOST_WAIT");
-    v = (e && std::strcmp(e, "stream") == 0) ? 0 : 1;
-  }
-  return v == 1;
-}
-
 int ph_policy_act_host(ph_ctx* ctx, const ph_spec* spec, const float* params, const float* obs_host, int n,
                        const float* episode_start_host, unsigned long long seed, unsigned long long counter, int deterministic,
                        int* actions_host, float* values_host, float* log_probs_host, const ph_rollout* rb, int pos, int gemm_mode) {
@@ -1066,7 +1109,7 @@ int ph_policy_act_host(ph_ctx* ctx, const ph_spec* spec, const float* params, co
   float *d_val = d_out + (size_t)n * nd.A, *d_lp = d_val + n;
   // One tile of the 16-row forward = one policy and one value workgroup: each stores the launch's sequence number into its word
   // after its last output, and the host polls the two words (the outputs are in the same coherent memory, ordered before them).
-  const bool words = act_host_waits_on_words() && n <= 16 && ph::fwd16_eligible(nd, n);
+  const bool words = n <= 16 && ph::fwd16_eligible(nd, n);
   if (words && !ctx->act_done_host) {
     PH_HIP(hipHostMalloc((void**)&ctx->act_done_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
     PH_HIP(hipHostGetDevicePointer((void**)&ctx->act_done_dev, ctx->act_done_host, 0));
@@ -1390,7 +1433,7 @@ int ph_selfplay_rollout_p2p(ph_ctx* ctx, int n_calls, const ph_step_call* calls,
   DevGuard dev_guard(ctx);
   if (!ctx || !calls || !local || T <= 0) return fail("ph_selfplay_rollout_p2p: bad argument");
   if (check_p2p(x)) return 1;
-  bool fused = x->count == n_calls * calls[0].n && getenv("PH_P2P_UNFUSED") == nullptr;
+  bool fused = x->count == n_calls * calls[0].n;
   for (int i = 0; i < n_calls && fused; ++i) {
     ph::NetDims nd;
     if (resolve(ctx, calls[i].spec, &nd)) return 1;
@@ -1840,14 +1883,9 @@ int ensure_train_ws(ph_ctx* ctx, int P, int slab_len, int nwg_max, int n_mb_tota
   return 0;
 }
 
-// reduce + clip + Adam of an exclusive learner's minibatch as ONE launch?  (PH_STEP_FUSED=0 keeps the two launches)
+// reduce + clip + Adam of an exclusive learner's minibatch as ONE launch?
 bool step_fused_wanted(const ph_ctx* ctx, int slab_len, bool alone) {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("PH_STEP_FUSED");
-    enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  return enabled && alone && ctx->exclusive && ctx->step_words && ctx->step_gen &&
+  return alone && ctx->exclusive && ctx->step_words && ctx->step_gen &&
          ph::step_fused_fits(ph::reduce_blocks(slab_len), slab_len, ctx->num_cu);
 }
 
@@ -2033,14 +2071,7 @@ int train_launch_step(const TrainPlan& t, int mbi, const MbPlan& pl) {
     const MbWalk w = minibatch_walk(ctx, t.perms, t.N, t.n_mb, t.batch_size, mbi);
     if (adap_launch(ctx, t.nd, t.opt->params, t.rb, t.adap, w.idx, w.nb, mbi, &r)) return 1;
   }
-  const bool fused = step_fused_wanted(ctx, slab_len_of(t.nd), t.alone != 0);
-#ifdef PH_EXPERIMENT_SKIP_STEP   // TIMING EXPERIMENTS ONLY (never in the default build; scripts/build_variants.sh): what the gradient launches
-  (void)fused;                   // of two learners cost each other WITHOUT the other learner's reduce / Adam kernels beside them
-  if (PH_EXPERIMENT_SKIP_STEP == 1) return 0;                                        // 1: neither kernel
-  if (PH_EXPERIMENT_SKIP_STEP == 2) { PH_HIP(ph::launch_ppo_reduce(r, s)); return 0; }   // 2: the reduction only
-  if (PH_EXPERIMENT_SKIP_STEP == 3) { PH_HIP(ph::launch_ppo_adam(ad, s)); return 0; }    // 3: clip + Adam only (on a stale gradient)
-#endif                           // (profiles/r06_bn_*)
-  if (fused) {
+  if (step_fused_wanted(ctx, slab_len_of(t.nd), t.alone != 0)) {
     PH_HIP(ph::launch_ppo_step(r, ad, ctx->step_words, ctx->step_gen, ctx->step_gen + 1, STEP_WAIT_TICKS, s));
   } else {
     PH_HIP(ph::launch_ppo_reduce(r, s));
@@ -2426,8 +2457,7 @@ int ph_bench_ppo_grad(ph_ctx* ctx, const ph_spec* spec, const float* params, con
   const int N = rb->T * rb->E;
   const int nb = batch_size < N ? batch_size : N;
   const MbPlan pl = plan_minibatch(ctx, nd, nb);
-  const char* same_env = getenv("PH_BENCH_GRAD_SAME_ROWS");
-  const int n_mb = (same_env && same_env[0] == '1') ? 1 : N / nb;   // whole minibatches of one epoch's order
+  const int n_mb = N / nb;   // whole minibatches of one epoch's order
   if (ensure_train_ws(ctx, nd.lay.P, slab_len_of(nd), pl.nwg, n_mb, (size_t)N, (size_t)N)) return 1;
   hipStream_t s = ctx->stream;
   PH_HIP(ph::launch_set_int(ctx->stop_flag, 0, s));

@@ -506,14 +506,7 @@ __global__ __launch_bounds__(256) void adap_context_kernel(AdapArgs a) {
 
 hipError_t launch_adap_context(const AdapArgs& a, int nwg, hipStream_t s) {
   const size_t lds = adap_lds_bytes(a.nd, a.n_ctx, a.ctx_size);
-  static bool opted[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (lds > 48 * 1024 && dev >= 0 && dev < 64 && !opted[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)adap_context_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    opted[dev] = true;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)adap_context_kernel, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(adap_context_kernel, dim3(nwg), dim3(256), lds, s, a);
   return hipGetLastError();
 }

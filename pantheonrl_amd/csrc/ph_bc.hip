@@ -801,9 +801,6 @@ hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* pa
   a.ent_weight = hp.ent_weight;
   a.l2_weight = hp.l2_weight;
   a.stats = stats;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = (dev >= 0 && dev < 64) ? dev : 0;
   static int use_mfma = -1;
   if (use_mfma < 0) {
     const char* e = getenv("PH_BC_MFMA");
@@ -813,24 +810,14 @@ hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* pa
       bc_mfma_lds_bytes(nd.F, nd.L, lay.P, nd.A, false) <= 160 * 1024) {
     const bool moments = bc_mfma_lds_bytes(nd.F, nd.L, lay.P, nd.A, true) <= 160 * 1024;
     const size_t lds = bc_mfma_lds_bytes(nd.F, nd.L, lay.P, nd.A, moments);
-    static size_t allowed_m[2][64] = {{0}};
-    if (lds > allowed_m[moments][dev]) {
-      hipError_t e = moments ? hipFuncSetAttribute((const void*)bc_train_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                             : hipFuncSetAttribute((const void*)bc_train_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      allowed_m[moments][dev] = lds;
-    }
+    const void* fn = moments ? (const void*)bc_train_mfma_kernel<true> : (const void*)bc_train_mfma_kernel<false>;
+    if (const hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
     if (moments) hipLaunchKernelGGL(bc_train_mfma_kernel<true>, dim3(1), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(bc_train_mfma_kernel<false>, dim3(1), dim3(256), lds, s, a);
     return hipGetLastError();
   }
   const size_t lds = bc_train_lds_bytes(nd.F, nd.L, lay.P, nd.A);
-  static size_t allowed[64] = {0};
-  if (lds > allowed[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)bc_train_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed[dev] = lds;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)bc_train_kernel, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(bc_train_kernel, dim3(1), dim3(256), lds, s, a);
   return hipGetLastError();
 }
@@ -971,15 +958,7 @@ hipError_t launch_bc_forward(const NetDims& nd, const ph_bc_layout& lay, const f
   a.entropy = entropy;
   a.logits = logits;
   const size_t lds = sizeof(float) * ((((size_t)lay.P + 3) & ~(size_t)3) + 64 * (size_t)PH_MAX_LOGITS);
-  static size_t allowed[64] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = (dev >= 0 && dev < 64) ? dev : 0;
-  if (lds > allowed[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)bc_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed[dev] = lds;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)bc_forward_kernel, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(bc_forward_kernel, dim3((n + 63) / 64), dim3(64), lds, s, a);
   return hipGetLastError();
 }

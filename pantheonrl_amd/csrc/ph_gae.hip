@@ -63,15 +63,10 @@ __global__ __launch_bounds__(64) void gae_serial_kernel(const float* __restrict_
 // coefficient products in registers, the NCH chunk composites are suffix-scanned through LDS (Hillis-Steele,
 // log2 NCH rounds), each lane fixes up its LC outputs with the carried-in advantage, and the advantage at the first
 // step of the super-chunk is carried to the next one.  One HBM read + one write per element, any T.
-#ifndef PH_GAE_NT
-#define PH_GAE_NT 1   // streaming (nontemporal) loads and stores of the five arrays -- every element is read once and written once:
-                      // 4.40 -> 4.64 TB/s at E = 16384, T = 2048 (profiles/r06_w_gae_nontemporal_and_chunk_sweep.txt); 0 = plain accesses
-#endif
-__device__ __forceinline__ float gae_ld(const float* p) { return PH_GAE_NT ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ void gae_st(float* p, float v) {
-  if (PH_GAE_NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
+// Streaming (nontemporal) loads and stores of the five arrays -- every element is read once and written once: 4.40 -> 4.64 TB/s at
+// E = 16384, T = 2048 (profiles/r06_w_gae_nontemporal_and_chunk_sweep.txt).
+__device__ __forceinline__ float gae_ld(const float* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void gae_st(float* p, float v) { __builtin_nontemporal_store(v, p); }
 
 template <int LC, int EB>
 __global__ __launch_bounds__(1024) void gae_scan_kernel(const float* __restrict__ rew, const float* __restrict__ val,
@@ -225,14 +220,7 @@ hipError_t launch_gae(const float* rew, const float* val, const float* es, const
   // one contiguous piece) and sixteen chunks: 5.07-5.16 -> 5.33-5.36 TB/s at E = 16384, T = 2048 (profiles/r06_ae_gae_*).  Below that
   // the grid of 64-environment workgroups no longer covers the CUs.  128 environments: 4.4 TB/s; requesting the next super-chunk's
   // elements ahead of the scan (a second register set): SLOWER, 4.6 against 4.9-5.4 (profiles/r06_ad_gae_explicit_prefetch_ab.txt).
-  static int eb_env = -1;   // PH_GAE_EB = 32 | 64 | 128: measurement override of the environments per workgroup
-  if (eb_env < 0) {
-    const char* e = getenv("PH_GAE_EB");
-    eb_env = e ? atoi(e) : 0;
-  }
-  const int eb = eb_env ? eb_env : (E >= 16384 ? 64 : 32);
-  if (eb == 64) return launch_scan<16, 64>(rew, val, es, lv, dn, adv, ret, T, E, g, gl, s, 16);
-  if (eb == 128) return launch_scan<16, 128>(rew, val, es, lv, dn, adv, ret, T, E, g, gl, s, 8);
+  if (E >= 16384) return launch_scan<16, 64>(rew, val, es, lv, dn, adv, ret, T, E, g, gl, s, 16);
   return launch_scan<16, 32>(rew, val, es, lv, dn, adv, ret, T, E, g, gl, s, 8);
 }
 

@@ -33,6 +33,13 @@ __device__ __forceinline__ void poll_backoff(int& polls) {
   ++polls;
 }
 
+// Dynamic LDS above 64 KiB is opt-in per kernel and device: grants `bytes` to `kernel` (the instantiation about to be launched) on
+// the current device unless at least that much was granted before, and returns the runtime's answer.  Safe under concurrent callers;
+// a call with nothing to do takes no lock and allocates nothing.
+hipError_t allow_dynamic_lds(const void* kernel, size_t bytes);
+// compute units of the current device (asked once per device), 0 if the runtime cannot say
+int device_cu_count();
+
 // NOTE for new fields: liar_rollout_kernel (ph_policy.hip) rebuilds its three records from {nd, n} plus the fields
 // launch_liar_rollout lists as patched, and the launcher refuses records whose other bytes are not zero -- a field added here must
 // either stay zero on that path or join both lists.
@@ -203,15 +210,9 @@ __device__ __forceinline__ int minibatch_row(const GradArgs& a, int gi) {
   return env_major_to_phys(n, a.T, a.E);
 }
 
-#ifndef PH_ADV_SPLIT
-#define PH_ADV_SPLIT 32
-#endif
-#ifndef PH_ADV_THREADS
-#define PH_ADV_THREADS 256
-#endif
-constexpr int ADV_SPLIT = PH_ADV_SPLIT;      // workgroups per minibatch in the advantage-statistics pass (32 x 256 lanes: 1 280 workgroups
-                                             // at the bench size spread evenly over the CUs; 8 x 1024 left a quarter of them with two: 21.3 -> 17.4 us)
-constexpr int ADV_THREADS = PH_ADV_THREADS;  // lanes of one of them
+constexpr int ADV_SPLIT = 32;     // workgroups per minibatch in the advantage-statistics pass (32 x 256 lanes: 1 280 workgroups
+                                  // at the bench size spread evenly over the CUs; 8 x 1024 left a quarter of them with two: 21.3 -> 17.4 us)
+constexpr int ADV_THREADS = 256;  // lanes of one of them
 struct AdvStatArgs {
   const float* rb_adv;
   int T, E;

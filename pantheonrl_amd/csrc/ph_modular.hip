@@ -395,15 +395,7 @@ size_t tower_lds_bytes() { return sizeof(float) * (size_t)(4 * 64 * LDH + HW_FLO
 template <bool VALU, bool BWD>
 static hipError_t launch_tower_inst(const TowerLaunch& L, int nwg, int n_towers, hipStream_t s) {
   const size_t lds = tower_lds_bytes();
-  static bool allowed[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = (dev >= 0 && dev < 64) ? dev : 0;
-  if (!allowed[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)tower_kernel<VALU, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed[dev] = true;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)tower_kernel<VALU, BWD>, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((tower_kernel<VALU, BWD>), dim3(nwg, n_towers), dim3(256), lds, s, L);
   return hipGetLastError();
 }

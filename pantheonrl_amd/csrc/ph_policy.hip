@@ -326,12 +326,7 @@ bool fwd_args_lean(const FwdArgs& a, bool joint_ok = false) {
          a.rb_es && a.rb_val && a.rb_logp && a.es_in;
 }
 
-// The head product of the 16-row forward split over the four waves' K quarters (1) or as one sixteen-MFMA chain in wave 0 (0: the
-// form up to round 6's third session; A/B switch, scripts/build_variants.sh)
-#ifndef PH_FWD16_HEAD_KSPLIT
-#define PH_FWD16_HEAD_KSPLIT 1
-#endif
-constexpr int ZS_FLOATS = (PH_FWD16_HEAD_KSPLIT ? 4 : 1) * 16 * 8;   // the head's output tile(s) in LDS
+constexpr int ZS_FLOATS = 4 * 16 * 8;   // the head's four partial output tiles in LDS (one per wave)
 
 template <bool VALU, int LEAN = 0>
 __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2p* px = nullptr, int px_t = 0, int px_a_local = 0,
@@ -385,15 +380,10 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
 #define pxslots (PXH ? pxslots_h : px->ll_slots)
 #define ll_self (PXH ? ll_self_h : px->ll[px->rank])
 #define PXLL(p) (PXH ? pxll[p] : px->ll[p])
-  // B operands: element [g + 4s][this lane's column] of W1 and W2; of the head, the K quarter of this wave (PH_FWD16_HEAD_KSPLIT):
-  // units 16 wave + g + 4j, j < 4 -- the head product is then four MFMAs in every wave instead of sixteen in wave 0 with three
-  // waves waiting, its partial tiles meet in LDS (zs) and are added in ONE fixed order by the row's lane
-#if PH_FWD16_HEAD_KSPLIT
-  constexpr int NBH = 4;
-#else
-  constexpr int NBH = 16;
-#endif
-  float bw1[16], bw2[16], bwh[NBH];
+  // B operands: element [g + 4s][this lane's column] of W1 and W2; of the head, the K quarter of this wave: units 16 wave + g + 4j,
+  // j < 4 -- the head product is then four MFMAs in every wave instead of sixteen in wave 0 with three waves waiting, its partial
+  // tiles meet in LDS (zs) and are added in ONE fixed order by the row's lane
+  float bw1[16], bw2[16], bwh[4];
   const int col = 16 * wave + c;
 #pragma unroll
   for (int s = 0; s < 16; ++s) {
@@ -402,15 +392,13 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
     bw2[s] = W2[k * HID + col];
   }
 #pragma unroll
-  for (int s = 0; s < NBH; ++s) {
-    const int k = g + 4 * (PH_FWD16_HEAD_KSPLIT ? 4 * wave + s : s);
+  for (int s = 0; s < 4; ++s) {
+    const int k = g + 4 * (4 * wave + s);
     bwh[s] = 0.f;
-    if (PH_FWD16_HEAD_KSPLIT || wave == 0) {
-      if (net == 0) {
-        if (c < nk) bwh[s] = a.params[lay.act_W + k * nk + c];
-      } else if (c == 0) {
-        bwh[s] = a.params[lay.val_W + k];
-      }
+    if (net == 0) {
+      if (c < nk) bwh[s] = a.params[lay.act_W + k * nk + c];
+    } else if (c == 0) {
+      bwh[s] = a.params[lay.val_W + k];
     }
   }
   const float bias1 = B1[col], bias2 = B2[col];
@@ -460,9 +448,7 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
     // all sixteen operand reads in flight before the first MFMA: left alone, the scheduler sinks each ds_read2 in front of the two
     // MFMAs that use it and recycles ONE register pair -- read, wait, two MFMAs, eight times per product: eight exposed LDS round
     // trips per layer of a step whose whole point is latency (round 6: one-launch rollout 0.333 -> 0.307 ms, profiles/r06_ah_*)
-#ifndef PH_FWD16_NO_HOIST   // (A/B switch: scripts/build_variants.sh)
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int s = 0; s < 16; s += 2) {
       e = mma16<VALU>(av[s], bw[s], e, lane);
@@ -498,9 +484,7 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
       a.ll_t = t - 1;
     }
     a.prof = nullptr;
-#if !PH_FWD16_HEAD_KSPLIT
-    lds_only_barrier();   // the previous step's head is done with xs (H2)
-#endif                    // (K-split head: every wave read its part of H2 before the head phase's own barrier)
+    // (no barrier before xs is overwritten: every wave read its part of H2 before the head phase's own barrier)
     xr.issue(rowphys, a.obs, nd, 0);
     xr.commit(xs, rowphys, a.obs, nd, 0);
     vm_drain();   // the rows are in (the commit waited for them): say so, or the observation copy at the end of the step waits
@@ -534,7 +518,6 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   PH_STAMP(pstep, 11);
 
   // ---- head: a third product (columns = logits, or the value in column 0) ----
-#if PH_FWD16_HEAD_KSPLIT
   {   // every wave: its K quarter (four MFMAs, two chains), the partial tile to zs[wave]; wave 0's partial carries the bias
     if (wave == 0 && pre_ok) value_row_preload_words(a, row0 + lane, vpre);   // (exchange rollouts: the joint action's words, under the product)
     const float* ap = xs + c * LDH + g + 16 * wave;
@@ -576,25 +559,6 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
         }
       }
       if (net == 0) {
-#else
-  if (wave == 0) {
-    if (pre_ok) value_row_preload_words(a, row0 + lane, vpre);   // (exchange rollouts: the joint action's words, under the head product)
-    const f32x4 zh = product(xs, bwh);
-    PH_STAMP(pstep, 12);
-    if (c < 8) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) zs[(4 * g + r) * 8 + c] = zh[r] + hbias;
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // zs is written and read by this wave only
-    __builtin_amdgcn_wave_barrier();
-    PH_STAMP(pstep, 13);
-    const int r = lane, grow = row0 + lane;   // lane r < 16 owns row r
-    if (r < R && grow < a.n) {
-      if (net == 0) {
-        const float4 z0 = *reinterpret_cast<const float4*>(zs + r * 8), z1 = *reinterpret_cast<const float4*>(zs + r * 8 + 4);
-        float z[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
-#endif
         const float* up = draw_ahead ? upre + (t & 1) * R + r : nullptr;
         const uint64_t ctr = fwd_counter(a);
         int act;
@@ -618,12 +582,7 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
             __hip_atomic_store(PXLL(p) + off, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       } else {
-#if PH_FWD16_HEAD_KSPLIT
-        const float v = z[0];
-#else
-        const float v = zs[r * 8];
-#endif
-        value_row_tail(a, grow, v, pre_ok, vpre);
+        value_row_tail(a, grow, z[0], pre_ok, vpre);
         // (scripted rollout) the last step's own reward: the flush that precedes GAE on the launch-by-launch path
         if (sc && t == n_steps - 1) {
           float add = sc->rew_seq[(size_t)t * a0.n + grow];
@@ -706,13 +665,6 @@ __global__ __launch_bounds__(256, 3) void policy_fwd16_exchange_rollout_kernel(F
   policy_fwd16_body<false, LEAN ? 2 : 0>(m.a[blockIdx.z], m.px.x, 0, m.px.a_local, blockIdx.z, &sm.sc[blockIdx.z], 1);
 }
 
-// index of the current device into the per-device "LDS opt-in done" tables of the launchers below
-static int current_device_slot() {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  return (dev >= 0 && dev < 64) ? dev : 0;
-}
-
 static size_t fwd16_lds_bytes() { return sizeof(float) * (size_t)(2 * 16 * LDH + ZS_FLOATS + 16 + 32) + sizeof(void*) * PH_MAX_RANKS; }
 
 bool fwd16_eligible(const NetDims& nd, int n) {
@@ -726,17 +678,12 @@ bool fwd16_eligible(const NetDims& nd, int n) {
 
 template <bool VALU>
 static hipError_t launch_fwd16_variant(const FwdArgs& a, hipStream_t s) {
-  static bool allowed_dev[64] = {false};  // dynamic LDS above 64 KiB is opt-in, per kernel and device
   const size_t lds = fwd16_lds_bytes();
-  bool& allowed = allowed_dev[current_device_slot()];
-  if (!allowed && lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)policy_fwd16_kernel<VALU>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-    allowed = true;
-  }
-  if (!VALU && fwd_args_lean(a)) hipLaunchKernelGGL((policy_fwd16_kernel<false, true>), dim3((a.n + 15) / 16, 2), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((policy_fwd16_kernel<VALU>), dim3((a.n + 15) / 16, 2), dim3(256), lds, s, a);
+  const bool general = VALU || !fwd_args_lean(a);
+  const void* fn = general ? (const void*)policy_fwd16_kernel<VALU> : (const void*)policy_fwd16_kernel<false, true>;
+  if (const hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
+  if (general) hipLaunchKernelGGL((policy_fwd16_kernel<VALU>), dim3((a.n + 15) / 16, 2), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((policy_fwd16_kernel<false, true>), dim3((a.n + 15) / 16, 2), dim3(256), lds, s, a);
   return hipGetLastError();
 }
 
@@ -744,23 +691,11 @@ static hipError_t launch_fwd16_variant(const FwdArgs& a, hipStream_t s) {
 // the chip: when two learners' rollouts run side by side the dispatcher is free to put a workgroup of each on the SAME CU while
 // other CUs stay empty, and the two chains then share SIMDs for the whole launch (measured: 390 us alone, 440-470 us side by side).
 // Asking for more than half a CU's LDS makes a CU take ONE rollout workgroup, whoever launched it (same-box A/B 107.6 -> 109.7 M
-// agent-steps/s, profiles/r04_g_ab_hoist_spread.txt; PH_ROLLOUT_SPREAD=0 switches it off; only
-// for launches of at most #CUs / 2 workgroups, so that two of them still fit on the chip at once).
+// agent-steps/s, profiles/r04_g_ab_hoist_spread.txt; only for launches of at most #CUs / 2 workgroups, so that two of them still
+// fit on the chip at once).
 static size_t rollout_lds_bytes(int nwg_total) {
-  static int spread = -1, num_cu[64] = {0};
-  if (spread < 0) {
-    const char* e = getenv("PH_ROLLOUT_SPREAD");
-    spread = (e && e[0] == '0') ? 0 : 1;
-  }
-  const size_t lds = fwd16_lds_bytes();
-  if (!spread) return lds;
-  int& cu = num_cu[current_device_slot()];
-  if (cu == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = -1;
-  }
-  return (cu > 0 && 2 * nwg_total <= cu) ? (size_t)81 * 1024 + 512 : lds;
+  const int cu = device_cu_count();
+  return (cu > 0 && 2 * nwg_total <= cu) ? (size_t)81 * 1024 + 512 : fwd16_lds_bytes();
 }
 hipError_t launch_policy_fwd16_rollout(const FwdArgs& a, const ScriptedSteps& sc, int gemm_mode, hipStream_t s) {
   dim3 grid((a.n + 15) / 16, 2), block(256);
@@ -768,15 +703,7 @@ hipError_t launch_policy_fwd16_rollout(const FwdArgs& a, const ScriptedSteps& sc
   const int variant = gemm_mode == 1 ? 1 : ((fwd_args_lean(a) && !sc.mask_seq) ? 2 : 0);   // 1: VALU cross-check, 2: lean, 0: general
   const void* fn = variant == 1 ? (const void*)policy_fwd16_rollout_kernel<true, false>
                                 : (variant == 2 ? (const void*)policy_fwd16_rollout_kernel<false, true> : (const void*)policy_fwd16_rollout_kernel<false, false>);
-  if (lds > 64 * 1024) {   // dynamic LDS above 64 KiB is opt-in, per kernel and device
-    static bool allowed_dev[3][64] = {{false}};
-    bool& allowed = allowed_dev[variant][current_device_slot()];
-    if (!allowed) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      allowed = true;
-    }
-  }
+  if (const hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
   if (variant == 1) hipLaunchKernelGGL((policy_fwd16_rollout_kernel<true, false>), grid, block, lds, s, a, sc);
   else if (variant == 2) hipLaunchKernelGGL((policy_fwd16_rollout_kernel<false, true>), grid, block, lds, s, a, sc);
   else hipLaunchKernelGGL((policy_fwd16_rollout_kernel<false, false>), grid, block, lds, s, a, sc);
@@ -786,7 +713,7 @@ hipError_t launch_policy_fwd16_rollout(const FwdArgs& a, const ScriptedSteps& sc
 hipError_t exchange_rollout_blocks_per_cu(int* blocks_out) {
   const size_t lds = fwd16_lds_bytes();
   int api = 0;
-  // (the general form: the lean form of the same kernel needs no more registers)
+  // (the general form: the lean form of the same kernel needs no more registers -- tests/test_kernel_resources.py)
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&api, (const void*)policy_fwd16_exchange_rollout_kernel<false>, 256, lds);
   if (e != hipSuccess) return e;
   const int by_lds = (int)((size_t)160 * 1024 / lds);
@@ -1800,39 +1727,25 @@ hipError_t launch_liar_rollout(const ph_liar_selfplay& s, const FwdArgs& ego, co
   }
   const size_t half = (sizeof(float) * (size_t)(RES_SCRATCH_FLOATS + 2 * RES_NET_FLOATS) + 15) & ~(size_t)15;
   const size_t lds = 2 * half + 80 * sizeof(int) + ((LIAR_MIRROR_BYTES + 15) & ~15);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = (dev >= 0 && dev < 64) ? dev : 0;
   // Tables per workgroup.  The forward's tile is 16 rows, but its one-hot first layer gathers D rows of W1 (256 B each) per
   // table, forward and net through ONE CU's L2 port, and a 256-table game on a 256-CU part leaves 240 CUs idle at 16 tables
   // per workgroup: spread the tables over as many CUs as there are (3.58 -> 2.99 ms per 128-step rollout of 256 tables;
   // 8 / 4 / 2 tables per workgroup: 3.32 / 3.12 / 3.04 ms).  Rows are independent in every phase, so the numbers do not change.
-  static int cus[64] = {0};
   // read per launch (two getenv calls against a 2 ms kernel) so that one test process can walk the settings
   const char* e_rpw = getenv("PH_LIAR_RPW");
   const int v_rpw = e_rpw ? atoi(e_rpw) : 0;
   const int forced = (v_rpw >= 1 && v_rpw <= 16) ? v_rpw : 0;
   const char* e_skip = getenv("PH_LIAR_SKIP");
   r.no_skip = (e_skip && e_skip[0] == '0') ? 1 : 0;
-  if (cus[dev] == 0) {
-    int n_cu = 0;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    cus[dev] = n_cu;
-  }
-  int rpw = forced ? forced : (s.n + cus[dev] - 1) / cus[dev];
+  int cu = device_cu_count();
+  if (cu <= 0) cu = 256;
+  int rpw = forced ? forced : (s.n + cu - 1) / cu;
   rpw = rpw < 1 ? 1 : (rpw > 16 ? 16 : rpw);
   // the forward's form: one wave per net for up to four tables per workgroup, the 16-row tile above that (bitwise the same rows)
-  const char* e_form = getenv("PH_LIAR_WAVE_FORWARD");
-  const bool wave_form = !(e_form && e_form[0] == '0');
-  const int form = !wave_form ? 0 : (rpw == 1 ? 1 : (rpw == 2 ? 2 : (rpw <= 4 ? 3 : 0)));
-  static bool allowed[64][4] = {};
+  const int form = rpw == 1 ? 1 : (rpw == 2 ? 2 : (rpw <= 4 ? 3 : 0));
   const void* fn = form == 1 ? (const void*)liar_rollout_kernel<1> : form == 2 ? (const void*)liar_rollout_kernel<2>
                    : form == 3 ? (const void*)liar_rollout_kernel<4> : (const void*)liar_rollout_kernel<0>;
-  if (!allowed[dev][form]) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed[dev][form] = true;
-  }
+  if (const hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
   const dim3 grid((s.n + rpw - 1) / rpw), block(512);
   const int hf = (int)(half / sizeof(float));
   switch (form) {
@@ -1883,15 +1796,7 @@ template <int R, int LP, bool VALU>
 static hipError_t launch_fwd_variant(const FwdArgs& a, hipStream_t s) {
   dim3 grid((a.n + R - 1) / R, 2), block(R * 4);
   const size_t lds = fwd_lds_bytes(R, LP);
-  static size_t allowed_dev[64] = {0};  // dynamic LDS above 64 KiB is opt-in, per kernel and device (hipFuncSetAttribute)
-  size_t& allowed = allowed_dev[current_device_slot()];
-  if (allowed == 0) allowed = 64 * 1024;
-  if (lds > allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)policy_fwd_kernel<R, LP, VALU>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed = lds;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)policy_fwd_kernel<R, LP, VALU>, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((policy_fwd_kernel<R, LP, VALU>), grid, block, lds, s, a);
   return hipGetLastError();
 }
@@ -1900,15 +1805,7 @@ template <int R, int LP>
 static hipError_t launch_fwd_multi_variant(const FwdMulti& m, int n_agents, hipStream_t s) {
   dim3 grid((m.a[0].n + R - 1) / R, 2, n_agents), block(R * 4);
   const size_t lds = fwd_lds_bytes(R, LP);
-  static size_t allowed_dev[64] = {0};
-  size_t& allowed = allowed_dev[current_device_slot()];
-  if (allowed == 0) allowed = 64 * 1024;
-  if (lds > allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)policy_fwd_multi_kernel<R, LP>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed = lds;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)policy_fwd_multi_kernel<R, LP>, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((policy_fwd_multi_kernel<R, LP>), grid, block, lds, s, m);
   return hipGetLastError();
 }

@@ -805,29 +805,12 @@ static size_t grad_lds_bytes_ohr(int R, int Lp, int nchunk) {
   return sizeof(float) * (size_t)(2 * R * LDH + regW_sz + HID * LDH + 3 * 64 + 3 * R + NSTATP * 4 + 8 * R + R + R * 2 * nchunk +
                                   nchunk * HID * 2);
 }
-static bool grad_ohr_enabled() {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("PH_GRAD_OHR");
-    enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  return enabled != 0;
-}
 
 template <int LP, bool VALU, bool OH, bool H16, bool OHR>
 static hipError_t launch_grad_inst(const GradArgs& a, int nwg, size_t lds, hipStream_t s) {
   constexpr int R = 64;
   dim3 grid(nwg, 2), block(R * 4);
-  static size_t allowed[64] = {0};  // > 64 KiB of dynamic LDS is opt-in per kernel and device (kept out of graph capture)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = (dev >= 0 && dev < 64) ? dev : 0;
-  if (lds > allowed[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_kernel<R, LP, VALU, OH, H16, OHR>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed[dev] = lds;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)ppo_grad_kernel<R, LP, VALU, OH, H16, OHR>, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((ppo_grad_kernel<R, LP, VALU, OH, H16, OHR>), grid, block, lds, s, a);
   return hipGetLastError();
 }
@@ -837,7 +820,7 @@ static hipError_t launch_grad_variant(const GradArgs& a, int nwg, hipStream_t s)
   if constexpr (OH) {
     // one-hot observations: the first layer's products take their X operands from bit tables, no materialised X
     const size_t ohr = grad_lds_bytes_ohr(R, LP, a.nd.nchunk);
-    if (grad_ohr_enabled() && ohr <= 80 * 1024) return launch_grad_inst<LP, VALU, true, H16, true>(a, nwg, ohr, s);
+    if (ohr <= 80 * 1024) return launch_grad_inst<LP, VALU, true, H16, true>(a, nwg, ohr, s);
   }
   return launch_grad_inst<LP, VALU, OH, H16, false>(a, nwg, grad_lds_bytes(R, LP, OH ? a.nd.D : 0, a.nd.nchunk), s);
 }
@@ -875,16 +858,9 @@ hipError_t launch_ppo_grad(const GradArgs& a, int nwg, int gemm_mode, hipStream_
 // ---- advantage statistics of every minibatch of a train() call: mean and unbiased std (torch .mean()/.std()) ----
 // a 16-byte row record is written once and read once, launches later, by ONE gradient workgroup: a streaming store (the 42 MB of a
 // call's records otherwise displace the per-row table the kernel gathers from out of the L2)
-#ifndef PH_ADV_STORE
-#define PH_ADV_STORE 1
-#endif
 __device__ __forceinline__ void st_rec(uint4* p, const uint4& v) {
-#if PH_ADV_STORE == 1
   typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
   __builtin_nontemporal_store((u32x4_t){v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4_t*>(p));
-#else
-  *p = v;
-#endif
 }
 __global__ __launch_bounds__(ADV_THREADS) void adv_stats_kernel(AdvStatArgs a) {
   __shared__ double sh[2][ADV_THREADS / 64];
@@ -1022,13 +998,7 @@ __global__ __launch_bounds__(256) void obs_planes_kernel(const float* __restrict
     pl[2][e] = l;
   }
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {
-#if defined(PH_OBS_STORE_NT)
-    st_rec(image + row * XIMG_ROW_U4 + p * 8 + g, __builtin_bit_cast(uint4, pl[p]));
-#else
-    image[row * XIMG_ROW_U4 + p * 8 + g] = __builtin_bit_cast(uint4, pl[p]);
-#endif
-  }
+  for (int p = 0; p < 3; ++p) image[row * XIMG_ROW_U4 + p * 8 + g] = __builtin_bit_cast(uint4, pl[p]);
 }
 hipError_t launch_obs_planes(const float* obs, int n, int D, int F, int fold, uint4* image, const float* adv, const float* logp,
                              const float* act, const float* ret, const float* val, uint4* rowrec, hipStream_t s) {
@@ -1044,28 +1014,13 @@ __global__ __launch_bounds__(RED_PARAMS * 4) void ppo_reduce_kernel(ReduceArgs a
   // ONE kilobyte of LDS, not two: a slab block uses gsum, the statistics block part / means -- never both.  Beside another learner's
   // gradient launch that is the difference between fitting into what two resident gradient workgroups leave of a CU's LDS (2 x 79 680
   // of ~160.7 KB usable: ~1.4 KB) and waiting for one of them to leave -- or, placed first, keeping the second one out for the
-  // reduction's 5.7 us (PH_REDUCE_LDS_UNION=0: the two arrays side by side, 2 112 bytes; same-box A/B profiles/r06_bn_*)
-#ifndef PH_REDUCE_LDS_UNION
-#define PH_REDUCE_LDS_UNION 1
-#endif
-#if PH_REDUCE_LDS_UNION
+  // reduction's 5.7 us (same-box A/B profiles/r06_bn_*)
   __shared__ float lds_union[4 * RED_PARAMS];
   static_assert(4 * RED_PARAMS >= 32 * NSTATP + NSTATP || 4 * RED_PARAMS >= 32 * NSTATP, "statistics scratch within the slab scratch");
   float (*gsum)[RED_PARAMS] = reinterpret_cast<float (*)[RED_PARAMS]>(lds_union);
   float (*part)[NSTATP] = reinterpret_cast<float (*)[NSTATP]>(lds_union);
   __shared__ float means[NSTATP];
-#else
-  __shared__ float gsum[4][RED_PARAMS];
-  __shared__ float part[32][NSTATP];
-  __shared__ float means[NSTATP];
-#endif
   const int tid = threadIdx.x;
-#ifdef PH_REDUCE_START_DELAY_TICKS   // experiment (scripts/build_variants.sh; 100 MHz ticks): the reduction's loads held back so that they do not
-  {                                  // meet the OTHER learner's gradient prologue, which starts when this learner's gradient launch ends
-    const long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < (long long)(PH_REDUCE_START_DELAY_TICKS)) __builtin_amdgcn_s_sleep(8);
-  }
-#endif
   if (*a.stop_flag != 0) {  // a previous minibatch of this train() call hit the KL early stop
     if (blockIdx.x == 0 && tid < PH_NSTAT && a.stats_out) a.stats_out[tid] = 0.f;
     if (blockIdx.x == 0 && tid == 0) {
@@ -1101,9 +1056,6 @@ __global__ __launch_bounds__(RED_PARAMS * 4) void ppo_step_kernel(StepArgs s) {
   const unsigned tag = *s.gen + 1u;
   const int step_new = *s.ad.step + 1;
   const unsigned err = *s.sweep_error;
-#if !PH_STEP_LATE_CHECKS
-  if (step_refused(s.r, blockIdx.x, stopped, err)) return;
-#endif
   // (the two reasons to do nothing -- an expired wait of this context, a KL early stop earlier in this train() call -- are tested
   // inside, behind the slab walk: ph_step.h)
   step_body<VEC>(s, blockIdx.x, nblk, tag, step_new, gsum, part, means, nullptr, stopped, err);

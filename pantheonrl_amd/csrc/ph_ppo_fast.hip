@@ -17,26 +17,14 @@
 #include "ph_head.h"
 
 // Issue-slot cuts of round 3 (f32 MFMA and VALU share the SIMD's lanes, DESIGN.md 3.1: every VALU / LDS instruction removed
-// from the tile walk is time).  Each can be switched off at build time for same-box A/B (scripts/build_variants.sh):
-//   PH_FAST_NK      the policy head's loops run over the L logits that exist (template parameter), not over 8 padded slots
-//   PH_FAST_GHROWS  d act_W accumulated per wave over ITS 16 rows for all logits (48 LDS reads + 6*16 FMAs per tile) instead of
-//                   two logit columns over all 64 rows (128 reads + 128 FMAs), cross-wave sum once in the epilogue
-//   PH_FAST_PHYS    the minibatch order arrives as physical buffer rows (adv_stats_kernel translates once per train()): no
-//                   integer division per row in the tile walk
-//   PH_FAST_FOLDB1  F < 64 Box observations: column 63 of X is 1 and row 63 of the staged W1 is b1, so the MFMA adds the bias
-//                   (bitwise: fmaf(1, b, acc) = acc + b) and d b1 is row 63 of the dW1 accumulators
-#ifndef PH_FAST_NK
-#define PH_FAST_NK 1
-#endif
-#ifndef PH_FAST_GHROWS
-#define PH_FAST_GHROWS 1
-#endif
-#ifndef PH_FAST_PHYS
-#define PH_FAST_PHYS 1
-#endif
-#ifndef PH_FAST_FOLDB1
-#define PH_FAST_FOLDB1 1
-#endif
+// from the tile walk is time):
+//   * the policy head's loops run over the L logits that exist (template parameter NK), not over 8 padded slots
+//   * d act_W accumulated per wave over ITS 16 rows for all logits (48 LDS reads + 6*16 FMAs per tile), cross-wave sum once in
+//     the epilogue
+//   * the minibatch order arrives as physical buffer rows (adv_stats_kernel translates once per train()): no integer division
+//     per row in the tile walk
+//   * F < 64 Box observations (FOLD): column 63 of X is 1 and row 63 of the staged W1 is b1, so the MFMA adds the bias
+//     (bitwise: fmaf(1, b, acc) = acc + b) and d b1 is row 63 of the dW1 accumulators
 
 namespace ph {
 
@@ -113,9 +101,7 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
   auto row_index = [&](int tile, int wave, int lane) -> int {
     const int gi = tile * R + wave + 4 * lane;
     if (lane >= 16 || gi >= a.nb) return -1;
-#if PH_FAST_PHYS
     if (a.idx_phys) return a.idx_phys[gi];     // already a physical row
-#endif
     return a.idx ? a.idx[gi] : (int)feistel_perm((uint32_t)(a.mb_start + gi), a.perm_n, a.perm_hb, perm_key);
   };
   auto row_scalars = [&](int n) -> RowMeta {
@@ -123,11 +109,7 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
     m.phys = -1;
     m.adv = m.old = m.act = 0.f;
     if (n >= 0) {
-#if PH_FAST_PHYS
       m.phys = a.idx_phys ? n : env_major_to_phys(n, a.T, a.E);
-#else
-      m.phys = env_major_to_phys(n, a.T, a.E);
-#endif
       if (net == 0) {
         m.adv = a.rb_adv[m.phys];   // normalised when it is committed to LDS (no wait on the gather here)
         m.old = a.rb_logp[m.phys];
@@ -187,13 +169,9 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
 
   f32x16 gW1 = {0}, gW2 = {0};
   float gh0 = 0.f;              // value: d val_W[j] partial of this wave
-#if !PH_FAST_GHROWS
-  float gh1 = 0.f;              // policy: gh0 / gh1 = d act_W[j][2w], [j][2w+1] over all rows
-#else
   float ghr[NK];                // policy: d act_W[lane][k] partial over THIS wave's rows
 #pragma unroll
   for (int k = 0; k < NK; ++k) ghr[k] = 0.f;
-#endif
   float gb1 = 0.f, gb2 = 0.f;   // bias-gradient partials of this wave's 16 rows (lane = hidden unit)
   float ghb = 0.f;              // policy: d act_b[lane] partial (lane < 8) | value: d val_b partial
   float st[NSTATP];
@@ -370,7 +348,6 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
     {
       gb2 += lds_sum16(bufC + wave * 16 * LDH + lane, LDH);
       if (net == 0) {
-#if PH_FAST_GHROWS
         // d act_W[lane][k] += sum over this wave's 16 rows of H2[row][lane] * dz[row][k]: the dz reads are wave-uniform
         // (LDS broadcasts), four rows of reads in flight, then their FMAs
         const float* hp = bufA + wave * 16 * LDH + lane;
@@ -396,28 +373,6 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
           __builtin_amdgcn_sched_barrier(0);
         }
         if (lane < NK) ghb += lds_sum16(dzs + wave * 16 * 8 + lane, 8);
-#else
-        const float* hp = bufA + lane;
-        const float* dp = dzs + 2 * wave;
-#pragma unroll 1
-        for (int r0 = 0; r0 < R; r0 += 8, hp += 8 * LDH, dp += 8 * 8) {  // a real loop: 8 rows of reads, then their FMAs
-          float hv[8];
-          float2 d[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            hv[i] = hp[i * LDH];
-            d[i] = *reinterpret_cast<const float2*>(dp + i * 8);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            gh0 = __builtin_fmaf(hv[i], d[i].x, gh0);
-            gh1 = __builtin_fmaf(hv[i], d[i].y, gh1);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (lane < 8) ghb += lds_sum16(dzs + wave * 16 * 8 + lane, 8);
-#endif
       } else {
         float hv[16], dv[16];
 #pragma unroll
@@ -476,9 +431,6 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
       *reinterpret_cast<float4*>(rslab + RS_W2 + o) = make_float4(gW2[4 * r4], gW2[4 * r4 + 1], gW2[4 * r4 + 2], gW2[4 * r4 + 3]);
       *reinterpret_cast<float4*>(rslab + RS_W1 + o) = make_float4(gW1[4 * r4], gW1[4 * r4 + 1], gW1[4 * r4 + 2], gW1[4 * r4 + 3]);
     }
-#if !PH_FAST_GHROWS
-    if (net == 0) *reinterpret_cast<float2*>(rslab + RS_HW + lane * 8 + 2 * wave) = make_float2(gh0, gh1);
-#endif
 #pragma unroll
     for (int k = 0; k < NSTATP; ++k) {
       float v = st[k];
@@ -495,12 +447,10 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
 #pragma unroll
       for (int k = 0; k < NSTATP; ++k) part[(4 * 4 + wave) * 64 + k] = st[k];
     }
-#if PH_FAST_GHROWS
     if (net == 0) {
 #pragma unroll
       for (int k = 0; k < NK; ++k) part[((5 + k) * 4 + wave) * 64 + lane] = ghr[k];
     }
-#endif
     lds_barrier();
     auto wsum = [&](int which, int idx) {
       return ((part[(which * 4 + 0) * 64 + idx] + part[(which * 4 + 1) * 64 + idx]) + part[(which * 4 + 2) * 64 + idx]) +
@@ -511,7 +461,6 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
       rslab[RS_B2 + tid] = wsum(1, tid);
       if (net == 1) rslab[RS_HW + tid] = wsum(2, tid);
     }
-#if PH_FAST_GHROWS
     if (net == 0) {   // d act_W[j][k], j = tid & 63, k = tid >> 6 (+ 4): fixed-order sum of the four waves' row partials
 #pragma unroll
       for (int k0 = 0; k0 < NK; k0 += 4) {
@@ -519,7 +468,6 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_fast_kernel(GradArgs a) {
         if (k < NK) rslab[RS_HW + j * 8 + k] = wsum(5 + k, j);
       }
     }
-#endif
     if (net == 0 && tid < 8) rslab[RS_HB + tid] = wsum(3, tid);
     if (net == 1 && tid == 0) rslab[RS_HB] = wsum(3, 0);
     if (tid < NSTATP) a.statpart[((size_t)net * gridDim.x + blockIdx.x) * NSTATP + tid] = wsum(4, tid);
@@ -541,21 +489,12 @@ bool grad_fast_eligible(const NetDims& nd) {
 }
 
 // FOLD variant: Box observations with a free 64th feature column
-bool grad_fast_fold(const NetDims& nd) { return PH_FAST_FOLDB1 && nd.obs_kind == PH_SPACE_BOX && nd.F < HID; }
+bool grad_fast_fold(const NetDims& nd) { return nd.obs_kind == PH_SPACE_BOX && nd.F < HID; }
 
 template <bool VALU, int NK, bool FOLD>
 static hipError_t launch_fast_inst(const GradArgs& a, int nwg, hipStream_t s) {
   const size_t lds = grad_fast_lds_bytes();
-  static bool allowed_dev[64] = {false};  // > 64 KiB of dynamic LDS is opt-in per kernel and device (kept out of graph capture)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  bool& allowed = allowed_dev[(dev >= 0 && dev < 64) ? dev : 0];
-  if (!allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_fast_kernel<VALU, NK, FOLD>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed = true;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)ppo_grad_fast_kernel<VALU, NK, FOLD>, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((ppo_grad_fast_kernel<VALU, NK, FOLD>), dim3(nwg, 2), dim3(256), lds, s, a);
   return hipGetLastError();
 }
@@ -565,7 +504,6 @@ static hipError_t launch_fast_nk(const GradArgs& a, int nwg, hipStream_t s) {
 }
 template <bool VALU>
 static hipError_t launch_fast_variant(const GradArgs& a, int nwg, hipStream_t s) {
-#if PH_FAST_NK
   switch (a.nd.L) {     // the head's loops are unrolled over the logits that exist
     case 1: return launch_fast_nk<VALU, 1>(a, nwg, s);
     case 2: return launch_fast_nk<VALU, 2>(a, nwg, s);
@@ -574,10 +512,8 @@ static hipError_t launch_fast_variant(const GradArgs& a, int nwg, hipStream_t s)
     case 5: return launch_fast_nk<VALU, 5>(a, nwg, s);
     case 6: return launch_fast_nk<VALU, 6>(a, nwg, s);
     case 7: return launch_fast_nk<VALU, 7>(a, nwg, s);
-    default: break;
+    default: return launch_fast_nk<VALU, 8>(a, nwg, s);
   }
-#endif
-  return launch_fast_nk<VALU, 8>(a, nwg, s);
 }
 
 // slab position -> parameter index (-1 = padding) for both nets of one workgroup's register-order slab: [net][RS_NET]

@@ -655,11 +655,8 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_split_kernel(GradArgs a) {
   PH_STAMP(a.prof, 13);
 }
 
-#ifndef PH_SPLIT_LDS_PAD
-#define PH_SPLIT_LDS_PAD 0   // occupancy experiment only (scripts/build_variants.sh): > 640 leaves ONE workgroup per CU
-#endif
 static size_t grad_split_lds_bytes() {
-  return (size_t)3 * PB_BYTES + sizeof(float) * (size_t)(HW_FLOATS + 64 * 8 + 2 * HID + 16 + 3 * 64 + 64) + PH_SPLIT_LDS_PAD;
+  return (size_t)3 * PB_BYTES + sizeof(float) * (size_t)(HW_FLOATS + 64 * 8 + 2 * HID + 16 + 3 * 64 + 64);
 }
 
 // the split kernel takes Box observations of the fast kernel's shape class (PH_GRAD_SPLIT=0 switches it off)
@@ -675,16 +672,7 @@ bool grad_split_eligible(const NetDims& nd) {
 template <int NK, bool FOLD>
 static hipError_t launch_split_inst(const GradArgs& a, int nwg, hipStream_t s) {
   const size_t lds = grad_split_lds_bytes();
-  static bool allowed_dev[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  bool& allowed = allowed_dev[(dev >= 0 && dev < 64) ? dev : 0];
-  if (!allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_split_kernel<NK, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-    allowed = true;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)ppo_grad_split_kernel<NK, FOLD>, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((ppo_grad_split_kernel<NK, FOLD>), dim3(nwg, 2), dim3(256), lds, s, a);
   return hipGetLastError();
 }

@@ -241,10 +241,7 @@ __global__ __launch_bounds__(256, 1) void ppo_grad_split_oh_kernel(GradArgs a) {
   // issued).  All NCH up front is as fast alone (20.3 vs 20.0 us) but takes the kernel from 427 to 499 VGPRs -- and at 427 a wave of
   // the OTHER learner's reduce / Adam kernels (64 VGPRs) still fits on every SIMD beside this kernel's one wave, so the two
   // learners' updates overlap: 4.2 -> 4.0 ms per Liar's Dice iteration (profiles/r05_z_liar_grad_w1_slots_ab.txt).
-#ifndef PH_OH_W1_SLOTS
-#define PH_OH_W1_SLOTS 2
-#endif
-  constexpr int W1S = NCH < PH_OH_W1_SLOTS ? NCH : PH_OH_W1_SLOTS;
+  constexpr int W1S = NCH < 2 ? NCH : 2;
   Frag3 W1f[W1S][2];
 #pragma unroll
   for (int ch = 0; ch < W1S; ++ch)
@@ -765,14 +762,8 @@ static size_t grad_split_oh_lds_bytes(int nch, bool box) {
 
 // one-hot observations of up to five feature chunks and D <= 64 components, or Box observations of up to four chunks that the
 // single-chunk / small-head kernels do not take; up to four action components and 32 logits
-// (PH_GRAD_SPLIT_OH=0 switches the kernel off: the exact-f32 general kernel then takes the shape)
 bool grad_split_oh_eligible(const NetDims& nd) {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("PH_GRAD_SPLIT_OH");
-    enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!enabled || nd.gauss || nd.A < 1 || nd.A > 4 || nd.L > 16 * OH_LBMAX || nd.nchunk < 1 || grad_fast_eligible(nd)) return false;
+  if (nd.gauss || nd.A < 1 || nd.A > 4 || nd.L > 16 * OH_LBMAX || nd.nchunk < 1 || grad_fast_eligible(nd)) return false;
   if (nd.obs_kind == PH_SPACE_BOX) return nd.nchunk <= 4;
   return nd.nchunk <= 5 && nd.D <= 64;
 }
@@ -782,15 +773,7 @@ int grad_split_oh_wimage_elems(const NetDims& nd) { return 2 * oh_nfrag(nd.nchun
 template <int NCH, int LB, bool BOX>
 static hipError_t launch_split_oh_inst(const GradArgs& a, int nwg, hipStream_t s) {
   const size_t lds = grad_split_oh_lds_bytes(NCH, BOX);
-  static bool allowed_dev[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  bool& allowed = allowed_dev[(dev >= 0 && dev < 64) ? dev : 0];
-  if (!allowed) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_split_oh_kernel<NCH, LB, BOX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    allowed = true;
-  }
+  if (const hipError_t e = allow_dynamic_lds((const void*)ppo_grad_split_oh_kernel<NCH, LB, BOX>, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL((ppo_grad_split_oh_kernel<NCH, LB, BOX>), dim3(nwg, 2), dim3(256), lds, s, a);
   return hipGetLastError();
 }

@@ -100,10 +100,7 @@ __device__ __forceinline__ void range_walk(const ReduceArgs& a, const RSRC& rsrc
     // buffer loads: descriptor + one 32-bit lane offset (range start + position) + a scalar offset (slab j of the range) --
     // no 64-bit address per load in flight (flat loads cost the 8-byte shape 32 VGPRs of addresses)
     const unsigned lane_off = (unsigned)k0 * stride + (unsigned)p0 * (unsigned)sizeof(float);
-#ifndef PH_REDUCE_NT
-#define PH_REDUCE_NT 0   // experiment (scripts/build_variants.sh): 1 = the slab walk's loads carry the nontemporal bit (each slab byte is read once)
-#endif
-    constexpr int AUX = COH ? 16 : (PH_REDUCE_NT ? 2 : 0);   // 16 = sc1, 2 = nt
+    constexpr int AUX = COH ? 16 : 0;   // 16 = sc1
     auto ld = [&](int j) -> VT {
       if constexpr (VEC == 4) return __builtin_bit_cast(VT, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, (unsigned)j * stride, AUX));
       else if constexpr (VEC == 2) return __builtin_bit_cast(VT, __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane_off, (unsigned)j * stride, AUX));
@@ -392,11 +389,8 @@ __device__ __forceinline__ void step_stopped(const ReduceArgs& a) {
 // `stopped` (an earlier minibatch of this train() call hit the KL early stop) and `err` (an earlier wait of this context expired) are
 // the launch's two reasons to do nothing.  They arrive as VALUES the caller loaded at the top of the kernel and are TESTED here behind
 // the slab walk: tested at the top, every block waited for that round trip of scalar loads before its first slab load went out
-// (PH_STEP_LATE_CHECKS=0 restores the test at the top; same-box A/B profiles/r06_bl_*).  A block that walked for nothing publishes and
-// writes nothing; the statistics block, whose reduction has side effects, still tests first.
-#ifndef PH_STEP_LATE_CHECKS
-#define PH_STEP_LATE_CHECKS 1
-#endif
+// (same-box A/B profiles/r06_bl_*).  A block that walked for nothing publishes and writes nothing; the statistics block, whose
+// reduction has side effects, still tests first.
 __device__ __forceinline__ bool step_refused(const ReduceArgs& a, int blk, int stopped, unsigned err) {
   if (err != 0u) {
     // (ph_ctx_step_errors) blocks of the expired launch which could not be scheduled in time may still publish words -- tagged with a

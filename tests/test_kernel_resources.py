@@ -28,7 +28,7 @@ def _usage(source, tmp_path_factory):
         if m:
             cur = kernels.setdefault(m.group(1), {})
             continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|LDS Size \[bytes/block\]):\s+(\d+)", line)
+        m = re.search(r"remark:\s+(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|LDS Size \[bytes/block\]):\s+(\d+)", line)
         if m and cur is not None:
             cur[m.group(1).split(" [")[0]] = int(m.group(2))
     return kernels
@@ -42,6 +42,11 @@ def split(tmp_path_factory):
 @pytest.fixture(scope="module")
 def ppo(tmp_path_factory):
     return _usage("ph_ppo.hip", tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def pol(tmp_path_factory):
+    return _usage("ph_policy.hip", tmp_path_factory)
 
 
 def _alloc(k):     # registers a wave of the kernel occupies: VGPRs + AGPRs in the unified file, in granules of 8
@@ -112,10 +117,9 @@ def test_update_step_kernels_have_no_one_load_per_iteration_loops(tmp_path_facto
     assert not hits, "\n".join(hits)
 
 
-def test_rollout_kernels_have_no_scratch(tmp_path_factory):
+def test_rollout_kernels_have_no_scratch(pol):
     """The persistent rollout kernels hold their state for thousands of dependent steps: a spilled register is a scratch round trip
     per step.  (The Liar's Dice rollout once kept 31 spilled registers: per-lane mirror addresses hoisted out of its loop.)"""
-    pol = _usage("ph_policy.hip", tmp_path_factory)
     want = ["liar_rollout_kernel", "policy_fwd16_rollout_kernelILb0ELb0E", "policy_fwd16_rollout_kernelILb0ELb1E", "policy_fwd16_exchange_rollout_kernel",
             "policy_fwd16_multi_kernel", "policy_fwd16_kernelILb0ELb0E", "policy_fwd16_kernelILb0ELb1E", "policy_fwd16h_kernelILb0E"]
     for w in want:
@@ -130,3 +134,10 @@ def test_rollout_kernels_have_no_scratch(tmp_path_factory):
                 continue
             assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0, (n, k)
 
+
+def test_lean_exchange_rollout_needs_no_more_registers_than_the_general_one(pol):
+    """exchange_rollout_blocks_per_cu sizes the persistent exchange rollout's grid from the occupancy of the GENERAL instantiation
+    only; that bound holds for the lean one as long as it needs no more vector or scalar registers."""
+    lean = pol["_ZN2ph36policy_fwd16_exchange_rollout_kernelILb1EEEvNS_8FwdMultiENS_13ScriptedMultiE"]
+    general = pol["_ZN2ph36policy_fwd16_exchange_rollout_kernelILb0EEEvNS_8FwdMultiENS_13ScriptedMultiE"]
+    assert lean["VGPRs"] <= general["VGPRs"] and lean["TotalSGPRs"] <= general["TotalSGPRs"], (lean, general)

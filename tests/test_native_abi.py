@@ -36,6 +36,21 @@ def test_struct_sizes_match_the_header_layout():
     assert C.sizeof(nat.PhOptState) == 8 * 4
 
 
+def test_readme_switch_table_lists_exactly_the_switches_that_are_read():
+    """Every getenv("PH_...") of the native layer has a row in README.md's switch table, and every PH_ name of the table is read
+    (as a string literal) somewhere in the package or bench.py: a retired switch leaves the table with its code."""
+    section = open(os.path.join(ROOT, "README.md")).read().split("## Switches", 1)[1].split("\n## ", 1)[0]
+    table = set(re.findall(r"PH_[A-Z0-9_]+", "\n".join(re.findall(r"^\|([^|]*)\|", section, flags=re.M))))
+    sources = [os.path.join(ROOT, "bench.py")]
+    for base, _, files in os.walk(os.path.join(ROOT, "pantheonrl_amd")):
+        sources += [os.path.join(base, f) for f in files if f.endswith((".py", ".hip", ".h"))]
+    text = {p: open(p).read() for p in sources}
+    native = set(re.findall(r'getenv\("(PH_[A-Z0-9_]+)"\)', "\n".join(t for p, t in text.items() if not p.endswith(".py"))))
+    assert native and native <= table, sorted(native - table)
+    unread = sorted(n for n in table if not any(f'"{n}"' in t for t in text.values()))
+    assert not unread, unread
+
+
 @pytest.mark.parametrize("obs,act,expect", [
     (sp.Discrete(1), sp.Discrete(3), dict(D=1, F=1, A=1, L=3, P=8836)),                                  # RPS
     (sp.MultiDiscrete([7] * 6 + [7, 12] * 12), sp.MultiDiscrete([7, 12]), dict(D=30, F=270, A=2, L=19, P=44308)),
