@@ -41,7 +41,8 @@ extern "C" {
                               5: + ph_policy_act_host, ph_buffer_add_reward_const, ph_adapmult_*, ph_ctx_set_joint_reward_rule (additions only)
                               6: + ph_bench_train_kernels, ph_debug_split_oh_tables, ph_ctx_step_errors (additions only)
                               7: ph_spec.act may be PH_SPACE_BOX on ph_layout_of / ph_policy_forward / ph_ppo_minibatch_grad / ph_ppo_train
-                                  (an error before; no signature or struct changed) */
+                                  (an error before; no signature or struct changed)
+                                 still 7: + ph_block_reset / _step / _obs, ph_block_selfplay_step, ph_block_replay_host (additions only) */
 #define PH_HIDDEN 64     /* SB3 MlpPolicy default net_arch pi=[64,64], vf=[64,64] (modular/policies.py:112-114) */
 #define PH_MAX_COMP 256  /* max MultiDiscrete components per space */
 #define PH_MAX_LOGITS 64 /* max total policy logits L */
@@ -555,6 +556,67 @@ int ph_liar_selfplay_step(ph_ctx *ctx, const ph_liar_selfplay *s, int ego_pos, u
  * outputs such a forward would have left for tables that do not move (partner action / log-prob cache entries nothing reads)
  * are then stale.  Needs the 16-row one-hot forward's shape class (<= 64 observation components, <= 32 logits). */
 int ph_liar_selfplay_rollout(ph_ctx *ctx, const ph_liar_selfplay *s, int ego_pos, int n_steps, unsigned long long counter);
+
+/* ---- the block worlds: BlockEnv-v0 (variant 0, simpleblockworld.py:36-131) and BlockEnv-v1 (variant 1, blockworld.py:34-83,
+ * gridutils.py:8-64).  The planner (ego) always moves first; the constructor is the partner.  A table is PH_BLOCK_STATE_WORDS
+ * int32 words, 16-byte aligned (layout: csrc/ph_block.h).  Observations are the raw integer components as f32:
+ *   planner  (n,98) target grid then built grid      | (n,40) true blocks then the constructor's view (orientation, y, x, colour)
+ *   constructor (n,50) last token then built grid    | (n,21) last token then its view of the blocks
+ * Actions int32: planner (n) one token; constructor (n,3) = (x, orientation, colour - 1) | (n,2) = (block, colour). */
+#define PH_BLOCK_STATE_WORDS 12
+/* multi_reset of every table with reset_mask[e] != 0 (NULL = all): a world from Philox4x32-10 keyed (seed, counter [+ the context's
+ * RNG epoch word << 32, when one is attached], table, draw); one Philox block per draw in the reference's draw order, draws that
+ * do not fit discarded, at most 64 draws, then a deterministic placement (never seen in practice; the loop is bounded) */
+int ph_block_reset(ph_ctx *ctx, int variant, int *state, const unsigned char *reset_mask, unsigned long long seed,
+                   unsigned long long counter, int n);
+/* ego_step (is_ego != 0: actions (n) tokens) or alt_step (actions (n,3) | (n,2)) of every table with active[e] != 0 (NULL = all):
+ * obs_next = the OTHER seat's observation, rewards (n,2) (ego, partner), done (n) u8.  Only the last token ends a game; the reward
+ * is then 2 tp / (built cells + target cells) as one f32 division | 100 * correctly coloured blocks / 5. */
+int ph_block_step(ph_ctx *ctx, int variant, int *state, const int *actions, int is_ego, const unsigned char *active,
+                  float *obs_next, float *rewards, unsigned char *done, int n);
+/* get_obs(is_ego) of the active tables */
+int ph_block_obs(ph_ctx *ctx, int variant, const int *state, int is_ego, const unsigned char *active, float *obs_out, int n);
+
+/* One vectorised MultiAgentEnv.step of n block-world tables with a PPO planner and a PPO constructor, entirely on the device, as ONE
+ * host call of four launches and no host synchronisation: the ego's forward (recorded at row ego_pos) -> token played, partner
+ * credited where it moved in this game, ego reward / episode flag / episode count, finished tables regenerated (world counter =
+ * `counter`), both observation rows, the partner's record mask -> the partner's ragged forward -> its move where the game goes on,
+ * the ego's next observation.  The seats have different spaces: two specs.  RNG counters: both forwards and the worlds `counter`. */
+typedef struct ph_block_selfplay {
+  int n, variant;
+  const ph_spec *ego_spec, *alt_spec;        /* planner / constructor spaces */
+  int *state;                                /* (n, PH_BLOCK_STATE_WORDS) */
+  unsigned long long world_seed;
+  /* ego: rectangular rollout buffer */
+  const float *ego_params;
+  const ph_rollout *ego_rb;
+  int *ego_actions;                          /* (n) */
+  float *ego_values, *ego_log_probs;         /* (n) */
+  float *ego_episode_start;                  /* (n) in: flags of the previous step; out: this step's done */
+  unsigned long long ego_seed;
+  /* partner: ragged rollout buffer */
+  const float *alt_params;
+  const ph_rollout *alt_rb;
+  int *alt_actions;                          /* (n,3) | (n,2) */
+  float *alt_values, *alt_log_probs;         /* (n) */
+  int *alt_pos;                              /* (n) per-table write row */
+  unsigned char *alt_boundary, *alt_term, *alt_open, *alt_acted;   /* (n) OnPolicyAgent book-keeping per table */
+  unsigned long long alt_seed;
+  float *obs_ego, *obs_alt;                  /* planner / constructor observation of every table */
+  unsigned long long *episodes;              /* finished games */
+  /* scratch */
+  float *es_alt;                             /* (n) */
+  unsigned char *running, *can, *done;       /* (n); done = tables whose game ended in this step */
+} ph_block_selfplay;
+int ph_block_selfplay_step(ph_ctx *ctx, const ph_block_selfplay *s, int ego_pos, unsigned long long counter);
+/* Host only (no context, no device): the same rule text on the CPU.  With do_reset != 0 every table e of `state` (host, (n,12)) is
+ * first generated from (seed, counter, e) -- the full counter, there is no epoch word -- with at most max_draws draws (< 0: the
+ * device's 64; 0 reaches the deterministic placement at once).  Then `rounds` rounds are played, every one whether or not a game
+ * ended: ego_step(tokens[r][e]) -> alt_obs_out[r][e], rewards_out[r][e][2], done_out[r][e]; alt_step(alt_actions[r][e]) ->
+ * ego_obs_out[r][e].  Output pointers may be NULL. */
+int ph_block_replay_host(int variant, int n, int rounds, int *state, const int *tokens, const int *alt_actions, float *alt_obs_out,
+                         float *rewards_out, unsigned char *done_out, float *ego_obs_out, int do_reset, unsigned long long seed,
+                         unsigned long long counter, int max_draws);
 
 /* n_steps vectorised agent steps against a SCRIPTED environment -- observations, rewards and dones of every step already
  * resident on the device (the synthetic rollout driver of SURVEY.md 8d; a recorded trajectory being replayed) -- in ONE launch:

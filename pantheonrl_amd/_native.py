@@ -175,6 +175,23 @@ class PhLiarSelfPlay(C.Structure):
                 ("zeros8", C.c_void_p), ("ones8", C.c_void_p)]
 
 
+class PhBlockSelfPlay(C.Structure):
+    """ph_block_selfplay: every device pointer of the vectorised block-world self-play step (two specs: planner, constructor)"""
+    _fields_ = [("n", C.c_int), ("variant", C.c_int), ("ego_spec", C.POINTER(PhSpec)), ("alt_spec", C.POINTER(PhSpec)),
+                ("state", C.c_void_p), ("world_seed", C.c_ulonglong),
+                ("ego_params", C.c_void_p), ("ego_rb", C.POINTER(PhRollout)), ("ego_actions", C.c_void_p),
+                ("ego_values", C.c_void_p), ("ego_log_probs", C.c_void_p), ("ego_episode_start", C.c_void_p),
+                ("ego_seed", C.c_ulonglong),
+                ("alt_params", C.c_void_p), ("alt_rb", C.POINTER(PhRollout)), ("alt_actions", C.c_void_p),
+                ("alt_values", C.c_void_p), ("alt_log_probs", C.c_void_p), ("alt_pos", C.c_void_p),
+                ("alt_boundary", C.c_void_p), ("alt_term", C.c_void_p), ("alt_open", C.c_void_p), ("alt_acted", C.c_void_p),
+                ("alt_seed", C.c_ulonglong),
+                ("obs_ego", C.c_void_p), ("obs_alt", C.c_void_p), ("episodes", C.c_void_p),
+                ("es_alt", C.c_void_p), ("running", C.c_void_p), ("can", C.c_void_p), ("done", C.c_void_p)]
+
+
+PH_BLOCK_STATE_WORDS = 12
+
 SIGNATURES = {
     "ph_abi_version": [],
     "ph_roundrobin_env_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, _i],
@@ -228,6 +245,11 @@ SIGNATURES = {
     "ph_liar_obs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ph_liar_selfplay_step": [_vp, C.POINTER(PhLiarSelfPlay), _i, _ull, _i],
     "ph_liar_selfplay_rollout": [_vp, C.POINTER(PhLiarSelfPlay), _i, _i, _ull],
+    "ph_block_reset": [_vp, _i, _vp, _vp, _ull, _ull, _i],
+    "ph_block_step": [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i],
+    "ph_block_obs": [_vp, _i, _vp, _i, _vp, _vp, _i],
+    "ph_block_selfplay_step": [_vp, C.POINTER(PhBlockSelfPlay), _i, _ull],
+    "ph_block_replay_host": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ull, _ull, _i],
     "ph_framestack_push": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "ph_scripted_rollout": [_vp, C.POINTER(PhSpec), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp, _vp,
                             C.POINTER(PhRollout), _i, _i],
@@ -415,3 +437,27 @@ def feistel_indices(n: int, perm_seed: int, epoch: int, start: int = 0, count: O
     out = (C.c_int * count)()
     check(load().ph_feistel_indices(int(n), int(perm_seed), int(epoch), int(start), int(count), out))
     return np.frombuffer(out, dtype=np.int32).copy()
+
+
+def block_replay_host(variant: int, state=None, tokens=None, alt_actions=None, n: Optional[int] = None, seed: Optional[int] = None,
+                      counter: int = 0, max_draws: int = -1):
+    """the block-world rules on the CPU (ph_block_replay_host: the text the device kernels run).  `state` (n, 12) int32 packed
+    tables, or None with `n` and `seed`: tables generated from (seed, counter, table).  tokens (R, n), alt_actions (R, n, 3 | 2):
+    R rounds of planner token then constructor move.  -> dict(state, alt_obs (R, n, Da), rewards (R, n, 2), done (R, n),
+    ego_obs (R, n, De))"""
+    import numpy as np
+    reset = state is None
+    if reset:
+        state = np.zeros((int(n), PH_BLOCK_STATE_WORDS), np.int32)
+    state = np.ascontiguousarray(state, np.int32).copy()
+    n = state.shape[0]
+    R = 0 if tokens is None else int(np.shape(tokens)[0])
+    De, Da, A = ((98, 50, 3) if variant == 1 else (40, 21, 2))
+    tok = np.ascontiguousarray(np.zeros((0, n)) if tokens is None else tokens, np.int32).reshape(R, n)
+    act = np.ascontiguousarray(np.zeros((0, n, A)) if alt_actions is None else alt_actions, np.int32).reshape(R, n, A)
+    alt_obs, ego_obs = np.zeros((R, n, Da), np.float32), np.zeros((R, n, De), np.float32)
+    rew, done = np.zeros((R, n, 2), np.float32), np.zeros((R, n), np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check(load().ph_block_replay_host(int(variant), n, R, p(state), p(tok), p(act), p(alt_obs), p(rew), p(done), p(ego_obs),
+                                      int(reset), int(seed or 0), int(counter), int(max_draws)))
+    return dict(state=state, alt_obs=alt_obs, rewards=rew, done=done, ego_obs=ego_obs)

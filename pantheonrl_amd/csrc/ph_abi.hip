@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ph_launch.h"
+#include "ph_block.h"
 
 namespace ph {
 
@@ -1688,6 +1689,103 @@ int ph_liar_selfplay_step(ph_ctx* ctx, const ph_liar_selfplay* sp, int ego_pos, 
                                s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
     return 1;
   PH_HIP(ph::launch_liar_sp_after_opening(s, st));
+  return 0;
+}
+
+// ---- the block worlds (ph_block.h / ph_block.hip) ----
+int ph_block_reset(ph_ctx* ctx, int variant, int* state, const unsigned char* reset_mask, unsigned long long seed,
+                   unsigned long long counter, int n) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!state) return fail("ph_block_reset: null argument");
+  if (variant != 0 && variant != 1) return fail("ph_block_reset: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (n <= 0) return fail("ph_block_reset: n must be positive");
+  if ((uintptr_t)state % 16) return fail("ph_block_reset: state must be 16-byte aligned");
+  PH_HIP(ph::launch_block_reset(variant, state, reset_mask, seed, counter, ctx->rng_epoch, n, ctx->stream));
+  return 0;
+}
+
+int ph_block_step(ph_ctx* ctx, int variant, int* state, const int* actions, int is_ego, const unsigned char* active,
+                  float* obs_next, float* rewards, unsigned char* done, int n) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!state || !actions || !obs_next || !rewards || !done) return fail("ph_block_step: null argument");
+  if (variant != 0 && variant != 1) return fail("ph_block_step: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (n <= 0) return fail("ph_block_step: n must be positive");
+  if ((uintptr_t)state % 16) return fail("ph_block_step: state must be 16-byte aligned");
+  PH_HIP(ph::launch_block_step(variant, state, actions, is_ego != 0, active, obs_next, rewards, done, n, ctx->stream));
+  return 0;
+}
+
+int ph_block_obs(ph_ctx* ctx, int variant, const int* state, int is_ego, const unsigned char* active, float* obs_out, int n) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!state || !obs_out) return fail("ph_block_obs: null argument");
+  if (variant != 0 && variant != 1) return fail("ph_block_obs: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (n <= 0) return fail("ph_block_obs: n must be positive");
+  if ((uintptr_t)state % 16) return fail("ph_block_obs: state must be 16-byte aligned");
+  PH_HIP(ph::launch_block_obs(variant, state, is_ego != 0, active, obs_out, n, ctx->stream));
+  return 0;
+}
+
+int ph_block_selfplay_step(ph_ctx* ctx, const ph_block_selfplay* sp, int ego_pos, unsigned long long counter) {
+  DevGuard dev_guard(ctx);
+  if (!ctx || !sp) return fail("ph_block_selfplay_step: null argument");
+  const ph_block_selfplay& s = *sp;
+  if (s.variant != 0 && s.variant != 1) return fail("ph_block_selfplay_step: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (s.n <= 0) return fail("ph_block_selfplay_step: n must be positive");
+  if (!s.ego_spec || !s.alt_spec || !s.ego_rb || !s.alt_rb || !s.state || !s.ego_actions || !s.alt_actions || !s.ego_episode_start ||
+      !s.alt_pos || !s.alt_boundary || !s.alt_term || !s.alt_open || !s.alt_acted || !s.obs_ego || !s.obs_alt || !s.episodes ||
+      !s.es_alt || !s.running || !s.can || !s.done)
+    return fail("ph_block_selfplay_step: incomplete description");
+  if (check_rb(s.ego_rb) || check_rb(s.alt_rb)) return 1;
+  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail("ph_block_selfplay_step: buffers must have E = n");
+  if ((uintptr_t)s.state % 16) return fail("ph_block_selfplay_step: state must be 16-byte aligned");
+  if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail("ph_block_selfplay_step: ego_pos out of range (buffer full?)");
+  // the specs must be the variant's: the book-keeping kernels write rows of these lengths
+  ph_layout le, la;
+  if (ph_layout_of(s.ego_spec, &le) || ph_layout_of(s.alt_spec, &la)) return 1;
+  if (le.D != ph::bw_ego_obs_len(s.variant) || le.A != 1 || le.L != ph::bw_tokens(s.variant) ||
+      la.D != ph::bw_alt_obs_len(s.variant) || la.A != ph::bw_alt_act_len(s.variant))
+    return fail("ph_block_selfplay_step: the specs are not the variant's planner / constructor spaces");
+  // the planner moves in every table
+  if (ph_policy_forward(ctx, s.ego_spec, s.ego_params, s.obs_ego, s.n, nullptr, nullptr, nullptr, s.ego_seed, counter, 0,
+                        s.ego_actions, nullptr, s.ego_values, s.ego_log_probs, nullptr, nullptr, s.ego_rb, ego_pos,
+                        s.ego_episode_start, nullptr, 0))
+    return 1;
+  PH_HIP(ph::launch_block_sp_after_ego(s, s.ego_rb->rewards + (size_t)ego_pos * s.n, counter, ctx->rng_epoch, ctx->stream));
+  // the constructor replies where the game goes on
+  if (ph_policy_forward_ragged(ctx, s.alt_spec, s.alt_params, s.obs_alt, nullptr, s.alt_seed, counter, 0, s.alt_actions,
+                               s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
+    return 1;
+  PH_HIP(ph::launch_block_sp_after_alt(s, ctx->stream));
+  return 0;
+}
+
+int ph_block_replay_host(int variant, int n, int rounds, int* state, const int* tokens, const int* alt_actions, float* alt_obs_out,
+                         float* rewards_out, unsigned char* done_out, float* ego_obs_out, int do_reset, unsigned long long seed,
+                         unsigned long long counter, int max_draws) {
+  if (variant != 0 && variant != 1) return fail("ph_block_replay_host: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (!state || n <= 0 || rounds < 0) return fail("ph_block_replay_host: bad arguments");
+  if (rounds > 0 && (!tokens || !alt_actions)) return fail("ph_block_replay_host: moves missing");
+  const int Da = ph::bw_alt_obs_len(variant), De = ph::bw_ego_obs_len(variant), A = ph::bw_alt_act_len(variant);
+  for (int e = 0; e < n; ++e) {
+    ph::BwTable t;
+    int* w = state + (size_t)e * ph::BW_WORDS;
+    if (do_reset) ph::bw_reset(t, variant, seed, counter, (uint32_t)e, max_draws < 0 ? ph::BW_MAX_DRAWS : max_draws);
+    else ph::bw_unpack(t, variant, w);
+    for (int r = 0; r < rounds; ++r) {
+      const size_t i = (size_t)r * n + e;
+      const ph::BwOutcome o = ph::bw_ego_step(t, variant, tokens[i]);
+      if (alt_obs_out) ph::bw_write_alt_obs(t, variant, alt_obs_out + i * Da);
+      if (rewards_out) rewards_out[2 * i] = rewards_out[2 * i + 1] = o.reward;
+      if (done_out) done_out[i] = o.done ? 1 : 0;
+      int a[3] = {alt_actions[i * A], alt_actions[i * A + 1], variant ? alt_actions[i * A + 2] : 0};
+      ph::bw_alt_step(t, variant, a);
+      if (ego_obs_out) ph::bw_write_ego_obs(t, variant, ego_obs_out + i * De);
+    }
+    ph::bw_pack(t, variant, w);
+  }
   return 0;
 }
 

@@ -1,0 +1,151 @@
+// The block worlds on the device (BlockEnv-v0 / BlockEnv-v1): the masked per-call kernels and the two book-keeping launches of
+// the vectorised self-play step.  One lane per table; the rules are ph_block.h's, the partner seat's ragged book-keeping is
+// ph_liar.h's (liar_sp_credit / liar_sp_prepare / liar_sp_commit).
+#include "ph_block.h"
+#include "ph_liar.h"
+
+namespace ph {
+
+// a table's 12 words as three 16-byte accesses
+__device__ __forceinline__ void bw_load(BwTable& t, int variant, const int* state, int e) {
+  int w[BW_WORDS];
+  const int4* p = reinterpret_cast<const int4*>(state + (size_t)e * BW_WORDS);
+#pragma unroll
+  for (int i = 0; i < BW_WORDS / 4; ++i) {
+    const int4 v = p[i];
+    w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+  }
+  bw_unpack(t, variant, w);
+}
+__device__ __forceinline__ void bw_store(const BwTable& t, int variant, int* state, int e) {
+  int w[BW_WORDS];
+  bw_pack(t, variant, w);
+  int4* p = reinterpret_cast<int4*>(state + (size_t)e * BW_WORDS);
+#pragma unroll
+  for (int i = 0; i < BW_WORDS / 4; ++i) p[i] = make_int4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+}
+__device__ __forceinline__ uint64_t bw_counter(uint64_t counter, const unsigned long long* epoch) {
+  return counter + (epoch ? (uint64_t)(*epoch) << 32 : 0ull);
+}
+
+__global__ void block_reset_kernel(int variant, int* __restrict__ state, const unsigned char* __restrict__ reset_mask,
+                                   uint64_t seed, uint64_t counter, const unsigned long long* __restrict__ epoch, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  if (reset_mask && !reset_mask[e]) return;
+  BwTable t;
+  bw_reset(t, variant, seed, bw_counter(counter, epoch), (uint32_t)e, BW_MAX_DRAWS);
+  bw_store(t, variant, state, e);
+}
+hipError_t launch_block_reset(int variant, int* state, const unsigned char* reset_mask, unsigned long long seed,
+                              unsigned long long counter, const unsigned long long* epoch, int n, hipStream_t s) {
+  hipLaunchKernelGGL(block_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, variant, state, reset_mask, (uint64_t)seed,
+                     (uint64_t)counter, epoch, n);
+  return hipGetLastError();
+}
+
+// ego_step (is_ego) or alt_step of every active table: the OTHER seat's observation, rewards (ego, partner), done
+__global__ void block_step_kernel(int variant, int* __restrict__ state, const int* __restrict__ actions, int is_ego,
+                                  const unsigned char* __restrict__ active, float* __restrict__ obs_next,
+                                  float* __restrict__ rewards, unsigned char* __restrict__ done, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  if (active && !active[e]) return;
+  BwTable t;
+  bw_load(t, variant, state, e);
+  BwOutcome o{0.f, false};
+  if (is_ego) {
+    o = bw_ego_step(t, variant, actions[e]);
+    bw_write_alt_obs(t, variant, obs_next + (size_t)e * bw_alt_obs_len(variant));
+  } else {
+    const int A = bw_alt_act_len(variant);
+    int a[3] = {actions[(size_t)e * A], actions[(size_t)e * A + 1], variant ? actions[(size_t)e * A + 2] : 0};
+    bw_alt_step(t, variant, a);
+    bw_write_ego_obs(t, variant, obs_next + (size_t)e * bw_ego_obs_len(variant));
+  }
+  bw_store(t, variant, state, e);
+  rewards[2 * (size_t)e] = o.reward;
+  rewards[2 * (size_t)e + 1] = o.reward;
+  done[e] = o.done ? 1 : 0;
+}
+hipError_t launch_block_step(int variant, int* state, const int* actions, int is_ego, const unsigned char* active, float* obs_next,
+                             float* rewards, unsigned char* done, int n, hipStream_t s) {
+  hipLaunchKernelGGL(block_step_kernel, dim3((n + 255) / 256), dim3(256), 0, s, variant, state, actions, is_ego, active, obs_next,
+                     rewards, done, n);
+  return hipGetLastError();
+}
+
+__global__ void block_obs_kernel(int variant, const int* __restrict__ state, int is_ego, const unsigned char* __restrict__ active,
+                                 float* __restrict__ obs_out, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  if (active && !active[e]) return;
+  BwTable t;
+  bw_load(t, variant, state, e);
+  if (is_ego) bw_write_ego_obs(t, variant, obs_out + (size_t)e * bw_ego_obs_len(variant));
+  else bw_write_alt_obs(t, variant, obs_out + (size_t)e * bw_alt_obs_len(variant));
+}
+hipError_t launch_block_obs(int variant, const int* state, int is_ego, const unsigned char* active, float* obs_out, int n,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(block_obs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, variant, state, is_ego, active, obs_out, n);
+  return hipGetLastError();
+}
+
+// ---- vectorised self-play: ego forward | after_ego | partner forward (ragged) | after_alt -------------------------------------
+// The planner always opens, so a step needs no opening pass: every table is at the planner's turn before and after it.
+//
+// after_ego: the planner's token is played.  The partner is credited where it already moved in this game (MultiAgentEnv.
+// _update_players), the ego's reward row / episode flag / the episode count follow; a finished table gets its next world at once
+// (the step's counter) and its planner observation, a running one the constructor's observation and the partner's record flags.
+__global__ void block_sp_after_ego_kernel(ph_block_selfplay s, float* alt_rewards, int alt_T, float* ego_rew_row, uint64_t counter,
+                                          const unsigned long long* __restrict__ epoch) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= s.n) return;
+  BwTable t;
+  bw_load(t, s.variant, s.state, e);
+  LiarSeat q = liar_seat_load(s, e);
+  const BwOutcome o = bw_ego_step(t, s.variant, s.ego_actions[e]);
+  liar_sp_credit(s, q, alt_rewards, alt_T, e, o.reward, o.done, q.acted);
+  liar_add_f32(ego_rew_row + e, o.reward);
+  s.ego_episode_start[e] = o.done ? 1.f : 0.f;
+  s.done[e] = o.done ? 1 : 0;
+  s.running[e] = o.done ? 0 : 1;
+  if (o.done) {
+    atomicAdd(s.episodes, 1ull);
+    bw_reset(t, s.variant, s.world_seed, bw_counter(counter, epoch), (uint32_t)e, BW_MAX_DRAWS);
+    s.alt_acted[e] = 0;
+    bw_write_ego_obs(t, s.variant, s.obs_ego + (size_t)e * bw_ego_obs_len(s.variant));
+  } else {
+    bw_write_alt_obs(t, s.variant, s.obs_alt + (size_t)e * bw_alt_obs_len(s.variant));
+  }
+  bw_store(t, s.variant, s.state, e);
+  liar_sp_prepare(s, q, alt_T, e, !o.done);
+}
+// after_alt: where the game goes on the constructor's move is played (it pays nothing and never ends a game) and the planner
+// sees the result
+__global__ void block_sp_after_alt_kernel(ph_block_selfplay s) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= s.n) return;
+  if (!s.running[e]) return;
+  BwTable t;
+  bw_load(t, s.variant, s.state, e);
+  LiarSeat q = liar_seat_load(s, e);
+  liar_sp_commit(s, q, e, s.can[e] != 0);
+  const int A = bw_alt_act_len(s.variant);
+  int a[3] = {s.alt_actions[(size_t)e * A], s.alt_actions[(size_t)e * A + 1], s.variant ? s.alt_actions[(size_t)e * A + 2] : 0};
+  bw_alt_step(t, s.variant, a);
+  bw_store(t, s.variant, s.state, e);
+  bw_write_ego_obs(t, s.variant, s.obs_ego + (size_t)e * bw_ego_obs_len(s.variant));
+}
+hipError_t launch_block_sp_after_ego(const ph_block_selfplay& s, float* ego_rew_row, unsigned long long counter,
+                                     const unsigned long long* epoch, hipStream_t st) {
+  hipLaunchKernelGGL(block_sp_after_ego_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s, s.alt_rb->rewards, s.alt_rb->T,
+                     ego_rew_row, (uint64_t)counter, epoch);
+  return hipGetLastError();
+}
+hipError_t launch_block_sp_after_alt(const ph_block_selfplay& s, hipStream_t st) {
+  hipLaunchKernelGGL(block_sp_after_alt_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s);
+  return hipGetLastError();
+}
+
+}  // namespace ph

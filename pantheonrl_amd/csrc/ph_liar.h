@@ -155,7 +155,8 @@ struct LiarSeat {
   bool open;       // alt_open: the last forward was recorded, later rewards belong to it
   bool acted;      // alt_acted: the partner has moved in the current game
 };
-__device__ __forceinline__ LiarSeat liar_seat_load(const ph_liar_selfplay& s, int e) {
+template <class SelfPlay>   // ph_liar_selfplay, or another description with the same partner-seat fields (ph_block_selfplay)
+__device__ __forceinline__ LiarSeat liar_seat_load(const SelfPlay& s, int e) {
   LiarSeat q;
   q.pos = s.alt_pos[e];
   q.boundary = s.alt_boundary[e] != 0;
@@ -164,7 +165,8 @@ __device__ __forceinline__ LiarSeat liar_seat_load(const ph_liar_selfplay& s, in
   return q;
 }
 // a reward r / an episode end that follows the partner's last forward (credited: that forward happened in this game)
-__device__ __forceinline__ void liar_sp_credit(const ph_liar_selfplay& s, LiarSeat& q, float* alt_rewards, int alt_T, int e, float r,
+template <class SelfPlay>
+__device__ __forceinline__ void liar_sp_credit(const SelfPlay& s, LiarSeat& q, float* alt_rewards, int alt_T, int e, float r,
                                                bool done, bool credited) {
   const bool m = credited && q.open;
   // no-return float atomic: the address is this table's alone, so the sum is the plain "+=" -- but the lane does not wait a
@@ -177,13 +179,15 @@ __device__ __forceinline__ void liar_sp_credit(const ph_liar_selfplay& s, LiarSe
   if (m && done) s.alt_term[e] = 1;
 }
 // what the partner's next forward records: a row where it is asked to move and its column still has room
-__device__ __forceinline__ void liar_sp_prepare(const ph_liar_selfplay& s, const LiarSeat& q, int alt_T, int e, bool requested) {
+template <class SelfPlay>
+__device__ __forceinline__ void liar_sp_prepare(const SelfPlay& s, const LiarSeat& q, int alt_T, int e, bool requested) {
   s.can[e] = (requested && q.pos < alt_T) ? 1 : 0;
   s.es_alt[e] = q.boundary ? 1.f : 0.f;
 }
 // after a partner forward (can: it recorded a row): advance the recorded column, open / close the reward window, mark the
 // partner as having acted
-__device__ __forceinline__ void liar_sp_commit(const ph_liar_selfplay& s, LiarSeat& q, int e, bool can) {
+template <class SelfPlay>
+__device__ __forceinline__ void liar_sp_commit(const SelfPlay& s, LiarSeat& q, int e, bool can) {
   if (can) {
     q.pos += 1;
     s.alt_pos[e] = q.pos;

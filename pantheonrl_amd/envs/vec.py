@@ -487,3 +487,179 @@ class LiarIterationGraph:
     def launch(self) -> None:
         with th.cuda.stream(self.stream):
             self._iteration(eager=self.graph_id is None)
+
+
+class VecBlockWorld:
+    """n_envs tables of BlockEnv-v0 (variant 0) or BlockEnv-v1 (variant 1) resident on the device, stepped by the per-call entry
+    points `ph_block_reset` / `ph_block_step` / `ph_block_obs`.  The planner (ego) and the constructor (partner) have different
+    spaces, so the class carries two pairs."""
+    GAMES = {0: "BlockEnv-v0", 1: "BlockEnv-v1"}
+
+    def __init__(self, variant: int, n_envs: int, ctx: nat.Context, device):
+        from .blockworld import BlockEnv, SimpleBlockEnv
+        game = (SimpleBlockEnv, BlockEnv)[int(variant)]
+        self.variant, self.E, self.ctx, self.device = int(variant), n_envs, ctx, device
+        self.observation_space, self.action_space = game.observation_space, game.action_space
+        self.partner_observation_space, self.partner_action_space = game.partner_observation_space, game.partner_action_space
+        self.D_ego, self.D_alt = len(self.observation_space.nvec), len(self.partner_observation_space.nvec)
+        self.state = th.zeros((n_envs, nat.PH_BLOCK_STATE_WORDS), dtype=th.int32, device=device)
+        self.obs_next_alt = th.zeros((n_envs, self.D_alt), dtype=th.float32, device=device)
+        self.obs_next_ego = th.zeros((n_envs, self.D_ego), dtype=th.float32, device=device)
+        self.rewards = th.zeros((n_envs, 2), dtype=th.float32, device=device)
+        self.done = th.zeros(n_envs, dtype=th.uint8, device=device)
+
+    @classmethod
+    def seat_spaces(cls, variant: int):
+        """-> (planner, constructor): two space carriers a PPO model can be built from"""
+        from .blockworld import BlockEnv, SimpleBlockEnv
+        game = (SimpleBlockEnv, BlockEnv)[int(variant)]
+        carrier = lambda o, a: type("Spaces", (), dict(observation_space=o, action_space=a, _is_dummy_space_env=True))()  # noqa: E731
+        return (carrier(game.observation_space, game.action_space),
+                carrier(game.partner_observation_space, game.partner_action_space))
+
+    def _bind(self):
+        self.ctx.set_stream(th.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self, seed: int, counter: int, reset_mask: th.Tensor = None) -> None:
+        self._bind()
+        nat.check(self.ctx.lib.ph_block_reset(self.ctx.handle, self.variant, self.state.data_ptr(), nat.ptr(reset_mask), int(seed),
+                                              int(counter), self.E))
+
+    def load(self, state: np.ndarray) -> None:
+        """packed tables (E, 12) int32, e.g. from envs.blockworld.pack_state"""
+        self.state.copy_(th.as_tensor(np.ascontiguousarray(state, np.int32)))
+
+    def player_step(self, actions: th.Tensor, is_ego: bool, active: th.Tensor = None):
+        """the planner's tokens (E) or the constructor's moves (E, A) int32 -> (the OTHER seat's observation, rewards (E, 2), done)"""
+        self._bind()
+        out = self.obs_next_alt if is_ego else self.obs_next_ego
+        nat.check(self.ctx.lib.ph_block_step(self.ctx.handle, self.variant, self.state.data_ptr(), actions.data_ptr(), int(is_ego),
+                                             nat.ptr(active), out.data_ptr(), self.rewards.data_ptr(), self.done.data_ptr(), self.E))
+        return out, self.rewards, self.done
+
+    def observe(self, is_ego: bool, out: th.Tensor, active: th.Tensor = None) -> th.Tensor:
+        self._bind()
+        nat.check(self.ctx.lib.ph_block_obs(self.ctx.handle, self.variant, self.state.data_ptr(), int(is_ego), nat.ptr(active),
+                                            out.data_ptr(), self.E))
+        return out
+
+
+class VecBlockSelfPlay:
+    """`trainer.py BlockEnv-v0|v1 PPO PPO` with n_envs tables resident on the device.
+
+    One vectorised step is one `MultiAgentEnv.step` of every table: the planner speaks; where that was not its last token the
+    constructor moves; a finished table gets its next world at once, so every table is back at the planner's turn.  The planner
+    is a rectangular VecOnPolicyAgent, the constructor a RaggedVecOnPolicyAgent: it is not asked to act in a table whose game
+    the planner just ended (but is paid there, if it moved in that game).
+
+    native=True: the step is ONE engine call (`ph_block_selfplay_step`: two forwards and one book-keeping launch after each,
+    every mask on the device, no host synchronisation).  native=False walks the same step with the per-call entry points and
+    torch masks -- the readable statement and the bitwise cross-check (same RNG counters: step c -> both forwards and the
+    worlds of the games that start in it draw with counter c; the first worlds with counter 0)."""
+
+    def __init__(self, variant: int, n_envs: int, ego: VecOnPolicyAgent, alt: RaggedVecOnPolicyAgent, seed: int = 0,
+                 native: bool = True):
+        self.variant, self.E, self.ego, self.alt, self.native = int(variant), n_envs, ego, alt, bool(native)
+        pol = ego.model.policy
+        self.dev = pol.device
+        self.env = VecBlockWorld(variant, n_envs, pol.ctx, self.dev)
+        self.seed = int(seed)
+        E, dev = n_envs, self.dev
+        u8 = lambda v=0: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
+        self.obs_ego = th.zeros((E, self.env.D_ego), dtype=th.float32, device=dev)
+        self.obs_alt = th.zeros((E, self.env.D_alt), dtype=th.float32, device=dev)
+        self.alt_acted = u8()
+        self._done, self._running, self._can = u8(), u8(), u8()
+        self._es_alt = th.zeros(E, dtype=th.float32, device=dev)
+        self._episodes_dev = th.zeros(1, dtype=th.int64, device=dev)
+        self.steps_done = 0
+        self._bind()
+        self.env.reset(self.seed, 0)
+        self.env.observe(True, self.obs_ego)
+        if self.native:
+            self._build_native()
+
+    @property
+    def episodes(self) -> int:
+        return int(self._episodes_dev.item())
+
+    def _bind(self):
+        stream = th.cuda.current_stream(self.dev).cuda_stream
+        self.env.ctx.set_stream(stream)
+        for agent in (self.ego, self.alt):
+            agent.model.policy.ctx.set_stream(stream)
+
+    def _build_native(self) -> None:
+        ego, alt = self.ego, self.alt
+        ego._last_episode_starts = ego._last_episode_starts.clone()    # updated in place by the step from here on
+        s = nat.PhBlockSelfPlay()
+        pe, pa = ego.model.policy, alt.model.policy
+        s.n, s.variant = self.E, self.variant
+        s.ego_spec, s.alt_spec = C.pointer(pe.spec), C.pointer(pa.spec)
+        s.state, s.world_seed = self.env.state.data_ptr(), self.seed
+        self._ego_rbc, self._alt_rbc = ego.model.rollout_buffer.c_struct(), alt.model.rollout_buffer.c_struct()
+        s.ego_params, s.ego_rb, s.ego_actions = pe.params.data_ptr(), C.pointer(self._ego_rbc), ego.actions.data_ptr()
+        s.ego_values, s.ego_log_probs = ego.values.data_ptr(), ego.log_probs.data_ptr()
+        s.ego_episode_start, s.ego_seed = ego._last_episode_starts.data_ptr(), pe._seed
+        s.alt_params, s.alt_rb, s.alt_actions = pa.params.data_ptr(), C.pointer(self._alt_rbc), alt.actions.data_ptr()
+        s.alt_values, s.alt_log_probs, s.alt_pos = alt.values.data_ptr(), alt.log_probs.data_ptr(), alt.pos.data_ptr()
+        s.alt_boundary, s.alt_term, s.alt_open = alt.boundary.data_ptr(), alt.term.data_ptr(), alt.open.data_ptr()
+        s.alt_acted, s.alt_seed = self.alt_acted.data_ptr(), pa._seed
+        s.obs_ego, s.obs_alt, s.episodes = self.obs_ego.data_ptr(), self.obs_alt.data_ptr(), self._episodes_dev.data_ptr()
+        s.es_alt, s.running, s.can, s.done = (t.data_ptr() for t in (self._es_alt, self._running, self._can, self._done))
+        self._desc = s
+
+    def _native_call(self, counter: int, ego_pos: int = -1) -> None:
+        self._bind()
+        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
+        nat.check(ctx.lib.ph_block_selfplay_step(ctx.handle, C.byref(self._desc), int(rb.pos if ego_pos < 0 else ego_pos),
+                                                 int(counter)))
+
+    def step(self):
+        """-> (E,) uint8 device tensor: tables whose game ended in this step"""
+        ego, alt, env = self.ego, self.alt, self.env
+        self.steps_done += 1
+        c = self.steps_done
+        if self.native:
+            model, rb = ego.model, ego.model.rollout_buffer
+            if ego.n_steps >= model.n_steps:
+                ego.learn_from_buffer()
+            self._native_call(c)
+            rb.pos += 1
+            rb.full = rb.pos == rb.buffer_size
+            ego.n_steps += 1
+            ego.num_timesteps += self.E
+            alt.num_timesteps += self.E
+            return self._done
+        self._bind()
+        ego.model.policy._counter = c - 1
+        tokens = ego.get_action(self.obs_ego)                                  # every table is at the planner's turn
+        obs_alt, rew, done = env.player_step(tokens, True)
+        done8 = done.clone()
+        d = done8.bool()
+        # a partner that already moved in this game is credited this transition (multiagentenv.py:167-173)
+        alt.update(rew[:, 1].contiguous(), done8, self.alt_acted)
+        ego.update(rew[:, 0].contiguous(), done8.to(th.float32))
+        ego.flush_rewards()
+        self._episodes_dev += done8.sum()
+        running = (~d).to(th.uint8)
+        self.obs_alt.copy_(th.where(~d[:, None], obs_alt, self.obs_alt))
+        # finished tables: the next world, nobody has acted in it, the planner's first observation
+        env.reset(self.seed, c, done8)
+        self.alt_acted.copy_(th.where(d, th.zeros_like(self.alt_acted), self.alt_acted))
+        env.observe(True, self.obs_ego, done8)
+        # the constructor moves where the game goes on
+        alt.model.policy._counter = c - 1
+        moves = alt.get_action(self.obs_alt, running)
+        self.alt_acted.copy_((self.alt_acted.bool() | ~d).to(th.uint8))
+        obs_ego, _, _ = env.player_step(moves, False, running)
+        self.obs_ego.copy_(th.where(~d[:, None], obs_ego, self.obs_ego))
+        return done8
+
+    def rollout_and_learn(self, n_steps: int) -> None:
+        """n_steps vectorised steps, the planner's update, and the constructor's whenever all its columns are full"""
+        for _ in range(n_steps):
+            self.step()
+        self.ego.learn_from_buffer()
+        if self.alt.full():
+            self.alt.learn_from_buffer()

@@ -3,7 +3,7 @@
     python -m pantheonrl_amd.trainer RPS-v0 PPO PPO --preset 1 --seed 0 -t 10000        (BASELINE config 1)
 
 Same positional arguments and flags as the reference for the part of the surface that sits on the PPO path:
-env in {RPS-v0, LiarsDice-v0}; ego in {PPO, ADAP, ADAP_MULT, ModularAlgorithm, LOAD}; each partner in {PPO, ADAP, ADAP_MULT, FIXED, DEFAULT}; JSON configs splatted
+env in {RPS-v0, LiarsDice-v0, BlockEnv-v0, BlockEnv-v1}; ego in {PPO, ADAP, ADAP_MULT, ModularAlgorithm, LOAD}; each partner in {PPO, ADAP, ADAP_MULT, FIXED, DEFAULT}; JSON configs splatted
 into the constructors; `--framestack`, `--preset 1`, `--ego-save/--alt-save`, `--tensorboard-log/-name`, `--seed`, `--device`,
 `--total-timesteps`, `--share-latent` (ADAP ego + ADAP partners act under the ego's context).  `--record FILE` writes the episode
 transitions in the reference's `.npy` format.  A ModularAlgorithm ego gets one partner module per partner agent
@@ -20,6 +20,7 @@ import numpy as np
 from . import envs as _envs
 from .common import OnPolicyAgent, StaticPolicyAgent
 from .common.wrappers import frame_wrap, recorder_wrap
+from .envs.blockworld import BlockEnv, DefaultConstructorAgent, SBWDefaultAgent, SimpleBlockEnv
 from .envs.liar import LiarDefaultAgent, LiarEnv
 from .envs.rps import RPSEnv, RPSWeightedAgent
 from .adap import ADAP, AdapAgent, AdapPolicy, AdapPolicyMult
@@ -151,6 +152,10 @@ def gen_partner(kind: str, config: dict, altenv, ego, args, index: int):
             raise EnvException("No config possible for this default agent")
         if isinstance(base, LiarEnv):
             return LiarDefaultAgent()
+        if base is SimpleBlockEnv.partner_env or isinstance(base, SimpleBlockEnv):     # trainer.py:172-175
+            return SBWDefaultAgent()
+        if base is BlockEnv.partner_env or isinstance(base, BlockEnv):
+            return DefaultConstructorAgent()
         raise EnvException("No default policy available")
     agentarg = {}
     if args.tensorboard_log is not None:
@@ -232,14 +237,21 @@ def run_vectorised(args):
         raise EnvException("--n-envs supports the PPO-vs-PPO self-play pairing")
     if args.framestack > 1 or args.record is not None:
         raise EnvException("--n-envs cannot be combined with --framestack / --record")
+    block_variant = {"BlockEnv-v0": 0, "BlockEnv-v1": 1}.get(args.env)
     game = {"RPS-v0": VecRPS, "LiarsDice-v0": VecLiarsDice}.get(args.env)
-    if game is None:
+    if game is None and block_variant is None:
         raise EnvException(f"no device-resident form of {args.env}")
     E = int(args.n_envs)
-    spaces = type("Spaces", (), dict(observation_space=game.observation_space, action_space=game.action_space,
-                                     _is_dummy_space_env=True))()
+    if block_variant is not None:      # the planner and the constructor have spaces of their own
+        from .envs.vec import VecBlockSelfPlay, VecBlockWorld
+        seat_spaces = VecBlockWorld.seat_spaces(block_variant)
+    else:
+        spaces = type("Spaces", (), dict(observation_space=game.observation_space, action_space=game.action_space,
+                                         _is_dummy_space_env=True))()
+        seat_spaces = (spaces, spaces)
     models = []
     for offset, config in enumerate((dict(args.ego_config), dict(args.alt_config[0]))):
+        spaces = seat_spaces[offset]
         config.setdefault("n_steps", 128)
         config.setdefault("batch_size", max(64, E * config["n_steps"] // 4))
         config.update(env=spaces, device=args.device, n_envs=E)
@@ -256,6 +268,14 @@ def run_vectorised(args):
         env = VecRPS(E, models[0].policy.ctx, models[0].device)
         for _ in range(iterations):
             selfplay_iteration(env, ego, alt, n_steps)
+    elif block_variant is not None:
+        alt = RaggedVecOnPolicyAgent(models[1])
+        import random as _random
+        base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
+        world_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xB10CB10CB10C) & 0x7FFFFFFFFFFFFFFF      # a Philox key of the worlds' own
+        env = VecBlockSelfPlay(block_variant, E, ego, alt, seed=world_seed, **args.env_config)
+        for _ in range(iterations):
+            env.rollout_and_learn(n_steps)
     else:
         alt = RaggedVecOnPolicyAgent(models[1])
         # the dice get a Philox key of their own: keyed by the bare seed they would BE the ego's sampling uniforms (same key,
