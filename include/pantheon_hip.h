@@ -873,6 +873,45 @@ int ph_bc_train(ph_ctx *ctx, const ph_spec *spec, const ph_opt_state *opt, const
                 const float *acts /* (N,A) f32 */, const int *order /* (n_epochs, N) int32 */, int N, int batch_size,
                 int n_epochs, int max_batches, const ph_bc_hyper *hyper /* host */, float *stats);
 
+/* ---- MLP towers of a run-time shape (policy_kwargs net_arch; kernels: ph_arch.hip) ---------------------------------------
+ * SB3's MlpPolicy with net_arch = [dict(pi = W, vf = W)]: both towers the same list W of one to PH_ARCH_MAX_LAYERS widths, every
+ * width a multiple of 32 in [32, PH_ARCH_MAX_WIDTH], Tanh after every layer (the extractor loop is reference
+ * pantheonrl/algos/adap/policies.py:152-200), categorical heads.  Parameter vector, float32, input-major like ph_layout: policy
+ * tower W1 b1 .. Wn bn, value tower the same, act_W[w_n][L], act_b[L], val_W[w_n], val_b:
+ *   P = 2 * sum_l (in_l * w_l + w_l) + w_n * L + L + w_n + 1;  at widths (64, 64) every offset equals ph_layout_of's.
+ * The entry points take the arguments of ph_policy_forward / ph_ppo_minibatch_grad / ph_ppo_train plus the arch, and mean the same.
+ * gemm_mode: 0 = f32 MFMA, 1 = the same kernel's VALU fmaf instantiation (bitwise the same results), 2 = answered by mode 0.
+ * Gradient slabs are P floats per workgroup in parameter order; their allocation is capped (256 MiB per context), and the
+ * workgroup count of a gradient launch follows from the cap.  Box action spaces are refused. */
+#define PH_ARCH_MAX_LAYERS 3
+#define PH_ARCH_MAX_WIDTH 256
+typedef struct ph_arch {
+  int n_layers;
+  int width[PH_ARCH_MAX_LAYERS];   /* of both towers */
+} ph_arch;
+typedef struct ph_arch_layout {
+  int D, F, A, L, P;
+  int pi_W[PH_ARCH_MAX_LAYERS], pi_b[PH_ARCH_MAX_LAYERS], vf_W[PH_ARCH_MAX_LAYERS], vf_b[PH_ARCH_MAX_LAYERS];
+  int act_W, act_b, val_W, val_b;
+} ph_arch_layout;
+int ph_arch_layout_of(const ph_spec *spec /* host */, const ph_arch *arch /* host */, ph_arch_layout *out /* host */);
+/* dynamic LDS bytes of the gradient launch (rows_out: its tile height, 64 or 32) and of the forward launch for this spec and arch;
+ * host only */
+int ph_arch_lds_bytes(const ph_spec *spec /* host */, const ph_arch *arch /* host */, int *grad_bytes_out, int *grad_rows_out,
+                      int *fwd_bytes_out);
+int ph_arch_forward(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch /* host */, const float *params, const float *obs, int n,
+                    const unsigned char *action_mask, const float *uniforms, const float *given_actions,
+                    unsigned long long seed, unsigned long long counter, int deterministic, int *actions_i32,
+                    float *actions_f32, float *values, float *log_probs, float *entropy, float *logits,
+                    const ph_rollout *rb /* or NULL */, int pos, const float *episode_start_in,
+                    const float *pending_reward /* or NULL */, int gemm_mode);
+int ph_arch_minibatch_grad(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch /* host */, const float *params,
+                           const ph_rollout *rb, const ph_ppo_hyper *hyper /* host */, const int *indices, int nb,
+                           float *grad_out, float *stats_out, int gemm_mode);
+int ph_arch_train(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch /* host */, const ph_opt_state *opt, const ph_rollout *rb,
+                  const ph_ppo_hyper *hyper /* host */, int n_epochs, int batch_size, const int *perms,
+                  unsigned long long perm_seed, float *stats, int gemm_mode);
+
 /* ---- owning handle: one agent = its rollout buffer, weights and Adam state on the device ----------------------------------
  *   The pointer-level entry points above take device memory owned by the caller (the Python host uses torch
  * allocations).  This layer is the same path for a binder that has NO device runtime of its own: the handle owns every device

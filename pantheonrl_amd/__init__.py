@@ -7,7 +7,7 @@ without one (there is no CPU fallback).
 from . import _native  # noqa: F401
 from .common import (Agent, DummyEnv, MultiAgentEnv, Observation, OnPolicyAgent, PlayerException,  # noqa: F401
                      SimultaneousEnv, StaticPolicyAgent, TurnBasedEnv)
-from .ppo import PPO, ActorCriticPolicy, RolloutBuffer  # noqa: F401
+from .ppo import PPO, ActorCriticPolicy, ArchActorCriticPolicy, RolloutBuffer  # noqa: F401
 from .adap import ADAP, AdapAgent, AdapPolicy  # noqa: F401
 from .modular import ModularAlgorithm, ModularPolicy  # noqa: F401
 

@@ -44,6 +44,21 @@ class PhAdapMultLayout(C.Structure):
                                         "vf_Ws", "vf_bs", "vf_W2", "vf_b2", "act_W", "act_b", "val_W", "val_b")]
 
 
+PH_ARCH_MAX_LAYERS = 3
+PH_ARCH_MAX_WIDTH = 256
+
+
+class PhArch(C.Structure):
+    """ph_arch: the widths of both MLP towers (policy_kwargs net_arch)"""
+    _fields_ = [("n_layers", C.c_int), ("width", C.c_int * PH_ARCH_MAX_LAYERS)]
+
+
+class PhArchLayout(C.Structure):
+    _fields_ = ([(k, C.c_int) for k in ("D", "F", "A", "L", "P")] +
+                [(k, C.c_int * PH_ARCH_MAX_LAYERS) for k in ("pi_W", "pi_b", "vf_W", "vf_b")] +
+                [(k, C.c_int) for k in ("act_W", "act_b", "val_W", "val_b")])
+
+
 class PhRollout(C.Structure):
     _fields_ = [("T", C.c_int), ("E", C.c_int)] + [(k, C.c_void_p) for k in (
         "observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")]
@@ -294,6 +309,14 @@ SIGNATURES = {
     "ph_bench_train_kernels": [_vp, C.POINTER(PhSpec), C.POINTER(PhOptState), C.POINTER(PhRollout), C.POINTER(PhPpoHyper),
                                _i, _i, _i, _i, C.POINTER(C.c_float)],
     "ph_feistel_indices": [_i, _ull, _i, _i, _i, C.POINTER(_i)],
+    "ph_arch_layout_of": [C.POINTER(PhSpec), C.POINTER(PhArch), C.POINTER(PhArchLayout)],
+    "ph_arch_lds_bytes": [C.POINTER(PhSpec), C.POINTER(PhArch), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "ph_arch_forward": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _i, _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp, _vp,
+                        _vp, _vp, C.POINTER(PhRollout), _i, _vp, _vp, _i],
+    "ph_arch_minibatch_grad": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, C.POINTER(PhRollout), C.POINTER(PhPpoHyper), _vp,
+                               _i, _vp, _vp, _i],
+    "ph_arch_train": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), C.POINTER(PhOptState), C.POINTER(PhRollout),
+                      C.POINTER(PhPpoHyper), _i, _i, _vp, _ull, _vp, _i],
     "ph_bc_layout_of": [C.POINTER(PhSpec), C.POINTER(PhBcLayout)],
     "ph_bc_forward": [_vp, C.POINTER(PhSpec), _vp, _vp, _i, _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp, _vp, _vp],
     "ph_bc_train": [_vp, C.POINTER(PhSpec), C.POINTER(PhOptState), _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(PhBcHyper), _vp],
@@ -366,6 +389,28 @@ def layout_of(spec: PhSpec) -> PhLayout:
     lay = PhLayout()
     check(load().ph_layout_of(C.byref(spec), C.byref(lay)))
     return lay
+
+
+def make_arch(widths: Sequence[int]) -> PhArch:
+    """ph_arch of a tower width list; the library validates it (ph_arch_layout_of)"""
+    a = PhArch()
+    a.n_layers = len(widths)
+    for i, w in enumerate(list(widths)[:PH_ARCH_MAX_LAYERS]):
+        a.width[i] = int(w)
+    return a
+
+
+def arch_layout_of(spec: PhSpec, arch: PhArch) -> PhArchLayout:
+    lay = PhArchLayout()
+    check(load().ph_arch_layout_of(C.byref(spec), C.byref(arch), C.byref(lay)))
+    return lay
+
+
+def arch_lds_bytes(spec: PhSpec, arch: PhArch):
+    """-> (dynamic LDS bytes of the gradient launch, its tile height, dynamic LDS bytes of the forward launch)"""
+    g, r, f = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(load().ph_arch_lds_bytes(C.byref(spec), C.byref(arch), C.byref(g), C.byref(r), C.byref(f)))
+    return g.value, r.value, f.value
 
 
 def adapmult_layout_of(spec: PhSpec, context_size: int) -> PhAdapMultLayout:

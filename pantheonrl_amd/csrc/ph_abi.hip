@@ -16,6 +16,7 @@
 
 #include "ph_launch.h"
 #include "ph_block.h"
+#include "ph_arch.h"
 
 namespace ph {
 
@@ -1862,11 +1863,65 @@ struct MbPlan {
   int nb, ntiles, nwg;
 };
 
-MbPlan plan_minibatch(const ph_ctx* ctx, const ph::NetDims& nd, int nb) {
+// `arch`: the towers of a run-time shape (ph_arch.hip) plan their own tile height and workgroup count
+MbPlan plan_minibatch(const ph_ctx* ctx, const ph::NetDims& nd, int nb, const ph::ArchDims* arch = nullptr) {
   MbPlan p;
   p.nb = nb;
-  ph::grad_plan(nd, nb, ctx->num_cu, &p.ntiles, &p.nwg);
+  if (arch) ph::arch_grad_plan(nd, *arch, nb, ctx->num_cu, &p.ntiles, &p.nwg);
+  else ph::grad_plan(nd, nb, ctx->num_cu, &p.ntiles, &p.nwg);
   return p;
+}
+
+// ph_arch validated and resolved: offsets in the documented order (ph_arch_layout_of)
+int arch_layout(const ph_spec* spec, const ph_arch* arch, ph_arch_layout* o) {
+  if (!arch || !o) return fail("null arch/layout");
+  ph_layout base;
+  if (layout_of(spec, &base)) return 1;
+  if (spec->act.kind == PH_SPACE_BOX) return fail("net_arch towers are written for the categorical heads (Discrete / MultiDiscrete actions)");
+  if (arch->n_layers < 1 || arch->n_layers > PH_ARCH_MAX_LAYERS)
+    return fail("ph_arch: n_layers must be between 1 and PH_ARCH_MAX_LAYERS (3)");
+  for (int l = 0; l < arch->n_layers; ++l)
+    if (arch->width[l] < 32 || arch->width[l] > PH_ARCH_MAX_WIDTH || arch->width[l] % 32 != 0)
+      return fail("ph_arch: width " + std::to_string(arch->width[l]) + " of layer " + std::to_string(l + 1) +
+                  " is not a multiple of 32 in [32, PH_ARCH_MAX_WIDTH (256)]");
+  std::memset(o, 0, sizeof(*o));
+  o->D = base.D; o->F = base.F; o->A = base.A; o->L = base.L;
+  long long off = 0;
+  for (int net = 0; net < 2; ++net) {
+    int in = base.F;
+    for (int l = 0; l < arch->n_layers; ++l) {
+      const int w = arch->width[l];
+      (net == 0 ? o->pi_W : o->vf_W)[l] = (int)off; off += (long long)in * w;
+      (net == 0 ? o->pi_b : o->vf_b)[l] = (int)off; off += w;
+      in = w;
+    }
+  }
+  const int wn = arch->width[arch->n_layers - 1];
+  o->act_W = (int)off; off += (long long)wn * base.L;
+  o->act_b = (int)off; off += base.L;
+  o->val_W = (int)off; off += wn;
+  o->val_b = (int)off; off += 1;
+  if (off >= (1ll << 31)) return fail("ph_arch: parameter count must fit in int32");
+  o->P = (int)off;
+  return 0;
+}
+
+// spec and arch resolved for the tower kernels: nd as `resolve` leaves it, minus every table of the 64-wide gradient kernels,
+// with lay.P the ARCH's parameter count (slab length, reduce / Adam extent)
+int arch_resolve(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, ph::NetDims* nd, ph::ArchDims* ad) {
+  std::memset(ad, 0, sizeof(*ad));
+  if (arch_layout(spec, arch, &ad->lay)) return 1;
+  if (resolve(ctx, spec, nd, false)) return 1;
+  ad->nl = arch->n_layers;
+  for (int l = 0; l < arch->n_layers; ++l) ad->w[l] = arch->width[l];
+  nd->slab_map = nd->slab_map_split = nd->wimage_map = nullptr;
+  nd->split = nd->split_kind = 0;
+  nd->lay.P = ad->lay.P;
+  // the smallest carve (32-row tiles: the forward launch, and the gradient launch's fall-back) must fit the CU's LDS
+  if (ph::arch_grad_lds_bytes(*nd, *ad, ph::ARCH_FWD_ROWS) > ph::ARCH_LDS_MAX)
+    return fail("ph_arch: observation space too large for the tower kernels' LDS tile (" +
+                std::to_string(ph::arch_grad_lds_bytes(*nd, *ad, ph::ARCH_FWD_ROWS)) + " bytes at 32 rows, 163840 available)");
+  return 0;
 }
 
 void fill_grad_args(ph::GradArgs& g, const ph::NetDims& nd, const float* params, const ph_rollout* rb,
@@ -2005,6 +2060,8 @@ struct TrainPlan {
   int n_epochs, batch_size, gemm_mode, N, n_mb, P;
   uint32_t hb;
   const ph_adap_loss* adap = nullptr;   // ADAP's context term, or null = plain PPO
+  bool arch = false;                    // towers of a run-time shape: arch_dims is set, the gradient launch is ph_arch.hip's
+  ph::ArchDims arch_dims;
 };
 
 // ---- ADAP's context term: validation, workspace, the launch next to a minibatch's gradient launch ----
@@ -2085,10 +2142,15 @@ void train_adv_args(const TrainPlan& t, bool need_idx, ph::AdvStatArgs& aa) {
 // validation, workspace, stop-flag reset and the advantage statistics / minibatch order of every minibatch
 int train_prepare(const char* who, TrainPlan& t, ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb,
                   const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms, unsigned long long perm_seed,
-                  float* stats, int gemm_mode, bool need_idx = false) {
+                  float* stats, int gemm_mode, bool need_idx = false, const ph_arch* arch = nullptr) {
   if (check_train_call(who, ctx, opt, hp, n_epochs, batch_size) || check_rb(rb)) return 1;
-  if (resolve(ctx, spec, &t.nd, true)) return 1;
-  select_gemm(t.nd, gemm_mode);
+  t.arch = arch != nullptr;
+  if (arch) {
+    if (arch_resolve(ctx, spec, arch, &t.nd, &t.arch_dims)) return 1;
+  } else {
+    if (resolve(ctx, spec, &t.nd, true)) return 1;
+    select_gemm(t.nd, gemm_mode);
+  }
   t.ctx = ctx;
   t.opt = opt;
   t.rb = rb;
@@ -2102,7 +2164,7 @@ int train_prepare(const char* who, TrainPlan& t, ph_ctx* ctx, const ph_spec* spe
   t.N = rb->T * rb->E;
   t.n_mb = (t.N + batch_size - 1) / batch_size;
   t.P = t.nd.lay.P;
-  const MbPlan big = plan_minibatch(ctx, t.nd, batch_size < t.N ? batch_size : t.N);
+  const MbPlan big = plan_minibatch(ctx, t.nd, batch_size < t.N ? batch_size : t.N, t.arch ? &t.arch_dims : nullptr);
   if (ensure_train_ws(ctx, t.P, slab_len_of(t.nd), big.nwg, n_epochs * t.n_mb, perms ? 0 : (size_t)n_epochs * t.N,
                       (size_t)n_epochs * t.N))
     return 1;
@@ -2125,7 +2187,7 @@ int train_launch_grad(const TrainPlan& t, int mbi, MbPlan* pl_out) {
   ph_ctx* ctx = t.ctx;
   const MbWalk w = minibatch_walk(ctx, t.perms, t.N, t.n_mb, t.batch_size, mbi);
   const size_t pos = (size_t)w.ep * t.N + w.start;   // of the minibatch's first row in the call's (n_epochs, N) order
-  const MbPlan pl = plan_minibatch(ctx, t.nd, w.nb);
+  const MbPlan pl = plan_minibatch(ctx, t.nd, w.nb, t.arch ? &t.arch_dims : nullptr);
   ph::GradArgs g;
   std::memset(&g, 0, sizeof(g));
   fill_grad_args(g, t.nd, t.opt->params, t.rb, t.hp, ctx);
@@ -2145,7 +2207,8 @@ int train_launch_grad(const TrainPlan& t, int mbi, MbPlan* pl_out) {
   g.advstats = ctx->advstats + 2 * (size_t)mbi;
   g.ntiles = pl.ntiles;
   *pl_out = pl;
-  PH_HIP(ph::launch_ppo_grad(g, pl.nwg, t.gemm_mode, ctx->stream));
+  if (t.arch) PH_HIP(ph::launch_arch_grad(g, t.arch_dims, pl.nwg, t.gemm_mode, ctx->stream));
+  else PH_HIP(ph::launch_ppo_grad(g, pl.nwg, t.gemm_mode, ctx->stream));
   return 0;
 }
 
@@ -2183,9 +2246,9 @@ int train_launch_step(const TrainPlan& t, int mbi, const MbPlan& pl) {
 namespace {
 int train_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const ph_rollout* rb,
               const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms, unsigned long long perm_seed, float* stats,
-              int gemm_mode, const ph_adap_loss* adap) {
+              int gemm_mode, const ph_adap_loss* adap, const ph_arch* arch = nullptr) {
   TrainPlan t;
-  if (train_prepare(who, t, ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, adap != nullptr))
+  if (train_prepare(who, t, ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, adap != nullptr, arch))
     return 1;
   if (adap && t.nd.gauss) return fail("ph_adap_train: the context term is written for the categorical heads");
   if (adap && adap_check(ctx, t.nd, adap, "ph_adap_train")) return 1;
@@ -2257,7 +2320,7 @@ int ph_ppo_train_multi(const ph_train_call* calls, int n_calls) {
 namespace {
 int minibatch_grad_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb,
                        const ph_ppo_hyper* hp, const int* indices, int nb, float* grad_out, float* stats_out, int gemm_mode,
-                       const ph_adap_loss* adap);
+                       const ph_adap_loss* adap, const ph_arch* arch = nullptr);
 }  // namespace
 
 int ph_ppo_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb,
@@ -2278,13 +2341,18 @@ int ph_adap_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const float* params
 namespace {
 int minibatch_grad_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const float* params, const ph_rollout* rb,
                        const ph_ppo_hyper* hp, const int* indices, int nb, float* grad_out, float* stats_out, int gemm_mode,
-                       const ph_adap_loss* adap) {
+                       const ph_adap_loss* adap, const ph_arch* arch) {
   if (check_minibatch_call(who, ctx, params, rb, hp, indices, nb, grad_out)) return 1;
   ph::NetDims nd;
-  if (resolve(ctx, spec, &nd, adap == nullptr)) return 1;
-  select_gemm(nd, gemm_mode);
+  ph::ArchDims ad;
+  if (arch) {
+    if (arch_resolve(ctx, spec, arch, &nd, &ad)) return 1;
+  } else {
+    if (resolve(ctx, spec, &nd, adap == nullptr)) return 1;
+    select_gemm(nd, gemm_mode);
+  }
   const int P = nd.lay.P;
-  const MbPlan pl = plan_minibatch(ctx, nd, nb);
+  const MbPlan pl = plan_minibatch(ctx, nd, nb, arch ? &ad : nullptr);
   if (ensure_train_ws(ctx, P, slab_len_of(nd), pl.nwg, 1, 0, (size_t)nb)) return 1;
   hipStream_t s = ctx->stream;
   PH_HIP(ph::launch_set_int(ctx->stop_flag, 0, s));
@@ -2301,7 +2369,8 @@ int minibatch_grad_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const 
   g.nb = nb;
   g.advstats = ctx->advstats;
   g.ntiles = pl.ntiles;
-  PH_HIP(ph::launch_ppo_grad(g, pl.nwg, gemm_mode, s));
+  if (arch) PH_HIP(ph::launch_arch_grad(g, ad, pl.nwg, gemm_mode, s));
+  else PH_HIP(ph::launch_ppo_grad(g, pl.nwg, gemm_mode, s));
   ph::ReduceArgs r = reduce_args(ctx, hp, nullptr, P, slab_len_of(nd), nd.slab_map, pl.nwg, nb, grad_out, stats_out);
   if (adap) {
     if (adap_check(ctx, nd, adap, who)) return 1;
@@ -2311,6 +2380,78 @@ int minibatch_grad_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const 
   return 0;
 }
 }  // namespace
+
+// ---- MLP towers of a run-time shape (policy_kwargs net_arch; kernels: ph_arch.hip) ------------------------------------------------
+int ph_arch_layout_of(const ph_spec* spec, const ph_arch* arch, ph_arch_layout* out) { return arch_layout(spec, arch, out); }
+
+int ph_arch_lds_bytes(const ph_spec* spec, const ph_arch* arch, int* grad_bytes_out, int* grad_rows_out, int* fwd_bytes_out) {
+  ph::ArchDims ad;
+  std::memset(&ad, 0, sizeof(ad));
+  if (arch_layout(spec, arch, &ad.lay)) return 1;
+  ad.nl = arch->n_layers;
+  for (int l = 0; l < arch->n_layers; ++l) ad.w[l] = arch->width[l];
+  ph::NetDims nd;
+  std::memset(&nd, 0, sizeof(nd));
+  nd.obs_kind = spec->obs.kind;
+  nd.D = ad.lay.D;
+  nd.nchunk = (ad.lay.F + PH_HIDDEN - 1) / PH_HIDDEN;
+  const int R = ph::arch_grad_rows(nd, ad);
+  if (grad_bytes_out) *grad_bytes_out = (int)ph::arch_grad_lds_bytes(nd, ad, R);
+  if (grad_rows_out) *grad_rows_out = R;
+  if (fwd_bytes_out) *fwd_bytes_out = (int)ph::arch_fwd_lds_bytes(nd, ad);
+  return 0;
+}
+
+int ph_arch_forward(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs, int n,
+                    const unsigned char* action_mask, const float* uniforms, const float* given_actions,
+                    unsigned long long seed, unsigned long long counter, int deterministic, int* actions_i32,
+                    float* actions_f32, float* values, float* log_probs, float* entropy, float* logits,
+                    const ph_rollout* rb, int pos, const float* episode_start_in, const float* pending_reward, int gemm_mode) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!params || !obs) return fail("ph_arch_forward: null params/obs");
+  if ((uintptr_t)params % 16 != 0) return fail("ph_arch_forward: params must be 16-byte aligned");
+  if (n <= 0) return fail("ph_arch_forward: n must be positive");
+  ph::FwdArgs a;
+  ph::ArchDims ad;
+  std::memset(&a, 0, sizeof(a));
+  if (arch_resolve(ctx, spec, arch, &a.nd, &ad)) return 1;
+  a.params = params;
+  a.obs = obs;
+  a.n = n;
+  a.seed = seed;
+  a.counter = counter;
+  a.epoch = ctx->rng_epoch;
+  a.act_i32 = actions_i32;
+  a.values = values;
+  a.logp = log_probs;
+  a.mask = action_mask;
+  a.uniforms = uniforms;
+  a.given_actions = given_actions;
+  a.deterministic = deterministic;
+  a.act_f32 = actions_f32;
+  a.entropy = entropy;
+  a.logits = logits;
+  if (fwd_bind_row("ph_arch_forward", a, rb, pos, episode_start_in, pending_reward)) return 1;
+  PH_HIP(ph::launch_arch_fwd(a, ad, gemm_mode, ctx->stream));
+  return 0;
+}
+
+int ph_arch_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const ph_rollout* rb,
+                           const ph_ppo_hyper* hp, const int* indices, int nb, float* grad_out, float* stats_out, int gemm_mode) {
+  DevGuard dev_guard(ctx);
+  if (!arch) return fail("ph_arch_minibatch_grad: null arch");
+  return minibatch_grad_run("ph_arch_minibatch_grad", ctx, spec, params, rb, hp, indices, nb, grad_out, stats_out, gemm_mode, nullptr,
+                            arch);
+}
+
+int ph_arch_train(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const ph_opt_state* opt, const ph_rollout* rb,
+                  const ph_ppo_hyper* hp, int n_epochs, int batch_size, const int* perms, unsigned long long perm_seed, float* stats,
+                  int gemm_mode) {
+  DevGuard dev_guard(ctx);
+  if (!arch) return fail("ph_arch_train: null arch");
+  return train_run("ph_arch_train", ctx, spec, opt, rb, hp, n_epochs, batch_size, perms, perm_seed, stats, gemm_mode, nullptr, arch);
+}
 
 // ---- AdapPolicyMult (adap/policies.py:136-283; kernels: ph_adapmult.hip) ------------------------------------------------------
 int ph_adapmult_layout_of(const ph_spec* spec, int C, ph_adapmult_layout* o) {

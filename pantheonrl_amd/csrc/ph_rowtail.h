@@ -1,6 +1,6 @@
 // Per-row tails of the policy forward shared by the forward kernels (ph_policy.hip) and the ModularPolicy action kernel
 // (ph_modular.hip): rollout-buffer row addressing, the stamp-in-band word poll, the value-side row write with the late reward,
-// the observation copy of RolloutBuffer.add, and the Discrete (<= 8 logits) distribution tail.
+// the observation copy of RolloutBuffer.add, the Discrete (<= 8 logits) distribution tail and the general one (also: ph_arch.hip).
 #pragma once
 #include "ph_launch.h"
 
@@ -247,6 +247,102 @@ __device__ __forceinline__ int discrete8_row_tail(const FwdArgs& a, const NetDim
     }
   }
   return env_act;
+}
+
+// General action head of one row, one lane per row, the row's logits z[0..L) in LDS (modified in place): optional mask
+// offset, logits output, then per action component sampling / argmax / given action, log-prob, entropy and the
+// rollout-buffer writes (Discrete and MultiDiscrete; Discrete with <= 8 logits takes the register path)
+__device__ __forceinline__ void general_row_tail(const FwdArgs& a, const NetDims& nd, int g, float* z, uint64_t ctr) {
+  const bool small = !nd.gauss && nd.A == 1 && nd.L <= 8;
+  if (a.mask && !small) {  // modular/policies.py:330-333 : logits - 30*(~mask)
+    for (int k = 0; k < nd.L; ++k) z[k] = z[k] - 30.0f * (1.0f - (float)(a.mask[(size_t)g * nd.L + k] != 0));
+  }
+  if (a.logits && !small)
+    for (int k = 0; k < nd.L; ++k) a.logits[(size_t)g * nd.L + k] = z[k];
+  float logp = 0.f, ent = 0.f;
+  if (nd.gauss) {
+    // Box action space: SB3's DiagGaussianDistribution -- z[0..A) are the means, log_std[A] follows val_b in the parameter vector.
+    // action = mean + exp(log_std) * eps; log-prob and entropy are the sums over the dimensions of Normal's.  `uniforms` carries
+    // the STANDARD-NORMAL draws eps when given (teacher forcing), else Box-Muller over two Philox uniforms per dimension.
+    const float* ls = a.params + nd.lay.val_b + 1;
+    for (int c = 0; c < nd.A; ++c) {
+      const float mu = z[c], lsd = ls[c];
+      float act;
+      if (a.given_actions) act = a.given_actions[(size_t)g * nd.A + c];
+      else if (a.deterministic) act = mu;
+      else {
+        float eps;
+        if (a.uniforms) eps = a.uniforms[(size_t)g * nd.A + c];
+        else {
+          const float u1 = philox_uniform(a.seed, ctr, (uint32_t)g, (uint32_t)c);
+          const float u2 = philox_uniform(a.seed, ctr, (uint32_t)g, (uint32_t)(c + 128));
+          eps = __builtin_sqrtf(-2.0f * fast_log(fmaxf(u1, 1.0e-30f))) * __builtin_cosf(6.28318530717958647692f * u2);
+        }
+        act = mu + fast_exp(lsd) * eps;
+      }
+      const float d = (act - mu) * fast_exp(-lsd);
+      logp += (-0.5f * d * d - lsd) - 0.91893853320467274178f;   // - log sqrt(2 pi)
+      ent += 1.41893853320467274178f + lsd;                       // 0.5 + 0.5 log(2 pi) + log_std
+      if (a.act_f32) a.act_f32[(size_t)g * nd.A + c] = act;
+      if (a.rb_act) {
+        const long long ridx = rb_row(a, g);
+        if (ridx >= 0) a.rb_act[(size_t)ridx * nd.A + c] = act;
+      }
+    }
+  } else if (small) {
+    // fast path (Discrete action space, <= 8 logits): the row lives in registers, one exp per logit
+    float zr[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) zr[k] = (k < nd.L) ? z[k] : 0.f;
+    discrete8_row_tail(a, nd, g, zr, fwd_counter(a));
+    return;
+  } else
+  for (int c = 0; c < nd.A; ++c) {
+    const int lo = nd.act_off[c], nk = nd.act_off[c + 1] - lo;
+    float m = z[lo];
+    for (int k = 1; k < nk; ++k) m = fmaxf(m, z[lo + k]);
+    float se = 0.f;
+    for (int k = 0; k < nk; ++k) se += fast_exp(z[lo + k] - m);
+    const float lse = m + fast_log(se);
+    int act;
+    if (a.given_actions) {
+      act = (int)a.given_actions[(size_t)g * nd.A + c];
+      act = act < 0 ? 0 : (act >= nk ? nk - 1 : act);
+    } else if (a.deterministic) {
+      act = 0;
+      float best = z[lo];
+      for (int k = 1; k < nk; ++k)
+        if (z[lo + k] > best) { best = z[lo + k]; act = k; }
+    } else {
+      const float u = a.uniforms ? a.uniforms[(size_t)g * nd.A + c]
+                                 : philox_uniform(a.seed, ctr, (uint32_t)g, (uint32_t)c);
+      float cum = 0.f;
+      act = 0;
+      for (int k = 0; k < nk - 1; ++k) {  // inverse CDF: count prefix sums <= u
+        cum += fast_exp(z[lo + k] - lse);
+        act += (u >= cum) ? 1 : 0;
+      }
+    }
+    float e = 0.f;
+    for (int k = 0; k < nk; ++k) {
+      const float lp = z[lo + k] - lse;
+      e -= fast_exp(lp) * lp;
+    }
+    logp += z[lo + act] - lse;
+    ent += e;
+    if (a.act_i32) a.act_i32[(size_t)g * nd.A + c] = act;
+    if (a.act_f32) a.act_f32[(size_t)g * nd.A + c] = (float)act;
+    if (a.rb_act) {
+      const long long ridx = rb_row(a, g);
+      if (ridx >= 0) a.rb_act[(size_t)ridx * nd.A + c] = (float)act;
+    }
+  }
+  if (a.logp) a.logp[g] = logp;
+  if (a.entropy) a.entropy[g] = ent;
+  if (a.rb_logp) {
+    const long long ridx = rb_row(a, g);
+    if (ridx >= 0) a.rb_logp[ridx] = logp;
+  }
 }
 
 }  // namespace ph

@@ -18,6 +18,7 @@ import torch as th
 
 from .. import _native as nat
 from ..spaces import Discrete, MultiDiscrete
+from ..ppo import require_mlp_kernels
 from ..vec import VecOnPolicyAgent
 
 
@@ -106,6 +107,7 @@ class RaggedVecOnPolicyAgent:
     def __init__(self, model):
         self.model = model
         pol, rb = model.policy, model.rollout_buffer
+        require_mlp_kernels(pol, type(self).__name__)     # ph_policy_forward_ragged and the self-play steps read a ph_layout vector
         E, lay, dev = rb.n_envs, pol.layout, pol.device
         self.E, self.T = E, rb.buffer_size
         u8 = lambda v: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731

@@ -313,12 +313,16 @@ class ActorCriticPolicy:
         es = None if episode_start is None else _f32_dev(episode_start, dev, (n,))
         self._bind()
         self._counter += 1
-        nat.check(self.ctx.lib.ph_policy_forward(
-            self.ctx.handle, C.byref(self.spec), self.params.data_ptr(), obs_t.data_ptr(), n, nat.ptr(m), nat.ptr(u),
+        nat.check(self._native_forward(
+            self.params.data_ptr(), obs_t.data_ptr(), n, nat.ptr(m), nat.ptr(u),
             nat.ptr(g), self._seed, self._counter, int(bool(deterministic)), acts.data_ptr(), None, values.data_ptr(),
             logp.data_ptr(), nat.ptr(ent), nat.ptr(logits), C.byref(rb.c_struct()) if rb is not None else None,
             int(pos), nat.ptr(es), None, int(self.gemm_mode)))
         return acts, values, logp, ent, logits
+
+    def _native_forward(self, *args) -> int:
+        """the forward entry point of this policy's network: ph_policy_forward's arguments after the spec"""
+        return self.ctx.lib.ph_policy_forward(self.ctx.handle, C.byref(self.spec), *args)
 
     def _shape_actions(self, acts: th.Tensor) -> th.Tensor:
         # SB3: actions.reshape((-1,) + action_space.shape); Discrete has shape ()
@@ -469,6 +473,75 @@ class GaussianActorCriticPolicy(ActorCriticPolicy):
         raise nat.NativeError("GaussianActorCriticPolicy: the one-call host step returns integer actions; use forward_and_store")
 
 
+class ArchActorCriticPolicy(ActorCriticPolicy):
+    """SB3's MlpPolicy with `policy_kwargs=dict(net_arch=[dict(pi=W, vf=W)])`: both towers the same list W of one to three widths,
+    each a multiple of 32 up to 256, Tanh after every layer (the extractor loop: reference pantheonrl/algos/adap/policies.py:152-200),
+    categorical heads.  Parameters: one flat input-major vector in ph_arch_layout order -- at (64, 64) the offsets of
+    ActorCriticPolicy's.  Runs on the tower kernels of a run-time shape (ph_arch_forward / ph_arch_train); the one-launch rollouts,
+    the 16-row forwards, the vectorised agents, train_joint and the exchange engines are built around 64-wide blocks and refuse it
+    through require_mlp_kernels."""
+
+    host_step_path = False
+    fused_mlp_kernels = False
+
+    def __init__(self, observation_space, action_space, net_arch: Sequence[int] = (64, 64), **kwargs):
+        self.net_arch = check_tower_widths(net_arch, net_arch)
+        self.arch = nat.make_arch(self.net_arch)
+        super().__init__(observation_space, action_space, **kwargs)
+
+    def _tensors(self):
+        """(SB3 module name, weight offset, bias offset, fan-in, fan-out, init gain) in SB3's module order"""
+        lay, ws, out = self.layout, self.net_arch, []
+        for tower, oW, ob in (("policy_net", lay.pi_W, lay.pi_b), ("value_net", lay.vf_W, lay.vf_b)):
+            fin = lay.F
+            for l, w in enumerate(ws):
+                out.append((f"mlp_extractor.{tower}.{2 * l}", oW[l], ob[l], fin, w, np.sqrt(2)))
+                fin = w
+        out.append(("action_net", lay.act_W, lay.act_b, ws[-1], lay.L, 0.01))
+        out.append(("value_net", lay.val_W, lay.val_b, ws[-1], 1, 1.0))
+        return out
+
+    def _shapes(self):
+        return {mod: (fin, fout) for mod, _, _, fin, fout, _ in self._tensors()}
+
+    def _init_weights(self, ortho_init: bool) -> None:
+        """orthogonal init with SB3's gains in SB3's module order (modular/policies.py:229-241); host-side, once."""
+        self.layout = nat.arch_layout_of(self.spec, self.arch)
+        P = self.layout.P
+        if self.params.numel() != P:
+            self.params = th.zeros(P, dtype=th.float32, device=self.device)
+            self.adam_m, self.adam_v = th.zeros_like(self.params), th.zeros_like(self.params)
+        flat = th.zeros(P, dtype=th.float32)
+        for _, woff, _, fin, fout, gain in self._tensors():
+            w = th.empty(fout, fin)
+            if ortho_init:
+                th.nn.init.orthogonal_(w, gain=gain)
+            else:
+                th.nn.init.kaiming_uniform_(w, a=np.sqrt(5))
+            flat[woff:woff + fin * fout] = w.t().contiguous().reshape(-1)
+        self.params.copy_(flat)
+
+    def state_dict(self) -> Dict[str, th.Tensor]:
+        flat, out = self.params.detach().cpu(), {}
+        for mod, woff, boff, fin, fout, _ in self._tensors():
+            out[mod + ".weight"] = flat[woff:woff + fin * fout].reshape(fin, fout).t().contiguous()
+            out[mod + ".bias"] = flat[boff:boff + fout].clone()
+        return out
+
+    def load_state_dict(self, sd: Dict[str, th.Tensor]) -> None:
+        flat = th.zeros(self.layout.P)
+        for mod, woff, boff, fin, fout, _ in self._tensors():
+            flat[woff:woff + fin * fout] = th.as_tensor(sd[mod + ".weight"]).float().reshape(fout, fin).t().reshape(-1)
+            flat[boff:boff + fout] = th.as_tensor(sd[mod + ".bias"]).float().reshape(-1)
+        self.params.copy_(flat)
+
+    def _native_forward(self, *args) -> int:
+        return self.ctx.lib.ph_arch_forward(self.ctx.handle, C.byref(self.spec), C.byref(self.arch), *args)
+
+    def forward_and_store_host(self, *a, **k):
+        raise nat.NativeError("ArchActorCriticPolicy: the one-call host step belongs to the 64-wide kernels; use forward_and_store")
+
+
 def require_mlp_kernels(policy, who: str) -> None:
     """refuse a policy whose parameter vector is not the plain MLP's before an engine path would read it as one"""
     if not getattr(policy, "fused_mlp_kernels", True):
@@ -509,19 +582,38 @@ class UnsupportedPolicyConfig(ValueError):
     asks for a network the gfx950 kernels do not implement.  Raised at construction, never at the first forward."""
 
 
+_NET_ARCH_RULE = ("the MI355X engine implements net_arch=[dict(pi=W, vf=W)] (or the bare dict): separate towers with the SAME "
+                  "list W of one to three widths, every width a multiple of 32 between 32 and 256 (SB3 1.7.0's default is "
+                  "W = [64, 64], reference pantheonrl/algos/modular/policies.py:112-114); shared trunk layers, unequal towers, "
+                  "deeper towers and other widths are not implemented")
+
+
+def check_tower_widths(widths, shown) -> Tuple[int, ...]:
+    """one tower's width list -> tuple of ints, or UnsupportedPolicyConfig naming net_arch"""
+    ok = isinstance(widths, (list, tuple)) and 1 <= len(widths) <= nat.PH_ARCH_MAX_LAYERS and all(
+        isinstance(w, (int, np.integer)) and not isinstance(w, bool) and 32 <= int(w) <= nat.PH_ARCH_MAX_WIDTH and int(w) % 32 == 0
+        for w in widths)
+    if not ok:
+        raise UnsupportedPolicyConfig(f"policy_kwargs['net_arch'] = {shown!r}: {_NET_ARCH_RULE}")
+    return tuple(int(w) for w in widths)
+
+
 def check_policy_kwargs(policy_kwargs: Optional[Dict[str, Any]]) -> Dict[str, Any]:
-    """What the kernels implement is SB3 1.7.0's MlpPolicy default and nothing else: FlattenExtractor, separate towers
-    `net_arch=[dict(pi=[64, 64], vf=[64, 64])]`, Tanh, no gSDE (modular/policies.py:112-114,214-218).  `policy_kwargs` may restate that
-    default (and pick `ortho_init`); any other entry is refused by name.  -> the keyword arguments for ActorCriticPolicy"""
+    """What the kernels implement of SB3 1.7.0's MlpPolicy: FlattenExtractor, separate towers `net_arch=[dict(pi=W, vf=W)]` of equal
+    shape (check_tower_widths), Tanh, no gSDE (modular/policies.py:112-114,214-218).  `policy_kwargs` may restate the default
+    W = [64, 64] (and pick `ortho_init`); any other entry is refused by name.  -> the keyword arguments for the policy class: a
+    non-default W arrives as `net_arch=(w1, ..)` and selects ArchActorCriticPolicy, the default adds nothing"""
     out: Dict[str, Any] = {}
     for key, val in dict(policy_kwargs or {}).items():
         if key == "net_arch":
             arch = val[0] if isinstance(val, (list, tuple)) and len(val) == 1 else val
-            ok = isinstance(arch, dict) and sorted(arch) == ["pi", "vf"] and all(list(arch[k]) == [64, 64] for k in ("pi", "vf"))
-            if not ok:
-                raise UnsupportedPolicyConfig(
-                    f"policy_kwargs['net_arch'] = {val!r}: the MI355X engine implements net_arch=[dict(pi=[64, 64], vf=[64, 64])] "
-                    "only (SB3 1.7.0's MlpPolicy default, reference pantheonrl/algos/modular/policies.py:112-114)")
+            if not (isinstance(arch, dict) and sorted(arch) == ["pi", "vf"]):
+                raise UnsupportedPolicyConfig(f"policy_kwargs['net_arch'] = {val!r}: {_NET_ARCH_RULE}")
+            pi, vf = check_tower_widths(arch["pi"], val), check_tower_widths(arch["vf"], val)
+            if pi != vf:
+                raise UnsupportedPolicyConfig(f"policy_kwargs['net_arch'] = {val!r}: {_NET_ARCH_RULE}")
+            if pi != (HID, HID):
+                out["net_arch"] = pi
         elif key == "activation_fn":
             name = val if isinstance(val, str) else getattr(val, "__name__", repr(val))
             if name.lower() != "tanh":
@@ -574,6 +666,12 @@ class PPO:
         self._policy_args = check_policy_kwargs(policy_kwargs)
         if env is not None and hasattr(env, "action_space"):
             check_action_space(env.action_space)
+        if "net_arch" in self._policy_args and (type(self) is not PPO or (
+                env is not None and type(getattr(env, "action_space", None)).__name__ == "Box")):
+            raise UnsupportedPolicyConfig(
+                f"policy_kwargs['net_arch'] = {list(self._policy_args['net_arch'])!r}: towers other than [64, 64] run on PPO with a "
+                f"categorical head (Discrete / MultiDiscrete actions) only, not on {type(self).__name__}"
+                + (" with a Box action space" if type(self) is PPO else ""))
         self.device = _require_cuda(device)
         self.learning_rate, self.n_steps, self.batch_size, self.n_epochs = learning_rate, n_steps, batch_size, n_epochs
         self.gamma, self.gae_lambda, self.clip_range, self.clip_range_vf = gamma, gae_lambda, clip_range, clip_range_vf
@@ -619,7 +717,14 @@ class PPO:
 
     def _setup_model(self) -> None:
         check_action_space(self.action_space)
+        args = getattr(self, "_policy_args", {})
         policy_cls = GaussianActorCriticPolicy if type(self.action_space).__name__ == "Box" else ActorCriticPolicy
+        if "net_arch" in args:
+            if policy_cls is not ActorCriticPolicy or type(self) is not PPO:
+                raise UnsupportedPolicyConfig(
+                    f"policy_kwargs['net_arch'] = {list(args['net_arch'])!r}: towers other than [64, 64] run on PPO with a "
+                    "categorical head (Discrete / MultiDiscrete actions) only")
+            policy_cls = ArchActorCriticPolicy
         self.policy = policy_cls(self.observation_space, self.action_space, lr=self.learning_rate,
                                  device=self.device, seed=self.seed, sampling_stream=self.sampling_stream,
                                  **getattr(self, "_policy_args", {}))
@@ -717,6 +822,11 @@ class PPO:
 
     def _train_native(self, pol, opt, rb, hp, perm_t, stats) -> None:
         """the update itself; subclasses with an additional loss term (ADAP) issue their own entry point here"""
+        if isinstance(pol, ArchActorCriticPolicy):
+            nat.check(pol.ctx.lib.ph_arch_train(pol.ctx.handle, C.byref(pol.spec), C.byref(pol.arch), C.byref(opt),
+                                                C.byref(rb.c_struct()), C.byref(hp), int(self.n_epochs), int(self.batch_size),
+                                                nat.ptr(perm_t), int(self.permutation_seed), stats.data_ptr(), int(pol.gemm_mode)))
+            return
         if not getattr(pol, "gaussian_head", False):
             require_mlp_kernels(pol, "PPO.train")
         nat.check(pol.ctx.lib.ph_ppo_train(pol.ctx.handle, C.byref(pol.spec), C.byref(opt), C.byref(rb.c_struct()),
@@ -915,6 +1025,8 @@ class PPO:
                     action_space=self._space_to_json(self.action_space), num_timesteps=self.num_timesteps,
                     _n_updates=self._n_updates, format="pantheonrl_amd-1", extra=self._extra_state())
         pol = self.policy
+        if isinstance(pol, ArchActorCriticPolicy):      # absent key = the default [64, 64] towers
+            data["net_arch"] = list(pol.net_arch)
         with zipfile.ZipFile(path, "w") as zf:
             zf.writestr("data", json.dumps(data))
             b = io.BytesIO()
@@ -943,6 +1055,15 @@ class PPO:
             opt = th.load(io.BytesIO(zf.read("policy.optimizer.pth")), map_location="cpu")
         hp = {k: data[k] for k in cls._HP if k in data}
         hp.update(kwargs)
+        if data.get("net_arch") is not None:
+            # the checkpoint's towers join the caller's policy_kwargs (ortho_init, ...); a caller who names OTHER towers is refused
+            w = [int(x) for x in data["net_arch"]]
+            pk = dict(hp.get("policy_kwargs") or {})
+            if "net_arch" in pk and check_policy_kwargs({"net_arch": pk["net_arch"]}).get("net_arch", (HID, HID)) != tuple(w):
+                raise UnsupportedPolicyConfig(f"policy_kwargs['net_arch'] = {pk['net_arch']!r} does not match the checkpoint's towers "
+                                              f"{w} ({path})")
+            pk["net_arch"] = [dict(pi=w, vf=w)]
+            hp["policy_kwargs"] = pk
         model = cls(env=None, device=device, **hp)
         model.observation_space = cls._space_from_json(data["observation_space"])
         model.action_space = cls._space_from_json(data["action_space"])

@@ -1,0 +1,429 @@
+"""-m gpu: `policy_kwargs net_arch` -- the tower kernels of a run-time shape (ph_arch.hip) through ArchActorCriticPolicy and PPO
+against the CPU checker of tests/arch_oracle.py.
+
+Tolerances are the project's own (tests/test_gpu_parity.py), none new:
+  * logits / values / log-probs / entropy: 2e-5 * s, s = max(1, w_last / 64).  The scale is derived, not measured: a head output is a
+    sum over w_last latents whose errors (float32 rounding, fast_tanh's 2e-7 absolute) add linearly in the worst case, and 2e-5 is
+    what the project allows at 64 latents.
+  * teacher-forced actions equal the checker's except rows whose uniform lies within 1e-5 * s of a CDF edge (at most
+    max(2, 0.02 n) such rows); deterministic actions equal where the top-2 logit gap exceeds 1e-4 * s.
+  * gradients: 1e-6 + 2e-4 of the largest entry; loss statistics 1e-5 + 1e-4 relative; post-Adam weights 2e-6 per step + 1e-6.
+  * integers, buffer rows, gemm_mode 1 / 2 against 0, repeated train() calls: bit-exact.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch as th
+
+from oracle import sb3_oracle as orc
+from tests import arch_oracle as A
+from tests import helpers as H
+from tests.arch_oracle import ARCHES, SPECS, arch_id
+
+pytestmark = pytest.mark.gpu
+
+
+def _scale(arch):
+    return max(1.0, arch[-1] / 64.0)
+
+
+# ---- forward family ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", SPECS)
+@pytest.mark.parametrize("arch", ARCHES, ids=arch_id)
+def test_forward_family_matches_the_checker(arch, name):
+    orac = A.oracle_policy(name, arch, seed=3)
+    pol = A.device_policy(name, orac)
+    obs_s, act_s = H.CONFIGS[name]
+    s = _scale(arch)
+    for n in (1, 33, 256, 1000):
+        rng = np.random.default_rng(n)
+        obs = H.sample_obs(obs_s, n, rng)
+        u = rng.random((n, act_s.stored_len)).astype(np.float32)
+        with th.no_grad():
+            z_ref = orac.logits(th.as_tensor(obs)).numpy()
+            a_ref, v_ref, lp_ref = orac.forward(th.as_tensor(obs), uniforms=th.as_tensor(u))
+        z = pol.get_logits(obs).cpu().numpy()
+        print(arch, name, n, "logits", np.abs(z - z_ref).max())
+        np.testing.assert_allclose(z, z_ref, atol=2e-5 * s, rtol=0)
+        acts, values, logp = pol.forward(obs, uniforms=u)
+        np.testing.assert_allclose(values.cpu().numpy(), v_ref.numpy(), atol=2e-5 * s, rtol=0)
+        np.testing.assert_allclose(pol.predict_values(obs).cpu().numpy(), v_ref.numpy(), atol=2e-5 * s, rtol=0)
+        acts = acts.cpu().numpy().reshape(n, -1)
+        probs = [th.softmax(zc, 1).numpy() for zc in th.split(th.as_tensor(z_ref), list(act_s.nvec), dim=1)]
+        near = np.zeros(n, bool)
+        for c, p in enumerate(probs):
+            near |= (np.abs(np.cumsum(p, 1) - u[:, c:c + 1]) < 1e-5 * s).any(1)
+        assert near.sum() <= max(2, 0.02 * n), (near.sum(), n)
+        assert np.array_equal(acts[~near], a_ref.numpy()[~near])
+        np.testing.assert_allclose(logp.cpu().numpy()[~near], lp_ref.numpy()[~near], atol=2e-5 * s, rtol=0)
+        with th.no_grad():
+            d_ref = orac.forward(th.as_tensor(obs), deterministic=True)[0].numpy()
+        d = pol.forward(obs, deterministic=True)[0].cpu().numpy().reshape(n, -1)
+        gap_ok = np.ones(n, bool)
+        for zc in np.split(z_ref, np.cumsum(act_s.nvec)[:-1], axis=1):
+            if zc.shape[1] > 1:
+                top = np.sort(zc, 1)
+                gap_ok &= (top[:, -1] - top[:, -2]) > 1e-4 * s
+        assert np.array_equal(d[gap_ok], d_ref[gap_ok])
+        given = H.sample_obs(act_s, n, rng)
+        with th.no_grad():
+            ve_ref, lpe_ref, e_ref = orac.evaluate_actions(th.as_tensor(obs), th.as_tensor(given))
+        ve, lpe, e = pol.evaluate_actions(obs, given)
+        np.testing.assert_allclose(ve.cpu().numpy(), ve_ref.numpy(), atol=2e-5 * s, rtol=0)
+        np.testing.assert_allclose(lpe.cpu().numpy(), lpe_ref.numpy(), atol=2e-5 * s, rtol=0)
+        np.testing.assert_allclose(e.cpu().numpy(), e_ref.numpy(), atol=2e-5 * s, rtol=0)
+    # gemm_mode 1 (VALU restatement) and 2 give the bits of mode 0
+    obs = H.sample_obs(obs_s, 200, np.random.default_rng(1))
+    out = []
+    for mode in (0, 1, 2):
+        pol.gemm_mode = mode
+        out.append((pol.get_logits(obs).cpu().numpy(), pol.predict_values(obs).cpu().numpy()))
+    for z, v in out[1:]:
+        assert np.array_equal(z, out[0][0]) and np.array_equal(v, out[0][1])
+
+
+@pytest.mark.parametrize("name,L", [("discrete20", 20), ("overcooked", 6)])
+@pytest.mark.parametrize("arch", [(128, 128), (96, 160, 32), (256, 256, 256)], ids=arch_id)
+def test_action_mask_is_integer_exact(arch, name, L):
+    orac = A.oracle_policy(name, arch, seed=6)
+    pol = A.device_policy(name, orac)
+    rng = np.random.default_rng(2)
+    n = 2048
+    obs = H.sample_obs(H.CONFIGS[name][0], n, rng)
+    mask = (rng.random((n, L)) < 0.6)
+    mask[np.arange(n), rng.integers(0, L, n)] = True
+    z = pol.get_logits(obs).cpu().numpy()
+    zm = pol.get_logits(obs, action_mask=mask.astype(np.uint8)).cpu().numpy()
+    assert np.array_equal(zm, (z - np.float32(30.0) * (1 - mask.astype(np.float32))).astype(np.float32))
+    with th.no_grad():
+        zm_ref = orac.logits(th.as_tensor(obs), th.as_tensor(mask)).numpy()
+    np.testing.assert_allclose(zm, zm_ref, atol=2e-5 * _scale(arch))
+    acts = pol.forward(obs, deterministic=True, action_mask=mask.astype(np.uint8))[0].cpu().numpy().ravel()
+    assert mask[np.arange(n), acts].all()
+    with th.no_grad():
+        a_ref = orac.forward(th.as_tensor(obs), deterministic=True, action_mask=th.as_tensor(mask))[0].numpy().ravel()
+    top = np.sort(zm_ref, 1)
+    ok = (top[:, -1] - top[:, -2]) > 1e-4 * _scale(arch)
+    assert np.array_equal(acts[ok], a_ref[ok])
+
+
+@pytest.mark.parametrize("name,arch", [("liar", (256, 128)), ("overcooked", (128, 128)), ("rps", (32,)), ("wide", (64, 64, 64))])
+def test_forward_and_store_writes_the_row_forward_plus_add_writes(name, arch):
+    T, E = 5, 37
+    orac = A.oracle_policy(name, arch, seed=7)
+    pol = A.device_policy(name, orac)
+    obs_s, act_s = H.CONFIGS[name]
+    fused, plain = H.make_device_buffer(name, pol, T, E), H.make_device_buffer(name, pol, T, E)
+    rng = np.random.default_rng(3)
+    starts = np.ones(E, np.float32)
+    for t in range(T):
+        obs = H.sample_obs(obs_s, E, rng)
+        u = rng.random((E, act_s.stored_len)).astype(np.float32)
+        a1, v1, lp1 = pol.forward_and_store(obs, fused, starts, uniforms=u)
+        a2, v2, lp2 = pol.forward(obs, uniforms=u)
+        plain.add(obs, a2.cpu().numpy(), np.zeros(E, np.float32), starts, v2, lp2)
+        assert th.equal(a1, a2) and th.equal(v1, v2) and th.equal(lp1, lp2)
+        starts = (rng.random(E) < 0.3).astype(np.float32)
+    assert fused.full and fused.pos == T
+    got, want = fused.host(), plain.host()
+    for k in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs"):
+        assert np.array_equal(got[k], want[k]), k
+    from pantheonrl_amd import _native as nat
+    with pytest.raises(nat.NativeError, match="full buffer"):
+        pol.forward_and_store(obs, fused, starts)
+
+
+# ---- minibatch gradient --------------------------------------------------------------------------------------------------------
+def _grad_pair(name, arch, T, E, idx, hp, seed=11, gemm_mode=0):
+    from pantheonrl_amd import _native as nat
+    from pantheonrl_amd.ppo import PPO
+    orac = A.oracle_policy(name, arch, seed=seed)
+    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
+    pol = A.device_policy(name, orac)
+    buf = H.make_device_buffer(name, pol, T, E)
+    H.upload_buffer(buf, ob)
+    mb = {k: th.as_tensor(v[idx]) for k, v in ob.flat().items()}
+    orac.optimizer.zero_grad()
+    loss, stats_ref = orc.ppo_minibatch_loss(orac, mb, hp)
+    loss.backward()
+    g_ref = orac.flat_grads()
+    model = PPO.__new__(PPO)
+    for k in ("learning_rate", "clip_range", "clip_range_vf", "ent_coef", "vf_coef", "max_grad_norm", "target_kl", "normalize_advantage"):
+        setattr(model, k, getattr(hp, k))
+    h = PPO.hyper(model)
+    idx_t = th.as_tensor(np.asarray(idx, np.int32)).cuda()
+    modes = (gemm_mode,) if isinstance(gemm_mode, int) else gemm_mode
+    out = []
+    for mode in modes:
+        g = th.zeros(pol.layout.P, device="cuda")
+        st = th.zeros(nat.PH_NSTAT, device="cuda")
+        pol._bind()
+        nat.check(pol.ctx.lib.ph_arch_minibatch_grad(pol.ctx.handle, C.byref(pol.spec), C.byref(pol.arch), pol.params.data_ptr(),
+                                                     C.byref(buf.c_struct()), C.byref(h), idx_t.data_ptr(), len(idx), g.data_ptr(),
+                                                     st.data_ptr(), mode))
+        th.cuda.synchronize()
+        out.append((g.cpu().numpy(), st.cpu().numpy()))
+    return out, g_ref, stats_ref
+
+
+def _assert_grads(g, g_ref, where):
+    scale = np.abs(g_ref).max()
+    err = np.abs(g - g_ref)
+    print(where, "gradient error", err.max(), "of", scale, "allowed", 1e-6 + 2e-4 * scale)
+    assert err.max() <= 1e-6 + 2e-4 * scale, (where, err.max(), scale, int(err.argmax()), g.size)
+
+
+def _assert_stats(st, st_ref, where):
+    for i, k in enumerate(("policy_loss", "value_loss", "entropy_loss", "clip_fraction", "approx_kl", "loss")):
+        assert abs(st[i] - st_ref[k]) <= 1e-5 + 1e-4 * abs(st_ref[k]), (where, k, st[i], st_ref[k])
+
+
+@pytest.mark.parametrize("name", ["overcooked", "liar", "wide", "quad16"])
+@pytest.mark.parametrize("arch", ARCHES, ids=arch_id)
+def test_minibatch_gradient_matches_autograd(arch, name):
+    for T, E, nb in ((16, 8, 64), (16, 8, 100), (8, 12, 37)):
+        idx = np.random.default_rng(nb).permutation(T * E)[:nb]
+        modes = (0, 1, 2) if nb == 100 else 0
+        out, g_ref, st_ref = _grad_pair(name, arch, T, E, idx, orc.PPOHyper(), gemm_mode=modes)
+        _assert_grads(out[0][0], g_ref, (arch, name, T, E, nb))
+        _assert_stats(out[0][1], st_ref, (arch, name, nb))
+        for g, st in out[1:]:                                   # gemm_mode 1 and 2: the bits of mode 0
+            assert np.array_equal(g, out[0][0]) and np.array_equal(st, out[0][1])
+
+
+@pytest.mark.parametrize("name,arch", [("overcooked", (128, 128)), ("liar", (256, 128)), ("quad16", (96, 160, 32)),
+                                       ("wide", (256, 256, 256)), ("overcooked", (32,))])
+def test_minibatch_gradient_options(name, arch):
+    idx = np.random.default_rng(0).permutation(16 * 8)[:100]
+    hp = orc.PPOHyper(clip_range=0.1, clip_range_vf=0.3, ent_coef=0.02, vf_coef=0.7, normalize_advantage=False)
+    out, g_ref, st_ref = _grad_pair(name, arch, 16, 8, idx, hp)
+    _assert_grads(out[0][0], g_ref, (arch, name))
+    _assert_stats(out[0][1], st_ref, (arch, name))
+
+
+def test_minibatch_gradient_full_size():
+    T, E, nb = 128, 256, 32768
+    idx = np.random.default_rng(nb).permutation(T * E)[:nb]
+    out, g_ref, st_ref = _grad_pair("overcooked", (128, 128), T, E, idx, orc.PPOHyper())
+    _assert_grads(out[0][0], g_ref, "full size")
+    _assert_stats(out[0][1], st_ref, "full size")
+
+
+# ---- train() ---------------------------------------------------------------------------------------------------------------------
+def _model(name, arch, T, E, hp, cls_kwargs=True):
+    from pantheonrl_amd.ppo import PPO
+    return PPO("MlpPolicy", A.space_env(name), n_steps=T, n_envs=E, batch_size=hp.batch_size, n_epochs=hp.n_epochs,
+               learning_rate=hp.learning_rate, clip_range=hp.clip_range, clip_range_vf=hp.clip_range_vf,
+               normalize_advantage=hp.normalize_advantage, ent_coef=hp.ent_coef, vf_coef=hp.vf_coef, max_grad_norm=hp.max_grad_norm,
+               target_kl=hp.target_kl, seed=0, policy_kwargs=A.kwargs_of(arch) if cls_kwargs else None)
+
+
+def _train_pair(name, arch, T, E, hp, seed=21):
+    from pantheonrl_amd.ppo import ArchActorCriticPolicy
+    orac = A.oracle_policy(name, arch, seed=seed)
+    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
+    model = _model(name, arch, T, E, hp)
+    assert type(model.policy) is ArchActorCriticPolicy and model.policy.net_arch == tuple(arch)
+    model.policy.set_flat_params(orac.flat_params())
+    H.upload_buffer(model.rollout_buffer, ob)
+    perms = np.stack([np.random.default_rng(seed + ep).permutation(T * E) for ep in range(hp.n_epochs)])
+    model.train(perms=perms)
+    stats_ref = orc.ppo_train(orac, ob, hp, perms)
+    return model, orac, stats_ref
+
+
+def _assert_train_stats(row, ref, nb, where=()):     # tests/test_gpu_parity.py's rule
+    tol = {"policy_loss": lambda x: 2e-5 + 2e-4 * abs(x), "value_loss": lambda x: 2e-5 + 2e-4 * abs(x),
+           "entropy_loss": lambda x: 2e-5 + 2e-4 * abs(x), "loss": lambda x: 3e-5 + 2e-4 * abs(x),
+           "approx_kl": lambda x: 3e-6 + 2e-4 * abs(x), "clip_fraction": lambda x: 1.0 / nb + 1e-7,
+           "grad_norm": lambda x: 1e-5 + 2e-4 * abs(x)}
+    for j, k in enumerate(("policy_loss", "value_loss", "entropy_loss", "clip_fraction", "approx_kl", "loss", "grad_norm")):
+        assert abs(row[j] - ref[k]) <= tol[k](ref[k]), (where, k, row[j], ref[k])
+
+
+@pytest.mark.parametrize("name,arch,T,E,batch,epochs", [
+    ("overcooked", (128, 128), 32, 8, 64, 3), ("overcooked", (256, 256), 32, 8, 64, 3), ("overcooked", (64, 64, 64), 32, 8, 64, 3),
+    ("liar", (256, 128), 16, 6, 32, 2), ("rps", (32,), 25, 5, 64, 2)])
+def test_train_matches_the_checker(name, arch, T, E, batch, epochs):
+    hp = orc.PPOHyper(batch_size=batch, n_epochs=epochs)
+    model, orac, stats_ref = _train_pair(name, arch, T, E, hp)
+    st = model.last_train_stats
+    steps = len(stats_ref)
+    assert steps == st.shape[0]
+    p, p_ref = model.policy.get_flat_params(), orac.flat_params()
+    print(name, arch, "parameter drift", np.abs(p - p_ref).max(), "allowed", 2e-6 * steps + 1e-6)
+    assert np.abs(p - p_ref).max() <= 2e-6 * steps + 1e-6, np.abs(p - p_ref).max()
+    assert int(model.policy.opt_step.item()) == steps
+    N = T * E
+    for i, s in enumerate(stats_ref):
+        nb_i = min(batch, N - (i % (-(-N // batch))) * batch)
+        _assert_train_stats(st[i], s, nb_i, (name, arch, i))
+
+
+def test_train_target_kl_early_stop_matches_the_checker():
+    """Default learning rate, target_kl 0.01: on this buffer the checker's approx_kl stays below 5e-3 for the eight minibatches of the
+    first epoch and is 2.2e-2 on the first minibatch of the second (threshold 1.5e-2), so the stop is far from a rounding tie."""
+    batch = 32
+    hp = orc.PPOHyper(batch_size=batch, n_epochs=6, target_kl=0.01)
+    model, orac, stats_ref = _train_pair("overcooked", (128, 128), 32, 8, hp, seed=5)
+    st = model.last_train_stats
+    applied_ref = sum(0 if s.get("stopped") else 1 for s in stats_ref)
+    assert stats_ref[-1].get("stopped") and 0 < applied_ref < st.shape[0], "test must exercise the early stop"
+    assert int(model.policy.opt_step.item()) == applied_ref           # step count exact
+    assert int((st[:, 7] > 0).sum()) == applied_ref and (st[:applied_ref, 7] > 0).all()
+    p, p_ref = model.policy.get_flat_params(), orac.flat_params()
+    print("early stop after", applied_ref, "steps: parameter drift", np.abs(p - p_ref).max(), "allowed", 2e-6 * applied_ref + 1e-6)
+    assert np.abs(p - p_ref).max() <= 2e-6 * applied_ref + 1e-6, np.abs(p - p_ref).max()
+    for i, s in enumerate(stats_ref):                                  # the stopping minibatch has losses and KL, no step
+        ref = dict(s, grad_norm=st[i, 6]) if s.get("stopped") else s
+        _assert_train_stats(st[i], ref, batch, ("early stop", i))
+
+
+def test_old_and_new_kernels_side_by_side_at_64_64():
+    """ArchActorCriticPolicy(net_arch=(64, 64)) and ActorCriticPolicy on the same flat parameters: a layout slip shows directly."""
+    from pantheonrl_amd.ppo import ActorCriticPolicy, ArchActorCriticPolicy, PPO
+    name, T, E = "overcooked", 32, 8
+    hp = orc.PPOHyper(batch_size=64, n_epochs=3)
+    orac = H.oracle_policy(name, seed=21)
+    ob = H.filled_oracle_buffer(name, orac, T, E, seed=21)
+    perms = np.stack([np.random.default_rng(21 + ep).permutation(T * E) for ep in range(hp.n_epochs)])
+    old = _model(name, (64, 64), T, E, hp)
+    assert type(old.policy) is ActorCriticPolicy                       # the default arch keeps today's class
+    new = _model(name, (64, 64), T, E, hp, cls_kwargs=False)
+    obs_s, act_s = H.CONFIGS[name]
+    new.policy = ArchActorCriticPolicy(H.to_space(obs_s), H.to_space(act_s, "act"), net_arch=(64, 64), device="cuda", seed=0)
+    new.rollout_buffer = H.make_device_buffer(name, new.policy, T, E)
+    assert new.policy.layout.P == old.policy.layout.P
+    obs = H.sample_obs(obs_s, 500, np.random.default_rng(0))
+    for m in (old, new):
+        m.policy.set_flat_params(orac.flat_params())
+        H.upload_buffer(m.rollout_buffer, ob)
+    np.testing.assert_allclose(new.policy.get_logits(obs).cpu().numpy(), old.policy.get_logits(obs).cpu().numpy(), atol=2e-5, rtol=0)
+    np.testing.assert_allclose(new.policy.predict_values(obs).cpu().numpy(), old.policy.predict_values(obs).cpu().numpy(), atol=2e-5, rtol=0)
+    for m in (old, new):
+        m.train(perms=perms)
+    steps = hp.n_epochs * (T * E // hp.batch_size)
+    assert int(old.policy.opt_step.item()) == int(new.policy.opt_step.item()) == steps
+    d = np.abs(new.policy.get_flat_params() - old.policy.get_flat_params()).max()
+    assert d <= 2 * (2e-6 * steps + 1e-6), d
+    assert list(new.policy.state_dict()) == list(old.policy.state_dict())
+
+
+@pytest.mark.parametrize("name,arch", [("overcooked", (128, 128)), ("liar", (256, 256, 256))])
+def test_train_is_deterministic(name, arch):
+    T, E = 16, 8
+    hp = orc.PPOHyper(batch_size=32, n_epochs=2)
+    orac = A.oracle_policy(name, arch, seed=4)
+    ob = H.filled_oracle_buffer(name, orac, T, E, seed=4)
+    perms = np.stack([np.random.default_rng(ep).permutation(T * E) for ep in range(hp.n_epochs)])
+    model = _model(name, arch, T, E, hp)
+    H.upload_buffer(model.rollout_buffer, ob)
+    got = []
+    for _ in range(2):
+        model.policy.set_flat_params(orac.flat_params())
+        model.policy.adam_m.zero_()
+        model.policy.adam_v.zero_()
+        model.policy.opt_step.zero_()
+        model.train(perms=perms)
+        got.append((model.policy.get_flat_params(), model.policy.adam_v.cpu().numpy(), model.last_train_stats.copy()))
+    for a, b in zip(got[0], got[1]):
+        assert np.array_equal(a, b)
+
+
+# ---- end to end --------------------------------------------------------------------------------------------------------------------
+def test_rps_end_to_end_save_load_and_refusals(tmp_path):
+    from pantheonrl_amd import OnPolicyAgent, PPO, StaticPolicyAgent
+    from pantheonrl_amd import _native as nat
+    from pantheonrl_amd.envs import make
+    from pantheonrl_amd.ppo import ActorCriticPolicy, ArchActorCriticPolicy
+    env = make("RPS-v0")
+    ego = PPO("MlpPolicy", env, n_steps=256, seed=0, policy_kwargs=A.kwargs_of((128, 128)))
+    partner = OnPolicyAgent(PPO("MlpPolicy", env.getDummyEnv(1), n_steps=256, seed=1, policy_kwargs={"net_arch": dict(pi=[32], vf=[32])}))
+    env.add_partner_agent(partner)
+    assert type(ego.policy) is ArchActorCriticPolicy and partner.model.policy.net_arch == (32,)
+    before = ego.policy.get_flat_params()
+    ego.learn(total_timesteps=768)
+    assert ego.num_timesteps == 768 and partner.num_timesteps == 768
+    assert partner.iteration == 2                          # trains at the NEXT get_action after its buffer fills
+    assert ego._n_updates == 3 * 10 and int(ego.policy.opt_step.item()) == 3 * 10 * 4
+    after = ego.policy.get_flat_params()
+    assert np.isfinite(after).all() and np.isfinite(partner.model.policy.get_flat_params()).all()
+    assert (after != before).any() and int(partner.model.policy.opt_step.item()) == 2 * 10 * 4
+    path = str(tmp_path / "models" / "rps-ego")
+    ego.save(path)
+    loaded = PPO.load(path)
+    assert type(loaded.policy) is ArchActorCriticPolicy and loaded.policy.net_arch == (128, 128)
+    assert np.array_equal(loaded.policy.get_flat_params(), after)
+    assert np.array_equal(loaded.policy.adam_m.cpu().numpy(), ego.policy.adam_m.cpu().numpy())
+    assert np.array_equal(loaded.policy.adam_v.cpu().numpy(), ego.policy.adam_v.cpu().numpy())
+    assert int(loaded.policy.opt_step.item()) == int(ego.policy.opt_step.item())
+    obs = np.zeros((5, 1), np.float32)
+    assert th.equal(loaded.policy.get_logits(obs), ego.policy.get_logits(obs))
+    sd = ego.policy.state_dict()
+    assert sd["mlp_extractor.policy_net.2.weight"].shape == (128, 128) and sd["action_net.weight"].shape == (3, 128) and len(sd) == 12
+    fixed = StaticPolicyAgent(PPO.load(path).policy)      # a FIXED partner from such a checkpoint
+    env2 = make("RPS-v0")
+    env2.add_partner_agent(fixed)
+    env2.reset()
+    assert env2.step(env2.action_space.sample())[2]
+    # a default-arch checkpoint (no arch key in its data) still loads as ActorCriticPolicy
+    plain = PPO("MlpPolicy", make("RPS-v0"), n_steps=32, seed=2)
+    plain.save(str(tmp_path / "models" / "plain"))
+    import json
+    import zipfile
+    with zipfile.ZipFile(str(tmp_path / "models" / "plain.zip")) as zf:
+        assert "net_arch" not in json.loads(zf.read("data"))
+    assert type(PPO.load(str(tmp_path / "models" / "plain")).policy) is ActorCriticPolicy
+    # the vectorised agents are built around the 64-wide kernels
+    from pantheonrl_amd.vec import VecOnPolicyAgent
+    with pytest.raises(nat.NativeError, match="fused MLP kernels"):
+        VecOnPolicyAgent(PPO("MlpPolicy", env.getDummyEnv(1), n_steps=8, n_envs=16, policy_kwargs=A.kwargs_of((128, 128))))
+    from pantheonrl_amd.envs.vec import RaggedVecOnPolicyAgent
+    with pytest.raises(nat.NativeError, match="fused MLP kernels"):    # the ragged partner seat of the device-resident self-play
+        RaggedVecOnPolicyAgent(PPO("MlpPolicy", make("LiarsDice-v0").getDummyEnv(1), n_steps=8, n_envs=16,
+                                   policy_kwargs=A.kwargs_of((256, 128))))
+
+
+def test_a_spec_too_large_for_the_lds_tile_is_refused_by_name():
+    from pantheonrl_amd import _native as nat
+    from pantheonrl_amd import spaces as sp
+    from pantheonrl_amd.ppo import ArchActorCriticPolicy, RolloutBuffer
+    obs_space, act_space = sp.MultiDiscrete([2] * 256), sp.Discrete(3)
+    pol = ArchActorCriticPolicy(obs_space, act_space, net_arch=(256, 256, 256), device="cuda", seed=0)
+    with pytest.raises(nat.NativeError, match="LDS tile"):
+        pol.get_logits(np.zeros((4, 256), np.float32))
+    buf = RolloutBuffer(4, obs_space, act_space, pol.device, pol.ctx, pol.spec, n_envs=4)
+    buf.pos, buf.full = 4, True
+    from pantheonrl_amd.ppo import PPO
+    model = PPO.__new__(PPO)
+    for k, v in dict(learning_rate=3e-4, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, target_kl=None,
+                     normalize_advantage=True).items():
+        setattr(model, k, v)
+    h = PPO.hyper(model)
+    idx = th.arange(8, dtype=th.int32, device="cuda")
+    g, st = th.zeros(pol.layout.P, device="cuda"), th.zeros(nat.PH_NSTAT, device="cuda")
+    pol._bind()
+    with pytest.raises(nat.NativeError, match="LDS tile"):
+        nat.check(pol.ctx.lib.ph_arch_minibatch_grad(pol.ctx.handle, C.byref(pol.spec), C.byref(pol.arch), pol.params.data_ptr(),
+                                                     C.byref(buf.c_struct()), C.byref(h), idx.data_ptr(), 8, g.data_ptr(), st.data_ptr(), 0))
+
+
+def test_trainer_cli_takes_net_arch_in_ego_and_alt_config(tmp_path, monkeypatch):
+    from pantheonrl_amd import trainer
+    from pantheonrl_amd.ppo import ArchActorCriticPolicy
+    monkeypatch.chdir(tmp_path)
+    cfg = '{"n_steps": 256, "policy_kwargs": {"net_arch": [{"pi": [128,128], "vf": [128,128]}]}}'
+    ego, partners, env = trainer.run(["RPS-v0", "PPO", "PPO", "--seed", "0", "-t", "512", "--ego-config", cfg, "--alt-config", cfg,
+                                      "--ego-save", "models/ego", "--alt-save", "models/alt"])
+    assert type(ego.policy) is ArchActorCriticPolicy and type(partners[0].model.policy) is ArchActorCriticPolicy
+    assert ego.num_timesteps == 512 and np.isfinite(ego.policy.get_flat_params()).all()
+    # FIXED / LOAD partners from such a checkpoint
+    ego2, partners2, _ = trainer.run(["RPS-v0", "PPO", "FIXED", "--seed", "0", "-t", "256", "--ego-config", cfg, "--alt-config",
+                                      '{"type": "PPO", "location": "models/alt"}'])
+    assert type(partners2[0].policy) is ArchActorCriticPolicy and ego2.num_timesteps == 256
+    # LOAD: the ego continues from its checkpoint (trainer.py:116-124)
+    ego3, _, _ = trainer.run(["RPS-v0", "LOAD", "PPO", "--seed", "0", "-t", "256", "--ego-config",
+                              '{"type": "PPO", "location": "models/ego"}', "--alt-config", cfg])
+    assert type(ego3.policy) is ArchActorCriticPolicy and ego3.policy.net_arch == (128, 128)
+    assert int(ego3.policy.opt_step.item()) > int(ego.policy.opt_step.item())
