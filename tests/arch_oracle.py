@@ -113,3 +113,8 @@ def space_env(name: str):
 
 def kwargs_of(widths) -> dict:
     return {"net_arch": [dict(pi=list(widths), vf=list(widths))]}
+
+
+# the checker's Adam state in ArchPolicyOracle.flat_params()'s order: helpers' functions read the layout off flat_params() itself
+flat_adam_state = H.flat_adam_state
+load_flat_adam_state = H.load_flat_adam_state

@@ -117,5 +117,177 @@ def make_device_buffer(name: str, pol, T: int, E: int):
     return RolloutBuffer(T, to_space(obs_s), to_space(act_s, "act"), pol.device, pol.ctx, pol.spec, n_envs=E)
 
 
+# --------------------------------------------------------------------------------------
+# Adam state of a checker in the flat layout of its parameters (tests/test_optimizer_checks.py, tests/test_gpu_optimizer.py)
+# --------------------------------------------------------------------------------------
+def _flat_layout(oracle, flat_fn=None):
+    """(parameters in optimizer order, idx): flat vector entry i is entry idx[i] of the concatenated parameters.  Read off the
+    class's own flat_params() (or `flat_fn(oracle)`, e.g. test_gpu_modular._flat) by filling every parameter with its running
+    index -- float32 holds integers below 2**24 exactly -- so the order and the transpositions can never differ from it."""
+    params = list(oracle.parameters())
+    total = sum(p.numel() for p in params)
+    assert total < 2 ** 24
+    saved = [p.detach().clone() for p in params]
+    try:
+        with th.no_grad():
+            o = 0
+            for p in params:
+                p.copy_(th.arange(o, o + p.numel(), dtype=th.float32).reshape(p.shape))
+                o += p.numel()
+        flat = flat_fn(oracle) if flat_fn is not None else oracle.flat_params()
+    finally:
+        with th.no_grad():
+            for p, s in zip(params, saved):
+                p.copy_(s)
+    idx = np.asarray(flat, np.float64).astype(np.int64)
+    assert np.array_equal(idx.astype(np.float32), np.asarray(flat, np.float32))
+    return params, idx
+
+
+def flat_adam_state(oracle, optimizer=None, flat_fn=None):
+    """-> (m, v, steps): exp_avg, exp_avg_sq (float32) and the per-parameter step (int64, one per flat entry) of the checker's
+    Adam in the order and transposition of flat_params() / flat_grads().  A parameter without state gives zeros and step 0."""
+    opt = optimizer if optimizer is not None else oracle.optimizer
+    params, idx = _flat_layout(oracle, flat_fn)
+    ms, vs, ts = [], [], []
+    for p in params:
+        st = opt.state.get(p, {})
+        n = p.numel()
+        if len(st) == 0:
+            ms.append(np.zeros(n, np.float32)), vs.append(np.zeros(n, np.float32)), ts.append(np.zeros(n, np.int64))
+        else:
+            ms.append(st["exp_avg"].detach().reshape(-1).numpy().copy())      # (float64 for a .double() checker)
+            vs.append(st["exp_avg_sq"].detach().reshape(-1).numpy().copy())
+            ts.append(np.full(n, int(round(float(st["step"]))), np.int64))
+    return np.concatenate(ms)[idx], np.concatenate(vs)[idx], np.concatenate(ts)[idx]
+
+
+def load_flat_adam_state(oracle, m, v, steps, optimizer=None, flat_fn=None) -> None:
+    """the inverse of flat_adam_state: afterwards optimizer.step() continues from (m, v, steps).  `steps`: one integer, or one
+    per flat entry (equal within a parameter).  A parameter whose step is 0 is left without state (torch creates it at the
+    parameter's first gradient); one with state gets a zero gradient tensor where it has none, which is what a parameter that
+    has taken part in a step carries under torch 1.13's zero_grad (oracle.modular_train)."""
+    opt = optimizer if optimizer is not None else oracle.optimizer
+    params, idx = _flat_layout(oracle, flat_fn)
+    total = sum(p.numel() for p in params)
+    m, v = np.asarray(m, np.float32), np.asarray(v, np.float32)
+    steps = np.broadcast_to(np.asarray(steps, np.int64), (len(idx),))
+    assert m.shape == v.shape == (len(idx),)
+    cm, cv, ct = np.zeros(total, np.float32), np.zeros(total, np.float32), np.zeros(total, np.int64)
+    cm[idx], cv[idx], ct[idx] = m, v, steps
+    o = 0
+    for p in params:
+        n = p.numel()
+        t = ct[o:o + n]
+        assert (t == t[0]).all(), "one step count per parameter tensor"
+        opt.state.pop(p, None)
+        if t[0] > 0:
+            opt.state[p] = {"step": th.tensor(float(t[0]), dtype=th.float32),
+                            "exp_avg": th.as_tensor(cm[o:o + n].copy()).reshape(p.shape).to(p.dtype),
+                            "exp_avg_sq": th.as_tensor(cv[o:o + n].copy()).reshape(p.shape).to(p.dtype)}
+            if p.grad is None:
+                p.grad = th.zeros_like(p)
+        else:
+            assert not cm[o:o + n].any() and not cv[o:o + n].any(), "moments without a step count"
+        o += n
+
+
+def load_device_adam_state(obj, m, v, step, mod_first=None) -> None:
+    """the device side: obj.adam_m / adam_v / opt_step (a policy, or a BC object) <- (m, v, step); mod_first for ModularPolicy"""
+    obj.adam_m.copy_(th.as_tensor(np.asarray(m, np.float32)))
+    obj.adam_v.copy_(th.as_tensor(np.asarray(v, np.float32)))
+    obj.opt_step.fill_(int(step))
+    if mod_first is not None:
+        obj.mod_first.copy_(th.as_tensor(np.asarray(mod_first, np.int32)))
+
+
+def read_device_adam_state(obj):
+    return obj.adam_m.cpu().numpy().copy(), obj.adam_v.cpu().numpy().copy(), int(obj.opt_step.item())
+
+
+# --------------------------------------------------------------------------------------
+# Adam moments after a CHAIN of steps: the allowance is measured on the checker (float32 run against a float64 run)
+# --------------------------------------------------------------------------------------
+class float64_checker:
+    """context: the checker computes in float64 on a `.double()` copy of a checker class -- preprocess_obs hands out float64
+    features and the rollout buffer float64 minibatches (the stored numbers are the same float32 values)"""
+
+    def __enter__(self):
+        from oracle import sb3_oracle as orc
+        self._orc, self._pre, self._get = orc, orc.preprocess_obs, orc.RolloutBufferOracle.get
+        pre, get = self._pre, self._get
+
+        def get64(buf, batch_size, indices=None):
+            for mb in get(buf, batch_size, indices):
+                yield {k: t.double() for k, t in mb.items()}
+        orc.preprocess_obs = lambda obs, space: pre(obs, space).double()
+        orc.RolloutBufferOracle.get = get64
+        return self
+
+    def __exit__(self, *exc):
+        self._orc.preprocess_obs, self._orc.RolloutBufferOracle.get = self._pre, self._get
+        return False
+
+
+def double_copy(oracle, optimizer=None):
+    """(float64 deep copy of a checker BEFORE a chain, its fresh Adam with the same lr / eps / betas)"""
+    import copy
+    src = optimizer if optimizer is not None else oracle.optimizer
+    assert all(len(s) == 0 for s in src.state.values()) or len(src.state) == 0, "copy before the first step"
+    o64 = copy.deepcopy(oracle).double()
+    g = src.param_groups[0]
+    opt = th.optim.Adam(o64.parameters(), lr=g["lr"], betas=g["betas"], eps=g["eps"])
+    if optimizer is None:
+        o64.optimizer = opt
+    return o64, opt
+
+
+def unit_hyper(hp: PPOHyper, n_rows: int, max_grad_norm: float, learning_rate: float = 3e-4) -> PPOHyper:
+    """the hyper-parameters of ONE optimizer step: one epoch, the whole buffer as one minibatch"""
+    import dataclasses
+    return dataclasses.replace(hp, n_epochs=1, batch_size=n_rows, max_grad_norm=max_grad_norm, learning_rate=learning_rate)
+
+
+def unit_gradient(oracle, run):
+    """(gradient of the unit's loss in flat_grads() order as float64, its norm as the checker computed it): `run(checker,
+    max_grad_norm)` takes one step on a deep copy with max_grad_norm = 1e9, which multiplies the gradient by exactly 1"""
+    import copy
+    c = copy.deepcopy(oracle)
+    stats = run(c, 1e9)
+    return c.flat_grads().astype(np.float64), float(stats[0]["grad_norm"])
+
+
+CHAIN_FLOOR, CHAIN_FACTOR = 4e-4, 4.0
+
+
+def chain64_state(o64, run, optimizer=None, flat_fn=None):
+    """run(o64): the chain on the float64 copy (same buffer, same permutations) -> its (m, v, steps)"""
+    with float64_checker():
+        run(o64)
+    return flat_adam_state(o64, optimizer, flat_fn)
+
+
+def assert_chain_moments(dev_m, dev_v, ref32, ref64, where=()):
+    """Adam moments of the device after a chain of steps against the float32 checker's (`ref32`, `ref64`: (m, v, steps) from
+    flat_adam_state of the float32 run and of the float64 run of the same chain).  d = largest entrywise |float32 - float64|
+    relative to the largest float64 entry; the device is allowed max(4 d, 4e-4) of the largest entry: 4e-4 is the one-step
+    figure (the 2e-4 gradient tolerance plus the 2e-4 of the clip coefficient), the factor 4 is for what separates the device
+    from torch's float32 rather than from float64 (another summation order in every reduction, fast_tanh's 2e-7 per activation).
+    Prints d and the observed error beside the allowance; returns (d_m, d_v)."""
+    out = []
+    for name, dev, a32, a64 in (("adam_m", dev_m, ref32[0], ref64[0]), ("adam_v", dev_v, ref32[1], ref64[1])):
+        a64 = np.asarray(a64, np.float64)
+        scale = np.abs(a64).max()
+        d = np.abs(np.asarray(a32, np.float64) - a64).max() / scale
+        allowed = max(CHAIN_FACTOR * d, CHAIN_FLOOR)
+        err = np.abs(np.asarray(dev, np.float64) - np.asarray(a32, np.float64)).max() / scale
+        print(where, name, "chain: checker f32 vs f64 d = %.3g, device vs checker %.3g, allowed %.3g (of max entry %.3g)"
+              % (d, err, allowed, scale))
+        assert err <= allowed, (where, name, err, allowed, d)
+        out.append(d)
+    return tuple(out)
+
+
 __all__ = ["CONFIGS", "PPOHyper", "to_space", "sample_obs", "oracle_policy", "device_policy",
-           "filled_oracle_buffer", "upload_buffer", "make_device_buffer"]
+           "filled_oracle_buffer", "upload_buffer", "make_device_buffer", "flat_adam_state", "load_flat_adam_state",
+           "load_device_adam_state", "read_device_adam_state", "unit_hyper", "unit_gradient", "float64_checker", "double_copy", "chain64_state", "assert_chain_moments"]

@@ -177,6 +177,7 @@ def test_adap_train_matches_oracle(name, T, E, batch, epochs, coef):
     hp = orc.PPOHyper(batch_size=batch, n_epochs=epochs)
     cs, n_ctx, n_states, seed = CTX[name], 5, 32, 31
     orac = H.oracle_policy(name, seed=seed)
+    o64, _ = H.double_copy(orac)          # the float64 copy of the checker, for the chain allowance of the Adam moments
     ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
     model = _adap_model(name, T, E, hp, coef=coef)
     model.policy.set_flat_params(orac.flat_params())
@@ -200,6 +201,9 @@ def test_adap_train_matches_oracle(name, T, E, batch, epochs, coef):
     assert st.shape[0] == steps
     p, p_ref = model.policy.get_flat_params(), orac.flat_params()
     assert np.abs(p - p_ref).max() <= 2e-6 * steps + 1e-6, np.abs(p - p_ref).max()
+    ref64 = H.chain64_state(o64, lambda o: orc.ppo_train(o, ob, hp, perms, adap=orc.AdapTerm(cs, coef, sidx_l, ctxs)))
+    m, v, _ = H.read_device_adam_state(model.policy)        # Adam's moments after the chain against the checker's
+    H.assert_chain_moments(m, v, H.flat_adam_state(orac), ref64, (name, T, E, steps))
     for i, s in enumerate(stats_ref):
         for j, k in enumerate(("policy_loss", "value_loss", "entropy_loss", "clip_fraction", "approx_kl", "loss",
                                "grad_norm")):

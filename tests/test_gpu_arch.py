@@ -219,9 +219,11 @@ def _model(name, arch, T, E, hp, cls_kwargs=True):
                target_kl=hp.target_kl, seed=0, policy_kwargs=A.kwargs_of(arch) if cls_kwargs else None)
 
 
-def _train_pair(name, arch, T, E, hp, seed=21):
+def _train_pair(name, arch, T, E, hp, seed=21, f64=False):
+    """f64: also the chain on a float64 copy of the checker, its Adam state left in model.checker64_state"""
     from pantheonrl_amd.ppo import ArchActorCriticPolicy
     orac = A.oracle_policy(name, arch, seed=seed)
+    o64 = H.double_copy(orac)[0] if f64 else None
     ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
     model = _model(name, arch, T, E, hp)
     assert type(model.policy) is ArchActorCriticPolicy and model.policy.net_arch == tuple(arch)
@@ -230,6 +232,8 @@ def _train_pair(name, arch, T, E, hp, seed=21):
     perms = np.stack([np.random.default_rng(seed + ep).permutation(T * E) for ep in range(hp.n_epochs)])
     model.train(perms=perms)
     stats_ref = orc.ppo_train(orac, ob, hp, perms)
+    if f64:
+        model.checker64_state = H.chain64_state(o64, lambda o: orc.ppo_train(o, ob, hp, perms))
     return model, orac, stats_ref
 
 
@@ -247,7 +251,7 @@ def _assert_train_stats(row, ref, nb, where=()):     # tests/test_gpu_parity.py'
     ("liar", (256, 128), 16, 6, 32, 2), ("rps", (32,), 25, 5, 64, 2)])
 def test_train_matches_the_checker(name, arch, T, E, batch, epochs):
     hp = orc.PPOHyper(batch_size=batch, n_epochs=epochs)
-    model, orac, stats_ref = _train_pair(name, arch, T, E, hp)
+    model, orac, stats_ref = _train_pair(name, arch, T, E, hp, f64=True)
     st = model.last_train_stats
     steps = len(stats_ref)
     assert steps == st.shape[0]
@@ -255,6 +259,8 @@ def test_train_matches_the_checker(name, arch, T, E, batch, epochs):
     print(name, arch, "parameter drift", np.abs(p - p_ref).max(), "allowed", 2e-6 * steps + 1e-6)
     assert np.abs(p - p_ref).max() <= 2e-6 * steps + 1e-6, np.abs(p - p_ref).max()
     assert int(model.policy.opt_step.item()) == steps
+    m, v, _ = H.read_device_adam_state(model.policy)        # Adam's moments after the chain against the checker's
+    H.assert_chain_moments(m, v, A.flat_adam_state(orac), model.checker64_state, (name, arch, steps))
     N = T * E
     for i, s in enumerate(stats_ref):
         nb_i = min(batch, N - (i % (-(-N // batch))) * batch)

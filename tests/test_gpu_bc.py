@@ -56,7 +56,9 @@ def test_bc_train_matches_oracle(name, N, epochs, l2):
     clone.l2_weight = l2
     orders = np.stack([np.random.default_rng(10 + ep).permutation(N) for ep in range(epochs)])
     st = clone.train(n_epochs=epochs, orders=orders)
-    ref = orc.bc_train(orac, obs, acts, orders, 32, ent_weight=1e-3, l2_weight=l2)
+    opt = th.optim.Adam(orac.parameters())                   # BC.train's optimizer (torch's defaults), passed in to be read
+    o64, opt64 = H.double_copy(orac, opt)
+    ref = orc.bc_train(orac, obs, acts, orders, 32, ent_weight=1e-3, l2_weight=l2, optimizer=opt)
     assert st.shape[0] == len(ref) == epochs * (-(-N // 32)) and int(clone.opt_step.item()) == len(ref)
     for i, s in enumerate(ref):
         for j, k in enumerate(("neglogp", "entropy", "ent_loss", "prob_true_act", "l2_norm", "l2_loss", "loss")):
@@ -66,6 +68,11 @@ def test_bc_train_matches_oracle(name, N, epochs, l2):
     d = np.abs(clone.policy.get_flat_params() - orac.flat_params())
     assert np.median(d) <= 2e-6 and d.max() <= 2.5e-3 * 1.0, (np.median(d), d.max())
     assert (d > 1e-4).mean() <= 0.01, (d > 1e-4).mean()
+    # Adam's moments after the chain against the checker's (one step from a loaded state: tests/test_gpu_optimizer.py)
+    ref64 = H.chain64_state(o64, lambda o: orc.bc_train(o, obs, acts, orders, 32, ent_weight=1e-3, l2_weight=l2, optimizer=opt64),
+                            optimizer=opt64)
+    H.assert_chain_moments(clone.adam_m.cpu().numpy(), clone.adam_v.cpu().numpy(), H.flat_adam_state(orac, opt), ref64,
+                           (name, N, epochs, l2))
 
 
 @pytest.mark.parametrize("batch", [50, 7, 200])

@@ -100,7 +100,7 @@ def test_gaussian_gradient_options():
 @pytest.mark.parametrize("name,T,E,batch,epochs", [("gauss5", 32, 8, 64, 3), ("gauss1", 25, 5, 64, 2), ("gauss_onehot", 16, 6, 32, 2)])
 def test_gaussian_train_matches_oracle(name, T, E, batch, epochs):
     hp = orc.PPOHyper(batch_size=batch, n_epochs=epochs, ent_coef=0.01)
-    model, orac, stats_ref = _train_pair(name, T, E, hp)
+    model, orac, stats_ref = _train_pair(name, T, E, hp, f64=True)
     from pantheonrl_amd.ppo import GaussianActorCriticPolicy
     assert isinstance(model.policy, GaussianActorCriticPolicy)
     st = model.last_train_stats
@@ -111,6 +111,8 @@ def test_gaussian_train_matches_oracle(name, T, E, batch, epochs):
     A = H.CONFIGS[name][1].dim
     assert np.abs(p[-A:] - p_ref[-A:]).max() <= 2e-6 * steps + 1e-6 and np.abs(p_ref[-A:]).max() > 0      # log_std moved, the same way
     assert int(model.policy.opt_step.item()) == steps
+    m, v, _ = H.read_device_adam_state(model.policy)        # Adam's moments after the chain, log_std's among them
+    H.assert_chain_moments(m, v, H.flat_adam_state(orac), model.checker64_state, (name, T, E, steps))
     N = T * E
     for i, s in enumerate(stats_ref):
         nb_i = min(batch, N - (i % (-(-N // batch))) * batch)

@@ -78,12 +78,17 @@ def test_handle_abi_end_to_end_without_torch_in_the_call_path():
     perms = np.stack([np.random.default_rng(ep).permutation(T * E) for ep in range(2)]).astype(np.int32)
     stats = np.zeros((2 * 3, nat.PH_NSTAT), np.float32)
     assert lib.ph_agent_train(h, C.byref(hp), 2, 20, _p(perms), 0, _p(stats)) == 0, lib.ph_agent_last_error()
+    o64, _ = H.double_copy(orac)                                # the float64 copy of the checker: the allowance of the Adam moments
     ref = orc.ppo_train(orac, ob, hpo, perms)
+    ref64 = H.chain64_state(o64, lambda o: orc.ppo_train(o, ob, hpo, perms))
     assert lib.ph_agent_get_params(h, _p(back)) == 0
     assert np.abs(back - orac.flat_params()).max() <= 2e-6 * len(ref) + 1e-6
     assert (stats[:, 7] == 1).all() and abs(stats[0, 5] - ref[0]["loss"]) < 1e-4
     m, v, step = np.zeros(lay.P, np.float32), np.zeros(lay.P, np.float32), C.c_int(0)
-    assert lib.ph_agent_get_optimizer(h, _p(m), _p(v), C.byref(step)) == 0 and step.value == len(ref) and np.abs(m).max() > 0
+    assert lib.ph_agent_get_optimizer(h, _p(m), _p(v), C.byref(step)) == 0 and step.value == len(ref)
+    ref32 = H.flat_adam_state(orac)                             # the checker's exp_avg / exp_avg_sq / step in the flat layout
+    assert (ref32[2] == len(ref)).all() and np.abs(ref32[0]).max() > 0
+    H.assert_chain_moments(m, v, ref32, ref64, "handle ABI")
 
     # buffer reset, import / export round trip, misuse is reported
     assert lib.ph_agent_buffer_reset(h) == 0 and lib.ph_agent_pos(h, C.byref(pos)) == 0 and pos.value == 0

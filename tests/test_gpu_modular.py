@@ -68,6 +68,27 @@ def _flat(pol, grads=False):
     return th.cat(out).numpy().astype(np.float32).copy()
 
 
+def _flat_adam_state(pol):
+    """(m, v, steps) of the checker's Adam in _flat's order (helpers.flat_adam_state)"""
+    return H.flat_adam_state(pol, flat_fn=_flat)
+
+
+def _load_flat_adam_state(pol, m, v, steps):
+    H.load_flat_adam_state(pol, m, v, steps, flat_fn=_flat)
+
+
+def _value_side(pol):
+    """per entry of _flat's order: j for the value side (value tower + value head) of distinct module j -- the parameters that
+    join the optimizer when that module's partner is first trained and count their own steps -- and -1 for everything else"""
+    params, idx = H._flat_layout(pol, _flat)
+    owner = {}
+    for j, pm in enumerate(_unique(pol)):
+        for p in list(pm["vf"].parameters()) + list(pm["val"].parameters()):
+            owner[id(p)] = j
+    label = np.concatenate([np.full(p.numel(), owner.get(id(p), -1), np.int64) for p in params])
+    return label[idx]
+
+
 def _device(name, orac, K, **kw):
     from pantheonrl_amd.modular import ModularPolicy
     obs_s, act_s = SHAPES[name]
@@ -295,6 +316,7 @@ def test_modular_train_chain_matches_the_oracle(name, K, T, E, batch, epochs, co
     joined the optimizer when that partner was first trained, torch 1.13 zero_grad leaves zero gradients behind)"""
     hp = orc.PPOHyper(batch_size=batch, n_epochs=epochs, ent_coef=0.01)
     orac = _oracle(name, K, seed=7, **kw)
+    o64, _ = H.double_copy(orac)          # the float64 copy of the checker runs the same chain: the allowance of the Adam moments
     model = _algo(name, K, T, E, hp, coef, kw)
     model.policy.set_flat_params(_flat(orac))
     n_steps = 0
@@ -308,6 +330,11 @@ def test_modular_train_chain_matches_the_oracle(name, K, T, E, batch, epochs, co
         n_steps += len(st_ref)
         d = np.abs(model.policy.get_flat_params() - _flat(orac)).max()
         assert d <= 2e-6 * n_steps, (round_, d, n_steps)
+        ref64 = H.chain64_state(o64, lambda o: orc.modular_train(o, bufs, hp, coef, perms=perms), flat_fn=_flat)
+        m, v, _ = H.read_device_adam_state(model.policy)    # Adam's moments, per-module step counts included
+        ref32 = _flat_adam_state(orac)
+        H.assert_chain_moments(m, v, ref32, ref64, (name, K, kw, round_))
+        assert np.array_equal(ref32[2], ref64[2])
         st = model.last_train_stats.reshape(-1, 8)
         assert len(st) == len(st_ref)
         for row, ref in zip(st, st_ref):

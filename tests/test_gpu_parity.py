@@ -566,10 +566,13 @@ def test_split_kernel_weight_image_tracks_the_parameters_through_adam_steps_and_
         assert mismatches(model) == 0
 
 
-def _train_pair(name, T, E, hp: orc.PPOHyper, seed=21, device_perms=False):
+def _train_pair(name, T, E, hp: orc.PPOHyper, seed=21, device_perms=False, f64=False):
+    """f64: also run the chain on a float64 copy of the checker (same buffer, same permutations) and leave its Adam state in
+    model.checker64_state -- the yardstick of helpers.assert_chain_moments"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
     orac = H.oracle_policy(name, seed=seed)
+    o64 = H.double_copy(orac)[0] if f64 else None
     ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
     obs_s, act_s = H.CONFIGS[name]
     env = type("E", (), dict(observation_space=H.to_space(obs_s), action_space=H.to_space(act_s),
@@ -589,6 +592,8 @@ def _train_pair(name, T, E, hp: orc.PPOHyper, seed=21, device_perms=False):
         perms = np.stack([np.random.default_rng(seed + ep).permutation(N) for ep in range(hp.n_epochs)])
         model.train(perms=perms)
     stats_ref = orc.ppo_train(orac, ob, hp, perms)
+    if f64:
+        model.checker64_state = H.chain64_state(o64, lambda o: orc.ppo_train(o, ob, hp, perms))
     return model, orac, stats_ref
 
 
@@ -610,13 +615,16 @@ def _assert_train_stats(row, ref, nb, where=()):
                                                    ("mpe8", 16, 16, 100, 2)])
 def test_train_matches_oracle(name, T, E, batch, epochs):
     hp = orc.PPOHyper(batch_size=batch, n_epochs=epochs)
-    model, orac, stats_ref = _train_pair(name, T, E, hp)
+    model, orac, stats_ref = _train_pair(name, T, E, hp, f64=True)
     st = model.last_train_stats
     assert len(stats_ref) == st.shape[0]
     steps = len(stats_ref)
     p, p_ref = model.policy.get_flat_params(), orac.flat_params()
     assert np.abs(p - p_ref).max() <= 2e-6 * steps + 1e-6, np.abs(p - p_ref).max()
     assert int(model.policy.opt_step.item()) == steps
+    # Adam's moments after the chain against the checker's (tests/test_gpu_optimizer.py compares them step by step)
+    m, v, _ = H.read_device_adam_state(model.policy)
+    H.assert_chain_moments(m, v, H.flat_adam_state(orac), model.checker64_state, (name, T, E, steps))
     N = T * E
     for i, s in enumerate(stats_ref):
         nb_i = min(batch, N - (i % (-(-N // batch))) * batch)
