@@ -557,6 +557,72 @@ int ph_liar_selfplay_step(ph_ctx *ctx, const ph_liar_selfplay *s, int ego_pos, u
  * are then stale.  Needs the 16-row one-hot forward's shape class (<= 64 observation components, <= 32 logits). */
 int ph_liar_selfplay_rollout(ph_ctx *ctx, const ph_liar_selfplay *s, int ego_pos, int n_steps, unsigned long long counter);
 
+/* ---- Liar's Dice against a pool of partners (csrc/ph_pool.h): seat 1 of table e is held by member partnerid[e] of K <=
+ * PH_MAX_POOL members, resampled at that table's own re-deal (MultiAgentEnv.add_partner_agent / resample_round_robin /
+ * resample_random, multiagentenv.py:92-147).  A member is a learner (its own ragged rollout buffer and per-table book-keeping
+ * vectors, as the partner block of ph_liar_selfplay), a frozen policy (samples like any forward, records nothing) or the
+ * scripted player (LiarDefaultAgent, integer rule).  All members share the Liar's Dice spaces and the 64-64 policy. */
+#define PH_MAX_POOL 8
+#define PH_POOL_LEARNER 0
+#define PH_POOL_FROZEN 1
+#define PH_POOL_SCRIPTED 2
+#define PH_POOL_ROBIN 0    /* partnerid <- (partnerid + 1) % K at every deal of the table */
+#define PH_POOL_RANDOM 1   /* partnerid <- (uint64(w) * K) >> 32, w = word 0 of Philox block 101 keyed (pool_seed, deal counter, table) */
+typedef struct ph_pool_member {
+  int kind;                                  /* PH_POOL_* */
+  const float *params;                       /* learner, frozen */
+  const ph_rollout *rb;                      /* learner: (T, n) ragged buffer; NULL otherwise */
+  int *pos;                                  /* (n) learner: per-table write row */
+  unsigned char *boundary, *term, *open;     /* (n) learner: OnPolicyAgent book-keeping per table */
+  float *values, *log_probs;                 /* (n) learner: caches of the last recorded forward; frozen: optional */
+  unsigned long long seed;                   /* learner, frozen: Philox key of its forwards */
+} ph_pool_member;
+/* The grouped forward on its own: ONE launch behind a bucket pass (stable counting sort of the tables with active[e] != 0 by
+ * partnerid[e], 16-row tiles per member).  A workgroup runs one tile with its member's weights: rows of a learner are recorded
+ * at pos[e] of its buffer where the column has room (episode_start_in[e] goes into the row; values cached for recorded rows
+ * only), rows of a frozen member write actions only, rows of the scripted member follow ph_liar_default_actions.  Row e draws
+ * with the Philox key (member seed, counter, e) -- what ph_policy_forward_ragged / ph_policy_forward use -- and stores its
+ * action into actions (n, 2); rows that are not active are not touched.  The spec must run on the 16-row one-hot forward
+ * (<= 64 observation components, <= 32 logits). */
+int ph_pool_forward(ph_ctx *ctx, const ph_spec *spec, const ph_pool_member *members, int n_members, const float *obs,
+                    const int *partnerid, const unsigned char *active, unsigned long long counter, int *actions,
+                    const float *episode_start_in, int n);
+/* LiarDefaultAgent.get_action for the rows with active[e] != 0 (NULL = all): obs (n, 30) f32, actions (n, 2) int32 */
+int ph_liar_default_actions(ph_ctx *ctx, const float *obs, const unsigned char *active, int *actions, int n);
+/* ph_liar_selfplay with the partner block replaced by the pool.  RNG counters of step c: ego forward c, member forwards 2c and
+ * 2c + 1 (each member under its own seed), dice c, resample c. */
+typedef struct ph_liar_pool {
+  int n;
+  const ph_spec *spec;
+  int *hands, *history, *nmoves;
+  unsigned char *ego_first;
+  unsigned long long dice_seed;
+  float probegostart;
+  const float *ego_params;
+  const ph_rollout *ego_rb;
+  int *ego_actions;
+  float *ego_values, *ego_log_probs;
+  float *ego_episode_start;
+  unsigned long long ego_seed;
+  const ph_pool_member *members;             /* host array [n_members] */
+  int n_members;
+  int *partnerid;                            /* (n) member of every table */
+  int resample;                              /* PH_POOL_ROBIN / PH_POOL_RANDOM */
+  unsigned long long pool_seed;
+  int *alt_actions;                          /* (n,2) shared by the members */
+  unsigned char *alt_acted;                  /* (n) the table's member has moved in the current game */
+  float *obs_ego, *obs_alt;
+  unsigned long long *episodes;
+  float *obs_next, *rew1, *rew2, *es_alt;
+  unsigned char *done1, *done2, *running, *can, *alt_opens, *ego_opens, *done;
+} ph_liar_pool;
+/* One vectorised step (deal_only: only the re-deal half, for the tables flagged in `done`): ego forward, book-keeping, bucket
+ * pass + ONE grouped forward for the replies, book-keeping + re-deal + resample, bucket pass + ONE grouped forward for the
+ * openers, book-keeping: 8 launches.  No host synchronisation; capturable once it ran outside capture.  The context keeps ONE
+ * device-side member table, uploaded (with a stream synchronisation) whenever the members passed in differ from it: a captured step
+ * replays against the table uploaded last, so pools that are replayed from graphs should not share a context. */
+int ph_liar_pool_step(ph_ctx *ctx, const ph_liar_pool *pool, int ego_pos, unsigned long long counter, int deal_only);
+
 /* ---- the block worlds: BlockEnv-v0 (variant 0, simpleblockworld.py:36-131) and BlockEnv-v1 (variant 1, blockworld.py:34-83,
  * gridutils.py:8-64).  The planner (ego) always moves first; the constructor is the partner.  A table is PH_BLOCK_STATE_WORDS
  * int32 words, 16-byte aligned (layout: csrc/ph_block.h).  Observations are the raw integer components as f32:

@@ -207,6 +207,34 @@ class PhBlockSelfPlay(C.Structure):
 
 PH_BLOCK_STATE_WORDS = 12
 
+PH_MAX_POOL = 8
+PH_POOL_LEARNER, PH_POOL_FROZEN, PH_POOL_SCRIPTED = 0, 1, 2
+POOL_RESAMPLE = {"robin": 0, "random": 1}
+
+
+class PhPoolMember(C.Structure):
+    """ph_pool_member: one member of a partner pool (learner / frozen / scripted)"""
+    _fields_ = [("kind", C.c_int), ("params", C.c_void_p), ("rb", C.POINTER(PhRollout)), ("pos", C.c_void_p),
+                ("boundary", C.c_void_p), ("term", C.c_void_p), ("open", C.c_void_p), ("values", C.c_void_p),
+                ("log_probs", C.c_void_p), ("seed", C.c_ulonglong)]
+
+
+class PhLiarPool(C.Structure):
+    """ph_liar_pool: ph_liar_selfplay with the partner block replaced by a pool of members"""
+    _fields_ = [("n", C.c_int), ("spec", C.POINTER(PhSpec)),
+                ("hands", C.c_void_p), ("history", C.c_void_p), ("nmoves", C.c_void_p), ("ego_first", C.c_void_p),
+                ("dice_seed", C.c_ulonglong), ("probegostart", C.c_float),
+                ("ego_params", C.c_void_p), ("ego_rb", C.POINTER(PhRollout)), ("ego_actions", C.c_void_p),
+                ("ego_values", C.c_void_p), ("ego_log_probs", C.c_void_p), ("ego_episode_start", C.c_void_p),
+                ("ego_seed", C.c_ulonglong),
+                ("members", C.POINTER(PhPoolMember)), ("n_members", C.c_int), ("partnerid", C.c_void_p),
+                ("resample", C.c_int), ("pool_seed", C.c_ulonglong),
+                ("alt_actions", C.c_void_p), ("alt_acted", C.c_void_p),
+                ("obs_ego", C.c_void_p), ("obs_alt", C.c_void_p), ("episodes", C.c_void_p),
+                ("obs_next", C.c_void_p), ("rew1", C.c_void_p), ("rew2", C.c_void_p), ("es_alt", C.c_void_p),
+                ("done1", C.c_void_p), ("done2", C.c_void_p), ("running", C.c_void_p), ("can", C.c_void_p),
+                ("alt_opens", C.c_void_p), ("ego_opens", C.c_void_p), ("done", C.c_void_p)]
+
 SIGNATURES = {
     "ph_abi_version": [],
     "ph_roundrobin_env_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, _i],
@@ -260,6 +288,9 @@ SIGNATURES = {
     "ph_liar_obs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ph_liar_selfplay_step": [_vp, C.POINTER(PhLiarSelfPlay), _i, _ull, _i],
     "ph_liar_selfplay_rollout": [_vp, C.POINTER(PhLiarSelfPlay), _i, _i, _ull],
+    "ph_pool_forward": [_vp, C.POINTER(PhSpec), C.POINTER(PhPoolMember), _i, _vp, _vp, _vp, _ull, _vp, _vp, _i],
+    "ph_liar_default_actions": [_vp, _vp, _vp, _vp, _i],
+    "ph_liar_pool_step": [_vp, C.POINTER(PhLiarPool), _i, _ull, _i],
     "ph_block_reset": [_vp, _i, _vp, _vp, _ull, _ull, _i],
     "ph_block_step": [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i],
     "ph_block_obs": [_vp, _i, _vp, _i, _vp, _vp, _i],

@@ -17,6 +17,7 @@
 #include "ph_launch.h"
 #include "ph_block.h"
 #include "ph_arch.h"
+#include "ph_pool.h"
 
 namespace ph {
 
@@ -173,6 +174,14 @@ struct ph_ctx {
   int num_cu = 256;
   int exchange_blocks_per_cu = 0;           // occupancy answer for the exchange rollout kernel (0 = not asked yet)
   unsigned long long* rng_epoch = nullptr;  // caller-owned device word
+  // partner pool (ph_pool.h): the member table the kernels read (device) with what it holds (host), the bucket pass's outputs
+  ph::PoolMemberDev* pool_dev = nullptr;
+  ph::PoolMemberDev pool_host[PH_MAX_POOL];
+  int pool_count = 0;                       // members pool_dev holds, 0 = nothing yet
+  int* pool_order = nullptr;                // (n)
+  size_t pool_order_cap = 0;
+  int* pool_tiles = nullptr;                // [pool_max_tiles + 1][3]; the last record's first word is the tile count
+  size_t pool_tiles_cap = 0;
   long long* prof = nullptr;                // caller-owned debug stamp buffer
   // ModularAlgorithm workspace (ph_modular_*): activations and head gradients in minibatch order, the towers' slab maps
   struct ModWs {
@@ -628,7 +637,7 @@ int ph_ctx_destroy(ph_ctx* ctx) {
     if (s.act_off) (void)hipFree(s.act_off);
   }
   void* ptrs[] = {ctx->wimage, ctx->mw.act, ctx->mw.maps, ctx->mw.kl_sum, ctx->mw.scratch, ctx->advpart, ctx->p2p_dev, ctx->slabs, ctx->statpart, ctx->grad, ctx->blocksq, ctx->advstats, ctx->perm_idx, ctx->perm_phys, ctx->ximg, ctx->rec_pi, ctx->rec_vf, ctx->rowrec, ctx->step_words, ctx->step_gen, ctx->scalars, ctx->stop_flag,
-                  ctx->adap_extra, ctx->adap_loss, ctx->am_buf};
+                  ctx->adap_extra, ctx->adap_loss, ctx->am_buf, ctx->pool_dev, ctx->pool_order, ctx->pool_tiles};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (ctx->act_stage_host) (void)hipHostFree(ctx->act_stage_host);
@@ -1690,6 +1699,165 @@ int ph_liar_selfplay_step(ph_ctx* ctx, const ph_liar_selfplay* sp, int ego_pos, 
                                s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
     return 1;
   PH_HIP(ph::launch_liar_sp_after_opening(s, st));
+  return 0;
+}
+
+// ---- Liar's Dice against a pool of partners (ph_pool.h) ----
+namespace {
+// validate the members and bring the device-side table up to date (uploaded only when it changed; never inside graph capture)
+int pool_members(ph_ctx* ctx, const char* who, const ph_pool_member* members, int K, int n) {
+  const std::string w(who);
+  if (!members) return fail(w + ": null member array");
+  if (K < 1 || K > PH_MAX_POOL) return fail(w + ": the pool holds 1..PH_MAX_POOL members");
+  ph::PoolMemberDev tab[PH_MAX_POOL];
+  std::memset(tab, 0, sizeof(tab));
+  for (int k = 0; k < K; ++k) {
+    const ph_pool_member& m = members[k];
+    ph::PoolMemberDev& d = tab[k];
+    const std::string wk = w + ": member " + std::to_string(k);
+    if (m.kind != PH_POOL_LEARNER && m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED) return fail(wk + ": unknown kind");
+    d.kind = m.kind;
+    if (m.kind == PH_POOL_SCRIPTED) continue;
+    if (!m.params) return fail(wk + ": null params");
+    if ((uintptr_t)m.params % 16 != 0) return fail(wk + ": params must be 16-byte aligned");
+    d.params = m.params;
+    d.seed = m.seed;
+    d.values = m.values;
+    d.log_probs = m.log_probs;
+    if (m.kind == PH_POOL_FROZEN) continue;
+    if (!m.rb) return fail(wk + ": a learner needs its rollout buffer");
+    if (check_rb(m.rb)) return 1;
+    if (m.rb->E != n) return fail(wk + ": the learner's buffer must have E = n");
+    if (!m.pos || !m.boundary || !m.term || !m.open || !m.values || !m.log_probs)
+      return fail(wk + ": a learner needs pos / boundary / term / open / values / log_probs");
+    d.rb_T = m.rb->T;
+    d.rb_obs = m.rb->observations;
+    d.rb_act = m.rb->actions;
+    d.rb_rew = m.rb->rewards;
+    d.rb_es = m.rb->episode_starts;
+    d.rb_val = m.rb->values;
+    d.rb_logp = m.rb->log_probs;
+    d.pos = m.pos;
+    d.boundary = m.boundary;
+    d.term = m.term;
+    d.open = m.open;
+  }
+  if (ctx->pool_count != K || std::memcmp(ctx->pool_host, tab, sizeof(tab)) != 0) {
+    if (ctx->capturing) return fail(w + ": the member table changed inside graph capture: run the same call once outside capture first");
+    if (!ctx->pool_dev) PH_HIP(hipMalloc((void**)&ctx->pool_dev, sizeof(tab)));
+    PH_HIP(hipStreamSynchronize(ctx->stream));   // launches in flight still read the table
+    std::memcpy(ctx->pool_host, tab, sizeof(tab));
+    ctx->pool_count = 0;
+    PH_HIP(hipMemcpyAsync(ctx->pool_dev, ctx->pool_host, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->pool_count = K;
+  }
+  return 0;
+}
+
+// bucket pass + the grouped forward over the tables with active[e] != 0
+int pool_forward(ph_ctx* ctx, const char* who, const ph_spec* spec, int K, const float* obs, const int* partnerid,
+                 const unsigned char* active, const unsigned char* rec_mask, unsigned long long counter, int* actions,
+                 const float* es_in, int n) {
+  ph::PoolFwd p;
+  std::memset(&p, 0, sizeof(p));
+  if (fwd_args(p.a, ctx, spec, false, nullptr, obs, n, 0, counter, actions, nullptr, nullptr)) return 1;
+  if (!ph::pool_fwd_eligible(p.a.nd, n))
+    return fail(std::string(who) + ": the spec is not the Liar's Dice 16-row one-hot class (30 observation components, <= 32 logits, "
+                                   "two action components, n < 16384)");
+  p.a.rec_mask = rec_mask;
+  p.a.es_in = es_in;
+  if (ensure(ctx, ctx->pool_order, ctx->pool_order_cap, (size_t)n)) return 1;
+  const size_t ntile = (size_t)ph::pool_max_tiles(n, PH_MAX_POOL);
+  if (ensure(ctx, ctx->pool_tiles, ctx->pool_tiles_cap, 3 * (ntile + 1))) return 1;
+  p.members = ctx->pool_dev;
+  p.b.order = ctx->pool_order;
+  p.b.tiles = ctx->pool_tiles;
+  p.b.ntiles = ctx->pool_tiles + 3 * ntile;
+  PH_HIP(ph::launch_pool_bucket(partnerid, active, n, K, p.b, ctx->stream));
+  PH_HIP(ph::launch_pool_fwd(p, K, ctx->stream));
+  return 0;
+}
+}  // namespace
+
+int ph_pool_forward(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* members, int n_members, const float* obs,
+                    const int* partnerid, const unsigned char* active, unsigned long long counter, int* actions,
+                    const float* episode_start_in, int n) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!spec || !obs || !partnerid || !active || !actions) return fail("ph_pool_forward: null argument");
+  if (n <= 0) return fail("ph_pool_forward: n must be positive");
+  if ((uintptr_t)actions % 8) return fail("ph_pool_forward: actions must be 8-byte aligned");
+  if (pool_members(ctx, "ph_pool_forward", members, n_members, n)) return 1;
+  for (int k = 0; k < n_members; ++k)
+    if (members[k].kind == PH_POOL_LEARNER && !episode_start_in) return fail("ph_pool_forward: learners need episode_start_in");
+  return pool_forward(ctx, "ph_pool_forward", spec, n_members, obs, partnerid, active, active, counter, actions, episode_start_in, n);
+}
+
+int ph_liar_default_actions(ph_ctx* ctx, const float* obs, const unsigned char* active, int* actions, int n) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!obs || !actions) return fail("ph_liar_default_actions: null argument");
+  if (n <= 0) return fail("ph_liar_default_actions: n must be positive");
+  if ((uintptr_t)actions % 8) return fail("ph_liar_default_actions: actions must be 8-byte aligned");
+  PH_HIP(ph::launch_liar_default_actions(obs, active, actions, n, ctx->stream));
+  return 0;
+}
+
+int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsigned long long counter, int deal_only) {
+  DevGuard dev_guard(ctx);
+  if (!ctx || !pool) return fail("ph_liar_pool_step: null argument");
+  const ph_liar_pool& s = *pool;
+  if (s.n <= 0 || !s.spec || !s.ego_rb) return fail("ph_liar_pool_step: incomplete description");
+  if (!s.hands || !s.history || !s.nmoves || !s.ego_first || !s.ego_params || !s.ego_actions || !s.ego_episode_start || !s.partnerid ||
+      !s.alt_actions || !s.alt_acted || !s.obs_ego || !s.obs_alt || !s.episodes || !s.obs_next || !s.rew1 || !s.rew2 || !s.es_alt ||
+      !s.done1 || !s.done2 || !s.running || !s.can || !s.alt_opens || !s.ego_opens || !s.done)
+    return fail("ph_liar_pool_step: incomplete description");
+  if (s.resample != PH_POOL_ROBIN && s.resample != PH_POOL_RANDOM) return fail("ph_liar_pool_step: unknown resample rule");
+  if (check_rb(s.ego_rb)) return 1;
+  if (s.ego_rb->E != s.n) return fail("ph_liar_pool_step: buffers must have E = n");
+  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
+      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
+       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
+    return fail("ph_liar_pool_step: hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
+  if (pool_members(ctx, "ph_liar_pool_step", s.members, s.n_members, s.n)) return 1;
+  {
+    ph::NetDims nd;
+    if (resolve(ctx, s.spec, &nd)) return 1;
+    if (!ph::pool_fwd_eligible(nd, s.n)) return fail("ph_liar_pool_step: the spec is not the Liar's Dice 16-row one-hot class");
+  }
+  if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail("ph_liar_pool_step: ego_pos out of range (buffer full?)");
+  ph::PoolStep d;
+  std::memset(&d, 0, sizeof(d));
+  d.n = s.n; d.K = s.n_members; d.resample = s.resample;
+  d.hands = s.hands; d.history = s.history; d.nmoves = s.nmoves; d.ego_first = s.ego_first;
+  d.dice_seed = s.dice_seed; d.pool_seed = s.pool_seed; d.probegostart = s.probegostart;
+  d.ego_actions = s.ego_actions; d.ego_episode_start = s.ego_episode_start;
+  d.members = ctx->pool_dev; d.partnerid = s.partnerid; d.alt_actions = s.alt_actions; d.alt_acted = s.alt_acted;
+  d.obs_ego = s.obs_ego; d.obs_alt = s.obs_alt; d.episodes = s.episodes;
+  d.obs_next = s.obs_next; d.rew1 = s.rew1; d.rew2 = s.rew2; d.es_alt = s.es_alt;
+  d.done1 = s.done1; d.done2 = s.done2; d.running = s.running; d.can = s.can;
+  d.alt_opens = s.alt_opens; d.ego_opens = s.ego_opens; d.done = s.done;
+  hipStream_t st = ctx->stream;
+  if (!deal_only) {
+    // the ego moves in every table
+    if (ph_policy_forward(ctx, s.spec, s.ego_params, s.obs_ego, s.n, nullptr, nullptr, nullptr, s.ego_seed, counter, 0,
+                          s.ego_actions, nullptr, s.ego_values, s.ego_log_probs, nullptr, nullptr, s.ego_rb, ego_pos,
+                          s.ego_episode_start, nullptr, 0))
+      return 1;
+    PH_HIP(ph::launch_pool_after_ego(d, st));
+    // every table's member replies where the game goes on: one grouped launch
+    if (pool_forward(ctx, "ph_liar_pool_step", s.spec, s.n_members, s.obs_next, s.partnerid, s.running, s.can, 2 * counter,
+                     s.alt_actions, s.es_alt, s.n))
+      return 1;
+  }
+  PH_HIP(ph::launch_pool_after_reply(d, deal_only ? nullptr : s.ego_rb->rewards + (size_t)ego_pos * s.n, counter, ctx->rng_epoch,
+                                     deal_only, st));
+  // the freshly sampled members open the games they start
+  if (pool_forward(ctx, "ph_liar_pool_step", s.spec, s.n_members, s.obs_alt, s.partnerid, s.alt_opens, s.can, 2 * counter + 1,
+                   s.alt_actions, s.es_alt, s.n))
+    return 1;
+  PH_HIP(ph::launch_pool_after_opening(d, st));
   return 0;
 }
 

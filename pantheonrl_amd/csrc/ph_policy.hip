@@ -10,6 +10,7 @@
 #include <initializer_list>
 #include "ph_rowtail.h"
 #include "ph_liar_group.h"
+#include "ph_pool.h"
 
 namespace ph {
 
@@ -761,11 +762,19 @@ __device__ __forceinline__ ResidentNet resident_net_at(float* base) {
 // scratch of one half (one net) of a fused forward in RES form: xs, hs, outs, feat, aoff, seg, ridxs (see the body)
 constexpr int RES_SCRATCH_FLOATS = 2 * 16 * LDH + 16 * 33 + 2 * 16 * 64 + 40 + 96 + 2 * 16 + 8;
 
-template <bool VALU, bool FUSED = false, bool RES = false>
+// MAP (the pool's grouped forward, ph_pool.h): the workgroup's rows are the tables map[0 .. map_n) instead of 16 consecutive ones --
+// observations are gathered through the map and every per-row output (Philox key, action, caches, rollout-buffer row) goes to the
+// row's table.  The tile arithmetic is the same, and a row's result does not depend on its position in the tile.
+template <bool MAP>
+__device__ __forceinline__ int fwd16h_row(const int* map, int row, int row0, int n_end) {
+  if constexpr (MAP) return map[row < n_end ? row : row0];
+  else return row;
+}
+template <bool VALU, bool FUSED = false, bool RES = false, bool MAP = false>
 __device__ __forceinline__ void policy_fwd16h_body(const FwdArgs& a, int row0_in = 0, int net_in = 0, int tid_in = 0,
                                                    float* smem_in = nullptr, int row_end_in = 0,
                                                    const ResidentNet resv = ResidentNet{nullptr, nullptr, nullptr, nullptr, nullptr},
-                                                   const int* ooff = nullptr) {
+                                                   const int* ooff = nullptr, const int* map = nullptr, int map_n = 0) {
   const ResidentNet* const res = &resv;   // (by value: a pointer to a caller's record would pin it in scratch memory)
   extern __shared__ __attribute__((aligned(16))) float smem_dyn[];
   float* smem = FUSED ? smem_in : smem_dyn;
@@ -788,10 +797,10 @@ __device__ __forceinline__ void policy_fwd16h_body(const FwdArgs& a, int row0_in
   const int tid = FUSED ? tid_in : (int)threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
   const int net = FUSED ? net_in : (int)blockIdx.y;
-  const int row0 = FUSED ? row0_in : (int)blockIdx.x * R;
+  const int row0 = (FUSED || MAP) ? row0_in : (int)blockIdx.x * R;
   // rows [row0, n_end) are this workgroup's; the persistent rollout may own fewer than 16 tables per workgroup (a.n stays the
   // row stride of the ragged rollout-buffer addressing)
-  const int n_end = FUSED ? row_end_in : a.n;
+  const int n_end = MAP ? map_n : (FUSED ? row_end_in : a.n);
   const ph_layout& lay = nd.lay;
   const float* W1 = a.params + (net == 0 ? lay.pi_W1 : lay.vf_W1);
   const float* B1 = a.params + (net == 0 ? lay.pi_b1 : lay.vf_b1);
@@ -818,7 +827,7 @@ __device__ __forceinline__ void policy_fwd16h_body(const FwdArgs& a, int row0_in
       const int cs = ok ? comp : 0, rs = ok ? row : row0;
       lo[i] = off[cs];
       hi[i] = off[cs + 1];
-      xo[i] = a.obs[(size_t)rs * D + cs];
+      xo[i] = a.obs[(size_t)fwd16h_row<MAP>(map, rs, row0, n_end) * D + cs];
     }
 #pragma unroll
     for (int i = 0; i < R * FS / NT; ++i) {
@@ -830,7 +839,7 @@ __device__ __forceinline__ void policy_fwd16h_body(const FwdArgs& a, int row0_in
     }
   }
   long long ridxv = -1;
-  if (net == 0 && tid < R && row0 + tid < n_end && (a.rb_act || a.rb_logp)) ridxv = rb_row(a, row0 + tid);
+  if (net == 0 && tid < R && row0 + tid < n_end && (a.rb_act || a.rb_logp)) ridxv = rb_row(a, fwd16h_row<MAP>(map, row0 + tid, row0, n_end));
   WStage<NT> w2r;
   const int gr = tid >> 4, gl = tid & 15;   // gather: row gr, hidden units 4*gl .. 4*gl+3
   float b1v[4];
@@ -930,8 +939,8 @@ __device__ __forceinline__ void policy_fwd16h_body(const FwdArgs& a, int row0_in
       }
       const uint64_t ctr = fwd_counter(a);
       const int r0 = row0 + (tid >> 5);
-      u_tail[0] = head_draw32(a, r0, r0 < n_end, comp, ctr);
-      u_tail[1] = (row0 + 8 < n_end) ? head_draw32(a, r0 + 8, r0 + 8 < n_end, comp, ctr) : 0.f;
+      u_tail[0] = head_draw32(a, fwd16h_row<MAP>(map, r0, row0, n_end), r0 < n_end, comp, ctr);
+      u_tail[1] = (row0 + 8 < n_end) ? head_draw32(a, fwd16h_row<MAP>(map, r0 + 8, row0, n_end), r0 + 8 < n_end, comp, ctr) : 0.f;
     }
     if (wave_live) {
       // (w[0] opaque: otherwise "0 + w[0]" moves into the block of the first gathers, with a full wait behind them; the uniforms
@@ -1035,7 +1044,8 @@ __device__ __forceinline__ void policy_fwd16h_body(const FwdArgs& a, int row0_in
       for (int pass = 0; pass < 2; ++pass) {   // 32 lanes per row, 8 rows per pass
         if (pass == 1 && row0 + 8 >= n_end) break;   // no live row in the second pass (workgroup-uniform)
         const int r = pass * 8 + (tid >> 5);
-        head_tail32(a, nd, row0 + r, row0 + r < n_end, ridxs[r], outs[r * LDO + k], k, lo, last, comp, u_tail[pass]);
+        head_tail32(a, nd, fwd16h_row<MAP>(map, row0 + r, row0, n_end), row0 + r < n_end, ridxs[r], outs[r * LDO + k], k, lo, last, comp,
+                    u_tail[pass]);
       }
     }
   } else {
@@ -1054,9 +1064,18 @@ __device__ __forceinline__ void policy_fwd16h_body(const FwdArgs& a, int row0_in
 #pragma unroll
       for (int m = 0; m < 16; ++m) v = __builtin_fmaf(hx[m], hw[m], v);
       v = quad_sum_f(v) + hbs[0];
-      if (q == 0 && row0 + r < n_end) value_row_tail(a, row0 + r, v);
+      if (q == 0 && row0 + r < n_end) value_row_tail(a, fwd16h_row<MAP>(map, row0 + r, row0, n_end), v);
     }
-    copy_obs_rows(a, row0, (n_end - row0 < R) ? n_end - row0 : R, nd.D, tid, NT);
+    if constexpr (MAP) {
+      if (a.rb_obs)
+        for (int e = tid; e < (n_end - row0) * nd.D; e += NT) {
+          const int r = e / nd.D, d = e - r * nd.D, gt = map[row0 + r];
+          const long long ridx = rb_row(a, gt);
+          if (ridx >= 0) a.rb_obs[(size_t)ridx * nd.D + d] = a.obs[(size_t)gt * nd.D + d];
+        }
+    } else {
+      copy_obs_rows(a, row0, (n_end - row0 < R) ? n_end - row0 : R, nd.D, tid, NT);
+    }
   }
   PH_STAMP(a.prof, 7);
 }
@@ -1068,6 +1087,51 @@ __global__ __launch_bounds__(256) void policy_fwd16h_kernel(FwdArgs a) {
 
 static size_t fwd16h_lds_bytes() {
   return sizeof(float) * (size_t)(2 * 16 * LDH + 2 * HID * LDH + 16 * 33 + HID + 32 + 2 * 16 * 64 + 40 + 96 + 2 * 16);
+}
+
+// ---- the pool's grouped forward (ph_pool.h): one workgroup per (tile of the bucket pass, net) ---------------------------------
+// The tile names a member and <= 16 sorted positions; the workgroup patches that member's weights, seed, caches and ragged buffer
+// into its copy of the shared record (uniform loads from the device-side member table) and runs the 16-row one-hot forward over
+// the tables order[first .. first + rows).  A frozen member has no buffer and no caches: its value net has nothing to write and is
+// skipped.  A scripted member's tile applies the integer rule instead of the net.
+template <bool VALU>
+__global__ __launch_bounds__(256) void pool_fwd16h_kernel(PoolFwd p) {
+  const int tile = blockIdx.x;
+  if (tile >= p.b.ntiles[0]) return;
+  const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1], rows = p.b.tiles[3 * tile + 2];
+  const int* map = p.b.order + first;
+  const PoolMemberDev& m = p.members[member];
+  const int kind = m.kind;
+  if (kind == PH_POOL_SCRIPTED) {
+    if (blockIdx.y == 0 && (int)threadIdx.x < rows) {
+      const int g = map[threadIdx.x];
+      *reinterpret_cast<int2*>(p.a.act_i32 + 2 * (size_t)g) = liar_default_move(p.a.obs + (size_t)g * p.a.nd.D);
+    }
+    return;
+  }
+  const bool learner = kind == PH_POOL_LEARNER;
+  if (blockIdx.y == 1 && !learner && !m.values) return;
+  FwdArgs a = p.a;
+  a.params = m.params;
+  a.seed = m.seed;
+  a.values = m.values;
+  a.logp = m.log_probs;
+  if (learner) {
+    a.rb_obs = m.rb_obs;
+    a.rb_act = m.rb_act;
+    a.rb_rew = m.rb_rew;
+    a.rb_es = m.rb_es;
+    a.rb_val = m.rb_val;
+    a.rb_logp = m.rb_logp;
+    a.pos_env = m.pos;
+    a.rb_T = m.rb_T;
+  } else {
+    a.pos_env = nullptr;
+    a.rec_mask = nullptr;
+    a.es_in = nullptr;
+  }
+  policy_fwd16h_body<VALU, false, false, true>(a, 0, 0, 0, nullptr, 0, ResidentNet{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr,
+                                               map, rows);
 }
 
 // one net (policy: net 0, value: net 1) of `params` into a resident set, by the 256 lanes of the half that runs that net -- the very
@@ -1674,6 +1738,13 @@ static bool fwd16h_eligible(const NetDims& nd, int n) {
 template <bool VALU>
 static hipError_t launch_fwd16h_variant(const FwdArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((policy_fwd16h_kernel<VALU>), dim3((a.n + 15) / 16, 2), dim3(256), fwd16h_lds_bytes(), s, a);
+  return hipGetLastError();
+}
+
+bool pool_fwd_eligible(const NetDims& nd, int n) { return fwd16h_eligible(nd, n) && !fwd16_eligible(nd, n) && nd.D == 30 && nd.A == 2; }
+hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s) {
+  if (!pool_fwd_eligible(p.a.nd, p.a.n)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((pool_fwd16h_kernel<false>), dim3(pool_max_tiles(p.a.n, K), 2), dim3(256), fwd16h_lds_bytes(), s, p);
   return hipGetLastError();
 }
 

@@ -384,6 +384,313 @@ class VecLiarSelfPlay:
             self.alt.learn_from_buffer()
 
 
+# ---- a pool of partners at seat 1 (MultiAgentEnv.add_partner_agent / resample_*, multiagentenv.py:92-147) -----------------------
+POOL_SEED_SALT = 0x9001C0DE9001C0DE          # the resample stream's own Philox key: pool seed = dice seed ^ this constant
+POOL_RESAMPLE_BLOCK = 101                    # Philox block of the resample word (the dice use blocks 0..2, the first mover 100)
+
+
+def pool_resample(prev: int, n_members: int, rule: str = "robin", word: int = None) -> int:
+    """the member that sits at a table's next game.  "robin": the next one in turn (resample_round_robin; applied at the first
+    deal too, so every table starts at 1 % K -- SURVEY quirk D-9).  "random": the 32-bit `word` scaled to [0, K) without a
+    division -- `word` is word 0 of Philox block POOL_RESAMPLE_BLOCK keyed (pool seed, deal counter, table)."""
+    if rule == "robin":
+        return (int(prev) + 1) % int(n_members)
+    if rule != "random":
+        raise ValueError(f"resample must be 'robin' or 'random', not {rule!r}")
+    return ((int(word) & 0xFFFFFFFF) * int(n_members)) >> 32
+
+
+def philox_word0(seed: int, counter: int, rows: np.ndarray, block: int) -> np.ndarray:
+    """word 0 of Philox4x32-10 for the counters (row, block, counter lo, counter hi) under the key `seed`: the host statement of
+    what the kernels draw (csrc/ph_device.h)"""
+    mask = np.uint64(0xFFFFFFFF)
+    c0 = np.asarray(rows, np.uint64) & mask
+    c1 = np.full_like(c0, int(block) & 0xFFFFFFFF)
+    c2 = np.full_like(c0, int(counter) & 0xFFFFFFFF)
+    c3 = np.full_like(c0, (int(counter) >> 32) & 0xFFFFFFFF)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0)) & mask, p1 & mask, \
+            ((p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1)) & mask, p0 & mask
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0.astype(np.uint32)
+
+
+class FrozenVecPartner:
+    """A pool member that plays a fixed policy: the E-table form of StaticPolicyAgent (agents.py:54-79).  It samples like any
+    forward (its own Philox key and counter), records nothing, and `update` is a no-op."""
+    kind = nat.PH_POOL_FROZEN
+
+    def __init__(self, policy):
+        require_mlp_kernels(policy, type(self).__name__)
+        self.policy = policy
+        self._out = {}
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
+        pol = self.policy
+        n = int(obs.shape[0])
+        out = self._out.get(n)
+        if out is None:
+            out = self._out[n] = (th.zeros((n, pol.layout.A), dtype=th.int32, device=pol.device),
+                                  th.zeros(n, dtype=th.float32, device=pol.device), th.zeros(n, dtype=th.float32, device=pol.device))
+        pol._bind()
+        pol._counter += 1
+        nat.check(pol.ctx.lib.ph_policy_forward(
+            pol.ctx.handle, C.byref(pol.spec), pol.params.data_ptr(), obs.data_ptr(), n, None, None, None, pol._seed, pol._counter,
+            0, out[0].data_ptr(), None, out[1].data_ptr(), out[2].data_ptr(), None, None, None, 0, None, None, 0))
+        return out[0]
+
+    def update(self, reward, done, mask=None) -> None:
+        return None
+
+
+class VecLiarDefaultPartner:
+    """The scripted pool member: LiarDefaultAgent (envs/liar.py) for E tables, integer-exact (`ph_liar_default_actions`)."""
+    kind = nat.PH_POOL_SCRIPTED
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor, out: th.Tensor, ctx: nat.Context) -> th.Tensor:
+        """writes the rule's move into `out` (E, 2) int32 where rec_mask is set; the other rows keep what they hold"""
+        nat.check(ctx.lib.ph_liar_default_actions(ctx.handle, obs.data_ptr(), nat.ptr(rec_mask), out.data_ptr(), int(obs.shape[0])))
+        return out
+
+    def update(self, reward, done, mask=None) -> None:
+        return None
+
+
+class VecLiarPartnerPool:
+    """`trainer.py LiarsDice-v0 PPO <alt>+ --n-envs E`: n_envs Liar's Dice tables resident on the device, seat 1 of every table
+    held by one of K <= 8 pool members -- learners (RaggedVecOnPolicyAgent), frozen policies (FrozenVecPartner) or the scripted
+    player (VecLiarDefaultPartner).  `partnerid[e]` names table e's member; it is resampled at that table's own re-deal
+    (`pool_resample`), the first deal included.
+
+    Per table the callbacks are VecLiarSelfPlay's, with every partner-side mask ANDed with `partnerid == k`: credit goes to the
+    member that has acted in this game (`alt_acted`, cleared at the deal), the member that opens a new game is the newly sampled
+    one, and a member's `boundary` flag of a table survives the games it sits out, so its next recorded row there starts an
+    episode.  RNG counters of step c: ego forward c, member forwards 2c and 2c + 1 (each member under its own seed), dice c,
+    resample c.  `rollout_and_learn` trains the ego, then every learner whose `full()` holds; a learner's `min_full` becomes
+    max(1, E // K) unless the caller lowered it already.
+
+    native=True: one `ph_liar_pool_step` per vectorised step -- a bucket pass and ONE grouped forward per partner move whatever
+    K is, no host synchronisation.  native=False: the readable walk -- per-member get_action / update calls with torch masks
+    (K full forwards per partner move), the per-call entry points only, the same counters; bitwise the native step."""
+
+    def __init__(self, n_envs: int, ego: VecOnPolicyAgent, members, seed: int = 0, probegostart: float = 0.5,
+                 resample: str = "robin", native: bool = True):
+        members = list(members)
+        if not 1 <= len(members) <= nat.PH_MAX_POOL:
+            raise nat.NativeError(f"VecLiarPartnerPool: the pool holds 1..{nat.PH_MAX_POOL} members, not {len(members)}")
+        if resample not in nat.POOL_RESAMPLE:
+            raise nat.NativeError(f"VecLiarPartnerPool: resample must be one of {sorted(nat.POOL_RESAMPLE)}, not {resample!r}")
+        self.E, self.ego, self.members, self.native, self.resample = n_envs, ego, members, bool(native), resample
+        self.K = len(members)
+        pol = ego.model.policy
+        self.dev = pol.device
+        for who in [ego] + members:
+            p = self._policy_of(who)
+            if p is None:
+                continue
+            require_mlp_kernels(p, type(self).__name__)
+            lay = p.layout
+            if (lay.D, lay.A, lay.L) != (30, 2, 19):
+                raise nat.NativeError("VecLiarPartnerPool: every member plays on the Liar's Dice spaces")
+        self.learners = [m for m in members if isinstance(m, RaggedVecOnPolicyAgent)]
+        for m in self.learners:
+            if m.E != n_envs:
+                raise nat.NativeError("VecLiarPartnerPool: a learner's rollout buffer must have n_envs columns")
+            if m.min_full >= m.E:
+                m.min_full = max(1, n_envs // self.K)
+        self.env = VecLiarsDice(n_envs, pol.ctx, self.dev)
+        self.seed, self.probegostart = int(seed), float(probegostart)
+        self.pool_seed = (self.seed ^ POOL_SEED_SALT) & 0x7FFFFFFFFFFFFFFF
+        E, dev = n_envs, self.dev
+        u8 = lambda v=0: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
+        self.partnerid = th.zeros(E, dtype=th.int32, device=dev)
+        self.ego_first = u8()
+        self.obs_ego = th.zeros((E, 30), dtype=th.float32, device=dev)
+        self.obs_alt = th.zeros((E, 30), dtype=th.float32, device=dev)
+        self.alt_actions = th.zeros((E, 2), dtype=th.int32, device=dev)
+        self.alt_acted = u8()
+        self.ones8, self.zeros8 = u8(1), u8(0)
+        self._rows = np.arange(E)
+        self._episodes_dev = th.zeros(1, dtype=th.int64, device=dev)
+        self.steps_done = 0
+        if self.native:
+            self._build_native()
+            self._done.fill_(1)
+            self._native_call(0, deal_only=True)
+        else:
+            self._deal(self.ones8, 0)
+
+    @staticmethod
+    def _policy_of(agent):
+        if isinstance(agent, VecLiarDefaultPartner):
+            return None
+        return agent.policy if isinstance(agent, FrozenVecPartner) else agent.model.policy
+
+    @property
+    def episodes(self) -> int:
+        return int(self._episodes_dev.item())
+
+    def _bind(self):
+        stream = th.cuda.current_stream(self.dev).cuda_stream
+        self.env.ctx.set_stream(stream)
+        for agent in [self.ego] + self.members:
+            p = self._policy_of(agent)
+            if p is not None:
+                p.ctx.set_stream(stream)
+
+    # -- the engine-side step ------------------------------------------------------------------------------------------------------
+    def _build_native(self) -> None:
+        E, dev, env, ego = self.E, self.dev, self.env, self.ego
+        f32 = lambda *shape: th.zeros(shape, dtype=th.float32, device=dev)  # noqa: E731
+        u8 = lambda: th.zeros(E, dtype=th.uint8, device=dev)               # noqa: E731
+        self._obs_next, self._rew1, self._rew2, self._es_alt = f32(E, 30), f32(E, 2), f32(E, 2), f32(E)
+        self._done1, self._done2, self._running, self._can = u8(), u8(), u8(), u8()
+        self._alt_opens, self._ego_opens, self._done = u8(), u8(), u8()
+        ego._last_episode_starts = ego._last_episode_starts.clone()    # updated in place by the step from here on
+        self._member_rbc = []
+        arr = (nat.PhPoolMember * self.K)()
+        for k, m in enumerate(self.members):
+            c = arr[k]
+            c.kind = m.kind if not isinstance(m, RaggedVecOnPolicyAgent) else nat.PH_POOL_LEARNER
+            p = self._policy_of(m)
+            if p is None:
+                continue
+            c.params, c.seed = p.params.data_ptr(), p._seed
+            if isinstance(m, RaggedVecOnPolicyAgent):
+                rbc = m.model.rollout_buffer.c_struct()
+                self._member_rbc.append(rbc)
+                c.rb = C.pointer(rbc)
+                c.pos, c.boundary, c.term, c.open = (t.data_ptr() for t in (m.pos, m.boundary, m.term, m.open))
+                c.values, c.log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
+        self._member_arr = arr
+        s = nat.PhLiarPool()
+        s.n, s.spec = E, C.pointer(ego.model.policy.spec)
+        s.hands, s.history, s.nmoves = env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr()
+        s.ego_first, s.dice_seed, s.probegostart = self.ego_first.data_ptr(), self.seed, self.probegostart
+        pe = ego.model.policy
+        self._ego_rbc = ego.model.rollout_buffer.c_struct()
+        s.ego_params, s.ego_rb, s.ego_actions = pe.params.data_ptr(), C.pointer(self._ego_rbc), ego.actions.data_ptr()
+        s.ego_values, s.ego_log_probs = ego.values.data_ptr(), ego.log_probs.data_ptr()
+        s.ego_episode_start, s.ego_seed = ego._last_episode_starts.data_ptr(), pe._seed
+        s.members, s.n_members, s.partnerid = arr, self.K, self.partnerid.data_ptr()
+        s.resample, s.pool_seed = nat.POOL_RESAMPLE[self.resample], self.pool_seed
+        s.alt_actions, s.alt_acted = self.alt_actions.data_ptr(), self.alt_acted.data_ptr()
+        s.obs_ego, s.obs_alt, s.episodes = self.obs_ego.data_ptr(), self.obs_alt.data_ptr(), self._episodes_dev.data_ptr()
+        s.obs_next, s.rew1, s.rew2, s.es_alt = (t.data_ptr() for t in (self._obs_next, self._rew1, self._rew2, self._es_alt))
+        s.done1, s.done2, s.running, s.can = (t.data_ptr() for t in (self._done1, self._done2, self._running, self._can))
+        s.alt_opens, s.ego_opens, s.done = self._alt_opens.data_ptr(), self._ego_opens.data_ptr(), self._done.data_ptr()
+        self._desc = s
+
+    def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
+        self._bind()
+        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
+        nat.check(ctx.lib.ph_liar_pool_step(ctx.handle, C.byref(self._desc), int(rb.pos if ego_pos < 0 else ego_pos), int(counter),
+                                            int(deal_only)))
+
+    # -- the walk: per-member calls with torch masks -------------------------------------------------------------------------------
+    def _members_act(self, obs: th.Tensor, mask: th.Tensor, counter: int) -> th.Tensor:
+        """every member's forward with Philox counter `counter`; member k's move lands in the tables of `mask` it sits at"""
+        for k, m in enumerate(self.members):
+            mk = (mask.bool() & (self.partnerid == k)).to(th.uint8)
+            if isinstance(m, VecLiarDefaultPartner):
+                m.get_action(obs, mk, self.alt_actions, self.env.ctx)
+                continue
+            self._policy_of(m)._counter = counter - 1
+            a = m.get_action(obs, mk)
+            self.alt_actions.copy_(th.where(mk.bool()[:, None], a, self.alt_actions))
+        return self.alt_actions
+
+    def _members_update(self, reward: th.Tensor, done: th.Tensor, mask: th.Tensor) -> None:
+        for k, m in enumerate(self.members):
+            if isinstance(m, RaggedVecOnPolicyAgent):
+                mine = self.partnerid == k
+                m.update(reward, (done.bool() & mine).to(th.uint8), (mask.bool() & mine).to(th.uint8))
+
+    def _resampled(self, c: int) -> th.Tensor:
+        if self.resample == "robin":
+            return (self.partnerid + 1) % self.K
+        words = philox_word0(self.pool_seed, c, self._rows, POOL_RESAMPLE_BLOCK).astype(np.uint64)
+        ids = (words * np.uint64(self.K)) >> np.uint64(32)
+        return th.as_tensor(ids.astype(np.int32)).to(self.dev)
+
+    def _deal(self, reset_mask: th.Tensor, c: int) -> None:
+        """re-deal the tables in reset_mask and seat their next members; where the member opens, it moves once"""
+        env, lib, h = self.env, self.env.ctx.lib, self.env.ctx.handle
+        self._bind()
+        nat.check(lib.ph_liar_reset(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
+                                    reset_mask.data_ptr(), self.ego_first.data_ptr(), self.seed, int(c),
+                                    self.probegostart, self.E))
+        rm = reset_mask.bool()
+        self.alt_acted.copy_(th.where(rm, self.zeros8, self.alt_acted))
+        self.partnerid.copy_(th.where(rm, self._resampled(c).to(th.int32), self.partnerid))
+        alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
+        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
+                                  self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
+        a_alt = self._members_act(self.obs_alt, alt_opens, 2 * c + 1)
+        self.alt_acted.copy_((self.alt_acted.bool() | alt_opens.bool()).to(th.uint8))
+        env.player_step(a_alt, self.zeros8, alt_opens)              # obs_next = ego's observation in those tables
+        self.obs_ego.copy_(th.where(alt_opens.bool()[:, None], env.obs_next, self.obs_ego))
+        ego_opens = (rm & self.ego_first.bool()).to(th.uint8)
+        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
+                                  self.ones8.data_ptr(), ego_opens.data_ptr(), self.obs_ego.data_ptr(), self.E))
+
+    # -- one vectorised MultiAgentEnv.step ---------------------------------------------------------------------------------------
+    def step(self):
+        """-> (E,) uint8 device tensor: tables whose game ended in this step"""
+        ego = self.ego
+        self.steps_done += 1
+        c = self.steps_done
+        if self.native:
+            model, rb = ego.model, ego.model.rollout_buffer
+            if ego.n_steps >= model.n_steps:
+                ego.learn_from_buffer()
+            self._native_call(c)
+            rb.pos += 1
+            rb.full = rb.pos == rb.buffer_size
+            ego.n_steps += 1
+            ego.num_timesteps += self.E
+            for m in self.learners:
+                m.num_timesteps += self.E
+            return self._done
+        env = self.env
+        self._bind()
+        ego.model.policy._counter = c - 1
+        a_ego = ego.get_action(self.obs_ego)                                   # every table is at the ego's turn
+        obs_alt, rew1, done1 = env.player_step(a_ego, self.ones8, None)
+        rew1, done1 = rew1.clone(), done1.clone()
+        running = (~done1.bool()).to(th.uint8)
+        # the member that already acted this game is credited this transition (multiagentenv.py:163-170)
+        self._members_update(rew1[:, 1].contiguous(), done1, self.alt_acted)
+        self.obs_alt.copy_(th.where(running.bool()[:, None], obs_alt, self.obs_alt))
+        # every table's member replies where the game goes on
+        a_alt = self._members_act(self.obs_alt, running, 2 * c)
+        self.alt_acted.copy_((self.alt_acted.bool() | running.bool()).to(th.uint8))
+        obs_ego, rew2, done2 = env.player_step(a_alt, self.zeros8, running)
+        rew2 = th.where(running.bool()[:, None], rew2, th.zeros_like(rew2))
+        done2 = (done2.bool() & running.bool())
+        self._members_update(rew2[:, 1].contiguous(), done2.to(th.uint8), running)
+        done = done1.bool() | done2
+        # the ego collects both transitions of the step; the last done wins (agents.py:44-47)
+        ego.update((rew1[:, 0] + rew2[:, 0]).contiguous(), done.to(th.float32))
+        ego.flush_rewards()
+        self.obs_ego.copy_(th.where((running.bool() & ~done2)[:, None], obs_ego, self.obs_ego))
+        done8 = done.to(th.uint8)
+        self._episodes_dev += done8.sum()
+        self._deal(done8, c)
+        return done8
+
+    def rollout_and_learn(self, n_steps: int) -> None:
+        """n_steps vectorised steps, the ego's update, then the update of every learner whose full() holds"""
+        for _ in range(n_steps):
+            self.step()
+        self.ego.learn_from_buffer()
+        for m in self.learners:
+            if m.full():
+                m.learn_from_buffer()
+
+
 class LiarIterationGraph:
     """One whole iteration of the device-resident Liar's Dice self-play with everything a replay must vary resident on the device:
     every random stream is keyed (RNG epoch word, counter) with the step-local counter baked in, and ONE epoch word -- shared by

@@ -226,17 +226,112 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+POOL_KINDS = ("PPO", "FIXED", "DEFAULT")
+
+
+def pool_plan(args):
+    """`LiarsDice-v0 PPO <alt>+ --n-envs E` with anything but exactly one PPO partner: the members of the device-resident partner
+    pool as (kind, config) pairs, the resample rule and what remains of --env-config for the game -- checked before a device is
+    touched.  None when the arguments are the single-learner self-play pairing (that path stays as it is)."""
+    alts = list(args.alt)
+    if alts == ["PPO"]:
+        return None
+    if args.ego != "PPO" or not all(kind in POOL_KINDS for kind in alts):
+        raise EnvException(f"--n-envs supports a PPO ego against PPO self-play or a pool of {list(POOL_KINDS)} partners")
+    if args.env != "LiarsDice-v0":
+        raise EnvException(f"the device-resident partner pool exists for LiarsDice-v0, not {args.env}: with --n-envs the other "
+                           "games take exactly one PPO partner")
+    from . import _native as nat
+    if len(alts) > nat.PH_MAX_POOL:
+        raise EnvException(f"the partner pool holds at most {nat.PH_MAX_POOL} members")
+    env_config = dict(args.env_config)
+    resample = env_config.pop("resample", "robin")
+    if resample not in nat.POOL_RESAMPLE:
+        raise EnvException(f"--env-config resample must be one of {sorted(nat.POOL_RESAMPLE)}")
+    members = []
+    for kind, config in zip(alts, args.alt_config):
+        config = dict(config)
+        if kind == "FIXED":
+            if "type" not in config or "location" not in config:
+                raise EnvException("a FIXED partner needs 'type' and 'location' in its --alt-config")
+            if config["type"] != "PPO":
+                raise EnvException("pool members play the 64-64 MlpPolicy: a FIXED member must be a PPO checkpoint")
+        elif kind == "DEFAULT" and config:
+            raise EnvException("No config possible for this default agent")
+        members.append((kind, config))
+    return dict(members=members, resample=resample, env_config=env_config)
+
+
+def run_pool(args, plan):
+    """the pool's object graph: the ego, one member per partner argument, `VecLiarPartnerPool.rollout_and_learn` per iteration"""
+    import random as _random
+
+    import torch as th
+
+    from .envs.vec import (FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner, VecLiarPartnerPool, VecLiarsDice)
+    from .vec import VecOnPolicyAgent
+    E = int(args.n_envs)
+    spaces = type("Spaces", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
+                                     _is_dummy_space_env=True))()
+
+    def learner(config, offset):
+        config = dict(config)
+        config.setdefault("n_steps", 128)
+        config.setdefault("batch_size", max(64, E * config["n_steps"] // 4))
+        config.update(env=spaces, device=args.device, n_envs=E)
+        if args.seed is not None:
+            config["seed"] = args.seed + offset
+        model = PPO(policy="MlpPolicy", **config)
+        model.device_permutations = True
+        return model
+
+    ego_model = learner(args.ego_config, 0)
+    ego = VecOnPolicyAgent(ego_model)
+    members, models = [], []
+    for i, (kind, config) in enumerate(plan["members"]):
+        if kind == "PPO":
+            models.append(learner(config, i + 1))
+            members.append(RaggedVecOnPolicyAgent(models[-1]))
+        elif kind == "FIXED":
+            members.append(FrozenVecPartner(gen_load(config, config["type"], config["location"]).policy))
+        else:
+            members.append(VecLiarDefaultPartner())
+        print(f"Partner {i}: {members[-1]}")
+    base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
+    dice_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xD1CE0D1CE0D1CE) & 0x7FFFFFFFFFFFFFFF
+    env = VecLiarPartnerPool(E, ego, members, seed=dice_seed, resample=plan["resample"], **plan["env_config"])
+    n_steps = ego_model.n_steps
+    iterations = max(1, -(-args.total_timesteps // (E * n_steps)))
+    for _ in range(iterations):
+        env.rollout_and_learn(n_steps)
+    th.cuda.synchronize()
+    updates = [m.iteration for m in env.learners]
+    print(f"vectorised pool play: {iterations} iterations x {E} envs x {n_steps} steps against {len(members)} members; "
+          f"ego updates {ego.iteration}, learner updates {updates}")
+    if args.ego_save:
+        ego_model.save(args.ego_save)
+    if args.alt_save:
+        for i, (kind, _) in enumerate(plan["members"]):
+            if kind == "PPO":       # FIXED / DEFAULT members have nothing to save (trainer.py:423-432)
+                members[i].model.save(f"{args.alt_save}/{i}" if len(models) > 1 else args.alt_save)
+    return ego_model, members, env
+
+
 def run_vectorised(args):
     """`<env> PPO PPO --n-envs E`: the reference's object graph with every table on the device.
-    total_timesteps counts ego transitions over all tables, as SB3 does for a VecEnv."""
+    total_timesteps counts ego transitions over all tables, as SB3 does for a VecEnv.  `LiarsDice-v0 PPO <alt>+` with any other
+    partner list (each of PPO / FIXED / DEFAULT) plays against the partner pool (`run_pool`)."""
     import torch as th
 
     from .envs.vec import RaggedVecOnPolicyAgent, VecLiarsDice, VecLiarSelfPlay, VecRPS, selfplay_iteration
     from .vec import VecOnPolicyAgent
-    if args.ego != "PPO" or list(args.alt) != ["PPO"]:
-        raise EnvException("--n-envs supports the PPO-vs-PPO self-play pairing")
     if args.framestack > 1 or args.record is not None:
         raise EnvException("--n-envs cannot be combined with --framestack / --record")
+    plan = pool_plan(args)
+    if plan is not None:
+        return run_pool(args, plan)
+    if args.ego != "PPO":
+        raise EnvException("--n-envs supports the PPO-vs-PPO self-play pairing")
     block_variant = {"BlockEnv-v0": 0, "BlockEnv-v1": 1}.get(args.env)
     game = {"RPS-v0": VecRPS, "LiarsDice-v0": VecLiarsDice}.get(args.env)
     if game is None and block_variant is None:
