@@ -104,6 +104,103 @@ def filled_oracle_buffer(name: str, oracle: MlpPolicyOracle, T: int, E: int, see
     return buf
 
 
+def stale_oracle_buffer(name: str, oracle, T: int, E: int, seed: int = 0, drift: float = 0.03, fill=None):
+    """a rollout buffer the policy under test did NOT fill: a deep copy of the checker with drift * N(0, 1) (seeded) added to every
+    parameter is the behaviour policy and fills the buffer through `fill(name, behaviour, T, E, seed=seed)` (filled_oracle_buffer
+    unless given); `oracle` itself is left as it was.  Against this buffer the checker's ratios leave 1 and its values leave the
+    stored ones, so both clips of the PPO loss are live (tests/offpolicy_cases.py)."""
+    import copy
+    beh = copy.deepcopy(oracle)
+    g = th.Generator().manual_seed(seed + 7919)
+    with th.no_grad():
+        for p in beh.parameters():
+            p.add_(drift * th.randn(p.shape, generator=g))
+    with th.random.fork_rng(devices=[]):       # the checker samples from torch's global stream: the same buffer on every call
+        th.manual_seed(seed)
+        return (fill or filled_oracle_buffer)(name, beh, T, E, seed=seed)
+
+
+OFFPOLICY_CLASSES = ("P1", "P2", "P3", "P4", "P5", "V1", "V2", "V3")
+EDGE_MARGIN = 1e-4      # five times the forward tolerance (2e-5 * s on log-probs and values)
+
+
+def offpolicy_rows(oracle64, mb, hp: PPOHyper, s: float = 1.0, always_normalize: bool = False, **eval_kw):
+    """per row of minibatch `mb`, on a float64 copy of the checker (double_copy): ratio = exp(logp - old_logp), the advantage as
+    the loss sees it (normalised where hp says so; always_normalize: Modular's loss has no switch) and dlt = v - old_v, with the
+    classes of the two clips as boolean masks:
+        P1 ratio > 1+c, adv > 0 (clipped: no policy gradient)     P2 ratio > 1+c, adv < 0 (outside, but live: pl1 < pl2)
+        P3 ratio < 1-c, adv > 0 (live)                            P4 ratio < 1-c, adv < 0 (clipped)       P5 inside [1-c, 1+c]
+        V1 dlt > c_vf       V2 dlt < -c_vf       V3 inside          (None where hp.clip_range_vf is None)
+    and `edge`: |ratio - (1 +- c)| < 1e-4 s ratio or ||dlt| - c_vf| < 1e-4 s, s = max(1, w_last / 64) -- rows a device within its
+    forward tolerance may put on the other side of a clip.  eval_kw goes to evaluate_actions (Modular: partner_idx)."""
+    mb64 = {k: (v.double() if v.is_floating_point() else v) for k, v in mb.items()}
+    actions = mb64["actions"]
+    if oracle64.act_space.kind == "discrete":
+        actions = actions.long().flatten()
+    with float64_checker(), th.no_grad():
+        values, logp, _ = oracle64.evaluate_actions(mb64["observations"], actions, **eval_kw)
+    assert logp.dtype == th.float64 and values.dtype == th.float64
+    adv = mb64["advantages"]
+    if (hp.normalize_advantage or always_normalize) and (len(adv) > 1 or always_normalize):
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    ratio = th.exp(logp - mb64["old_log_prob"]).numpy()
+    adv = adv.numpy()
+    dlt = (values.flatten() - mb64["old_values"]).numpy()
+    c, cv = hp.clip_range, hp.clip_range_vf
+    hi, lo = ratio > 1 + c, ratio < 1 - c
+    out = dict(ratio=ratio, adv=adv, dlt=dlt, P1=hi & (adv > 0), P2=hi & (adv < 0), P3=lo & (adv > 0), P4=lo & (adv < 0),
+               P5=~hi & ~lo, V1=None, V2=None, V3=None)
+    edge = np.minimum(np.abs(ratio - (1 + c)), np.abs(ratio - (1 - c))) < EDGE_MARGIN * s * ratio
+    if cv is not None:
+        out.update(V1=dlt > cv, V2=dlt < -cv, V3=np.abs(dlt) <= cv)
+        edge |= np.abs(np.abs(dlt) - cv) < EDGE_MARGIN * s
+    out["edge"] = edge
+    return out
+
+
+def flat_blocks(oracle, flat_fn=None):
+    """(block, names): block[i] = which parameter tensor (a weight matrix, a bias, the Gaussian log_std) flat entry i belongs to,
+    names[b] its module path -- read off the checker's own flat order like _flat_layout"""
+    params, idx = _flat_layout(oracle, flat_fn)
+    owner = np.concatenate([np.full(p.numel(), b, np.int64) for b, p in enumerate(params)])
+    by_id = {id(p): n for n, p in oracle.named_parameters()}
+    return owner[idx], [by_id.get(id(p), "param%d" % b) for b, p in enumerate(params)]
+
+
+def flat_grads_exact(oracle, flat_fn=None):
+    """the checker's gradients in flat order WITHOUT the float32 cast of flat_grads() (a float64 copy keeps float64); a parameter the
+    loss does not reach counts as zero"""
+    params, idx = _flat_layout(oracle, flat_fn)
+    g = np.concatenate([(th.zeros_like(p) if p.grad is None else p.grad).detach().reshape(-1).numpy().astype(np.float64)
+                        for p in params])
+    return g[idx]
+
+
+def assert_block_gradients(g, g32, g64, block, names, where=()):
+    """the device gradient against the float32 checker's: the project's rule over the whole vector (1e-6 + 2e-4 of the largest
+    entry), and per parameter block b  max|g_b - g32_b| <= 1e-6 + max(2e-4 M_b, 4 d_b), M_b the block's largest float64 entry and
+    d_b the checker's own float32-vs-float64 difference in the block (CHAIN_FACTOR, for assert_chain_moments' reason: the device
+    differs from torch's float32 by another summation order and fast_tanh, not only by rounding).  Prints every block."""
+    g, g32, g64 = np.asarray(g, np.float64), np.asarray(g32, np.float64), np.asarray(g64, np.float64)
+    assert g.shape == g32.shape == g64.shape == block.shape, (g.shape, g32.shape, g64.shape, block.shape)
+    bad = []
+    for b, name in enumerate(names):
+        sel = block == b
+        M = np.abs(g64[sel]).max()
+        d = np.abs(g32[sel] - g64[sel]).max()
+        err = np.abs(g[sel] - g32[sel]).max()
+        allowed = 1e-6 + max(2e-4 * M, CHAIN_FACTOR * d)
+        print(where, "block %-28s n=%-6d max %.3g  checker f32 vs f64 d = %.3g  device vs checker %.3g  allowed %.3g"
+              % (name, int(sel.sum()), M, d, err, allowed))
+        if not err <= allowed:
+            bad.append((name, err, allowed))
+    scale = np.abs(g32).max()
+    err = np.abs(g - g32).max()
+    print(where, "whole gradient: device vs checker %.3g allowed %.3g (of max entry %.3g)" % (err, 1e-6 + 2e-4 * scale, scale))
+    assert err <= 1e-6 + 2e-4 * scale, (where, err, scale, int(np.abs(g - g32).argmax()))
+    assert not bad, (where, bad)
+
+
 def upload_buffer(dev_buf, ob: RolloutBufferOracle) -> None:
     """copy every array of an oracle buffer into a device RolloutBuffer (marks it full)."""
     for k in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
@@ -290,4 +387,5 @@ def assert_chain_moments(dev_m, dev_v, ref32, ref64, where=()):
 
 __all__ = ["CONFIGS", "PPOHyper", "to_space", "sample_obs", "oracle_policy", "device_policy",
            "filled_oracle_buffer", "upload_buffer", "make_device_buffer", "flat_adam_state", "load_flat_adam_state",
-           "load_device_adam_state", "read_device_adam_state", "unit_hyper", "unit_gradient", "float64_checker", "double_copy", "chain64_state", "assert_chain_moments"]
+           "load_device_adam_state", "read_device_adam_state", "unit_hyper", "unit_gradient", "float64_checker", "double_copy", "chain64_state", "assert_chain_moments",
+           "stale_oracle_buffer", "offpolicy_rows", "OFFPOLICY_CLASSES", "flat_blocks", "flat_grads_exact", "assert_block_gradients"]

@@ -39,25 +39,35 @@ def _adap_struct(nat, cs, n_ctx, n_states, coef, keep, state_idx=None, contexts=
     return ad, loss, used
 
 
-def _grad_pair(name, T, E, idx, hp, n_ctx, n_states, coef, seed=5, sampler=None, gemm_mode=0):
-    """device and oracle gradient of one minibatch with the context term; samples teacher-forced unless `sampler`"""
+def _context_samples(cs, nb, n_ctx, n_states, seed):
+    """teacher-forced samples of one minibatch of nb rows: (state positions, -1 past min(n_states, nb); contexts)"""
+    rng = np.random.default_rng(seed + nb)
+    ns = min(n_states, nb)
+    sidx = np.full(n_states, -1, np.int32)
+    sidx[:ns] = rng.permutation(nb)[:ns]
+    return sidx, orc.adap_sample_contexts("l2", cs, n_ctx, rng.random((n_ctx, cs)))
+
+
+def _grad_pair(name, T, E, idx, hp, n_ctx, n_states, coef, seed=5, sampler=None, gemm_mode=0, fill=None):
+    """device and oracle gradient of one minibatch with the context term; samples teacher-forced unless `sampler`.  fill: another
+    buffer builder than helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py); idx may be a function (checker,
+    buffer) -> rows"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
     cs = CTX[name]
     orac = H.oracle_policy(name, seed=seed)
-    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
+    ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
+    if callable(idx):
+        idx = idx(orac, ob)
     pol = H.device_policy(name, orac)
     pol.gemm_mode = gemm_mode
     buf = H.make_device_buffer(name, pol, T, E)
     H.upload_buffer(buf, ob)
     nb = len(idx)
-    rng = np.random.default_rng(seed + nb)
     ns = min(n_states, nb)
     keep = []
     if sampler is None:
-        sidx = np.full(n_states, -1, np.int32)
-        sidx[:ns] = rng.permutation(nb)[:ns]
-        ctxs = orc.adap_sample_contexts("l2", cs, n_ctx, rng.random((n_ctx, cs)))
+        sidx, ctxs = _context_samples(cs, nb, n_ctx, n_states, seed)
         ad, loss_t, used = _adap_struct(nat, cs, n_ctx, n_states, coef, keep, sidx[None], ctxs[None])
     else:
         ad, loss_t, used = _adap_struct(nat, cs, n_ctx, n_states, coef, keep, sampler=sampler, seed=seed, want_used=True)

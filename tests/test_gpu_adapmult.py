@@ -104,23 +104,26 @@ def _hyper(nat, hp):
     return PPO.hyper(model)
 
 
-def _grad_pair(name, T, E, nb, hp, coef=None, n_ctx=5, n_states=32, seed=5):
+def _grad_pair(name, T, E, nb, hp, coef=None, n_ctx=5, n_states=32, seed=5, fill=None, idx=None):
+    """fill: another buffer builder than helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py); idx: the minibatch
+    rows, or a function (checker, buffer) -> rows, instead of the first nb of a seeded permutation"""
     from pantheonrl_amd import _native as nat
-    from tests.test_gpu_adap import _adap_struct
+    from tests.test_gpu_adap import _adap_struct, _context_samples
     cs = CTX[name]
     orac = _oracle(name, seed=seed)
-    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
+    ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
     pol = _device(name, orac)
     buf = H.make_device_buffer(name, pol, T, E)
     H.upload_buffer(buf, ob)
-    idx = np.random.default_rng(nb).permutation(T * E)[:nb]
+    if idx is None:
+        idx = np.random.default_rng(nb).permutation(T * E)[:nb]
+    elif callable(idx):
+        idx = idx(orac, ob)
+    idx = np.asarray(idx)
+    nb = len(idx)
     keep, ad, loss_t, sidx, ctxs = [], None, None, None, None
     if coef is not None:
-        rng = np.random.default_rng(seed + nb)
-        ns = min(n_states, nb)
-        sidx = np.full(n_states, -1, np.int32)
-        sidx[:ns] = rng.permutation(nb)[:ns]
-        ctxs = orc.adap_sample_contexts("l2", cs, n_ctx, rng.random((n_ctx, cs)))
+        sidx, ctxs = _context_samples(cs, nb, n_ctx, n_states, seed)
         ad, loss_t, _ = _adap_struct(nat, cs, n_ctx, n_states, coef, keep, sidx[None], ctxs[None])
     h = _hyper(nat, hp)
     idx_t = th.as_tensor(np.asarray(idx, np.int32)).cuda()

@@ -135,11 +135,15 @@ def test_forward_and_store_writes_the_row_forward_plus_add_writes(name, arch):
 
 
 # ---- minibatch gradient --------------------------------------------------------------------------------------------------------
-def _grad_pair(name, arch, T, E, idx, hp, seed=11, gemm_mode=0):
+def _grad_pair(name, arch, T, E, idx, hp, seed=11, gemm_mode=0, fill=None):
+    """fill: another buffer builder than helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py); idx may be a
+    function (checker, buffer) -> rows"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
     orac = A.oracle_policy(name, arch, seed=seed)
-    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
+    ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
+    if callable(idx):
+        idx = idx(orac, ob)
     pol = A.device_policy(name, orac)
     buf = H.make_device_buffer(name, pol, T, E)
     H.upload_buffer(buf, ob)
@@ -196,6 +200,8 @@ def test_minibatch_gradient_matches_autograd(arch, name):
                                        ("wide", (256, 256, 256)), ("overcooked", (32,))])
 def test_minibatch_gradient_options(name, arch):
     idx = np.random.default_rng(0).permutation(16 * 8)[:100]
+    # (an on-policy buffer: no row leaves either clip range, so these options exercise the parameter plumbing, not the clipping --
+    # tests/test_gpu_offpolicy.py runs the clips on a stale buffer)
     hp = orc.PPOHyper(clip_range=0.1, clip_range_vf=0.3, ent_coef=0.02, vf_coef=0.7, normalize_advantage=False)
     out, g_ref, st_ref = _grad_pair(name, arch, 16, 8, idx, hp)
     _assert_grads(out[0][0], g_ref, (arch, name))
@@ -219,12 +225,13 @@ def _model(name, arch, T, E, hp, cls_kwargs=True):
                target_kl=hp.target_kl, seed=0, policy_kwargs=A.kwargs_of(arch) if cls_kwargs else None)
 
 
-def _train_pair(name, arch, T, E, hp, seed=21, f64=False):
-    """f64: also the chain on a float64 copy of the checker, its Adam state left in model.checker64_state"""
+def _train_pair(name, arch, T, E, hp, seed=21, f64=False, fill=None):
+    """f64: also the chain on a float64 copy of the checker, its Adam state left in model.checker64_state.  fill: another buffer
+    builder than helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py)"""
     from pantheonrl_amd.ppo import ArchActorCriticPolicy
     orac = A.oracle_policy(name, arch, seed=seed)
     o64 = H.double_copy(orac)[0] if f64 else None
-    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
+    ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
     model = _model(name, arch, T, E, hp)
     assert type(model.policy) is ArchActorCriticPolicy and model.policy.net_arch == tuple(arch)
     model.policy.set_flat_params(orac.flat_params())

@@ -92,6 +92,8 @@ def test_gaussian_minibatch_gradient_matches_autograd(name, T, E, nb):
 
 def test_gaussian_gradient_options():
     idx = np.random.default_rng(0).permutation(16 * 8)[:100]
+    # (an on-policy buffer: no row leaves either clip range, so these options exercise the parameter plumbing, not the clipping --
+    # tests/test_gpu_offpolicy.py runs the clips on a stale buffer)
     hp = orc.PPOHyper(clip_range=0.1, clip_range_vf=0.3, ent_coef=0.02, vf_coef=0.7, normalize_advantage=False)
     g, g_ref, _, _, lay = _grad_pair("gauss5", 16, 8, idx, hp)
     _assert_grads(g, g_ref, lay)

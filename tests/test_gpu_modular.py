@@ -182,16 +182,23 @@ def test_forward_and_store_writes_the_partner_rollout_row():
 # ----------------------------------------------------------------------------------------------------------------
 # one minibatch: the gradient of the whole loss (learn.py:244-318) w.r.t. every parameter
 # ----------------------------------------------------------------------------------------------------------------
-def _grad_pair(name, K, partner, T, E, nb, coef, hp, kw=None, seed=5, gemm_mode=0):
+def _grad_pair(name, K, partner, T, E, nb, coef, hp, kw=None, seed=5, gemm_mode=0, fill=None, idx=None):
+    """fill: another buffer builder (name, checker, T, E, seed=) than _filled (a stale buffer: tests/offpolicy_cases.py); idx: the
+    minibatch rows, or a function (checker, buffer) -> rows, instead of the first nb of a seeded permutation"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.modular import ModularAlgorithm  # noqa: F401  (import check)
     kw = kw or {}
     orac = _oracle(name, K, seed=seed, **kw)
-    ob = _filled(orac, name, partner, T, E, seed=seed)
+    ob = fill(name, orac, T, E, seed=seed) if fill is not None else _filled(orac, name, partner, T, E, seed=seed)
     pol = _device(name, orac, K, **kw)
     pol.gemm_mode = gemm_mode
     buf = _device_buffer(pol, name, ob)
-    idx = np.random.default_rng(nb).permutation(T * E)[:nb]
+    if idx is None:
+        idx = np.random.default_rng(nb).permutation(T * E)[:nb]
+    elif callable(idx):
+        idx = idx(orac, ob)
+    idx = np.asarray(idx)
+    nb = len(idx)
     mb = ob.minibatch(idx) if hasattr(ob, "minibatch") else next(iter(ob.get(nb, idx)))
     for p in orac.parameters():
         p.grad = None

@@ -290,11 +290,12 @@ def test_buffer_add_reward_reset_and_fused_step():
 # ----------------------------------------------------------------------------------------------------------------
 # K3/K5/K6 PPO update
 # ----------------------------------------------------------------------------------------------------------------
-def _grad_pair(name, T, E, idx, hp: orc.PPOHyper, seed=11, gemm_mode=0, f64=False, obs_fn=None, w1_scale=1.0):
+def _grad_pair(name, T, E, idx, hp: orc.PPOHyper, seed=11, gemm_mode=0, f64=False, obs_fn=None, w1_scale=1.0, fill=None):
     """device minibatch gradient, the oracle's autograd gradient (float32 as the reference computes it; f64: the same graph in
     float64 -- the yardstick for "which float32 path is closer to the true gradient").  obs_fn: other observation
     distributions than N(0, 1); w1_scale multiplies both first-layer weight matrices (keeps pre-activations in tanh's live range
-    when the observations are rescaled)"""
+    when the observations are rescaled).  fill: another buffer builder than helpers.filled_oracle_buffer (a stale buffer:
+    tests/offpolicy_cases.py); idx may be a function (checker, buffer) -> rows"""
     import ctypes as C
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
@@ -303,7 +304,9 @@ def _grad_pair(name, T, E, idx, hp: orc.PPOHyper, seed=11, gemm_mode=0, f64=Fals
         with th.no_grad():
             orac.policy_net[0].weight.mul_(w1_scale)
             orac.value_net_mlp[0].weight.mul_(w1_scale)
-    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed, obs_fn=obs_fn)
+    ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed, obs_fn=obs_fn)
+    if callable(idx):
+        idx = idx(orac, ob)
     pol = H.device_policy(name, orac)
     pol.gemm_mode = gemm_mode
     buf = H.make_device_buffer(name, pol, T, E)
@@ -382,6 +385,8 @@ def test_minibatch_gradient_matches_autograd(name, T, E, nb):
 
 def test_minibatch_gradient_options_and_valu_cross_check():
     idx = np.random.default_rng(0).permutation(16 * 8)[:100]
+    # (an on-policy buffer: no row leaves either clip range, so these options exercise the parameter plumbing, not the clipping --
+    # tests/test_gpu_offpolicy.py runs the clips on a stale buffer)
     hp = orc.PPOHyper(clip_range=0.1, clip_range_vf=0.3, ent_coef=0.01, vf_coef=0.7, normalize_advantage=False)
     g, g_ref, st, st_ref, lay = _grad_pair("overcooked", 16, 8, idx, hp)
     _assert_grads(g, g_ref, lay)
@@ -420,7 +425,9 @@ def test_split_bf16_one_hot_gradient_matches_autograd(name, T, E, nb):
     Overcooked + ADAP row (65 features: two chunks), a 24-feature row with a three-component head, three and four chunks."""
     rng = np.random.default_rng(nb)
     idx = rng.permutation(T * E)[:nb]
-    # (non-default hyper-parameters -- value clipping, entropy and value coefficients, raw advantages -- on every second case)
+    # (non-default hyper-parameters -- clip ranges, entropy and value coefficients, raw advantages -- on every second case.  The buffer
+    # is on-policy, so no row leaves either clip range: this exercises the parameter plumbing, not the clipping, which
+    # tests/test_gpu_offpolicy.py does on a stale buffer)
     hp = orc.PPOHyper() if nb % 2 else orc.PPOHyper(clip_range=0.1, clip_range_vf=0.3, ent_coef=0.01, vf_coef=0.7, normalize_advantage=False)
     g2, g_ref, st, st_ref, lay = _grad_pair(name, T, E, idx, hp, gemm_mode=2)
     _assert_grads(g2, g_ref, lay)
@@ -566,14 +573,15 @@ def test_split_kernel_weight_image_tracks_the_parameters_through_adam_steps_and_
         assert mismatches(model) == 0
 
 
-def _train_pair(name, T, E, hp: orc.PPOHyper, seed=21, device_perms=False, f64=False):
+def _train_pair(name, T, E, hp: orc.PPOHyper, seed=21, device_perms=False, f64=False, fill=None, exclusive=None):
     """f64: also run the chain on a float64 copy of the checker (same buffer, same permutations) and leave its Adam state in
-    model.checker64_state -- the yardstick of helpers.assert_chain_moments"""
+    model.checker64_state -- the yardstick of helpers.assert_chain_moments.  fill: another buffer builder than
+    helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py); exclusive: set_exclusive_device before training"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
     orac = H.oracle_policy(name, seed=seed)
     o64 = H.double_copy(orac)[0] if f64 else None
-    ob = H.filled_oracle_buffer(name, orac, T, E, seed=seed)
+    ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
     obs_s, act_s = H.CONFIGS[name]
     env = type("E", (), dict(observation_space=H.to_space(obs_s), action_space=H.to_space(act_s),
                              _is_dummy_space_env=True))()
@@ -581,6 +589,8 @@ def _train_pair(name, T, E, hp: orc.PPOHyper, seed=21, device_perms=False, f64=F
                 learning_rate=hp.learning_rate, clip_range=hp.clip_range, clip_range_vf=hp.clip_range_vf,
                 normalize_advantage=hp.normalize_advantage, ent_coef=hp.ent_coef, vf_coef=hp.vf_coef,
                 max_grad_norm=hp.max_grad_norm, target_kl=hp.target_kl, seed=0)
+    if exclusive is not None:
+        model.policy.ctx.set_exclusive_device(exclusive)
     model.policy.set_flat_params(orac.flat_params())
     H.upload_buffer(model.rollout_buffer, ob)
     N = T * E
