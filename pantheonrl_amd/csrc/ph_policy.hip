@@ -154,6 +154,59 @@ __device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgk
 // s_waitcnt vmcnt(0) as the BUILTIN (gfx9 encoding: vmcnt 0, expcnt 7, lgkmcnt 15): the wait-insertion pass accounts for it
 __device__ __forceinline__ void vm_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
+// The 16 x D rows of the NEXT step of a one-launch rollout (Box observations), staged by waves 1..3 alone.  Wave 0 owns the row
+// tail -- the one stretch of a step the other three waves wait for -- and XStage's split (thread tid owns elements tid + 256 i)
+// left it a quarter of the rows: it asked for them only after its tail and then sat out a whole HBM round trip in front of the
+// barrier where everybody else already stood.  Here wave w >= 1 owns whole rows w - 1, w + 2, w + 5, ... (lane = feature: one
+// 256-byte segment per wave-instruction): six slots, of which wave 1 uses six and waves 2 and 3 five.  Same values into the same
+// LDS words as XStage (zeros for rows >= n and features >= F).  Callers: threads of waves 1..3 only.
+// Loads and stores go through a buffer descriptor of ONE step's (n, D) block and are predicated by their offset, not by a branch: a
+// slot without a row (r >= 16, row >= n) or a lane without a feature carries an offset outside the block -- the range check
+// returns 0 for the load and drops the store.  A conditional flat access is a branch of its own (the compiler keeps the skip
+// around memory instructions), and a load or store that MAY have been skipped makes every later wait of the wave a
+// `vmcnt(0)`; unconditional, the six loads and six stores are straight-line code the compiler counts one by one.
+struct RowStage3 {
+  static constexpr int ITERS = 6;
+  static constexpr unsigned NONE = 0x80000000u;   // beyond any block (fwd16_eligible: n < 16384, D <= 64 -> under 4 MB), also with 5 strides added
+  float v[ITERS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // Byte offset of this thread's first element (row w - 1 of the tile, feature kk) inside a step's (n, D) block, the same for every
+  // step; slot i lies 3 i rows further.  A row >= n lies behind the end of the block by itself; a lane without a feature and wave 0
+  // get NONE; the sixth slot exists in wave 1 alone (rows 16, 17 belong to the next tile).
+  __device__ __forceinline__ static unsigned base_offset(int row0, const NetDims& nd, int tid) {
+    const int kk = tid & 63, w = (tid >> 6) - 1;
+    return (w >= 0 && kk < nd.D && kk < nd.F) ? ((unsigned)(row0 + w) * (unsigned)nd.D + (unsigned)kk) * 4u : NONE;   // (Box rows: F = D)
+  }
+  __device__ __forceinline__ static unsigned slot_offset(unsigned base, int i, int D, int tid) {
+    return (i == 5 && (tid >> 6) != 1) ? NONE : base + (unsigned)(3 * i) * (unsigned)D * 4u;
+  }
+  // the descriptor of one step's block (wave-uniform arguments only)
+  __device__ __forceinline__ static __amdgpu_buffer_rsrc_t block(const float* blk, int n, int D) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(blk), 0, n * D * 4, 0x00020000);
+  }
+  __device__ __forceinline__ void issue(const float* obs, int n, const NetDims& nd, unsigned base, int tid) {
+    const __amdgpu_buffer_rsrc_t rs = block(obs, n, nd.D);
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i)
+      v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, slot_offset(base, i, nd.D, tid), 0, 0));
+  }
+  // caller: nobody reads dst any more, and a barrier follows before it is read
+  __device__ __forceinline__ void commit(float* dst, int tid) const {
+    const int kk = tid & 63, w = (tid >> 6) - 1;
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i) {
+      const int r = w + 3 * i;
+      if (r < 16) dst[r * LDH + kk] = v[i];
+    }
+  }
+  // RolloutBuffer.add's observation copy of the staged rows (stores only)
+  __device__ __forceinline__ void copy_out(float* rb_obs, int n, int D, unsigned base, int tid) const {
+    const __amdgpu_buffer_rsrc_t rs = block(rb_obs, n, D);
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[i]), rs, slot_offset(base, i, D, tid), 0, 0);
+  }
+};
+
 template <int CTRL>
 __device__ __forceinline__ float dpp_quad_f(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
@@ -316,12 +369,25 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   lds_only_barrier();  // rowphys visible
   if (sc) a.obs = sc->obs_seq;
   xr.issue(rowphys, a.obs, nd, 0);
+  // (one-launch rollouts, Box rows) steps t > 0 take their rows from waves 1..3 (RowStage3): the policy workgroup's behind the head
+  // barrier, under wave 0's row tail; the value workgroup's, which has no action to wait for, at the start of the head phase.  The
+  // value workgroup's waves 1..3 also issue RolloutBuffer.add's observation copy of a step straight from those registers, right
+  // behind the rows' commit to LDS -- a whole step ahead of the next wait on the memory counter, which therefore finds them done
+  // (one counter for loads and stores on gfx950), and with no second register set: the rows are dead once stored.  Step 0's rows
+  // are fetched into the same registers here, once per launch, so that the copy has ONE form for every step.
+  // (Per-step launches: one step, the prologue's rows, the copy at the end of the step from XStage's registers.)
+  const bool staged = sc != nullptr && nd.obs_kind == PH_SPACE_BOX;
+  const bool copy_staged = staged && net == 1 && a.rb_obs && !a.pos_env && wave != 0;
+  const unsigned roff = RowStage3::base_offset(row0, nd, tid);
+  RowStage3 rows;
+  if (copy_staged) rows.issue(a.obs, a0.n, nd, roff, tid);
   xr.commit(xs, rowphys, a.obs, nd, 0);
   // Every load issued so far (weights, biases, the first rows) is waited for HERE, once, as an instruction the compiler's wait
   // insertion can see: otherwise the registers loaded ahead of the step loop stay "pending" at its header, and every step waits
   // `vmcnt(k)` inside layer 1 and `vmcnt(0)` before the bias adds -- which, with ONE counter for loads and stores on gfx950, drains
   // the previous step's STORES in the middle of the products (round 6, third session: profiles/r06_al_*)
   vm_drain();
+  if (copy_staged) rows.copy_out(a.rb_obs, a0.n, nd.D, roff, tid);
   lds_only_barrier();
   PH_STAMP(a.prof, 1);
 
@@ -389,14 +455,20 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
       a.ll_t = t - 1;
     }
     a.prof = nullptr;
-    // (no barrier before xs is overwritten: every wave read its part of H2 before the head phase's own barrier)
-    xr.issue(rowphys, a.obs, nd, 0);
-    xr.commit(xs, rowphys, a.obs, nd, 0);
-    vm_drain();   // the rows are in (the commit waited for them): say so, or the observation copy at the end of the step waits
-                  // `vmcnt(0)` for registers that arrived a microsecond ago and drains the row tail's stores instead
+    // Box rows of this step: waves 1..3 put them into xs behind the previous step's head barrier (below).  One-hot rows are built
+    // here by the whole workgroup.  (No barrier before xs is overwritten: every wave read its part of H2 before the head phase's
+    // own barrier.)
+    if (!staged) {
+      xr.issue(rowphys, a.obs, nd, 0);
+      xr.commit(xs, rowphys, a.obs, nd, 0);
+      vm_drain();   // the rows are in (the commit waited for them): say so, or the compiler waits `vmcnt(0)` further down for
+                    // registers that arrived a microsecond ago and drains the row tail's stores instead
+    }
     lds_only_barrier();
   }
   PH_STAMP(pstep, 9);
+  const bool more = t + 1 < n_steps;   // (one-launch rollouts) waves 1..3 stage the rows of step t + 1 inside this step
+  const float* const obs_next = sc ? sc->obs_seq + (size_t)(t + 1) * a0.n * nd.D : nullptr;
 
   // value workgroup, rectangular rollout: what the row tail reads (previous done, pending reward, the reward row it adds to) is
   // fetched here, under the layers; RolloutBuffer.add's observation copy of Box rows goes out straight from the staged registers
@@ -422,6 +494,9 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   PH_STAMP(a.prof, 5);
   PH_STAMP(pstep, 11);
 
+  // value workgroup of a one-launch rollout: the rows of step t + 1 are requested HERE (nothing of it waits for an action)
+  if (staged && net == 1 && more && wave != 0) rows.issue(obs_next, a0.n, nd, roff, tid);
+
   // ---- head: a third product (columns = logits, or the value in column 0) ----
   {   // every wave: its K quarter (four MFMAs, two chains), the partial tile to zs[wave]; wave 0's partial carries the bias
     if (wave == 0 && pre_ok) value_row_preload_words(a, row0 + lane, vpre);   // (exchange rollouts: the joint action's words, under the product)
@@ -442,6 +517,18 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   }
   lds_only_barrier();   // the four partial tiles are in; nobody reads xs (H2) behind this point
   PH_STAMP(pstep, 12);
+  // (one-launch rollouts) Every load of the step issued so far is waited for HERE, by every wave, where it costs nothing: wave 0 of
+  // the value workgroup needs its preloads for the tail that starts now, its waves 1..3 need the rows, and the policy workgroup
+  // has no load in flight; the stores a wave still has out are a step old.  Without it the preloads, which one branch issues and
+  // another consumes, stay "pending" on the paths that skip the tail, and the compiler drains the counter at the loop's header
+  // instead -- behind the top-of-step barrier, where wave 0 has just issued the row tail's stores and waves 1..3 the copy's.
+  if (sc) vm_drain();
+  if (staged && more && wave != 0) {
+    if (net == 1) {   // value workgroup: in by now, or nearly; step t + 1's observation copy leaves with them (stores only, no drain)
+      rows.commit(xs, tid);
+      if (copy_staged) rows.copy_out(a0.rb_obs + (size_t)(t + 1) * a0.n * nd.D, a0.n, nd.D, roff, tid);
+    }
+  }
   if (wave == 0) {
     PH_STAMP(pstep, 13);
     const int r = lane, grow = row0 + lane;   // lane r < 16 owns row r
@@ -487,7 +574,9 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
             __hip_atomic_store(PXLL(p) + off, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       } else {
-        value_row_tail(a, grow, z[0], pre_ok, vpre);
+        // (inside this block pre_ok IS its last two terms: said so, the lean forms see a constant, the tail's own loads -- the arms
+        // without a preload, each a branch that may leave a load pending up to the loop's header -- fold away)
+        value_row_tail(a, grow, z[0], !a.pos_env && a.rb_val, vpre);
         // (scripted rollout) the last step's own reward: the flush that precedes GAE on the launch-by-launch path
         if (sc && t == n_steps - 1) {
           float add = sc->rew_seq[(size_t)t * a0.n + grow];
@@ -507,13 +596,23 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
     }
   }
   PH_STAMP(pstep, 14);
-  if (draw_ahead && wave == 1 && t + 1 < n_steps) draw_uniforms(t + 1);
-  if (copy_from_regs) {   // stores only, at the end of the step: nothing of this step waits behind them
-    const int kk = tid & 63;
+  // policy workgroup: waves 1..3 come here straight from the head barrier (the tail above is wave 0's) and request the rows where
+  // they always did -- but all sixteen of them, and in under the row tail; the registers are not live across the tail's code
+  const bool stage_here = staged && net == 0 && more && wave != 0;
+  if (stage_here) rows.issue(obs_next, a0.n, nd, roff, tid);
+  if (draw_ahead && wave == 1 && more) draw_uniforms(t + 1);
+  if (stage_here) {
+    rows.commit(xs, tid);
+    vm_drain();   // the rows are in (the commit waited for them): say so, or the loop's header keeps them pending
+  }
+  if (copy_from_regs) {   // stores only: nothing of this step waits behind them
+    if (!staged) {        // per-step launch, at the end of the step: the prologue's rows, XStage's split over all four waves
+      const int kk = tid & 63;
 #pragma unroll
-    for (int i = 0; i < XStage<R, NT>::ITERS; ++i) {
-      const int rr = (tid + NT * i) >> 6;
-      if (kk < nd.D && row0 + rr < a.n) a.rb_obs[(size_t)(row0 + rr) * nd.D + kk] = xr.v[i];
+      for (int i = 0; i < XStage<R, NT>::ITERS; ++i) {
+        const int rr = (tid + NT * i) >> 6;
+        if (kk < nd.D && row0 + rr < a.n) a.rb_obs[(size_t)(row0 + rr) * nd.D + kk] = xr.v[i];
+      }
     }
   } else if (net == 1) {
     copy_obs_rows(a, row0, (a.n - row0 < R) ? a.n - row0 : R, nd.D);
