@@ -965,6 +965,11 @@ int ph_arch_layout_of(const ph_spec *spec /* host */, const ph_arch *arch /* hos
  * host only */
 int ph_arch_lds_bytes(const ph_spec *spec /* host */, const ph_arch *arch /* host */, int *grad_bytes_out, int *grad_rows_out,
                       int *fwd_bytes_out);
+/* 0 when the tower kernels can run this spec and arch; otherwise the status and ph_last_error text with which every ph_arch entry
+ * point refuses the pair (a bad arch; a 32-row LDS carve above the CU's LDS: "... LDS tile ...").  Host only, no context: for
+ * callers that want the refusal when an agent is built, not at its first step (the reference has no such limit: its
+ * MlpExtractor is a chain of torch.nn.Linear, stable_baselines3/common/torch_layers.py) */
+int ph_arch_fits(const ph_spec *spec /* host */, const ph_arch *arch /* host */);
 int ph_arch_forward(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch /* host */, const float *params, const float *obs, int n,
                     const unsigned char *action_mask, const float *uniforms, const float *given_actions,
                     unsigned long long seed, unsigned long long counter, int deterministic, int *actions_i32,
@@ -977,6 +982,38 @@ int ph_arch_minibatch_grad(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch
 int ph_arch_train(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch /* host */, const ph_opt_state *opt, const ph_rollout *rb,
                   const ph_ppo_hyper *hyper /* host */, int n_epochs, int batch_size, const int *perms,
                   unsigned long long perm_seed, float *stats, int gemm_mode);
+/* The towers in the device-resident paths (additions; PH_ABI_VERSION unchanged).
+ *  ph_arch_forward_ragged: ph_policy_forward_ragged with a tower of run-time shape -- OnPolicyAgent.get_action of the partner seat
+ *      of a vectorised turn-based game (agents.py:111-184 per table: forward for all n = rb->E tables, the transition of table e
+ *      recorded at row pos_env[e] iff record_mask[e] != 0 and pos_env[e] < rb->T, `values` updated for recorded tables only).
+ *      Actions, values and log-probs are bitwise ph_arch_forward's for the same (seed, counter). */
+int ph_arch_forward_ragged(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch /* host */, const float *params, const float *obs,
+                           const unsigned char *action_mask, unsigned long long seed, unsigned long long counter,
+                           int deterministic, int *actions_i32, float *values, float *log_probs, const ph_rollout *rb,
+                           const int *pos_env, const unsigned char *record_mask, const float *episode_start_in, int gemm_mode);
+/*  ph_liar_selfplay_step_arch: ph_liar_selfplay_step -- one vectorised MultiAgentEnv.step of n Liar's Dice tables
+ *      (multiagentenv.py:149-215 + TurnBasedEnv.n_step / n_reset :307-327) -- with either seat's policy a tower: ego_arch / alt_arch
+ *      describe the parameter vectors s->ego_params / s->alt_params; NULL keeps that seat on the 64-wide kernels (mixed pairings),
+ *      and (NULL, NULL) is bit for bit ph_liar_selfplay_step.  Same launch sequence, same RNG counters (ego forward `counter`,
+ *      partner forwards 2*counter and 2*counter + 1, dice `counter`). */
+int ph_liar_selfplay_step_arch(ph_ctx *ctx, const ph_liar_selfplay *s, const ph_arch *ego_arch /* host or NULL */,
+                               const ph_arch *alt_arch /* host or NULL */, int ego_pos, unsigned long long counter, int deal_only);
+/*  ph_block_selfplay_step_arch: the same for ph_block_selfplay_step (one MultiAgentEnv.step of n block-world tables,
+ *      multiagentenv.py:149-215); both forwards and the worlds draw with `counter`. */
+int ph_block_selfplay_step_arch(ph_ctx *ctx, const ph_block_selfplay *s, const ph_arch *ego_arch /* host or NULL */,
+                                const ph_arch *alt_arch /* host or NULL */, int ego_pos, unsigned long long counter);
+/*  ph_arch_scripted_rollout: ph_scripted_rollout for towers -- OnPolicyAgent.get_action / update per step (agents.py:111-203)
+ *      against a scripted environment with the launch boundaries removed: ONE launch in which a workgroup owns 32 rows of one net
+ *      for all n_steps.  Exactly, bit for bit,
+ *          for t in 0 .. n_steps-1:  ph_arch_forward(obs_seq[t], counter0 + t, rb, pos0 + t,
+ *                                                    episode_start_in = t ? done_seq[t-1] : episode_start0,
+ *                                                    pending_reward   = t ? rew_seq[t-1]  : NULL)
+ *          ph_buffer_add_reward(rb, pos0 + n_steps - 1, rew_seq[n_steps-1], NULL)
+ *      for every spec / arch pair ph_arch_forward takes.  n must equal rb->E; rows pos0 .. pos0 + n_steps - 1 must lie in rb. */
+int ph_arch_scripted_rollout(ph_ctx *ctx, const ph_spec *spec, const ph_arch *arch /* host */, const float *params,
+                             const float *obs_seq, const float *rew_seq, const float *done_seq, int n, int n_steps,
+                             const float *episode_start0, unsigned long long seed, unsigned long long counter0, int *actions_i32,
+                             float *values, float *log_probs, const ph_rollout *rb, int pos0, int gemm_mode);
 
 /* ---- owning handle: one agent = its rollout buffer, weights and Adam state on the device ----------------------------------
  *   The pointer-level entry points above take device memory owned by the caller (the Python host uses torch

@@ -342,12 +342,19 @@ SIGNATURES = {
     "ph_feistel_indices": [_i, _ull, _i, _i, _i, C.POINTER(_i)],
     "ph_arch_layout_of": [C.POINTER(PhSpec), C.POINTER(PhArch), C.POINTER(PhArchLayout)],
     "ph_arch_lds_bytes": [C.POINTER(PhSpec), C.POINTER(PhArch), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "ph_arch_fits": [C.POINTER(PhSpec), C.POINTER(PhArch)],
     "ph_arch_forward": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _i, _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp, _vp,
                         _vp, _vp, C.POINTER(PhRollout), _i, _vp, _vp, _i],
     "ph_arch_minibatch_grad": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, C.POINTER(PhRollout), C.POINTER(PhPpoHyper), _vp,
                                _i, _vp, _vp, _i],
     "ph_arch_train": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), C.POINTER(PhOptState), C.POINTER(PhRollout),
                       C.POINTER(PhPpoHyper), _i, _i, _vp, _ull, _vp, _i],
+    "ph_arch_forward_ragged": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp,
+                               C.POINTER(PhRollout), _vp, _vp, _vp, _i],
+    "ph_liar_selfplay_step_arch": [_vp, C.POINTER(PhLiarSelfPlay), C.POINTER(PhArch), C.POINTER(PhArch), _i, _ull, _i],
+    "ph_block_selfplay_step_arch": [_vp, C.POINTER(PhBlockSelfPlay), C.POINTER(PhArch), C.POINTER(PhArch), _i, _ull],
+    "ph_arch_scripted_rollout": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp,
+                                 _vp, C.POINTER(PhRollout), _i, _i],
     "ph_bc_layout_of": [C.POINTER(PhSpec), C.POINTER(PhBcLayout)],
     "ph_bc_forward": [_vp, C.POINTER(PhSpec), _vp, _vp, _i, _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp, _vp, _vp],
     "ph_bc_train": [_vp, C.POINTER(PhSpec), C.POINTER(PhOptState), _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(PhBcHyper), _vp],
@@ -442,6 +449,11 @@ def arch_lds_bytes(spec: PhSpec, arch: PhArch):
     g, r, f = C.c_int(0), C.c_int(0), C.c_int(0)
     check(load().ph_arch_lds_bytes(C.byref(spec), C.byref(arch), C.byref(g), C.byref(r), C.byref(f)))
     return g.value, r.value, f.value
+
+
+def require_arch_fits(spec: PhSpec, arch: PhArch) -> None:
+    """raises the library's own refusal of a spec / arch pair (the "LDS tile" text of the ph_arch entry points) ahead of a launch"""
+    check(load().ph_arch_fits(C.byref(spec), C.byref(arch)))
 
 
 def adapmult_layout_of(spec: PhSpec, context_size: int) -> PhAdapMultLayout:

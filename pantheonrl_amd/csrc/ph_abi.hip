@@ -1666,40 +1666,79 @@ int ph_liar_obs(ph_ctx* ctx, const int* hands, const int* history, const int* nm
   return 0;
 }
 
-int ph_liar_selfplay_step(ph_ctx* ctx, const ph_liar_selfplay* sp, int ego_pos, unsigned long long counter, int deal_only) {
-  DevGuard dev_guard(ctx);
-  if (!ctx || !sp) return fail("ph_liar_selfplay_step: null argument");
+namespace {
+// One seat's forward inside a self-play step: the 64-wide kernels (arch == nullptr: exactly the calls the steps have always made)
+// or the towers of a run-time shape.  Rectangular: recorded at row `pos` of rb.  Ragged: recorded at pos_env[e] where rec[e].
+// A tower seat is always called with gemm_mode 0 although the per-call walk passes the policy's own mode.  The two agree only because
+// the tower forward answers mode 1 with a VALU instantiation in the accumulation order of mode 0 and mode 2 with the mode-0 kernel
+// itself, so every mode gives the bits of 0 (tests/test_gpu_arch_vec.py checks that for the ragged and the scripted calls).  A
+// tower forward whose bits ever depend on the mode must take it from the step's description instead.
+int seat_forward(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs, int n,
+                 unsigned long long seed, unsigned long long counter, int* actions, float* values, float* log_probs,
+                 const ph_rollout* rb, int pos, const float* episode_start) {
+  if (arch)
+    return ph_arch_forward(ctx, spec, arch, params, obs, n, nullptr, nullptr, nullptr, seed, counter, 0, actions, nullptr, values,
+                           log_probs, nullptr, nullptr, rb, pos, episode_start, nullptr, 0);
+  return ph_policy_forward(ctx, spec, params, obs, n, nullptr, nullptr, nullptr, seed, counter, 0, actions, nullptr, values, log_probs,
+                           nullptr, nullptr, rb, pos, episode_start, nullptr, 0);
+}
+int seat_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs,
+                        unsigned long long seed, unsigned long long counter, int* actions, float* values, float* log_probs,
+                        const ph_rollout* rb, const int* pos_env, const unsigned char* rec, const float* episode_start) {
+  if (arch)
+    return ph_arch_forward_ragged(ctx, spec, arch, params, obs, nullptr, seed, counter, 0, actions, values, log_probs, rb, pos_env, rec,
+                                  episode_start, 0);
+  return ph_policy_forward_ragged(ctx, spec, params, obs, nullptr, seed, counter, 0, actions, values, log_probs, rb, pos_env, rec,
+                                  episode_start);
+}
+
+// the launch sequence of one vectorised Liar's Dice step, written once: either seat on the 64-wide kernels (null arch) or on towers
+int liar_selfplay_step_run(const char* who, ph_ctx* ctx, const ph_liar_selfplay* sp, const ph_arch* ego_arch, const ph_arch* alt_arch,
+                           int ego_pos, unsigned long long counter, int deal_only) {
+  const std::string w(who);
+  if (!ctx || !sp) return fail(w + ": null argument");
   const ph_liar_selfplay& s = *sp;
-  if (s.n <= 0 || !s.spec || !s.ego_rb || !s.alt_rb) return fail("ph_liar_selfplay_step: incomplete description");
+  if (s.n <= 0 || !s.spec || !s.ego_rb || !s.alt_rb) return fail(w + ": incomplete description");
   if (check_rb(s.ego_rb) || check_rb(s.alt_rb)) return 1;
-  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail("ph_liar_selfplay_step: buffers must have E = n");
+  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail(w + ": buffers must have E = n");
   if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
       ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
        (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
-    return fail("ph_liar_selfplay_step: hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
+    return fail(w + ": hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
   hipStream_t st = ctx->stream;
   if (!deal_only) {
-    if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail("ph_liar_selfplay_step: ego_pos out of range (buffer full?)");
+    if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail(w + ": ego_pos out of range (buffer full?)");
     // ego moves in every table
-    if (ph_policy_forward(ctx, s.spec, s.ego_params, s.obs_ego, s.n, nullptr, nullptr, nullptr, s.ego_seed, counter, 0,
-                          s.ego_actions, nullptr, s.ego_values, s.ego_log_probs, nullptr, nullptr, s.ego_rb, ego_pos,
-                          s.ego_episode_start, nullptr, 0))
+    if (seat_forward(ctx, s.spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, counter, s.ego_actions, s.ego_values,
+                     s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start))
       return 1;
     PH_HIP(ph::launch_liar_sp_after_ego(s, st));
     // partner replies where the game goes on (obs_next = its observation there)
-    if (ph_policy_forward_ragged(ctx, s.spec, s.alt_params, s.obs_next, nullptr, s.alt_seed, 2 * counter, 0, s.alt_actions,
-                                 s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
+    if (seat_forward_ragged(ctx, s.spec, alt_arch, s.alt_params, s.obs_next, s.alt_seed, 2 * counter, s.alt_actions, s.alt_values,
+                            s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
       return 1;
   }
   // reply played and credited; finished tables (flagged in s.done) are re-dealt; where the partner opens the new game it
   // moves once
   PH_HIP(ph::launch_liar_sp_after_reply(s, deal_only ? nullptr : s.ego_rb->rewards + (size_t)ego_pos * s.n, counter,
                                         ctx->rng_epoch, deal_only, st));
-  if (ph_policy_forward_ragged(ctx, s.spec, s.alt_params, s.obs_alt, nullptr, s.alt_seed, 2 * counter + 1, 0, s.alt_actions,
-                               s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
+  if (seat_forward_ragged(ctx, s.spec, alt_arch, s.alt_params, s.obs_alt, s.alt_seed, 2 * counter + 1, s.alt_actions, s.alt_values,
+                          s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
     return 1;
   PH_HIP(ph::launch_liar_sp_after_opening(s, st));
   return 0;
+}
+}  // namespace
+
+int ph_liar_selfplay_step(ph_ctx* ctx, const ph_liar_selfplay* sp, int ego_pos, unsigned long long counter, int deal_only) {
+  DevGuard dev_guard(ctx);
+  return liar_selfplay_step_run("ph_liar_selfplay_step", ctx, sp, nullptr, nullptr, ego_pos, counter, deal_only);
+}
+
+int ph_liar_selfplay_step_arch(ph_ctx* ctx, const ph_liar_selfplay* sp, const ph_arch* ego_arch, const ph_arch* alt_arch, int ego_pos,
+                               unsigned long long counter, int deal_only) {
+  DevGuard dev_guard(ctx);
+  return liar_selfplay_step_run("ph_liar_selfplay_step_arch", ctx, sp, ego_arch, alt_arch, ego_pos, counter, deal_only);
 }
 
 // ---- Liar's Dice against a pool of partners (ph_pool.h) ----
@@ -1897,38 +1936,52 @@ int ph_block_obs(ph_ctx* ctx, int variant, const int* state, int is_ego, const u
   return 0;
 }
 
-int ph_block_selfplay_step(ph_ctx* ctx, const ph_block_selfplay* sp, int ego_pos, unsigned long long counter) {
-  DevGuard dev_guard(ctx);
-  if (!ctx || !sp) return fail("ph_block_selfplay_step: null argument");
+namespace {
+// the launch sequence of one vectorised block-world step, written once (seat_forward: 64-wide kernels or towers per seat)
+int block_selfplay_step_run(const char* who, ph_ctx* ctx, const ph_block_selfplay* sp, const ph_arch* ego_arch, const ph_arch* alt_arch,
+                            int ego_pos, unsigned long long counter) {
+  const std::string w(who);
+  if (!ctx || !sp) return fail(w + ": null argument");
   const ph_block_selfplay& s = *sp;
-  if (s.variant != 0 && s.variant != 1) return fail("ph_block_selfplay_step: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
-  if (s.n <= 0) return fail("ph_block_selfplay_step: n must be positive");
+  if (s.variant != 0 && s.variant != 1) return fail(w + ": variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (s.n <= 0) return fail(w + ": n must be positive");
   if (!s.ego_spec || !s.alt_spec || !s.ego_rb || !s.alt_rb || !s.state || !s.ego_actions || !s.alt_actions || !s.ego_episode_start ||
       !s.alt_pos || !s.alt_boundary || !s.alt_term || !s.alt_open || !s.alt_acted || !s.obs_ego || !s.obs_alt || !s.episodes ||
       !s.es_alt || !s.running || !s.can || !s.done)
-    return fail("ph_block_selfplay_step: incomplete description");
+    return fail(w + ": incomplete description");
   if (check_rb(s.ego_rb) || check_rb(s.alt_rb)) return 1;
-  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail("ph_block_selfplay_step: buffers must have E = n");
-  if ((uintptr_t)s.state % 16) return fail("ph_block_selfplay_step: state must be 16-byte aligned");
-  if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail("ph_block_selfplay_step: ego_pos out of range (buffer full?)");
+  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail(w + ": buffers must have E = n");
+  if ((uintptr_t)s.state % 16) return fail(w + ": state must be 16-byte aligned");
+  if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail(w + ": ego_pos out of range (buffer full?)");
   // the specs must be the variant's: the book-keeping kernels write rows of these lengths
   ph_layout le, la;
   if (ph_layout_of(s.ego_spec, &le) || ph_layout_of(s.alt_spec, &la)) return 1;
   if (le.D != ph::bw_ego_obs_len(s.variant) || le.A != 1 || le.L != ph::bw_tokens(s.variant) ||
       la.D != ph::bw_alt_obs_len(s.variant) || la.A != ph::bw_alt_act_len(s.variant))
-    return fail("ph_block_selfplay_step: the specs are not the variant's planner / constructor spaces");
+    return fail(w + ": the specs are not the variant's planner / constructor spaces");
   // the planner moves in every table
-  if (ph_policy_forward(ctx, s.ego_spec, s.ego_params, s.obs_ego, s.n, nullptr, nullptr, nullptr, s.ego_seed, counter, 0,
-                        s.ego_actions, nullptr, s.ego_values, s.ego_log_probs, nullptr, nullptr, s.ego_rb, ego_pos,
-                        s.ego_episode_start, nullptr, 0))
+  if (seat_forward(ctx, s.ego_spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, counter, s.ego_actions, s.ego_values,
+                   s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start))
     return 1;
   PH_HIP(ph::launch_block_sp_after_ego(s, s.ego_rb->rewards + (size_t)ego_pos * s.n, counter, ctx->rng_epoch, ctx->stream));
   // the constructor replies where the game goes on
-  if (ph_policy_forward_ragged(ctx, s.alt_spec, s.alt_params, s.obs_alt, nullptr, s.alt_seed, counter, 0, s.alt_actions,
-                               s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
+  if (seat_forward_ragged(ctx, s.alt_spec, alt_arch, s.alt_params, s.obs_alt, s.alt_seed, counter, s.alt_actions, s.alt_values,
+                          s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
     return 1;
   PH_HIP(ph::launch_block_sp_after_alt(s, ctx->stream));
   return 0;
+}
+}  // namespace
+
+int ph_block_selfplay_step(ph_ctx* ctx, const ph_block_selfplay* sp, int ego_pos, unsigned long long counter) {
+  DevGuard dev_guard(ctx);
+  return block_selfplay_step_run("ph_block_selfplay_step", ctx, sp, nullptr, nullptr, ego_pos, counter);
+}
+
+int ph_block_selfplay_step_arch(ph_ctx* ctx, const ph_block_selfplay* sp, const ph_arch* ego_arch, const ph_arch* alt_arch, int ego_pos,
+                                unsigned long long counter) {
+  DevGuard dev_guard(ctx);
+  return block_selfplay_step_run("ph_block_selfplay_step_arch", ctx, sp, ego_arch, alt_arch, ego_pos, counter);
 }
 
 int ph_block_replay_host(int variant, int n, int rounds, int* state, const int* tokens, const int* alt_actions, float* alt_obs_out,
@@ -2074,6 +2127,29 @@ int arch_layout(const ph_spec* spec, const ph_arch* arch, ph_arch_layout* o) {
   return 0;
 }
 
+// the smallest carve (32-row tiles: the forward launch, and the gradient launch's fall-back) must fit the CU's LDS; the one place
+// that says so, for the entry points (arch_resolve) and for ph_arch_fits
+int arch_lds_refusal(const ph::NetDims& nd, const ph::ArchDims& ad) {
+  const size_t need = std::max(ph::arch_grad_lds_bytes(nd, ad, ph::ARCH_FWD_ROWS), ph::arch_fwd_lds_bytes(nd, ad));
+  if (need > ph::ARCH_LDS_MAX)
+    return fail("ph_arch: observation space too large for the tower kernels' LDS tile (" + std::to_string(need) +
+                " bytes at 32 rows, " + std::to_string(ph::ARCH_LDS_MAX) + " available)");
+  return 0;
+}
+
+// the dimensions the LDS carves depend on, from host descriptions alone (no context)
+int arch_host_dims(const ph_spec* spec, const ph_arch* arch, ph::NetDims* nd, ph::ArchDims* ad) {
+  std::memset(ad, 0, sizeof(*ad));
+  if (arch_layout(spec, arch, &ad->lay)) return 1;
+  ad->nl = arch->n_layers;
+  for (int l = 0; l < arch->n_layers; ++l) ad->w[l] = arch->width[l];
+  std::memset(nd, 0, sizeof(*nd));
+  nd->obs_kind = spec->obs.kind;
+  nd->D = ad->lay.D;
+  nd->nchunk = (ad->lay.F + PH_HIDDEN - 1) / PH_HIDDEN;
+  return 0;
+}
+
 // spec and arch resolved for the tower kernels: nd as `resolve` leaves it, minus every table of the 64-wide gradient kernels,
 // with lay.P the ARCH's parameter count (slab length, reduce / Adam extent)
 int arch_resolve(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, ph::NetDims* nd, ph::ArchDims* ad) {
@@ -2085,11 +2161,7 @@ int arch_resolve(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, ph::NetD
   nd->slab_map = nd->slab_map_split = nd->wimage_map = nullptr;
   nd->split = nd->split_kind = 0;
   nd->lay.P = ad->lay.P;
-  // the smallest carve (32-row tiles: the forward launch, and the gradient launch's fall-back) must fit the CU's LDS
-  if (ph::arch_grad_lds_bytes(*nd, *ad, ph::ARCH_FWD_ROWS) > ph::ARCH_LDS_MAX)
-    return fail("ph_arch: observation space too large for the tower kernels' LDS tile (" +
-                std::to_string(ph::arch_grad_lds_bytes(*nd, *ad, ph::ARCH_FWD_ROWS)) + " bytes at 32 rows, 163840 available)");
-  return 0;
+  return arch_lds_refusal(*nd, *ad);
 }
 
 void fill_grad_args(ph::GradArgs& g, const ph::NetDims& nd, const float* params, const ph_rollout* rb,
@@ -2554,20 +2626,20 @@ int ph_arch_layout_of(const ph_spec* spec, const ph_arch* arch, ph_arch_layout* 
 
 int ph_arch_lds_bytes(const ph_spec* spec, const ph_arch* arch, int* grad_bytes_out, int* grad_rows_out, int* fwd_bytes_out) {
   ph::ArchDims ad;
-  std::memset(&ad, 0, sizeof(ad));
-  if (arch_layout(spec, arch, &ad.lay)) return 1;
-  ad.nl = arch->n_layers;
-  for (int l = 0; l < arch->n_layers; ++l) ad.w[l] = arch->width[l];
   ph::NetDims nd;
-  std::memset(&nd, 0, sizeof(nd));
-  nd.obs_kind = spec->obs.kind;
-  nd.D = ad.lay.D;
-  nd.nchunk = (ad.lay.F + PH_HIDDEN - 1) / PH_HIDDEN;
+  if (arch_host_dims(spec, arch, &nd, &ad)) return 1;
   const int R = ph::arch_grad_rows(nd, ad);
   if (grad_bytes_out) *grad_bytes_out = (int)ph::arch_grad_lds_bytes(nd, ad, R);
   if (grad_rows_out) *grad_rows_out = R;
   if (fwd_bytes_out) *fwd_bytes_out = (int)ph::arch_fwd_lds_bytes(nd, ad);
   return 0;
+}
+
+int ph_arch_fits(const ph_spec* spec, const ph_arch* arch) {
+  ph::ArchDims ad;
+  ph::NetDims nd;
+  if (arch_host_dims(spec, arch, &nd, &ad)) return 1;
+  return arch_lds_refusal(nd, ad);
 }
 
 int ph_arch_forward(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs, int n,
@@ -2602,6 +2674,81 @@ int ph_arch_forward(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const
   a.logits = logits;
   if (fwd_bind_row("ph_arch_forward", a, rb, pos, episode_start_in, pending_reward)) return 1;
   PH_HIP(ph::launch_arch_fwd(a, ad, gemm_mode, ctx->stream));
+  return 0;
+}
+
+int ph_arch_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs,
+                           const unsigned char* action_mask, unsigned long long seed, unsigned long long counter, int deterministic,
+                           int* actions_i32, float* values, float* log_probs, const ph_rollout* rb, const int* pos_env,
+                           const unsigned char* record_mask, const float* episode_start_in, int gemm_mode) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!params || !obs || !pos_env || !record_mask || !episode_start_in) return fail("ph_arch_forward_ragged: null argument");
+  if ((uintptr_t)params % 16 != 0) return fail("ph_arch_forward_ragged: params must be 16-byte aligned");
+  if (check_rb(rb)) return 1;
+  ph::FwdArgs a;
+  ph::ArchDims ad;
+  std::memset(&a, 0, sizeof(a));
+  if (arch_resolve(ctx, spec, arch, &a.nd, &ad)) return 1;
+  a.params = params;
+  a.obs = obs;
+  a.n = rb->E;
+  a.seed = seed;
+  a.counter = counter;
+  a.epoch = ctx->rng_epoch;
+  a.act_i32 = actions_i32;
+  a.values = values;
+  a.logp = log_probs;
+  a.mask = action_mask;
+  a.deterministic = deterministic;
+  a.rb_obs = rb->observations;  // array bases: rows are selected per env
+  a.rb_act = rb->actions;
+  a.rb_rew = rb->rewards;
+  a.rb_es = rb->episode_starts;
+  a.rb_val = rb->values;
+  a.rb_logp = rb->log_probs;
+  a.es_in = episode_start_in;
+  a.pos_env = pos_env;
+  a.rec_mask = record_mask;
+  a.rb_T = rb->T;
+  PH_HIP(ph::launch_arch_fwd(a, ad, gemm_mode, ctx->stream));
+  return 0;
+}
+
+int ph_arch_scripted_rollout(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs_seq,
+                             const float* rew_seq, const float* done_seq, int n, int n_steps, const float* episode_start0,
+                             unsigned long long seed, unsigned long long counter0, int* actions_i32, float* values, float* log_probs,
+                             const ph_rollout* rb, int pos0, int gemm_mode) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!params || !obs_seq || !rew_seq || !done_seq || !episode_start0) return fail("ph_arch_scripted_rollout: null argument");
+  if ((uintptr_t)params % 16 != 0) return fail("ph_arch_scripted_rollout: params must be 16-byte aligned");
+  if (n <= 0 || n_steps <= 0) return fail("ph_arch_scripted_rollout: n and n_steps must be positive");
+  if (check_rb(rb)) return 1;
+  if (n != rb->E) return fail("ph_arch_scripted_rollout: n must equal the rollout buffer's E");
+  if (pos0 < 0 || pos0 > rb->T - n_steps)
+    return fail("ph_arch_scripted_rollout: rows pos0 .. pos0 + n_steps - 1 must lie in the buffer");
+  ph::FwdArgs a;
+  ph::ArchDims ad;
+  std::memset(&a, 0, sizeof(a));
+  if (arch_resolve(ctx, spec, arch, &a.nd, &ad)) return 1;
+  a.params = params;
+  a.obs = obs_seq;
+  a.n = n;
+  a.seed = seed;
+  a.counter = counter0;
+  a.epoch = ctx->rng_epoch;
+  a.act_i32 = actions_i32;
+  a.values = values;
+  a.logp = log_probs;
+  if (fwd_bind_row("ph_arch_scripted_rollout", a, rb, pos0, episode_start0, nullptr)) return 1;   // step 0's row
+  ph::ScriptedSteps sc;
+  std::memset(&sc, 0, sizeof(sc));
+  sc.n_steps = n_steps;
+  sc.obs_seq = obs_seq;
+  sc.rew_seq = rew_seq;
+  sc.done_seq = done_seq;
+  PH_HIP(ph::launch_arch_rollout(a, ad, sc, gemm_mode, ctx->stream));
   return 0;
 }
 

@@ -73,5 +73,7 @@ size_t arch_fwd_lds_bytes(const NetDims& nd, const ArchDims& ad);
 void arch_grad_plan(const NetDims& nd, const ArchDims& ad, int nb, int num_cu, int* ntiles, int* nwg);
 hipError_t launch_arch_grad(const GradArgs& a, const ArchDims& ad, int nwg, int gemm_mode, hipStream_t s);
 hipError_t launch_arch_fwd(const FwdArgs& a, const ArchDims& ad, int gemm_mode, hipStream_t s);
+// sc.n_steps forwards against a scripted environment in one launch (tower_rollout_kernel)
+hipError_t launch_arch_rollout(const FwdArgs& a, const ArchDims& ad, const ScriptedSteps& sc, int gemm_mode, hipStream_t s);
 
 }  // namespace ph

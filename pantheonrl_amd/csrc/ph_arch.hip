@@ -255,22 +255,30 @@ __device__ __forceinline__ void policy_loss_row(const GradArgs& a, const NetDims
 }  // namespace
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
+// What a forward workgroup stages once: its tile's row indices (relative to a.obs), this net's biases and head vector, the
+// one-hot feature -> component table.  Caller barriers afterwards.
+__device__ __forceinline__ void tower_fwd_setup(float* smem, const ArchLds& S, const FwdArgs& a, const ArchDims& ad, int net, int row0,
+                                                int tid) {
+  constexpr int R = ARCH_FWD_ROWS;
+  int* rowphys = (int*)(smem + S.rowphys);
+  if (tid < R) rowphys[tid] = (row0 + tid < a.n) ? row0 + tid : -1;
+  stage_biases(smem, S, a.params, ad, a.nd, net, tid);
+  if (a.nd.obs_kind != PH_SPACE_BOX) XStage<R, TNT>::build_fcomp((int*)(smem + S.fcomp), a.nd, tid);
+}
+
+// One forward of the workgroup's tile after tower_fwd_setup (and a barrier): every layer's products, then the value net's row
+// tail and observation copy, or the head product and the sampling tail.  Every global store goes through value_row_tail /
+// copy_obs_rows / general_row_tail, i.e. through rb_row: rectangular and ragged rollout-buffer rows alike.
 template <bool VALU>
-__global__ __launch_bounds__(TNT) void tower_fwd_kernel(FwdArgs a, ArchDims ad) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void tower_fwd_body(float* smem, const ArchLds& S, const FwdArgs& a, const ArchDims& ad, int net, int row0,
+                                               int tid) {
   constexpr int R = ARCH_FWD_ROWS;
   const NetDims& nd = a.nd;
   const bool onehot = nd.obs_kind != PH_SPACE_BOX;
-  const ArchLds S = arch_lds(ad, R, onehot ? nd.D : 0, nd.nchunk);
-  const int tid = threadIdx.x, net = blockIdx.y, row0 = blockIdx.x * R;
   int* rowphys = (int*)(smem + S.rowphys);
   int* feat = (int*)(smem + S.feat);
   int* fcomp = (int*)(smem + S.fcomp);
-  if (tid < R) rowphys[tid] = (row0 + tid < a.n) ? row0 + tid : -1;
-  stage_biases(smem, S, a.params, ad, nd, net, tid);
   XStage<R, TNT> xr;
-  if (onehot) XStage<R, TNT>::build_fcomp(fcomp, nd, tid);
-  __syncthreads();
   if (onehot) xr.build_feat(feat, rowphys, a.obs, nd, tid);
   towers_forward<R, VALU>(smem, S, a.params, ad, nd, net, a.obs, rowphys, xr, fcomp, tid);
   const int wn = pick3(ad.w, ad.nl - 1), ldh = wn + 1;
@@ -286,6 +294,53 @@ __global__ __launch_bounds__(TNT) void tower_fwd_kernel(FwdArgs a, ArchDims ad) 
   }
   head_logits<R, VALU>(smem, S, a.params, ad, nd, tid);
   if (tid < R && rowphys[tid] >= 0) general_row_tail(a, nd, row0 + tid, smem + S.bufx + tid * (nd.Lp + 1), fwd_counter(a));
+}
+
+template <bool VALU>
+__global__ __launch_bounds__(TNT) void tower_fwd_kernel(FwdArgs a, ArchDims ad) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int R = ARCH_FWD_ROWS;
+  const bool onehot = a.nd.obs_kind != PH_SPACE_BOX;
+  const ArchLds S = arch_lds(ad, R, onehot ? a.nd.D : 0, a.nd.nchunk);
+  const int tid = threadIdx.x, net = blockIdx.y, row0 = blockIdx.x * R;
+  tower_fwd_setup(smem, S, a, ad, net, row0, tid);
+  __syncthreads();
+  tower_fwd_body<VALU>(smem, S, a, ad, net, row0, tid);
+}
+
+// ---- one-launch rollout against a scripted environment ---------------------------------------------------------------------------
+// sc.n_steps forwards of the same tile in one launch (the contract of ph_scripted_rollout, for towers): a workgroup owns its 32
+// rows of one net for the whole rollout, stages biases / head vector / fcomp once and loops tower_fwd_body, advancing the step's
+// argument record in registers -- observation row block t, rollout-buffer rows pos0 + t, episode starts and the late reward of
+// step t - 1, Philox counter counter0 + t.  A row's scalars are written by the same lane in every step and rows are independent:
+// no workgroup ever waits for another one.  Weights stream through LDS per step, as in the single forward.
+template <bool VALU>
+__global__ __launch_bounds__(TNT) void tower_rollout_kernel(FwdArgs a, ArchDims ad, ScriptedSteps sc) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int R = ARCH_FWD_ROWS;
+  const bool onehot = a.nd.obs_kind != PH_SPACE_BOX;
+  const ArchLds S = arch_lds(ad, R, onehot ? a.nd.D : 0, a.nd.nchunk);
+  const int tid = threadIdx.x, net = blockIdx.y, row0 = blockIdx.x * R;
+  tower_fwd_setup(smem, S, a, ad, net, row0, tid);
+  const size_t n = (size_t)a.n, nD = n * a.nd.D, nA = n * a.nd.A;
+  FwdArgs s = a;   // step t's record
+  for (int t = 0; t < sc.n_steps; ++t) {
+    __syncthreads();   // first pass: the staged vectors are visible; later: the previous step's tails are done with LDS
+    tower_fwd_body<VALU>(smem, S, s, ad, net, row0, tid);
+    s.obs += nD;
+    s.rb_obs += nD;
+    s.rb_act += nA;
+    s.prev_rew = s.rb_rew;
+    s.rb_rew += n;
+    s.rb_es += n;
+    s.rb_val += n;
+    s.rb_logp += n;
+    s.es_in = sc.done_seq + (size_t)t * n;
+    s.pending_reward = sc.rew_seq + (size_t)t * n;
+    s.counter += 1;
+  }
+  // the last step's reward: added to the 0 this lane stored in that row (ph_buffer_add_reward's arithmetic: 0 + (-0) is +0)
+  if (net == 1 && tid < R && row0 + tid < a.n) s.prev_rew[row0 + tid] += s.pending_reward[row0 + tid];
 }
 
 // ---- PPO minibatch gradient ----------------------------------------------------------------------------------------------------
@@ -594,11 +649,30 @@ static hipError_t launch_fwd_inst(const FwdArgs& a, const ArchDims& ad, size_t l
   return hipGetLastError();
 }
 
+// (ragged records -- a.pos_env set, rb_* the array bases -- are served: every global store of the kernel goes through rb_row)
 hipError_t launch_arch_fwd(const FwdArgs& a, const ArchDims& ad, int gemm_mode, hipStream_t s) {
-  if (a.nd.gauss || (a.nd.Lp != 32 && a.nd.Lp != 64) || a.n < 1 || a.pos_env) return hipErrorInvalidValue;
+  if (a.nd.gauss || (a.nd.Lp != 32 && a.nd.Lp != 64) || a.n < 1) return hipErrorInvalidValue;
+  if (a.pos_env && (!a.rec_mask || a.rb_T < 1)) return hipErrorInvalidValue;
   const size_t lds = arch_fwd_lds_bytes(a.nd, ad);
   if (lds > ARCH_LDS_MAX) return hipErrorInvalidValue;
   return gemm_mode == 1 ? launch_fwd_inst<true>(a, ad, lds, s) : launch_fwd_inst<false>(a, ad, lds, s);
+}
+
+template <bool VALU>
+static hipError_t launch_rollout_inst(const FwdArgs& a, const ArchDims& ad, const ScriptedSteps& sc, size_t lds, hipStream_t s) {
+  if (const hipError_t e = allow_dynamic_lds((const void*)tower_rollout_kernel<VALU>, lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((tower_rollout_kernel<VALU>), dim3((a.n + ARCH_FWD_ROWS - 1) / ARCH_FWD_ROWS, 2), dim3(TNT), lds, s, a, ad, sc);
+  return hipGetLastError();
+}
+
+// `a`: step 0's record (rectangular, rollout-buffer row pos0 bound, no pending reward); the kernel derives the others
+hipError_t launch_arch_rollout(const FwdArgs& a, const ArchDims& ad, const ScriptedSteps& sc, int gemm_mode, hipStream_t s) {
+  if (a.nd.gauss || (a.nd.Lp != 32 && a.nd.Lp != 64) || a.n < 1 || a.pos_env || sc.n_steps < 1) return hipErrorInvalidValue;
+  if (!a.rb_obs || !a.rb_act || !a.rb_rew || !a.rb_es || !a.rb_val || !a.rb_logp || !a.es_in || a.pending_reward) return hipErrorInvalidValue;
+  if (!sc.obs_seq || !sc.rew_seq || !sc.done_seq || sc.mask_seq || a.obs != sc.obs_seq) return hipErrorInvalidValue;
+  const size_t lds = arch_fwd_lds_bytes(a.nd, ad);
+  if (lds > ARCH_LDS_MAX) return hipErrorInvalidValue;
+  return gemm_mode == 1 ? launch_rollout_inst<true>(a, ad, sc, lds, s) : launch_rollout_inst<false>(a, ad, sc, lds, s);
 }
 
 }  // namespace ph

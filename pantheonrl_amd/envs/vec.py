@@ -19,7 +19,7 @@ import torch as th
 from .. import _native as nat
 from ..spaces import Discrete, MultiDiscrete
 from ..ppo import require_mlp_kernels
-from ..vec import VecOnPolicyAgent
+from ..vec import VecOnPolicyAgent, is_tower, require_tower_lds
 
 
 class VecRPS:
@@ -107,7 +107,7 @@ class RaggedVecOnPolicyAgent:
     def __init__(self, model):
         self.model = model
         pol, rb = model.policy, model.rollout_buffer
-        require_mlp_kernels(pol, type(self).__name__)     # ph_policy_forward_ragged and the self-play steps read a ph_layout vector
+        self._require_kernels(pol)
         E, lay, dev = rb.n_envs, pol.layout, pol.device
         self.E, self.T = E, rb.buffer_size
         u8 = lambda v: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
@@ -123,6 +123,13 @@ class RaggedVecOnPolicyAgent:
         self._lib, self._h = pol.ctx.lib, pol.ctx.handle
         self._spec, self._rb = C.byref(pol.spec), C.byref(rb.c_struct())
 
+    def _require_kernels(self, pol) -> None:
+        require_mlp_kernels(pol, type(self).__name__)     # ph_policy_forward_ragged and the self-play steps read a ph_layout vector
+
+    def _forward_ragged(self, pol, *args) -> int:
+        """ph_policy_forward_ragged's arguments from `params` on"""
+        return self._lib.ph_policy_forward_ragged(self._h, self._spec, *args)
+
     def get_action(self, obs: th.Tensor, rec_mask: th.Tensor) -> th.Tensor:
         """forward in every env; record the transition where rec_mask is set and the column still has room"""
         pol = self.model.policy
@@ -132,8 +139,8 @@ class RaggedVecOnPolicyAgent:
         blocked = rec_mask.bool() & ~room
         es = self.boundary.to(th.float32)
         pol._counter += 1
-        nat.check(self._lib.ph_policy_forward_ragged(
-            self._h, self._spec, pol.params.data_ptr(), obs.data_ptr(), None, pol._seed, pol._counter, 0,
+        nat.check(self._forward_ragged(
+            pol, pol.params.data_ptr(), obs.data_ptr(), None, pol._seed, pol._counter, 0,
             self.actions.data_ptr(), self.values.data_ptr(), self.log_probs.data_ptr(), self._rb, self.pos.data_ptr(),
             can.data_ptr(), es.data_ptr()))
         nat.check(self._lib.ph_ragged_advance(self._h, self._rb, self.pos.data_ptr(), can.data_ptr()))
@@ -207,6 +214,31 @@ class RaggedVecOnPolicyAgent:
         self.iteration += 1
 
 
+class TowerRaggedVecOnPolicyAgent(RaggedVecOnPolicyAgent):
+    """RaggedVecOnPolicyAgent for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): get_action is ph_arch_forward_ragged;
+    everything else is inherited (the updates end in model.train(), which dispatches to ph_arch_train)."""
+
+    def _require_kernels(self, pol) -> None:
+        if not is_tower(pol):
+            raise nat.NativeError(f"{type(self).__name__}: {type(pol).__name__} is not a net_arch tower policy; use "
+                                  "RaggedVecOnPolicyAgent")
+        require_tower_lds(pol, type(self).__name__)
+
+    def _forward_ragged(self, pol, *args) -> int:
+        return self._lib.ph_arch_forward_ragged(self._h, self._spec, C.byref(pol.arch), *args, int(pol.gemm_mode))
+
+
+def ragged_agent_for(model) -> RaggedVecOnPolicyAgent:
+    """the ragged vectorised agent class that runs `model`'s policy"""
+    return (TowerRaggedVecOnPolicyAgent if is_tower(model.policy) else RaggedVecOnPolicyAgent)(model)
+
+
+def seat_arch(agent):
+    """the ph_arch of a seat's policy for the `_arch` step entry points: a pointer, or None (the 64-wide kernels)"""
+    pol = agent.model.policy
+    return C.pointer(pol.arch) if is_tower(pol) else None
+
+
 class VecLiarSelfPlay:
     """`trainer.py LiarsDice-v0 PPO PPO` (BASELINE config 2) with n_envs tables resident on the device.
 
@@ -239,6 +271,10 @@ class VecLiarSelfPlay:
         self.steps_done = 0
         import os
         self.persistent = self.native and os.environ.get("LIAR_PERSISTENT", "1") != "0"   # whole rollouts as one launch
+        self._archs = (seat_arch(ego), seat_arch(alt))        # a tower in either seat: the `_arch` step, launch by launch
+        self.towers = any(a is not None for a in self._archs)
+        if self.towers:
+            self.persistent = False                           # ph_liar_selfplay_rollout is built around the 64-wide blocks
         if self.native:
             self._build_native()
             self._done.fill_(1)
@@ -288,12 +324,19 @@ class VecLiarSelfPlay:
     def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
         self._bind()
         ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
-        nat.check(ctx.lib.ph_liar_selfplay_step(ctx.handle, C.byref(self._desc), int(rb.pos if ego_pos < 0 else ego_pos),
-                                                int(counter), int(deal_only)))
+        pos = int(rb.pos if ego_pos < 0 else ego_pos)
+        if self.towers:
+            nat.check(ctx.lib.ph_liar_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
+                                                         int(counter), int(deal_only)))
+            return
+        nat.check(ctx.lib.ph_liar_selfplay_step(ctx.handle, C.byref(self._desc), pos, int(counter), int(deal_only)))
 
     def rollout_persistent(self, n_steps: int, first_counter: int, ego_pos: int = 0) -> None:
         """n_steps vectorised steps as ONE persistent launch (`ph_liar_selfplay_rollout`: one workgroup owns 16 tables for the
         whole rollout; bitwise the result of n_steps `_native_call`s with counters first_counter, first_counter + 1, ...)"""
+        if self.towers:
+            raise nat.NativeError("VecLiarSelfPlay.rollout_persistent: a net_arch tower policy does not run on the fused MLP kernels "
+                                  "of the persistent rollout; use step()")
         self._bind()
         ctx = self.env.ctx
         nat.check(ctx.lib.ph_liar_selfplay_rollout(ctx.handle, C.byref(self._desc), int(ego_pos), int(n_steps),
@@ -882,6 +925,8 @@ class VecBlockSelfPlay:
         self._es_alt = th.zeros(E, dtype=th.float32, device=dev)
         self._episodes_dev = th.zeros(1, dtype=th.int64, device=dev)
         self.steps_done = 0
+        self._archs = (seat_arch(ego), seat_arch(alt))        # a tower in either seat: the `_arch` step
+        self.towers = any(a is not None for a in self._archs)
         self._bind()
         self.env.reset(self.seed, 0)
         self.env.observe(True, self.obs_ego)
@@ -921,8 +966,12 @@ class VecBlockSelfPlay:
     def _native_call(self, counter: int, ego_pos: int = -1) -> None:
         self._bind()
         ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
-        nat.check(ctx.lib.ph_block_selfplay_step(ctx.handle, C.byref(self._desc), int(rb.pos if ego_pos < 0 else ego_pos),
-                                                 int(counter)))
+        pos = int(rb.pos if ego_pos < 0 else ego_pos)
+        if self.towers:
+            nat.check(ctx.lib.ph_block_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
+                                                          int(counter)))
+            return
+        nat.check(ctx.lib.ph_block_selfplay_step(ctx.handle, C.byref(self._desc), pos, int(counter)))
 
     def step(self):
         """-> (E,) uint8 device tensor: tables whose game ended in this step"""

@@ -323,8 +323,8 @@ def run_vectorised(args):
     partner list (each of PPO / FIXED / DEFAULT) plays against the partner pool (`run_pool`)."""
     import torch as th
 
-    from .envs.vec import RaggedVecOnPolicyAgent, VecLiarsDice, VecLiarSelfPlay, VecRPS, selfplay_iteration
-    from .vec import VecOnPolicyAgent
+    from .envs.vec import VecLiarsDice, VecLiarSelfPlay, VecRPS, ragged_agent_for, selfplay_iteration
+    from .vec import vec_agent_for
     if args.framestack > 1 or args.record is not None:
         raise EnvException("--n-envs cannot be combined with --framestack / --record")
     plan = pool_plan(args)
@@ -355,16 +355,16 @@ def run_vectorised(args):
         model = PPO(policy="MlpPolicy", **config)
         model.device_permutations = True
         models.append(model)
-    ego = VecOnPolicyAgent(models[0])
+    ego = vec_agent_for(models[0])
     n_steps = models[0].n_steps
     iterations = max(1, -(-args.total_timesteps // (E * n_steps)))
     if args.env == "RPS-v0":
-        alt = VecOnPolicyAgent(models[1])
+        alt = vec_agent_for(models[1])
         env = VecRPS(E, models[0].policy.ctx, models[0].device)
         for _ in range(iterations):
             selfplay_iteration(env, ego, alt, n_steps)
     elif block_variant is not None:
-        alt = RaggedVecOnPolicyAgent(models[1])
+        alt = ragged_agent_for(models[1])
         import random as _random
         base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
         world_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xB10CB10CB10C) & 0x7FFFFFFFFFFFFFFF      # a Philox key of the worlds' own
@@ -372,7 +372,7 @@ def run_vectorised(args):
         for _ in range(iterations):
             env.rollout_and_learn(n_steps)
     else:
-        alt = RaggedVecOnPolicyAgent(models[1])
+        alt = ragged_agent_for(models[1])
         # the dice get a Philox key of their own: keyed by the bare seed they would BE the ego's sampling uniforms (same key,
         # same step counter, same row); without --seed every run deals a fresh sequence
         import random as _random

@@ -29,7 +29,7 @@ class VecOnPolicyAgent:
     def __init__(self, model: PPO):
         self.model = model
         pol, rb = model.policy, model.rollout_buffer
-        require_mlp_kernels(pol, type(self).__name__)
+        self._require_kernels(pol)
         E, lay, dev = rb.n_envs, pol.layout, pol.device
         self.E = E
         self._last_episode_starts = th.ones(E, dtype=th.float32, device=dev)   # D-6: starts True
@@ -45,6 +45,18 @@ class VecOnPolicyAgent:
         self.sync_stats = False
         self._pending = None   # reward tensor of the previous update(), folded into the next step's launch
 
+    # -- which kernels serve the policy (overridden by the tower agent) ------------------------------------------------------
+    def _require_kernels(self, pol) -> None:
+        require_mlp_kernels(pol, type(self).__name__)
+
+    def _forward(self, *args) -> int:
+        """ph_policy_forward's arguments from `params` on"""
+        return self._lib.ph_policy_forward(self._h, self._spec, *args)
+
+    def _scripted(self, *args) -> int:
+        """ph_scripted_rollout's arguments from `params` on"""
+        return self._lib.ph_scripted_rollout(self._h, self._spec, *args)
+
     # -- callbacks --------------------------------------------------------------------------------------------------
     def get_action(self, obs: th.Tensor, record: bool = True, action_mask: Optional[th.Tensor] = None,
                    episode_start: Optional[th.Tensor] = None) -> th.Tensor:
@@ -55,8 +67,8 @@ class VecOnPolicyAgent:
         es = self._last_episode_starts if episode_start is None else episode_start
         pending = self._pending if (record and rb.pos >= 1) else None
         pol._counter += 1
-        nat.check(self._lib.ph_policy_forward(
-            self._h, self._spec, pol.params.data_ptr(), obs.data_ptr(), self.E, nat.ptr(action_mask), None, None,
+        nat.check(self._forward(
+            pol.params.data_ptr(), obs.data_ptr(), self.E, nat.ptr(action_mask), None, None,
             pol._seed, pol._counter, 0, self.actions.data_ptr(), None, self.values.data_ptr(),
             self.log_probs.data_ptr(), None, None, self._rb if record else None, rb.pos if record else 0,
             es.data_ptr() if record else None, nat.ptr(pending), int(pol.gemm_mode)))
@@ -79,8 +91,8 @@ class VecOnPolicyAgent:
         if rb.pos != 0 or data.T != rb.buffer_size or data.E != self.E:
             raise nat.NativeError("rollout_scripted: needs an empty rollout buffer of data.T rows and data.E environments")
         self.flush_rewards()
-        nat.check(self._lib.ph_scripted_rollout(
-            self._h, self._spec, pol.params.data_ptr(), data.obs.data_ptr(), data.rewards.data_ptr(), data.dones.data_ptr(),
+        nat.check(self._scripted(
+            pol.params.data_ptr(), data.obs.data_ptr(), data.rewards.data_ptr(), data.dones.data_ptr(),
             self.E, data.T, self._last_episode_starts.data_ptr(), pol._seed, pol._counter + 1, self.actions.data_ptr(),
             self.values.data_ptr(), self.log_probs.data_ptr(), self._rb, 0, int(pol.gemm_mode)))
         pol._counter += data.T
@@ -140,6 +152,42 @@ class VecOnPolicyAgent:
 
     def bind_stream(self) -> None:
         self.model.policy._bind()
+
+
+def require_tower_lds(pol, who: str) -> None:
+    """the tower forward's LDS carve must fit the CU: said when an agent is built, not at its first step"""
+    try:
+        nat.require_arch_fits(pol.spec, pol.arch)
+    except nat.NativeError as exc:
+        raise nat.NativeError(f"{who}: {exc}") from None
+
+
+def is_tower(pol) -> bool:
+    from .ppo import ArchActorCriticPolicy
+    return isinstance(pol, ArchActorCriticPolicy)
+
+
+class TowerVecOnPolicyAgent(VecOnPolicyAgent):
+    """VecOnPolicyAgent for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): the same callbacks on the tower kernels --
+    get_action is ph_arch_forward (row write and pending-reward fold included), rollout_scripted is ph_arch_scripted_rollout (any
+    spec / arch pair the forward takes), and model.train() already dispatches to ph_arch_train."""
+
+    def _require_kernels(self, pol) -> None:
+        if not is_tower(pol):
+            raise nat.NativeError(f"{type(self).__name__}: {type(pol).__name__} is not a net_arch tower policy; use VecOnPolicyAgent")
+        require_tower_lds(pol, type(self).__name__)
+        self._arch = C.byref(pol.arch)
+
+    def _forward(self, *args) -> int:
+        return self._lib.ph_arch_forward(self._h, self._spec, self._arch, *args)
+
+    def _scripted(self, *args) -> int:
+        return self._lib.ph_arch_scripted_rollout(self._h, self._spec, self._arch, *args)
+
+
+def vec_agent_for(model: PPO) -> VecOnPolicyAgent:
+    """the vectorised agent class that runs `model`'s policy"""
+    return (TowerVecOnPolicyAgent if is_tower(model.policy) else VecOnPolicyAgent)(model)
 
 
 class VecFrameStack:
@@ -326,6 +374,8 @@ class FusedSelfPlayRollout:
         persistent: None = use the one-launch exchange rollout (ph_selfplay_rollout_persistent) whenever the peer-to-peer
         route is up and the launch fits the chip."""
         self.agents, self.datas, self.exchange, self.stream, self.bonus = agents, datas, exchange, stream, bonus
+        for a in agents:      # the step records are ph_step_call's: 64-wide parameter vectors (a tower agent is refused here)
+            require_mlp_kernels(a.model.policy, type(self).__name__)
         # reward_rule "rps": the joint action pays rock-paper-scissors (bonus * payoff of (own, partner's), rps.py:41-45) instead of
         # the synthetic driver's match bonus -- with zero base rewards and every step a terminal one this IS RPSEnv for E tables
         for a in agents:

@@ -8,9 +8,20 @@ roofline convention: forward 2, backward 4 flops per multiply-add).
 
 Variants: the default policy with PH_GEMM_MODE=0 (the exact-float32 64-wide kernels: the yardstick, the same arithmetic class as
 the tower kernels), the default policy in mode 2 (split bf16, for context), ArchActorCriticPolicy at (64, 64), (128, 128),
-(256, 256), (64, 64, 64)."""
+(256, 256), (64, 64, 64).
+
+`python scripts/arch_speed.py rollout` measures the device-resident rollouts of towers instead (host clock around a device
+synchronise, median of REPS, variants of one table alternating):
+  * Overcooked shape, 1024 envs x 128 steps: TowerVecOnPolicyAgent.rollout_scripted (ONE launch, tower_rollout_kernel) against the
+    per-step walk of the same agent (128 x get_action + update) at (64, 64), (128, 128), (256, 256), and as the yardstick
+    VecOnPolicyAgent.rollout_scripted of the 64-wide kernels -- with PH_ROLLOUT_LEAN at its default here, and with PH_ROLLOUT_LEAN=0
+    in a child process of its own (the switch is read once per process);
+  * Liar's Dice, 256 tables x 128 steps: tower agents in both seats at (64, 64) and (128, 128) through LiarIterationGraph (6 x 128
+    launches + the ego's update as one graph, the partner's update after it) and the 64-wide agents under LIAR_PERSISTENT=0 the
+    same way: microseconds per 256-table step of the launch-by-launch rollout, and ego steps per second of whole iterations."""
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
@@ -85,5 +96,130 @@ def main():
               f"mode-0 yardstick  {mac:7d} MAC/row  {100 * share:5.2f} % of the f32 matrix peak  parameters finite: {ok}", flush=True)
 
 
+# ---- rollouts ----------------------------------------------------------------------------------------------------------------------
+def tower_model(env, widths, n_steps, n_envs, seed, n_epochs=10):
+    """PPO on ArchActorCriticPolicy at `widths` -- (64, 64) included, which policy_kwargs would hand to the 64-wide kernels"""
+    model = PPO("MlpPolicy", env, n_steps=n_steps, n_envs=n_envs, batch_size=n_envs * n_steps // 4, n_epochs=n_epochs, seed=seed,
+                _init_setup_model=False)
+    if widths is not None:
+        model._policy_args = {"net_arch": tuple(widths)}
+    model._setup_model()
+    model.device_permutations = True
+    return model
+
+
+def timed(fn):
+    th.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    th.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def scripted_variants(lean0_child):
+    from pantheonrl_amd.vec import SyntheticRollouts, vec_agent_for
+    env = type("Env", (), dict(observation_space=sp.Box(-np.inf, np.inf, (F,)), action_space=sp.Discrete(L), _is_dummy_space_env=True))()
+    data = SyntheticRollouts(env.observation_space, E, T, horizon=400, seed=0, device="cuda")
+    out = []
+
+    def add(label, widths, one_launch):
+        agent = vec_agent_for(tower_model(env, widths, T, E, 0))
+        agent.bind_stream()
+
+        def run():
+            if one_launch:
+                agent.rollout_scripted(data)
+            else:
+                for t in range(T):
+                    agent.get_action(data.obs[t])
+                    agent.update(data.rewards[t], data.dones[t])
+                agent.flush_rewards()
+            agent.finish_update()       # the buffer starts over, nothing is trained
+        out.append(dict(label=label, run=run, secs=[]))
+
+    if lean0_child:
+        add("VecOnPolicyAgent (64, 64) rollout_scripted, PH_ROLLOUT_LEAN=0", None, True)
+        return out
+    add("VecOnPolicyAgent (64, 64) rollout_scripted (64-wide yardstick)", None, True)
+    for w in ((64, 64), (128, 128), (256, 256)):
+        add(f"TowerVecOnPolicyAgent {w} rollout_scripted (one launch)", w, True)
+        add(f"TowerVecOnPolicyAgent {w} walk: {T} x (get_action + update)", w, False)
+    return out
+
+
+def rollout_scripted_section(lean0_child=False):
+    variants = scripted_variants(lean0_child)
+    for v in variants:
+        v["run"]()
+    for _ in range(REPS):
+        for v in variants:
+            v["secs"].append(timed(v["run"]))
+    if not lean0_child:
+        print(f"scripted rollouts, Box({F}) x Discrete({L}), {E} envs x {T} steps, {REPS} runs per variant, variants alternating")
+    for v in variants:
+        us = np.asarray(v["secs"]) * 1e6
+        print(f"{v['label']:64s} {np.median(us):9.1f} us per rollout = {np.median(us) / T:7.2f} us per step "
+              f"(min {us.min():.1f}, max {us.max():.1f})", flush=True)
+
+
+def liar_section():
+    from pantheonrl_amd.envs.vec import LiarIterationGraph, VecLiarsDice, VecLiarSelfPlay, ragged_agent_for
+    from pantheonrl_amd.vec import vec_agent_for
+    El, Tl = 256, 128
+    spaces = type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
+                                _is_dummy_space_env=True))()
+    variants = []
+    for label, widths in (("64-wide agents, LIAR_PERSISTENT=0", None), ("tower agents (64, 64)", (64, 64)),
+                          ("tower agents (128, 128)", (128, 128))):
+        ego, alt = vec_agent_for(tower_model(spaces, widths, Tl, El, 0)), ragged_agent_for(tower_model(spaces, widths, Tl, El, 1))
+        saved = os.environ.get("LIAR_PERSISTENT")
+        os.environ["LIAR_PERSISTENT"] = "0"
+        try:
+            play = VecLiarSelfPlay(El, ego, alt, seed=3)
+        finally:
+            if saved is None:
+                del os.environ["LIAR_PERSISTENT"]
+            else:
+                os.environ["LIAR_PERSISTENT"] = saved
+        assert not play.persistent
+        variants.append(dict(label=label, play=play, graph=LiarIterationGraph(play, Tl), it=[], roll=[]))
+    for v in variants:
+        v["graph"].launch()
+    for _ in range(REPS):
+        for v in variants:
+            v["it"].append(timed(v["graph"].launch))
+    for _ in range(REPS):
+        for v in variants:
+            def steps(play=v["play"]):
+                for t in range(Tl):
+                    play._native_call(t + 1, ego_pos=t)
+            with th.cuda.stream(v["graph"].stream):
+                v["roll"].append(timed(steps))
+                if v["play"].alt.full():        # outside the clock: the next rollout records the partner's rows again
+                    v["play"].alt.learn_from_buffer()
+    print(f"Liar's Dice self-play, {El} tables x {Tl} steps, LiarIterationGraph (launch-by-launch form captured as one graph), {REPS} "
+          "runs per variant, variants alternating")
+    for v in variants:
+        it, roll = np.asarray(v["it"]), np.asarray(v["roll"])
+        print(f"{v['label']:36s} {np.median(roll) / Tl * 1e6:8.1f} us per {El}-table step launch by launch (min "
+              f"{roll.min() / Tl * 1e6:.1f}, max {roll.max() / Tl * 1e6:.1f});  iteration with both updates {np.median(it) * 1e3:7.2f} ms "
+              f"(min {it.min() * 1e3:.2f}, max {it.max() * 1e3:.2f}) -> {El * Tl / np.median(it):12,.0f} ego steps/s;  partner updates "
+              f"{v['play'].alt.iteration}", flush=True)
+
+
+def rollout_main():
+    import subprocess
+    rollout_scripted_section()
+    env = dict(os.environ, PH_ROLLOUT_LEAN="0")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "rollout-lean0"], env=env, capture_output=True, text=True, timeout=600)
+    print(r.stdout.strip() if r.returncode == 0 else f"PH_ROLLOUT_LEAN=0 child failed: {r.stderr[-500:]}", flush=True)
+    liar_section()
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["rollout"]:
+        rollout_main()
+    elif sys.argv[1:2] == ["rollout-lean0"]:
+        rollout_scripted_section(lean0_child=True)
+    else:
+        main()
