@@ -382,11 +382,17 @@ int check_rb(const ph_rollout* rb) {
   return 0;
 }
 
-// a zeroed forward record with the spec resolved and the fields every forward entry point sets
+int fail_who(const char* who, const char* what) { return fail(std::string(who) + what); }
+
+int arch_resolve(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, ph::NetDims* nd, ph::ArchDims* ad);   // with the towers, below
+
+// a zeroed forward record with the spec resolved and the fields every forward entry point sets: for the 64-wide kernels (null
+// arch), or for the towers of `arch`, whose dimensions go to `ad` (arch_resolve: no Box actions, the LDS refusal, lay.P the arch's)
 int fwd_args(ph::FwdArgs& a, ph_ctx* ctx, const ph_spec* spec, bool box_act_ok, const float* params, const float* obs, int n,
-             unsigned long long seed, unsigned long long counter, int* act_i32, float* values, float* logp) {
+             unsigned long long seed, unsigned long long counter, int* act_i32, float* values, float* logp,
+             const ph_arch* arch = nullptr, ph::ArchDims* ad = nullptr) {
   std::memset(&a, 0, sizeof(a));
-  if (resolve(ctx, spec, &a.nd, box_act_ok)) return 1;
+  if (arch ? arch_resolve(ctx, spec, arch, &a.nd, ad) : resolve(ctx, spec, &a.nd, box_act_ok)) return 1;
   a.params = params;
   a.obs = obs;
   a.n = n;
@@ -403,12 +409,11 @@ int fwd_args(ph::FwdArgs& a, ph_ctx* ctx, const ph_spec* spec, bool box_act_ok, 
 // previous row's rewards (Agent.update folded into the next step's launch); messages name the entry point `who`
 int fwd_bind_row(const char* who, ph::FwdArgs& a, const ph_rollout* rb, int pos, const float* episode_start_in,
                  const float* pending_reward) {
-  const std::string w(who);
-  if (!rb) return pending_reward ? fail(w + ": pending_reward needs the fused rollout-buffer write") : 0;
+  if (!rb) return pending_reward ? fail_who(who, ": pending_reward needs the fused rollout-buffer write") : 0;
   if (check_rb(rb)) return 1;
-  if (a.n != rb->E) return fail(w + ": fused add needs n == rollout E");
-  if (pos < 0 || pos >= rb->T) return fail(w + ": pos out of range (buffer full?)");
-  if (!episode_start_in) return fail(w + ": fused add needs episode_start_in");
+  if (a.n != rb->E) return fail_who(who, ": fused add needs n == rollout E");
+  if (pos < 0 || pos >= rb->T) return fail_who(who, ": pos out of range (buffer full?)");
+  if (!episode_start_in) return fail_who(who, ": fused add needs episode_start_in");
   const size_t row = (size_t)pos * rb->E;
   a.rb_obs = rb->observations + row * a.nd.D;
   a.rb_act = rb->actions + row * a.nd.A;
@@ -418,10 +423,115 @@ int fwd_bind_row(const char* who, ph::FwdArgs& a, const ph_rollout* rb, int pos,
   a.rb_logp = rb->log_probs + row;
   a.es_in = episode_start_in;
   if (pending_reward) {
-    if (pos < 1) return fail(w + ": pending_reward needs pos >= 1");
+    if (pos < 1) return fail_who(who, ": pending_reward needs pos >= 1");
     a.prev_rew = rb->rewards + (row - rb->E);
     a.pending_reward = pending_reward;
   }
+  return 0;
+}
+// its ragged sibling: the array bases of a checked `rb`, the kernel selecting each env's row -- with pos_env the row pos_env[e] where
+// rec_mask[e] (ragged forwards), without it a row the kernel walks itself (one-launch rollouts)
+void fwd_bind_bases(ph::FwdArgs& a, const ph_rollout* rb, const float* es_in, const int* pos_env, const unsigned char* rec_mask) {
+  a.rb_obs = rb->observations;
+  a.rb_act = rb->actions;
+  a.rb_rew = rb->rewards;
+  a.rb_es = rb->episode_starts;
+  a.rb_val = rb->values;
+  a.rb_logp = rb->log_probs;
+  a.es_in = es_in;
+  if (!pos_env) return;
+  a.pos_env = pos_env;
+  a.rec_mask = rec_mask;
+  a.rb_T = rb->T;
+}
+
+// what an evaluating forward takes and returns besides the sampled step
+void fwd_eval_fields(ph::FwdArgs& a, const unsigned char* mask, const float* uniforms, const float* given_actions, int deterministic,
+                     float* act_f32, float* entropy, float* logits) {
+  a.mask = mask;
+  a.uniforms = uniforms;
+  a.given_actions = given_actions;
+  a.deterministic = deterministic;
+  a.act_f32 = act_f32;
+  a.entropy = entropy;
+  a.logits = logits;
+}
+
+// The three forward entry points, each written once: on the 64-wide kernels (null arch) or on the towers of `arch`.  Messages name
+// the entry point `who`.
+int forward_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs, int n,
+                const unsigned char* action_mask, const float* uniforms, const float* given_actions, unsigned long long seed,
+                unsigned long long counter, int deterministic, int* actions_i32, float* actions_f32, float* values, float* log_probs,
+                float* entropy, float* logits, const ph_rollout* rb, int pos, const float* episode_start_in,
+                const float* pending_reward, int gemm_mode) {
+  if (!ctx) return fail("null ctx");
+  if (!params || !obs) return fail_who(who, ": null params/obs");
+  if ((uintptr_t)params % 16 != 0) return fail_who(who, ": params must be 16-byte aligned");
+  if (n <= 0) return fail_who(who, ": n must be positive");
+  ph::FwdArgs a;
+  ph::ArchDims ad;
+  // Box actions: the 64-wide forward knows the DiagGaussian head; a tower refuses them whatever is said here
+  if (fwd_args(a, ctx, spec, true, params, obs, n, seed, counter, actions_i32, values, log_probs, arch, &ad)) return 1;
+  if (a.nd.gauss && action_mask) return fail_who(who, ": action masks belong to the categorical heads");
+  fwd_eval_fields(a, action_mask, uniforms, given_actions, deterministic, actions_f32, entropy, logits);
+  a.prof = ctx->prof;
+  if (fwd_bind_row(who, a, rb, pos, episode_start_in, pending_reward)) return 1;
+  if (arch) {
+    PH_HIP(ph::launch_arch_fwd(a, ad, gemm_mode, ctx->stream));
+    return 0;
+  }
+  a.host_done = ctx->fwd_host_done;   // ph_policy_act_host's arrival words: the 64-wide forward only
+  a.host_seq = ctx->act_seq;
+  PH_HIP(ph::launch_policy_fwd(a, gemm_mode, ctx->stream));
+  return 0;
+}
+
+int forward_ragged_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs,
+                       const unsigned char* action_mask, unsigned long long seed, unsigned long long counter, int deterministic,
+                       int* actions_i32, float* values, float* log_probs, const ph_rollout* rb, const int* pos_env,
+                       const unsigned char* record_mask, const float* episode_start_in, int gemm_mode) {
+  if (!ctx) return fail("null ctx");
+  if (!params || !obs || !pos_env || !record_mask || !episode_start_in) return fail_who(who, ": null argument");
+  if ((uintptr_t)params % 16 != 0) return fail_who(who, ": params must be 16-byte aligned");
+  if (check_rb(rb)) return 1;
+  ph::FwdArgs a;
+  ph::ArchDims ad;
+  if (fwd_args(a, ctx, spec, false, params, obs, rb->E, seed, counter, actions_i32, values, log_probs, arch, &ad)) return 1;
+  a.mask = action_mask;
+  a.prof = ctx->prof;
+  a.deterministic = deterministic;
+  fwd_bind_bases(a, rb, episode_start_in, pos_env, record_mask);
+  PH_HIP(arch ? ph::launch_arch_fwd(a, ad, gemm_mode, ctx->stream) : ph::launch_policy_fwd(a, gemm_mode, ctx->stream));
+  return 0;
+}
+
+int scripted_rollout_run(const char* who, ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params,
+                         const float* obs_seq, const float* rew_seq, const float* done_seq, int n, int n_steps,
+                         const float* episode_start0, unsigned long long seed, unsigned long long counter0, int* actions_i32,
+                         float* values, float* log_probs, const ph_rollout* rb, int pos0, int gemm_mode) {
+  if (!ctx) return fail("null ctx");
+  if (!params || !obs_seq || !rew_seq || !done_seq || !episode_start0) return fail_who(who, ": null argument");
+  if ((uintptr_t)params % 16 != 0) return fail_who(who, ": params must be 16-byte aligned");
+  if (n <= 0 || n_steps <= 0) return fail_who(who, ": n and n_steps must be positive");
+  if (check_rb(rb)) return 1;
+  if (n != rb->E) return fail_who(who, ": n must equal the rollout buffer's E");
+  if (pos0 < 0 || pos0 > rb->T - n_steps) return fail_who(who, ": rows pos0 .. pos0 + n_steps - 1 must lie in the buffer");
+  ph::FwdArgs a;
+  ph::ArchDims ad;
+  if (fwd_args(a, ctx, spec, false, params, obs_seq, n, seed, counter0, actions_i32, values, log_probs, arch, &ad)) return 1;
+  if (!arch && !ph::fwd16_eligible(a.nd, n))
+    return fail_who(who, ": needs the 16-row forward's shape class (one feature chunk, one Discrete head of <= 8 logits, "
+                         "n < 16384); use ph_policy_forward per step");
+  a.prof = ctx->prof;
+  if (fwd_bind_row(who, a, rb, pos0, episode_start0, nullptr)) return 1;   // step 0's row
+  ph::ScriptedSteps sc;
+  std::memset(&sc, 0, sizeof(sc));
+  sc.n_steps = n_steps;
+  sc.obs_seq = obs_seq;
+  sc.rew_seq = rew_seq;
+  sc.done_seq = done_seq;
+  PH_HIP(arch ? ph::launch_arch_rollout(a, ad, sc, gemm_mode, ctx->stream)
+              : ph::launch_policy_fwd16_rollout(a, sc, gemm_mode, ctx->stream));
   return 0;
 }
 
@@ -1065,26 +1175,9 @@ int ph_policy_forward(ph_ctx* ctx, const ph_spec* spec, const float* params, con
                       const ph_rollout* rb, int pos, const float* episode_start_in, const float* pending_reward,
                       int gemm_mode) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !obs) return fail("ph_policy_forward: null params/obs");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_policy_forward: params must be 16-byte aligned");
-  if (n <= 0) return fail("ph_policy_forward: n must be positive");
-  ph::FwdArgs a;
-  if (fwd_args(a, ctx, spec, true, params, obs, n, seed, counter, actions_i32, values, log_probs)) return 1;
-  if (a.nd.gauss && action_mask) return fail("ph_policy_forward: action masks belong to the categorical heads");
-  a.mask = action_mask;
-  a.uniforms = uniforms;
-  a.given_actions = given_actions;
-  a.prof = ctx->prof;
-  a.deterministic = deterministic;
-  a.act_f32 = actions_f32;
-  a.entropy = entropy;
-  a.logits = logits;
-  if (fwd_bind_row("ph_policy_forward", a, rb, pos, episode_start_in, pending_reward)) return 1;
-  a.host_done = ctx->fwd_host_done;
-  a.host_seq = ctx->act_seq;
-  PH_HIP(ph::launch_policy_fwd(a, gemm_mode, ctx->stream));
-  return 0;
+  return forward_run("ph_policy_forward", ctx, spec, nullptr, params, obs, n, action_mask, uniforms, given_actions, seed, counter,
+                     deterministic, actions_i32, actions_f32, values, log_probs, entropy, logits, rb, pos, episode_start_in,
+                     pending_reward, gemm_mode);
 }
 
 int ph_policy_act_host(ph_ctx* ctx, const ph_spec* spec, const float* params, const float* obs_host, int n,
@@ -1164,28 +1257,8 @@ int ph_scripted_rollout(ph_ctx* ctx, const ph_spec* spec, const float* params, c
                         unsigned long long counter0, int* actions_i32, float* values, float* log_probs, const ph_rollout* rb,
                         int pos0, int gemm_mode) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !obs_seq || !rew_seq || !done_seq || !episode_start0) return fail("ph_scripted_rollout: null argument");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_scripted_rollout: params must be 16-byte aligned");
-  if (n <= 0 || n_steps <= 0) return fail("ph_scripted_rollout: n and n_steps must be positive");
-  if (check_rb(rb)) return 1;
-  if (n != rb->E) return fail("ph_scripted_rollout: n must equal the rollout buffer's E");
-  if (pos0 < 0 || pos0 + n_steps > rb->T) return fail("ph_scripted_rollout: rows pos0 .. pos0 + n_steps - 1 must lie in the buffer");
-  ph::FwdArgs a;
-  if (fwd_args(a, ctx, spec, false, params, obs_seq, n, seed, counter0, actions_i32, values, log_probs)) return 1;
-  if (!ph::fwd16_eligible(a.nd, n))
-    return fail("ph_scripted_rollout: needs the 16-row forward's shape class (one feature chunk, one Discrete head of <= 8 logits, "
-                "n < 16384); use ph_policy_forward per step");
-  a.prof = ctx->prof;
-  if (fwd_bind_row("ph_scripted_rollout", a, rb, pos0, episode_start0, nullptr)) return 1;   // step 0's row
-  ph::ScriptedSteps sc;
-  sc.n_steps = n_steps;
-  sc.obs_seq = obs_seq;
-  sc.rew_seq = rew_seq;
-  sc.done_seq = done_seq;
-  sc.mask_seq = nullptr;
-  PH_HIP(ph::launch_policy_fwd16_rollout(a, sc, gemm_mode, ctx->stream));
-  return 0;
+  return scripted_rollout_run("ph_scripted_rollout", ctx, spec, nullptr, params, obs_seq, rew_seq, done_seq, n, n_steps, episode_start0,
+                              seed, counter0, actions_i32, values, log_probs, rb, pos0, gemm_mode);
 }
 
 namespace {
@@ -1526,13 +1599,7 @@ int ph_selfplay_rollout_persistent(ph_ctx* ctx, int n_calls, const ph_rollout_ca
     sm.sc[i].mask_env = (c.mask_seq && (c.mask_mode == 1 || c.mask_mode == 2)) ? 1 : 0;
     a.mask = sm.sc[i].mask_policy ? c.mask_seq : nullptr;
     a.env_mask = sm.sc[i].mask_env ? c.mask_seq : nullptr;
-    a.rb_obs = c.rb->observations;
-    a.rb_act = c.rb->actions;
-    a.rb_rew = c.rb->rewards;
-    a.rb_es = c.rb->episode_starts;
-    a.rb_val = c.rb->values;
-    a.rb_logp = c.rb->log_probs;
-    a.es_in = c.episode_start0;
+    fwd_bind_bases(a, c.rb, c.episode_start0, nullptr, nullptr);
     a.joint = x->joint[0][x->rank];      // non-null marks "the reward has a joint-action term"; the kernel reads the words
     a.n_seats = c.n_seats;
     a.seat = c.seat;
@@ -1565,28 +1632,8 @@ int ph_policy_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const float* para
                              int deterministic, int* actions_i32, float* values, float* log_probs, const ph_rollout* rb,
                              const int* pos_env, const unsigned char* record_mask, const float* episode_start_in) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !obs || !pos_env || !record_mask || !episode_start_in)
-    return fail("ph_policy_forward_ragged: null argument");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_policy_forward_ragged: params must be 16-byte aligned");
-  if (check_rb(rb)) return 1;
-  ph::FwdArgs a;
-  if (fwd_args(a, ctx, spec, false, params, obs, rb->E, seed, counter, actions_i32, values, log_probs)) return 1;
-  a.mask = action_mask;
-  a.prof = ctx->prof;
-  a.deterministic = deterministic;
-  a.rb_obs = rb->observations;  // array bases: rows are selected per env
-  a.rb_act = rb->actions;
-  a.rb_rew = rb->rewards;
-  a.rb_es = rb->episode_starts;
-  a.rb_val = rb->values;
-  a.rb_logp = rb->log_probs;
-  a.es_in = episode_start_in;
-  a.pos_env = pos_env;
-  a.rec_mask = record_mask;
-  a.rb_T = rb->T;
-  PH_HIP(ph::launch_policy_fwd(a, 0, ctx->stream));
-  return 0;
+  return forward_ragged_run("ph_policy_forward_ragged", ctx, spec, nullptr, params, obs, action_mask, seed, counter, deterministic,
+                            actions_i32, values, log_probs, rb, pos_env, record_mask, episode_start_in, 0);   // gemm mode 0
 }
 
 int ph_buffer_add_reward_ragged(ph_ctx* ctx, const ph_rollout* rb, const int* pos_env, const float* reward,
@@ -1676,38 +1723,39 @@ namespace {
 int seat_forward(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs, int n,
                  unsigned long long seed, unsigned long long counter, int* actions, float* values, float* log_probs,
                  const ph_rollout* rb, int pos, const float* episode_start) {
-  if (arch)
-    return ph_arch_forward(ctx, spec, arch, params, obs, n, nullptr, nullptr, nullptr, seed, counter, 0, actions, nullptr, values,
-                           log_probs, nullptr, nullptr, rb, pos, episode_start, nullptr, 0);
-  return ph_policy_forward(ctx, spec, params, obs, n, nullptr, nullptr, nullptr, seed, counter, 0, actions, nullptr, values, log_probs,
-                           nullptr, nullptr, rb, pos, episode_start, nullptr, 0);
+  return forward_run(arch ? "ph_arch_forward" : "ph_policy_forward", ctx, spec, arch, params, obs, n, nullptr, nullptr, nullptr, seed,
+                     counter, 0, actions, nullptr, values, log_probs, nullptr, nullptr, rb, pos, episode_start, nullptr, 0);
 }
 int seat_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs,
                         unsigned long long seed, unsigned long long counter, int* actions, float* values, float* log_probs,
                         const ph_rollout* rb, const int* pos_env, const unsigned char* rec, const float* episode_start) {
-  if (arch)
-    return ph_arch_forward_ragged(ctx, spec, arch, params, obs, nullptr, seed, counter, 0, actions, values, log_probs, rb, pos_env, rec,
-                                  episode_start, 0);
-  return ph_policy_forward_ragged(ctx, spec, params, obs, nullptr, seed, counter, 0, actions, values, log_probs, rb, pos_env, rec,
-                                  episode_start);
+  return forward_ragged_run(arch ? "ph_arch_forward_ragged" : "ph_policy_forward_ragged", ctx, spec, arch, params, obs, nullptr, seed,
+                            counter, 0, actions, values, log_probs, rb, pos_env, rec, episode_start, 0);
+}
+
+// a Liar's Dice self-play description is complete, its buffers hold one column per table, and what the kernels read in 16-byte and
+// 8-byte vectors is aligned for it
+int check_liar_selfplay(const char* who, const ph_ctx* ctx, const ph_liar_selfplay* sp) {
+  if (!ctx || !sp) return fail_who(who, ": null argument");
+  const ph_liar_selfplay& s = *sp;
+  if (s.n <= 0 || !s.spec || !s.ego_rb || !s.alt_rb) return fail_who(who, ": incomplete description");
+  if (check_rb(s.ego_rb) || check_rb(s.alt_rb)) return 1;
+  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail_who(who, ": buffers must have E = n");
+  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
+      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
+       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
+    return fail_who(who, ": hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
+  return 0;
 }
 
 // the launch sequence of one vectorised Liar's Dice step, written once: either seat on the 64-wide kernels (null arch) or on towers
 int liar_selfplay_step_run(const char* who, ph_ctx* ctx, const ph_liar_selfplay* sp, const ph_arch* ego_arch, const ph_arch* alt_arch,
                            int ego_pos, unsigned long long counter, int deal_only) {
-  const std::string w(who);
-  if (!ctx || !sp) return fail(w + ": null argument");
+  if (check_liar_selfplay(who, ctx, sp)) return 1;
   const ph_liar_selfplay& s = *sp;
-  if (s.n <= 0 || !s.spec || !s.ego_rb || !s.alt_rb) return fail(w + ": incomplete description");
-  if (check_rb(s.ego_rb) || check_rb(s.alt_rb)) return 1;
-  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail(w + ": buffers must have E = n");
-  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
-      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
-       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
-    return fail(w + ": hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
   hipStream_t st = ctx->stream;
   if (!deal_only) {
-    if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail(w + ": ego_pos out of range (buffer full?)");
+    if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail_who(who, ": ego_pos out of range (buffer full?)");
     // ego moves in every table
     if (seat_forward(ctx, s.spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, counter, s.ego_actions, s.ego_values,
                      s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start))
@@ -2013,57 +2061,27 @@ int ph_block_replay_host(int variant, int n, int rounds, int* state, const int* 
 
 int ph_liar_selfplay_rollout(ph_ctx* ctx, const ph_liar_selfplay* sp, int ego_pos, int n_steps, unsigned long long counter) {
   DevGuard dev_guard(ctx);
-  if (!ctx || !sp) return fail("ph_liar_selfplay_rollout: null argument");
+  const char* who = "ph_liar_selfplay_rollout";
+  if (check_liar_selfplay(who, ctx, sp)) return 1;
   const ph_liar_selfplay& s = *sp;
-  if (s.n <= 0 || !s.spec || !s.ego_rb || !s.alt_rb) return fail("ph_liar_selfplay_rollout: incomplete description");
-  if (check_rb(s.ego_rb) || check_rb(s.alt_rb)) return 1;
-  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail("ph_liar_selfplay_rollout: buffers must have E = n");
-  if (n_steps <= 0 || ego_pos < 0 || ego_pos + n_steps > s.ego_rb->T)
+  if (n_steps <= 0 || ego_pos < 0 || ego_pos > s.ego_rb->T - n_steps)
     return fail("ph_liar_selfplay_rollout: ego_pos + n_steps exceeds the ego's buffer");
-  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
-      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
-       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
-    return fail("ph_liar_selfplay_rollout: hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
   if (((uintptr_t)s.ego_params | (uintptr_t)s.alt_params) % 16) return fail("ph_liar_selfplay_rollout: params must be 16-byte aligned");
-  // exactly the argument records ph_liar_selfplay_step's three forwards build (ph_policy_forward / _ragged); the Philox
-  // counters are the kernel's
+  // the argument records of ph_liar_selfplay_step's three forwards, from the helpers its forwards build them with (forward_run's
+  // row, forward_ragged_run's bases); the Philox counters are the kernel's
   ph::FwdArgs ego, reply, opening;
   if (fwd_args(ego, ctx, s.spec, false, s.ego_params, s.obs_ego, s.n, s.ego_seed, 0, s.ego_actions, s.ego_values, s.ego_log_probs))
     return 1;
   if (!ph::liar_rollout_eligible(ego.nd, s.n))
     return fail("ph_liar_selfplay_rollout: the spec does not fit the 16-row one-hot forward (use ph_liar_selfplay_step)");
-  const size_t row = (size_t)ego_pos * s.n;
-  ego.rb_obs = s.ego_rb->observations + row * ego.nd.D;
-  ego.rb_act = s.ego_rb->actions + row * ego.nd.A;
-  ego.rb_rew = s.ego_rb->rewards + row;
-  ego.rb_es = s.ego_rb->episode_starts + row;
-  ego.rb_val = s.ego_rb->values + row;
-  ego.rb_logp = s.ego_rb->log_probs + row;
-  ego.es_in = s.ego_episode_start;
+  if (fwd_bind_row(who, ego, s.ego_rb, ego_pos, s.ego_episode_start, nullptr)) return 1;
   ego.prof = ctx->prof;   // debug stamps (scripts/liar_rollout_profile.py)
-  std::memset(&reply, 0, sizeof(reply));
-  reply.nd = ego.nd;
-  reply.params = s.alt_params;
-  reply.obs = s.obs_next;
-  reply.n = s.n;
-  reply.seed = s.alt_seed;
-  reply.epoch = ctx->rng_epoch;
-  reply.act_i32 = s.alt_actions;
-  reply.values = s.alt_values;
-  reply.logp = s.alt_log_probs;
-  reply.rb_obs = s.alt_rb->observations;
-  reply.rb_act = s.alt_rb->actions;
-  reply.rb_rew = s.alt_rb->rewards;
-  reply.rb_es = s.alt_rb->episode_starts;
-  reply.rb_val = s.alt_rb->values;
-  reply.rb_logp = s.alt_rb->log_probs;
-  reply.es_in = s.es_alt;
-  reply.pos_env = s.alt_pos;
-  reply.rec_mask = s.can;
-  reply.rb_T = s.alt_rb->T;
+  if (fwd_args(reply, ctx, s.spec, false, s.alt_params, s.obs_next, s.n, s.alt_seed, 0, s.alt_actions, s.alt_values, s.alt_log_probs))
+    return 1;
+  fwd_bind_bases(reply, s.alt_rb, s.es_alt, s.alt_pos, s.can);
   opening = reply;
   opening.obs = s.obs_alt;
-  PH_HIP(ph::launch_liar_rollout(s, ego, reply, opening, n_steps, counter, ctx->rng_epoch, s.ego_rb->rewards + row, ctx->stream));
+  PH_HIP(ph::launch_liar_rollout(s, ego, reply, opening, n_steps, counter, ctx->rng_epoch, ego.rb_rew, ctx->stream));
   return 0;
 }
 
@@ -2648,33 +2666,10 @@ int ph_arch_forward(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const
                     float* actions_f32, float* values, float* log_probs, float* entropy, float* logits,
                     const ph_rollout* rb, int pos, const float* episode_start_in, const float* pending_reward, int gemm_mode) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !obs) return fail("ph_arch_forward: null params/obs");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_arch_forward: params must be 16-byte aligned");
-  if (n <= 0) return fail("ph_arch_forward: n must be positive");
-  ph::FwdArgs a;
-  ph::ArchDims ad;
-  std::memset(&a, 0, sizeof(a));
-  if (arch_resolve(ctx, spec, arch, &a.nd, &ad)) return 1;
-  a.params = params;
-  a.obs = obs;
-  a.n = n;
-  a.seed = seed;
-  a.counter = counter;
-  a.epoch = ctx->rng_epoch;
-  a.act_i32 = actions_i32;
-  a.values = values;
-  a.logp = log_probs;
-  a.mask = action_mask;
-  a.uniforms = uniforms;
-  a.given_actions = given_actions;
-  a.deterministic = deterministic;
-  a.act_f32 = actions_f32;
-  a.entropy = entropy;
-  a.logits = logits;
-  if (fwd_bind_row("ph_arch_forward", a, rb, pos, episode_start_in, pending_reward)) return 1;
-  PH_HIP(ph::launch_arch_fwd(a, ad, gemm_mode, ctx->stream));
-  return 0;
+  if (!arch) return fail("null arch/layout");
+  return forward_run("ph_arch_forward", ctx, spec, arch, params, obs, n, action_mask, uniforms, given_actions, seed, counter,
+                     deterministic, actions_i32, actions_f32, values, log_probs, entropy, logits, rb, pos, episode_start_in,
+                     pending_reward, gemm_mode);
 }
 
 int ph_arch_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs,
@@ -2682,37 +2677,9 @@ int ph_arch_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch
                            int* actions_i32, float* values, float* log_probs, const ph_rollout* rb, const int* pos_env,
                            const unsigned char* record_mask, const float* episode_start_in, int gemm_mode) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !obs || !pos_env || !record_mask || !episode_start_in) return fail("ph_arch_forward_ragged: null argument");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_arch_forward_ragged: params must be 16-byte aligned");
-  if (check_rb(rb)) return 1;
-  ph::FwdArgs a;
-  ph::ArchDims ad;
-  std::memset(&a, 0, sizeof(a));
-  if (arch_resolve(ctx, spec, arch, &a.nd, &ad)) return 1;
-  a.params = params;
-  a.obs = obs;
-  a.n = rb->E;
-  a.seed = seed;
-  a.counter = counter;
-  a.epoch = ctx->rng_epoch;
-  a.act_i32 = actions_i32;
-  a.values = values;
-  a.logp = log_probs;
-  a.mask = action_mask;
-  a.deterministic = deterministic;
-  a.rb_obs = rb->observations;  // array bases: rows are selected per env
-  a.rb_act = rb->actions;
-  a.rb_rew = rb->rewards;
-  a.rb_es = rb->episode_starts;
-  a.rb_val = rb->values;
-  a.rb_logp = rb->log_probs;
-  a.es_in = episode_start_in;
-  a.pos_env = pos_env;
-  a.rec_mask = record_mask;
-  a.rb_T = rb->T;
-  PH_HIP(ph::launch_arch_fwd(a, ad, gemm_mode, ctx->stream));
-  return 0;
+  if (!arch) return fail("null arch/layout");
+  return forward_ragged_run("ph_arch_forward_ragged", ctx, spec, arch, params, obs, action_mask, seed, counter, deterministic,
+                            actions_i32, values, log_probs, rb, pos_env, record_mask, episode_start_in, gemm_mode);
 }
 
 int ph_arch_scripted_rollout(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const float* obs_seq,
@@ -2720,36 +2687,9 @@ int ph_arch_scripted_rollout(ph_ctx* ctx, const ph_spec* spec, const ph_arch* ar
                              unsigned long long seed, unsigned long long counter0, int* actions_i32, float* values, float* log_probs,
                              const ph_rollout* rb, int pos0, int gemm_mode) {
   DevGuard dev_guard(ctx);
-  if (!ctx) return fail("null ctx");
-  if (!params || !obs_seq || !rew_seq || !done_seq || !episode_start0) return fail("ph_arch_scripted_rollout: null argument");
-  if ((uintptr_t)params % 16 != 0) return fail("ph_arch_scripted_rollout: params must be 16-byte aligned");
-  if (n <= 0 || n_steps <= 0) return fail("ph_arch_scripted_rollout: n and n_steps must be positive");
-  if (check_rb(rb)) return 1;
-  if (n != rb->E) return fail("ph_arch_scripted_rollout: n must equal the rollout buffer's E");
-  if (pos0 < 0 || pos0 > rb->T - n_steps)
-    return fail("ph_arch_scripted_rollout: rows pos0 .. pos0 + n_steps - 1 must lie in the buffer");
-  ph::FwdArgs a;
-  ph::ArchDims ad;
-  std::memset(&a, 0, sizeof(a));
-  if (arch_resolve(ctx, spec, arch, &a.nd, &ad)) return 1;
-  a.params = params;
-  a.obs = obs_seq;
-  a.n = n;
-  a.seed = seed;
-  a.counter = counter0;
-  a.epoch = ctx->rng_epoch;
-  a.act_i32 = actions_i32;
-  a.values = values;
-  a.logp = log_probs;
-  if (fwd_bind_row("ph_arch_scripted_rollout", a, rb, pos0, episode_start0, nullptr)) return 1;   // step 0's row
-  ph::ScriptedSteps sc;
-  std::memset(&sc, 0, sizeof(sc));
-  sc.n_steps = n_steps;
-  sc.obs_seq = obs_seq;
-  sc.rew_seq = rew_seq;
-  sc.done_seq = done_seq;
-  PH_HIP(ph::launch_arch_rollout(a, ad, sc, gemm_mode, ctx->stream));
-  return 0;
+  if (!arch) return fail("null arch/layout");
+  return scripted_rollout_run("ph_arch_scripted_rollout", ctx, spec, arch, params, obs_seq, rew_seq, done_seq, n, n_steps,
+                              episode_start0, seed, counter0, actions_i32, values, log_probs, rb, pos0, gemm_mode);
 }
 
 int ph_arch_minibatch_grad(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, const float* params, const ph_rollout* rb,
@@ -2935,13 +2875,7 @@ int ph_adapmult_forward(ph_ctx* ctx, const ph_spec* spec, int context_size, cons
   if (ph_adapmult_layout_of(spec, context_size, &L)) return 1;
   ph::FwdArgs a;
   if (fwd_args(a, ctx, spec, false, params, obs, n, seed, counter, actions_i32, values, log_probs)) return 1;
-  a.mask = action_mask;
-  a.uniforms = uniforms;
-  a.given_actions = given_actions;
-  a.deterministic = deterministic;
-  a.act_f32 = actions_f32;
-  a.entropy = entropy;
-  a.logits = logits;
+  fwd_eval_fields(a, action_mask, uniforms, given_actions, deterministic, actions_f32, entropy, logits);
   if (fwd_bind_row("ph_adapmult_forward", a, rb, pos, episode_start_in, nullptr)) return 1;
   ph::AmWork w;
   if (am_work(ctx, L, a.nd.D, n, &w)) return 1;
@@ -3453,12 +3387,7 @@ int ph_modular_forward(ph_ctx* ctx, const ph_spec* spec, const ph_modular* mod, 
   if (mod_forward_towers(ctx, a.nd, ml, params, obs, a.nd.D, nullptr, 0, 0, n, b, mod->n_modules, k_mod, false, gemm_mode,
                          nullptr))
     return 1;
-  a.mask = action_mask;
-  a.uniforms = uniforms;
-  a.given_actions = given_actions;
-  a.deterministic = deterministic;
-  a.act_f32 = actions_f32;
-  a.entropy = entropy;
+  fwd_eval_fields(a, action_mask, uniforms, given_actions, deterministic, actions_f32, entropy, nullptr);   // logits: its own two
   if (fwd_bind_row("ph_modular_forward", a, rb, pos, episode_start_in, pending_reward)) return 1;
   PH_HIP(ph::launch_modular_act(a, b.zm, b.zmod + (size_t)k_mod * n * 8, b.vm, b.vk, mod->nomain, logits_main, logits_partner,
                                 ctx->stream));
