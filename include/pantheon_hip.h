@@ -42,7 +42,8 @@ extern "C" {
                               6: + ph_bench_train_kernels, ph_debug_split_oh_tables, ph_ctx_step_errors (additions only)
                               7: ph_spec.act may be PH_SPACE_BOX on ph_layout_of / ph_policy_forward / ph_ppo_minibatch_grad / ph_ppo_train
                                   (an error before; no signature or struct changed)
-                                 still 7: + ph_block_reset / _step / _obs, ph_block_selfplay_step, ph_block_replay_host (additions only) */
+                                 still 7: + ph_block_reset / _step / _obs, ph_block_selfplay_step, ph_block_replay_host (additions only)
+                                 still 7: + ph_bc_train_path (addition only) */
 #define PH_HIDDEN 64     /* SB3 MlpPolicy default net_arch pi=[64,64], vf=[64,64] (modular/policies.py:112-114) */
 #define PH_MAX_COMP 256  /* max MultiDiscrete components per space */
 #define PH_MAX_LOGITS 64 /* max total policy logits L */
@@ -931,6 +932,10 @@ typedef struct ph_bc_hyper { /* BC defaults: bc.py:189-191; torch.optim.Adam def
   float l2_weight;     /* 0.0   */
 } ph_bc_hyper;
 int ph_bc_layout_of(const ph_spec *spec /* host */, ph_bc_layout *out /* host */);
+/* host only, no launch: which kernel ph_bc_train runs for the spec -- 0 none (ph_bc_train refuses: the working set exceeds the LDS),
+ * 1 bc_train_kernel (VALU loops), 2 bc_train_mfma_kernel<false> (MFMA tiles, Adam moments through L2), 3 bc_train_mfma_kernel<true>
+ * (moments in LDS).  ph_bc_train dispatches through the same function; PH_BC_MFMA=0 (read once per process) leaves 0 and 1. */
+int ph_bc_train_path(const ph_spec *spec /* host */, int *out /* host */);
 int ph_bc_forward(ph_ctx *ctx, const ph_spec *spec, const float *params, const float *obs, int n,
                   const unsigned char *action_mask, const float *uniforms, const float *given_actions,
                   unsigned long long seed, unsigned long long counter, int deterministic, int *actions_i32, float *values,

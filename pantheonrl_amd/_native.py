@@ -356,6 +356,7 @@ SIGNATURES = {
     "ph_arch_scripted_rollout": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp,
                                  _vp, C.POINTER(PhRollout), _i, _i],
     "ph_bc_layout_of": [C.POINTER(PhSpec), C.POINTER(PhBcLayout)],
+    "ph_bc_train_path": [C.POINTER(PhSpec), C.POINTER(_i)],
     "ph_bc_forward": [_vp, C.POINTER(PhSpec), _vp, _vp, _i, _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp, _vp, _vp],
     "ph_bc_train": [_vp, C.POINTER(PhSpec), C.POINTER(PhOptState), _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(PhBcHyper), _vp],
     # owning-handle layer (host arrays in and out; see include/pantheon_hip.h)
@@ -454,6 +455,13 @@ def arch_lds_bytes(spec: PhSpec, arch: PhArch):
 def require_arch_fits(spec: PhSpec, arch: PhArch) -> None:
     """raises the library's own refusal of a spec / arch pair (the "LDS tile" text of the ph_arch entry points) ahead of a launch"""
     check(load().ph_arch_fits(C.byref(spec), C.byref(arch)))
+
+
+def bc_train_path(spec: PhSpec) -> int:
+    """which kernel ph_bc_train runs for the spec: 0 refused, 1 bc_train_kernel, 2 / 3 bc_train_mfma_kernel<false / true>"""
+    out = C.c_int(-1)
+    check(load().ph_bc_train_path(C.byref(spec), C.byref(out)))
+    return out.value
 
 
 def adapmult_layout_of(spec: PhSpec, context_size: int) -> PhAdapMultLayout:

@@ -3530,6 +3530,15 @@ int ph_bc_layout_of(const ph_spec* spec, ph_bc_layout* o) {
   return 0;
 }
 
+int ph_bc_train_path(const ph_spec* spec, int* out) {
+  if (!out) return fail("ph_bc_train_path: null out");
+  ph_bc_layout lay;
+  if (ph_bc_layout_of(spec, &lay)) return 1;
+  if (spec->act.kind != PH_SPACE_DISCRETE) return fail("ph_bc_train_path: BC clones categorical actions");
+  *out = ph::bc_train_path(lay.D, lay.F, lay.A, lay.L, lay.P);
+  return 0;
+}
+
 int ph_bc_forward(ph_ctx* ctx, const ph_spec* spec, const float* params, const float* obs, int n,
                   const unsigned char* action_mask, const float* uniforms, const float* given_actions,
                   unsigned long long seed, unsigned long long counter, int deterministic, int* actions_i32, float* values,
@@ -3541,7 +3550,7 @@ int ph_bc_forward(ph_ctx* ctx, const ph_spec* spec, const float* params, const f
   if (resolve(ctx, spec, &nd)) return 1;
   ph_bc_layout lay;
   if (ph_bc_layout_of(spec, &lay)) return 1;
-  if ((size_t)lay.P * sizeof(float) > 150 * 1024) return fail("ph_bc_forward: policy too large for the LDS-resident forward");
+  if (ph::bc_forward_lds_bytes(lay.P) > 160 * 1024) return fail("ph_bc_forward: policy too large for the LDS-resident forward");
   PH_HIP(ph::launch_bc_forward(nd, lay, params, obs, n, action_mask, uniforms, given_actions, seed, counter, deterministic,
                                actions_i32, values, log_probs, entropy, logits, ctx->stream));
   return 0;
@@ -3559,7 +3568,7 @@ int ph_bc_train(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state* opt, const
   if (resolve(ctx, spec, &nd)) return 1;
   ph_bc_layout lay;
   if (ph_bc_layout_of(spec, &lay)) return 1;
-  if (ph::bc_train_lds_bytes(nd.F, nd.L, lay.P, nd.A) > 160 * 1024) return fail("ph_bc_train: working set exceeds the CU's 160 KiB of LDS");
+  if (ph::bc_train_path(nd.D, nd.F, nd.A, nd.L, lay.P) == 0) return fail("ph_bc_train: working set exceeds the CU's 160 KiB of LDS");
   PH_HIP(ph::launch_bc_train(nd, lay, opt->params, opt->adam_m, opt->adam_v, opt->step, obs, acts, order, N, batch_size,
                              n_epochs, max_batches, *hyper, stats, ctx->stream));
   return 0;

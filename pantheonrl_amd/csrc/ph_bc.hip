@@ -772,10 +772,23 @@ size_t bc_train_lds_bytes(int F, int L, int P, int A) {
   return sizeof(float) * (size_t)(((P + 3) & ~3) + BR * (F + 1) + 4 * BR * BLD + BR * (L + 1) + 8 + BR + P + BR * A);
 }
 
-struct BcTrainLaunch {
-  NetDims nd;
-  ph_bc_layout lay;
-};
+constexpr size_t BC_LDS_LIMIT = 160 * 1024;   // the CU's LDS
+
+static bool bc_use_mfma() {   // PH_BC_MFMA=0: every shape on bc_train_kernel; read once per process
+  static int use_mfma = -1;
+  if (use_mfma < 0) {
+    const char* e = getenv("PH_BC_MFMA");
+    use_mfma = (e && e[0] == '0') ? 0 : 1;
+  }
+  return use_mfma != 0;
+}
+
+int bc_train_path(int D, int F, int A, int L, int P) {
+  if (bc_train_lds_bytes(F, L, P, A) > BC_LDS_LIMIT) return 0;
+  if (bc_use_mfma() && BR * D <= 256 * BC_XR && BR * A <= 256 && L <= 64 && bc_mfma_lds_bytes(F, L, P, A, false) <= BC_LDS_LIMIT)
+    return bc_mfma_lds_bytes(F, L, P, A, true) <= BC_LDS_LIMIT ? 3 : 2;
+  return 1;
+}
 
 hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* params, float* adam_m, float* adam_v, int* step,
                            const float* obs, const float* acts, const int* order, int N, int batch, int n_epochs,
@@ -801,14 +814,9 @@ hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* pa
   a.ent_weight = hp.ent_weight;
   a.l2_weight = hp.l2_weight;
   a.stats = stats;
-  static int use_mfma = -1;
-  if (use_mfma < 0) {
-    const char* e = getenv("PH_BC_MFMA");
-    use_mfma = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (use_mfma && BR * nd.D <= 256 * BC_XR && BR * nd.A <= 256 && nd.L <= 64 &&
-      bc_mfma_lds_bytes(nd.F, nd.L, lay.P, nd.A, false) <= 160 * 1024) {
-    const bool moments = bc_mfma_lds_bytes(nd.F, nd.L, lay.P, nd.A, true) <= 160 * 1024;
+  const int path = bc_train_path(nd.D, nd.F, nd.A, nd.L, lay.P);
+  if (path >= 2) {
+    const bool moments = path == 3;
     const size_t lds = bc_mfma_lds_bytes(nd.F, nd.L, lay.P, nd.A, moments);
     const void* fn = moments ? (const void*)bc_train_mfma_kernel<true> : (const void*)bc_train_mfma_kernel<false>;
     if (const hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;
@@ -816,6 +824,7 @@ hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* pa
     else hipLaunchKernelGGL(bc_train_mfma_kernel<false>, dim3(1), dim3(256), lds, s, a);
     return hipGetLastError();
   }
+  if (path != 1) return hipErrorInvalidValue;   // ph_bc_train refuses such a shape by name before it gets here
   const size_t lds = bc_train_lds_bytes(nd.F, nd.L, lay.P, nd.A);
   if (const hipError_t e = allow_dynamic_lds((const void*)bc_train_kernel, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(bc_train_kernel, dim3(1), dim3(256), lds, s, a);
@@ -936,6 +945,8 @@ __global__ __launch_bounds__(64) void bc_forward_kernel(BcFwdArgs a) {
   if (a.entropy) a.entropy[row] = ent_sum;
 }
 
+size_t bc_forward_lds_bytes(int P) { return sizeof(float) * ((((size_t)P + 3) & ~(size_t)3) + 64 * (size_t)PH_MAX_LOGITS); }
+
 hipError_t launch_bc_forward(const NetDims& nd, const ph_bc_layout& lay, const float* params, const float* obs, int n,
                              const unsigned char* mask, const float* uniforms, const float* given, uint64_t seed,
                              uint64_t counter, int deterministic, int* act_i32, float* values, float* logp, float* entropy,
@@ -957,7 +968,7 @@ hipError_t launch_bc_forward(const NetDims& nd, const ph_bc_layout& lay, const f
   a.logp = logp;
   a.entropy = entropy;
   a.logits = logits;
-  const size_t lds = sizeof(float) * ((((size_t)lay.P + 3) & ~(size_t)3) + 64 * (size_t)PH_MAX_LOGITS);
+  const size_t lds = bc_forward_lds_bytes(lay.P);
   if (const hipError_t e = allow_dynamic_lds((const void*)bc_forward_kernel, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(bc_forward_kernel, dim3((n + 63) / 64), dim3(64), lds, s, a);
   return hipGetLastError();

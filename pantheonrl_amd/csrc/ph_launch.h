@@ -498,6 +498,10 @@ hipError_t launch_ppo_grad_split_oh(const GradArgs& a, int nwg, hipStream_t s);
 hipError_t launch_set_int(int* p, int v, hipStream_t s);
 // behavioural cloning on the shared 32-32 policy (ph_bc.hip)
 size_t bc_train_lds_bytes(int F, int L, int P, int A);
+// which training kernel a shape takes: 0 none (even the VALU working set exceeds the LDS), 1 bc_train_kernel,
+// 2 bc_train_mfma_kernel<false>, 3 bc_train_mfma_kernel<true>; PH_BC_MFMA=0 (read once per process) leaves 0 and 1
+int bc_train_path(int D, int F, int A, int L, int P);
+size_t bc_forward_lds_bytes(int P);   // dynamic LDS of bc_forward_kernel: the parameters and 64 lanes' logits
 hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* params, float* adam_m, float* adam_v, int* step,
                            const float* obs, const float* acts, const int* order, int N, int batch, int n_epochs,
                            int max_batches, const ph_bc_hyper& hp, float* stats, hipStream_t s);

@@ -386,7 +386,8 @@ def test_modular_three_steps_from_a_loaded_state_with_per_module_step_counts(sc)
 @pytest.mark.parametrize("N", [32, 77])
 def test_bc_one_step_from_a_loaded_state(N, l2, sc):
     """BC: no clip, torch's default eps 1e-8, lr 1e-3, optional L2; batch_size 200 > N: the whole table is one batch, one step.
-    The gradient tolerance e_g = 1e-6 + 2e-4 max|g| is BORROWED from the PPO gradient tests: no existing test bounds BC's gradient."""
+    The gradient tolerance e_g = 1e-6 + 2e-4 max|g| is BORROWED from the PPO gradient tests; BC's gradient itself is bounded per
+    parameter block, on every shape class, in tests/test_gpu_bc_shapes.py."""
     from pantheonrl_amd.bc import BC
     from pantheonrl_amd.common import TransitionsMinimal
     name = "overcooked"
