@@ -118,6 +118,8 @@ struct ph_ctx {
   size_t blocksq_cap = 0;
   float* advstats = nullptr;
   size_t advstats_cap = 0;
+  ph::AdamBias* adam_bias = nullptr;   // Adam's bias corrections of the current train() call's steps, one per minibatch (adv_finalize_kernel)
+  size_t adam_bias_cap = 0;
   // ph_policy_act_host: pinned, coherent host staging the kernel accesses directly (host view, device view of the same memory)
   float* act_stage_host = nullptr;
   float* act_stage_dev = nullptr;
@@ -746,7 +748,7 @@ int ph_ctx_destroy(ph_ctx* ctx) {
     if (s.wimage_map) (void)hipFree(s.wimage_map);
     if (s.act_off) (void)hipFree(s.act_off);
   }
-  void* ptrs[] = {ctx->wimage, ctx->mw.act, ctx->mw.maps, ctx->mw.kl_sum, ctx->mw.scratch, ctx->advpart, ctx->p2p_dev, ctx->slabs, ctx->statpart, ctx->grad, ctx->blocksq, ctx->advstats, ctx->perm_idx, ctx->perm_phys, ctx->ximg, ctx->rec_pi, ctx->rec_vf, ctx->rowrec, ctx->step_words, ctx->step_gen, ctx->scalars, ctx->stop_flag,
+  void* ptrs[] = {ctx->wimage, ctx->mw.act, ctx->mw.maps, ctx->mw.kl_sum, ctx->mw.scratch, ctx->advpart, ctx->p2p_dev, ctx->slabs, ctx->statpart, ctx->grad, ctx->blocksq, ctx->advstats, ctx->adam_bias, ctx->perm_idx, ctx->perm_phys, ctx->ximg, ctx->rec_pi, ctx->rec_vf, ctx->rowrec, ctx->step_words, ctx->step_gen, ctx->scalars, ctx->stop_flag,
                   ctx->adap_extra, ctx->adap_loss, ctx->am_buf, ctx->pool_dev, ctx->pool_order, ctx->pool_tiles};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -2279,6 +2281,7 @@ int ensure_train_ws(ph_ctx* ctx, int P, int slab_len, int nwg_max, int n_mb_tota
   if (ensure(ctx, ctx->grad, ctx->grad_cap, (size_t)P)) return 1;
   if (ensure(ctx, ctx->blocksq, ctx->blocksq_cap, (size_t)ph::reduce_blocks(slab_len))) return 1;
   if (ensure(ctx, ctx->advstats, ctx->advstats_cap, (size_t)n_mb_total * 2)) return 1;
+  if (ensure(ctx, ctx->adam_bias, ctx->adam_bias_cap, (size_t)n_mb_total)) return 1;
   if (ensure(ctx, ctx->advpart, ctx->advpart_cap, (size_t)n_mb_total * 2 * ph::ADV_SPLIT)) return 1;
   if (n_idx && ensure(ctx, ctx->perm_idx, ctx->perm_idx_cap, n_idx)) return 1;
   const size_t n_words = (size_t)ph::reduce_blocks(slab_len) + 1;
@@ -2395,6 +2398,13 @@ void train_adv_args(const TrainPlan& t, bool need_idx, ph::AdvStatArgs& aa) {
   // for whoever else walks it -- the other gradient kernels, ADAP's context launch (need_idx)
   if (t.nd.split == 1 && !need_idx) aa.idx_out = aa.phys_out = nullptr;
   fill_adv_records(aa, t.ctx, t.nd, t.rb);
+  // Adam's bias corrections of the call's steps ride on the same launch (one thread per minibatch): rebuilt from the device step
+  // counter in every call, hence in every replay of a captured one
+  aa.adam_bias = t.ctx->adam_bias;
+  aa.opt_step = t.opt->step;
+  aa.lr = t.hp->learning_rate;
+  aa.beta1 = t.hp->adam_beta1;
+  aa.beta2 = t.hp->adam_beta2;
 }
 
 // validation, workspace, stop-flag reset and the advantage statistics / minibatch order of every minibatch
@@ -2477,6 +2487,7 @@ void fill_step_args(const TrainPlan& t, int mbi, const MbPlan& pl, ph::ReduceArg
   r = reduce_args(ctx, t.hp, t.opt, t.P, slab_len_of(t.nd), t.nd.slab_map, pl.nwg, pl.nb, ctx->grad, stats_out);
   r.wide = t.alone && ctx->exclusive;
   ad = adam_args(ctx, t.hp, t.opt, t.P, slab_len_of(t.nd), stats_out, t.nd.split ? ctx->wimage : nullptr, t.nd.wimage_map);
+  ad.bias = ctx->adam_bias + mbi;   // minibatch mbi takes step (the call's first) + mbi: every one before it stepped, or the call stopped
 }
 
 // slab reduction + statistics + KL decision, then clip + Adam, of the minibatch whose gradient launch returned `pl`
@@ -3022,6 +3033,9 @@ int ph_bench_train_kernels(ph_ctx* ctx, const ph_spec* spec, const ph_opt_state*
   if (timed(PH_BENCH_REDUCE, [&] { return hip(ph::launch_ppo_reduce(r, s)); })) return 1;
   r.wide = 1;
   if (timed(PH_BENCH_REDUCE_WIDE, [&] { return hip(ph::launch_ppo_reduce(r, s)); })) return 1;
+  // (the reduce launches above advanced the step counter: the bias corrections again from where it stands, and the one reduce that
+  // takes the step they were made for -- clip + Adam is timed as a train() call runs it)
+  if (hip(ph::launch_adv_stats(aa, n_epochs * t.n_mb, s)) || hip(ph::launch_ppo_reduce(r, s))) return 1;
   if (timed(PH_BENCH_ADAM, [&] { return hip(ph::launch_ppo_adam(ad, s)); })) return 1;
   if (ctx->step_words && ctx->step_gen && ph::step_fused_fits(ph::reduce_blocks(slab_len_of(t.nd)), slab_len_of(t.nd), ctx->num_cu)) {
     if (timed(PH_BENCH_STEP_FUSED, [&] {

@@ -210,6 +210,14 @@ __device__ __forceinline__ int minibatch_row(const GradArgs& a, int gi) {
   return env_major_to_phys(n, a.T, a.E);
 }
 
+// Adam's bias corrections of ONE optimizer step, computed ahead of it: they depend on the step count and the call's
+// hyper-parameters only.  `step` says which step the entry was made for; a reader whose step is another computes its own.
+struct alignas(16) AdamBias {
+  float ss, bc2s;   // lr / (1 - beta1^step), sqrt(1 - beta2^step)  (AdamScalars, ph_step.h)
+  int step;
+  int pad;
+};
+
 constexpr int ADV_SPLIT = 32;     // workgroups per minibatch in the advantage-statistics pass (32 x 256 lanes: 1 280 workgroups
                                   // at the bench size spread evenly over the CUs; 8 x 1024 left a quarter of them with two: 21.3 -> 17.4 us)
 constexpr int ADV_THREADS = 256;  // lanes of one of them
@@ -231,6 +239,11 @@ struct AdvStatArgs {
   const float *rb_logp = nullptr, *rb_act = nullptr, *rb_ret = nullptr, *rb_val = nullptr;   // read only when the records are written (action length 1)
   const uint4* rowrec = nullptr; // [T*E][2] the same scalars packed by physical row (obs_planes_kernel), or null: gather from the arrays
   int* clear_flag = nullptr;     // set to 0 by the launch (the train() call's KL stop flag), or null
+  // Adam's bias corrections of the call's optimizer steps (AdamBias below), or null: thread mb of adv_finalize_kernel writes the
+  // entry of step *opt_step + 1 + mb -- the step minibatch mb takes unless the KL stop ends the call first
+  AdamBias* adam_bias = nullptr;   // [n_epochs*n_mb]
+  const int* opt_step = nullptr;   // the optimizer's device step counter as the call finds it
+  float lr = 0.f, beta1 = 0.f, beta2 = 0.f;
 };
 
 struct ReduceArgs {
@@ -274,6 +287,9 @@ struct AdamArgs {
   float* stats_out;       // [PH_NSTAT] or null: writes grad_norm at [6]
   unsigned short* wimage; // the split gradient kernel's weight fragment image (ph_split.h) kept in step with params, or null
   const int* wimage_map;  // [P][2]
+  // this step's bias corrections as the train() call's advantage-statistics launch computed them, or null (entry points without
+  // that launch): used when its `step` is *step, otherwise -- a step counter the call did not start from -- computed here
+  const AdamBias* bias = nullptr;
 };
 
 // reduce + clip + Adam of one minibatch as ONE launch (ph_step.h: step_body; ppo_step_kernel) for a learner that has its device

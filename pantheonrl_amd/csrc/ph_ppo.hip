@@ -927,10 +927,19 @@ __global__ __launch_bounds__(ADV_THREADS) void adv_stats_kernel(AdvStatArgs a) {
     a.partial[((size_t)mb * ADV_SPLIT + seg) * 2 + 1] = tq;
   }
 }
-// mean and unbiased std of every minibatch from the segment partials, folded in a fixed order
+// mean and unbiased std of every minibatch from the segment partials, folded in a fixed order; and, one thread per minibatch
+// being what the call's optimizer steps need too, Adam's bias corrections of the step each minibatch takes (adam_step_scalars, the
+// very function ppo_adam_kernel falls back to), so that no launch of the update chain computes them between its barriers
 __global__ void adv_finalize_kernel(AdvStatArgs a, int n_total) {
   const int mb = blockIdx.x * blockDim.x + threadIdx.x;
   if (mb >= n_total) return;
+  if (a.adam_bias) {
+    AdamBias b;
+    b.step = *a.opt_step + 1 + mb;
+    b.pad = 0;
+    adam_step_scalars(b.step, a.lr, a.beta1, a.beta2, &b.ss, &b.bc2s);
+    a.adam_bias[mb] = b;
+  }
   const int k = mb % a.n_mb;
   const int start = k * a.batch;
   const int nb = (a.N - start < a.batch) ? a.N - start : a.batch;
@@ -1021,20 +1030,24 @@ __global__ __launch_bounds__(RED_PARAMS * 4) void ppo_reduce_kernel(ReduceArgs a
   float (*part)[NSTATP] = reinterpret_cast<float (*)[NSTATP]>(lds_union);
   __shared__ float means[NSTATP];
   const int tid = threadIdx.x;
-  if (*a.stop_flag != 0) {  // a previous minibatch of this train() call hit the KL early stop
-    if (blockIdx.x == 0 && tid < PH_NSTAT && a.stats_out) a.stats_out[tid] = 0.f;
-    if (blockIdx.x == 0 && tid == 0) {
-      a.scalars[1] = 0.f;
-      a.scalars[2] = 0.f;
-    }
-    return;
-  }
+  // Two loads go out here and are consumed BEHIND the slab walk, as in step_body: the KL stop flag of this train() call and the
+  // parameter index of this lane's slab position.  Waited for where they stand, each was a cold round trip every wave of every block
+  // sat through before its first slab load left.  A stopped launch now walks its slabs for nothing (valid memory) and stores what it
+  // always stored; the statistics block, whose reduction has side effects, still tests first.
+  // (the flag as a vector load -- uniform_word, ph_step.h -- which the walk's first wait covers)
+  const int stop_word = uniform_word(a.stop_flag);
   if (blockIdx.x == gridDim.x - 1) {   // the extra block: minibatch statistics and the KL decision, beside the slab blocks
-    (void)reduce_statistics(a, part, means, true);
+    if (__builtin_amdgcn_readfirstlane(stop_word) == 0) (void)reduce_statistics(a, part, means, true);
     return;
   }
-  const int dst = reduce_dst(a, blockIdx.x);
-  const float g = reduce_positions<VEC>(a, gsum, dst, blockIdx.x);
+  const int fetched = reduce_dst_fetch(a, blockIdx.x);
+  reduce_quarters<VEC>(a, gsum, blockIdx.x);
+  if (__builtin_amdgcn_readfirstlane(stop_word) != 0) {   // a previous minibatch of this train() call hit the KL early stop
+    if (blockIdx.x == 0) step_stopped(a);
+    return;
+  }
+  const int dst = reduce_dst_select(a, blockIdx.x, fetched);
+  const float g = reduce_fold(a, gsum, dst);
   if (tid < 64) {  // wave 0: store, square, wave-reduce
     if (dst >= 0) a.grad[dst] = g;
     float q = g * g;
@@ -1113,10 +1126,10 @@ hipError_t launch_ppo_reduce(const ReduceArgs& a, hipStream_t s) {
 // ---- clip_grad_norm_ + Adam (torch.optim.Adam single-tensor maths, eps = 1e-5) ----------------------------------------
 __global__ __launch_bounds__(256) void ppo_adam_kernel(AdamArgs a) {
   __shared__ float sh[4];
-  __shared__ AdamScalars ks;
   const int tid = threadIdx.x;
   // everything this thread's entry needs goes out first: the gradient, the moments, the parameter and its image positions do not
-  // depend on the norm, so they travel under the sum of squares, the two pow() of the bias corrections and the barriers
+  // depend on the norm, so they travel under the sum of squares and the barrier.  So do the step count and the bias corrections
+  // the train() call computed for it (AdamBias): nothing but the clip coefficient is left to do behind the barrier.
   const int p = blockIdx.x * blockDim.x + tid;
   const bool live = p < a.P;
   float gr = 0.f, m0 = 0.f, v0 = 0.f, p0 = 0.f;
@@ -1131,11 +1144,16 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(AdamArgs a) {
       i1 = a.wimage_map[2 * p + 1];
     }
   }
-  if (a.scalars[1] == 0.f) {  // KL early stop (or already stopped): no optimizer step
-    if (blockIdx.x == 0 && tid == 0 && a.scalars[2] != 0.f) *a.stop_flag = 1;
-    return;
+  // the launch's uniform words -- applied / stop requested, the step count, the table entry -- as vector loads in the same batch
+  // (uniform_word, ph_step.h): as scalar loads each was waited for, a cold round trip, before the loads behind it went out
+  const float applied_w = uniform_word(a.scalars + 1);
+  const int step_w = uniform_word(a.step);
+  unsigned long long b0 = 0ull, b1 = 0ull;
+  if (a.bias) {
+    const unsigned long long* bw = reinterpret_cast<const unsigned long long*>(a.bias);
+    b0 = uniform_word(bw);
+    b1 = uniform_word(bw + 1);
   }
-  const int step = (tid == 0) ? *a.step : 0;
   float q = 0.f;
   {   // this thread's entries of the per-block squares (k = tid, tid + 256, ...), loads batched, adds in index order
     float x[4];
@@ -1147,17 +1165,30 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(AdamArgs a) {
         if (k0 + 256 * u < a.nblk) q += x[u];
     }
   }
+  // (one wait has covered every load above: loads return in order)
+  const float applied = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, applied_w)));
+  if (applied == 0.f) {  // KL early stop (or already stopped): no optimizer step
+    if (blockIdx.x == 0 && tid == 0 && a.scalars[2] != 0.f) *a.stop_flag = 1;
+    return;
+  }
+  const int step = __builtin_amdgcn_readfirstlane(step_w);
+  AdamScalars k;
+  if (a.bias && __builtin_amdgcn_readfirstlane((int)(unsigned)b1) == step) {   // AdamBias: {ss, bc2s} {step, -}
+    k.ss = __uint_as_float((unsigned)b0);
+    k.bc2s = __uint_as_float((unsigned)(b0 >> 32));
+  } else {
+    // no table, or a step counter the train() call did not start from: the corrections are computed here, by every lane (the step
+    // is uniform) and in FRONT of the barrier, not between two of them on one lane
+    adam_step_scalars(step, a.lr, a.beta1, a.beta2, &k.ss, &k.bc2s);
+  }
   for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
   if ((tid & 63) == 0) sh[tid >> 6] = q;
   __syncthreads();
-  if (tid == 0) {
-    const float total = sqrtf((sh[0] + sh[1]) + (sh[2] + sh[3]));
-    ks = adam_scalars(total, a.max_norm, step, a.lr, a.beta1, a.beta2);
-    if (blockIdx.x == 0 && a.stats_out) a.stats_out[6] = total;
-  }
-  __syncthreads();
+  // every lane folds the four wave sums itself: one barrier, no single-lane section, nothing to broadcast
+  const float total = sqrtf((sh[0] + sh[1]) + (sh[2] + sh[3]));
+  k.coef = adam_clip_coef(total, a.max_norm);
+  if (blockIdx.x == 0 && tid == 0 && a.stats_out) a.stats_out[6] = total;
   if (!live) return;
-  const AdamScalars k = ks;
   float m, v;
   const float pn = adam_apply(gr, k, a.beta1, a.beta2, a.eps, m0, v0, p0, &m, &v);
   a.m[p] = m;

@@ -25,21 +25,41 @@ namespace ph {
 // 256-byte wave accesses: latency, not bandwidth (9.5 us = 1.8 TB/s).
 constexpr int RED_PARAMS = 64, RED_SUB = 16, RED_SHIFT = 6;
 
+// A device word every lane of a launch reads (a flag, a step count), fetched as a VECTOR load although its address is uniform.  As
+// a scalar load it comes back out of order with the kernel arguments the compiler fetches lazily, batch by batch: the wait for
+// the next batch (s_waitcnt lgkmcnt(0), there is no finer one) waits for the word as well -- a cold round trip in front of
+// everything behind it.  Vector loads return in order, so the first wait for the loads issued after it covers it.  (A relaxed
+// atomic load is what the compiler never turns into a scalar one.)  The value arrives in a vector register: readfirstlane before
+// branching on it.
+template <typename T>
+__device__ __forceinline__ T uniform_word(const T* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // clip_grad_norm_'s scaling and torch.optim.Adam's single-tensor update of ONE parameter (eps = 1e-5 default of SB3).  One
 // definition for ppo_adam_kernel and the fused ppo_step_kernel, with floating-point contraction OFF: which multiply-add pairs
 // the compiler fuses otherwise depends on the surrounding kernel, and the two paths must give bitwise the same parameters.
 struct AdamScalars {
   float coef, ss, bc2s;   // clip coefficient, lr / (1 - beta1^t), sqrt(1 - beta2^t)
 };
-__device__ __forceinline__ AdamScalars adam_scalars(float total_norm, float max_norm, int step, float lr, float beta1, float beta2) {
-  AdamScalars k;
-  const float cc = max_norm / (total_norm + 1e-6f);  // torch.nn.utils.clip_grad_norm_
-  k.coef = cc < 1.0f ? cc : 1.0f;
+// The two halves of adam_scalars.  The bias corrections depend on the step count only (two double-precision pow(): some 330
+// fp64 instructions), the clip coefficient on the gradient norm only -- whoever knows the step before the norm (the table
+// adv_finalize_kernel writes once per train(), ppo_adam_kernel's fallback in front of its barrier) calls the first half there.
+__device__ __forceinline__ void adam_step_scalars(int step, float lr, float beta1, float beta2, float* ss, float* bc2s) {
   const double t = (double)step;
   const double bc1 = 1.0 - pow((double)beta1, t);
   const double bc2 = 1.0 - pow((double)beta2, t);
-  k.ss = (float)((double)lr / bc1);
-  k.bc2s = (float)sqrt(bc2);
+  *ss = (float)((double)lr / bc1);
+  *bc2s = (float)sqrt(bc2);
+}
+__device__ __forceinline__ float adam_clip_coef(float total_norm, float max_norm) {
+  const float cc = max_norm / (total_norm + 1e-6f);  // torch.nn.utils.clip_grad_norm_
+  return cc < 1.0f ? cc : 1.0f;
+}
+__device__ __forceinline__ AdamScalars adam_scalars(float total_norm, float max_norm, int step, float lr, float beta1, float beta2) {
+  AdamScalars k;
+  k.coef = adam_clip_coef(total_norm, max_norm);
+  adam_step_scalars(step, lr, beta1, beta2, &k.ss, &k.bc2s);
   return k;
 }
 // value form: the caller fetched m0 / v0 / p0 (possibly long before the clip coefficient is known) and stores the results
@@ -76,13 +96,27 @@ template <>
 struct RedVec<2> { using T = float2; };
 template <>
 struct RedVec<4> { using T = float4; };
-// the parameter slab position blockIdx.x * 64 + tid belongs to (wave 0; -1 = padding / other waves): fetched by the callers BEFORE
-// the slab walk -- the table lookup is a memory round trip of its own and nothing in it depends on the slabs
+// the parameter slab position blockIdx.x * 64 + tid belongs to (wave 0; -1 = padding / other waves).  step_body needs the VALUE
+// before the slab walk (the moments' addresses hang on it), so this form waits for the table lookup where it stands.
 __device__ __forceinline__ int reduce_dst(const ReduceArgs& a, int blk) {
   const int tid = threadIdx.x;
   if (tid >= RED_PARAMS) return -1;
   const int p = blk * RED_PARAMS + tid;
   return p < a.slab_len ? (a.map ? a.map[p] : p) : -1;
+}
+// The same in two parts for ppo_reduce_kernel, which needs the value only where the gradient is stored.  reduce_dst_fetch ISSUES the
+// lookup in front of the slab walk: every lane, a clamped position -- a load inside `if (tid < 64 && p < slab_len)` is a load in a
+// divergent block, and the compiler waits for it (s_waitcnt vmcnt(0)) where the block ends, a cold round trip before the first
+// slab load.  reduce_dst_select turns what came back into reduce_dst's value BEHIND the walk; loads return in order, so the walk's
+// first wait has covered the lookup.
+__device__ __forceinline__ int reduce_dst_fetch(const ReduceArgs& a, int blk) {
+  const int p = blk * RED_PARAMS + ((int)threadIdx.x & (RED_PARAMS - 1));
+  const int pc = p < a.slab_len ? p : a.slab_len - 1;
+  return a.map ? a.map[pc] : pc;   // (a.map is uniform)
+}
+__device__ __forceinline__ int reduce_dst_select(const ReduceArgs& a, int blk, int fetched) {
+  const int tid = threadIdx.x;
+  return (tid < RED_PARAMS && blk * RED_PARAMS + tid < a.slab_len) ? fetched : -1;
 }
 // the sum of ONE range (slabs k0 .. k0 + per - 1, clipped to nslab) for the VEC positions p0 .. of a lane: eight interleaved
 // accumulators, folded pairwise
@@ -160,8 +194,10 @@ __device__ __forceinline__ float extra_terms(const ReduceArgs& a, int dst, float
 // lines an XCD's L2 kept from an earlier launch.  Used by the round-4 experiment that ran the minibatch step inside the gradient
 // launch (CHANGELOG.md: bitwise the separate launches, and no faster -- the step is a chain of memory round trips, the kernel
 // boundary is not its cost); the stand-alone kernels read plain.
+// reduce_positions in its two parts: the walk, which leaves the four quarters of every position in gsum behind a barrier and
+// needs no parameter index, and wave 0's fold, which does
 template <int VEC, bool COH = false>
-__device__ __forceinline__ float reduce_positions(const ReduceArgs& a, float (*gsum)[RED_PARAMS], int dst, int blk) {
+__device__ __forceinline__ void reduce_quarters(const ReduceArgs& a, float (*gsum)[RED_PARAMS], int blk) {
   static_assert(VEC == 1 || VEC == 2 || VEC == 4, "positions per lane");
   constexpr int LP = RED_PARAMS / VEC;   // lanes that cover the block's 64 positions
   constexpr int TURNS = 4 / VEC;         // ranges of the wave's quarter a lane walks in turn
@@ -208,6 +244,9 @@ __device__ __forceinline__ float reduce_positions(const ReduceArgs& a, float (*g
     }
   }
   __syncthreads();
+}
+__device__ __forceinline__ float reduce_fold(const ReduceArgs& a, float (*gsum)[RED_PARAMS], int dst) {
+  const int tid = threadIdx.x;
   float g = 0.f;
   if (tid < RED_PARAMS) {  // wave 0: fold the quarters
     g = (gsum[0][tid] + gsum[1][tid]) + (gsum[2][tid] + gsum[3][tid]);
@@ -216,9 +255,18 @@ __device__ __forceinline__ float reduce_positions(const ReduceArgs& a, float (*g
   }
   return g;
 }
-// minibatch statistics (means over the nb rows) and the KL decision, by one block (>= 256 threads); thread 0 returns `stop`
+template <int VEC, bool COH = false>
+__device__ __forceinline__ float reduce_positions(const ReduceArgs& a, float (*gsum)[RED_PARAMS], int dst, int blk) {
+  reduce_quarters<VEC, COH>(a, gsum, blk);
+  return reduce_fold(a, gsum, dst);
+}
+// minibatch statistics (means over the nb rows) and the KL decision, by one block (>= 256 threads); thread 0 returns `stop`.
+// zero_norm: this block also clears the gradient-norm slot (stats_out[6]), which a LATER launch fills (ppo_adam_kernel).  The fused
+// launch passes false: there block 0 stores the norm in the same launch, and two blocks storing to one word with nothing ordering
+// them left whichever store landed last -- at some grid sizes the zero (tests/test_gpu_step_chain.py, canonical slabs).
 template <bool COH = false>
-__device__ __forceinline__ bool reduce_statistics(const ReduceArgs& a, float (*part)[NSTATP], float* means, bool bump_step) {
+__device__ __forceinline__ bool reduce_statistics(const ReduceArgs& a, float (*part)[NSTATP], float* means, bool bump_step,
+                                                  bool zero_norm = true) {
   const int tid = threadIdx.x;
   bool stop = false;
   if (tid < 256) {  // 32 lanes per statistic, strided over the workgroup partials, then a fixed-order fold
@@ -264,7 +312,7 @@ __device__ __forceinline__ bool reduce_statistics(const ReduceArgs& a, float (*p
       a.stats_out[3] = cf;
       a.stats_out[4] = kl;
       a.stats_out[5] = pl_ + a.ent_coef * el + a.vf_coef * vl;
-      a.stats_out[6] = 0.f;
+      if (zero_norm) a.stats_out[6] = 0.f;
       a.stats_out[7] = stop ? 0.f : 1.f;
     }
     if (a.n_extra > 0) {   // raw additional term of this minibatch (adap_learn.py:313-320: loss += coeff * context_loss)
@@ -330,7 +378,10 @@ __device__ __forceinline__ void step_finish(const StepArgs& s, int nblk, unsigne
       atomicAdd(s.sweep_error, 1u);
       // (the generation is left alone: every later launch of this context bails out on *sweep_error before it sweeps --
       // ppo_step_kernel -- so words this launch's late blocks still publish are never taken for a later launch's)
-      if (first && a.stats_out) a.stats_out[7] = -1.f;
+      if (first && a.stats_out) {
+        a.stats_out[6] = 0.f;
+        a.stats_out[7] = -1.f;
+      }
     }
     return;
   }
@@ -358,7 +409,7 @@ __device__ __forceinline__ void step_finish(const StepArgs& s, int nblk, unsigne
     if (!stop && ad.step) *const_cast<int*>(ad.step) = step_new;
     if (stop) *a.stop_flag = 1;
     *s.gen = tag;
-    if (!stop && a.stats_out) a.stats_out[6] = total;
+    if (a.stats_out) a.stats_out[6] = stop ? 0.f : total;   // the only store to this slot in the launch
   }
   if (stop || dst < 0) return;
   {
@@ -413,7 +464,7 @@ __device__ __forceinline__ void step_body(const StepArgs& s, int blk, int nblk, 
   const int tid = threadIdx.x;
   if (blk == nblk) {   // the extra block: statistics + KL decision while the slab blocks reduce; its word carries `stop`
     if (step_refused(a, blk, stopped, err)) return;
-    const bool stop = reduce_statistics<COH>(a, part, means, false);
+    const bool stop = reduce_statistics<COH>(a, part, means, false, false);   // (the norm slot is block 0's: step_finish)
     if (tid == 0)
       __hip_atomic_store(s.words + nblk, ((unsigned long long)tag << 32) | (stop ? 1ull : 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
