@@ -12,6 +12,7 @@
 // the engine's own definitions (ph_device.h), shared with every other kernel, so the rollout's log-probabilities and the
 // update's agree as they do for MlpPolicy.  Sampling, log-prob and the fused RolloutBuffer.add are ph_rowtail.h's row tails.
 #include "ph_launch.h"
+#include "ph_ppo_loss.h"
 #include "ph_rowtail.h"
 
 namespace ph {
@@ -302,24 +303,12 @@ __global__ __launch_bounds__(256) void am_loss_pi_kernel(const float* __restrict
       ent -= fast_exp(lp) * lp;
     }
     const float logp = zr[a] - lse;
-    const float av = adv[r], lr = logp - oldlp[r], ratio = fast_exp(lr);
-    const float lo_c = 1.0f - clip, hi_c = 1.0f + clip;
-    const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-    const float pl1 = av * ratio, pl2 = av * rc;
-    // torch.min backward: the smaller branch gets the gradient, ties split 1/2 + 1/2; clamp passes it iff lo <= ratio <= hi
-    const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-    const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);
-    const float g_lp = -inv_nb * av * ratio * gate;   // dL/dlogp
-    const float g_en = -ent_coef * inv_nb;             // dL/dH
-    st[0] += -fminf(pl1, pl2);
-    st[2] += -ent;
-    st[3] += (fabsf(ratio - 1.0f) > clip) ? 1.f : 0.f;
-    st[4] += (ratio - 1.0f) - lr;
+    const float av = adv[r];
+    const PolicyRow pl = ppo_policy_row(logp, oldlp[r], av, clip, ent_coef, inv_nb);
+    ppo_policy_stats(st, pl, ent);
     for (int k = 0; k < L; ++k) {
-      const float lp = zr[k] - lse, p = fast_exp(lp);
-      const float dlogp = ((k == a) ? 1.f : 0.f) - p;
-      const float dent = -p * (lp + ent);
-      dz[(size_t)r * L + k] = g_lp * dlogp + g_en * dent;
+      const float lp = zr[k] - lse;
+      dz[(size_t)r * L + k] = ppo_logit_grad(pl.g_lp, pl.g_en, (k == a) ? 1.f : 0.f, fast_exp(lp), lp, ent);
     }
   }
   // block sums in a fixed order: lanes by shuffles, waves through LDS
@@ -343,15 +332,10 @@ __global__ __launch_bounds__(256) void am_loss_vf_kernel(const float* __restrict
   float s1 = 0.f;
   for (int r = r0 + tid; r < r1; r += 256) {
     const float val = v[r], old = oldv[r];
-    float vp = val, pass = 1.f;
-    if (clip_vf >= 0.f) {   // adap_learn.py:288-298
-      const float dlt = val - old;
-      pass = (dlt >= -clip_vf && dlt <= clip_vf) ? 1.f : 0.f;
-      vp = old + fminf(fmaxf(dlt, -clip_vf), clip_vf);
-    }
-    const float err = vp - ret[r];
-    s1 += err * err;
-    dv[r] = vf_coef * 2.0f * err * inv_nb * pass;
+    const ValueClip vc = ppo_value_clip(val, old, clip_vf);   // adap_learn.py:288-298
+    const ValueRow vr = ppo_value_row(vc, ret[r], vf_coef, inv_nb);
+    s1 += vr.err * vr.err;
+    dv[r] = vr.dv();
   }
   for (int off = 32; off > 0; off >>= 1) s1 += __shfl_down(s1, off, 64);
   if ((tid & 63) == 0) sh[tid >> 6] = s1;

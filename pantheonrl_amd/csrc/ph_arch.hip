@@ -11,6 +11,7 @@
 // floats in parameter order, so the reduce / clip / Adam launches of the 64-wide path take them unchanged.
 #include "ph_rowtail.h"
 #include "ph_arch.h"
+#include "ph_ppo_loss.h"
 
 namespace ph {
 
@@ -188,70 +189,6 @@ __device__ __forceinline__ void head_logits(float* smem, const ArchLds& S, const
   __syncthreads();
 }
 
-// Clipped-surrogate + entropy loss of one minibatch row, one lane per row: dL/dlogits over z[0..Lp), partial statistics into st.
-// The arithmetic of ppo_grad_kernel's one-lane-per-row head phase (SB3 PPO.train, adap_learn.py:253-344).
-__device__ __forceinline__ void policy_loss_row(const GradArgs& a, const NetDims& nd, float* z, int phys, float adv, float oldlp,
-                                                float inv_nb, float (&st)[NSTATP]) {
-  const int Lp = nd.Lp;
-  if (phys < 0) {
-    for (int k = 0; k < Lp; ++k) z[k] = 0.f;
-    return;
-  }
-  float logp = 0.f, ent = 0.f;
-  for (int c = 0; c < nd.A; ++c) {
-    const int lo = nd.act_off[c], nk = nd.act_off[c + 1] - lo;
-    float m = z[lo];
-    for (int k = 1; k < nk; ++k) m = fmaxf(m, z[lo + k]);
-    float se = 0.f;
-    for (int k = 0; k < nk; ++k) se += fast_exp(z[lo + k] - m);
-    const float lse = m + fast_log(se);
-    int act = (int)a.rb_act[(size_t)phys * nd.A + c];
-    act = act < 0 ? 0 : (act >= nk ? nk - 1 : act);
-    float e = 0.f;
-    for (int k = 0; k < nk; ++k) {
-      const float lp = z[lo + k] - lse;
-      e -= fast_exp(lp) * lp;
-    }
-    logp += z[lo + act] - lse;
-    ent += e;
-  }
-  const float lr = logp - oldlp;
-  const float ratio = fast_exp(lr);
-  const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
-  const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-  const float pl1 = adv * ratio, pl2 = adv * rc;
-  // torch.min backward: the smaller branch gets the gradient, ties split 1/2 + 1/2; clamp passes the gradient iff lo <= ratio <= hi
-  const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-  const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);
-  const float g_lp = -inv_nb * adv * ratio * gate;   // dL/dlogp
-  const float g_en = -a.ent_coef * inv_nb;            // dL/dH
-  st[0] += -fminf(pl1, pl2);
-  st[2] += -ent;
-  st[3] += (fabsf(ratio - 1.0f) > a.clip) ? 1.f : 0.f;
-  st[4] += (ratio - 1.0f) - lr;
-  for (int c = 0; c < nd.A; ++c) {
-    const int lo = nd.act_off[c], nk = nd.act_off[c + 1] - lo;
-    float m = z[lo];
-    for (int k = 1; k < nk; ++k) m = fmaxf(m, z[lo + k]);
-    float se = 0.f;
-    for (int k = 0; k < nk; ++k) se += fast_exp(z[lo + k] - m);
-    const float lse = m + fast_log(se);
-    int act = (int)a.rb_act[(size_t)phys * nd.A + c];
-    act = act < 0 ? 0 : (act >= nk ? nk - 1 : act);
-    float hc = 0.f;
-    for (int k = 0; k < nk; ++k) {
-      const float lp = z[lo + k] - lse;
-      hc -= fast_exp(lp) * lp;
-    }
-    for (int k = 0; k < nk; ++k) {
-      const float lp = z[lo + k] - lse;
-      const float p = fast_exp(lp);
-      z[lo + k] = g_lp * (((k == act) ? 1.f : 0.f) - p) + g_en * (-p * (lp + hc));
-    }
-  }
-  for (int k = nd.L; k < Lp; ++k) z[k] = 0.f;
-}
-
 }  // namespace
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
@@ -420,7 +357,15 @@ __global__ __launch_bounds__(TNT) void tower_grad_kernel(GradArgs a, ArchDims ad
 
     if (net == 0) {
       head_logits<R, VALU>(smem, S, a.params, ad, nd, tid);
-      if (tid < R) policy_loss_row(a, nd, outs + tid * LDO, rowphys[tid], radv[tid], rold[tid], inv_nb, st);
+      if (tid < R) {   // one lane per row: dL/dlogits over the row's logits, partial statistics into st
+        float* z = outs + tid * LDO;
+        const int phys = rowphys[tid];
+        if (phys < 0) {
+          for (int k = 0; k < Lp; ++k) z[k] = 0.f;
+        } else {
+          ppo_two_pass_row(nd, z, a.rb_act, phys, radv[tid], rold[tid], a.clip, a.ent_coef, inv_nb, st, Lp);
+        }
+      }
       __syncthreads();
       // d act_W = H_n^T dOut (tiles w_n/32 x Lp/32), d act_b = column sums of dOut
       for (int t = wave; t < (wn >> 5) * ntn; t += 4) {
@@ -473,15 +418,9 @@ __global__ __launch_bounds__(TNT) void tower_grad_kernel(GradArgs a, ArchDims ad
           for (int j = 0; j < wn; ++j) v = __builtin_fmaf(Hn[tid * ldh + j], bos[j], v);
           v += a.params[ad.lay.val_b];
           const float retn = radv[tid], oldv = rold[tid];
-          float vp = v, pass = 1.f;
-          if (a.clip_vf >= 0.f) {
-            const float dlt = v - oldv;
-            pass = (dlt >= -a.clip_vf && dlt <= a.clip_vf) ? 1.f : 0.f;
-            vp = oldv + fminf(fmaxf(dlt, -a.clip_vf), a.clip_vf);
-          }
-          const float err = vp - retn;
-          st[1] += err * err;
-          dv = a.vf_coef * 2.0f * err * inv_nb * pass;
+          const ValueRow vr = ppo_value_row(v, oldv, retn, a.clip_vf, a.vf_coef, inv_nb);
+          st[1] += vr.err * vr.err;
+          dv = vr.dv();
         }
         rdv[tid] = dv;
       }

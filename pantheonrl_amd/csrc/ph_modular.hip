@@ -20,6 +20,7 @@
 // product.  LDS budget and buffer rotation are the fast kernel's (72.6 KB, two workgroups per CU; X and W1 are fetched a second
 // time per backward tile under the tile's products); it has no cross-tile prefetch.
 #include "ph_head.h"
+#include "ph_ppo_loss.h"
 #include "ph_rowtail.h"
 
 namespace ph {
@@ -483,39 +484,22 @@ __global__ __launch_bounds__(256) void modular_loss_kernel(ModLossArgs a) {
     // advantages are ALWAYS normalised (learn.py:260-261: no normalize_advantage switch, no len > 1 guard)
     const float adv = (a.rb_adv[phys] - a.advstats[0]) / (a.advstats[1] + 1e-8f);
     const float oldlp = a.rb_logp[phys];
-    const float lr = logp - oldlp;
-    const float ratio = fast_exp(lr);
-    const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
-    const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-    const float pl1 = adv * ratio, pl2 = adv * rc;
-    const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-    const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);   // torch.min / clamp backward
     const float inv_nb = 1.0f / (float)a.nb;
-    const float g_lp = -inv_nb * adv * ratio * gate;
-    const float g_en = -a.ent_coef * inv_nb;
+    const PolicyRow pl = ppo_policy_row(logp, oldlp, adv, a.clip, a.ent_coef, inv_nb);
     float dzp[8];   // dL_ppo / d composed logits
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float dlogp = ((k == act) ? 1.f : 0.f) - pr[k];
-      const float dent = -pr[k] * ((z[k] - lse) + ent);
-      dzp[k] = (k < nk) ? g_lp * dlogp + g_en * dent : 0.f;
-    }
-    st[0] = -fminf(pl1, pl2);
+    for (int k = 0; k < 8; ++k)
+      dzp[k] = (k < nk) ? ppo_logit_grad(pl.g_lp, pl.g_en, (k == act) ? 1.f : 0.f, pr[k], z[k] - lse, ent) : 0.f;
+    st[0] = pl.loss();
     st[2] = -ent;
-    st[3] = (fabsf(ratio - 1.0f) > a.clip) ? 1.f : 0.f;
+    st[3] = pl.clipped();
     st[4] = oldlp - logp;                       // learn.py:327: plain mean(old_log_prob - log_prob)
     // ---- value term on the summed value (policies.py:286) ----
     const float v = a.vm[gi] + a.vk[gi];
     const float retn = a.rb_ret[phys], oldv = a.rb_val[phys];
-    float vp = v, pass = 1.f;
-    if (a.clip_vf >= 0.f) {
-      const float dlt = v - oldv;
-      pass = (dlt >= -a.clip_vf && dlt <= a.clip_vf) ? 1.f : 0.f;
-      vp = oldv + fminf(fmaxf(dlt, -a.clip_vf), a.clip_vf);
-    }
-    const float err = vp - retn;
-    st[1] = err * err;
-    a.dv[gi] = a.vf_coef * 2.0f * err * inv_nb * pass;
+    const ValueRow vr = ppo_value_row(v, oldv, retn, a.clip_vf, a.vf_coef, inv_nb);
+    st[1] = vr.err * vr.err;
+    a.dv[gi] = vr.dv();
     // ---- marginal regulariser (learn.py:298-318): | softmax(z_main) - mean_j softmax(z_main + z_j) | summed over actions.
     // Modules shared by several partners (baseline) enter with their multiplicity / num_partners.
     float pm[8], lsem;

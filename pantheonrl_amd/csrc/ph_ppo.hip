@@ -12,6 +12,7 @@
 // is initialised from the slab, so the add is free); a second kernel sums the slabs in a fixed order
 // (deterministic), a third applies clip_grad_norm_ + Adam.
 #include "ph_launch.h"
+#include "ph_ppo_loss.h"
 #include "ph_split.h"
 #include "ph_step.h"
 
@@ -410,24 +411,11 @@ __global__ __launch_bounds__(R * 4, 2) void ppo_grad_kernel(GradArgs a) {
               ent += hen[hrow * 4 + c];
             }
             const float adv = radv[hrow];
-            const float lr = logp - rold[hrow];
-            const float ratio = fast_exp(lr);
-            const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
-            const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-            const float pl1 = adv * ratio, pl2 = adv * rc;
-            const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-            const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);   // torch.min / clamp backward
-            const float g_lp = -inv_nb * adv * ratio * gate;
-            const float g_en = -a.ent_coef * inv_nb;
-            if (hcomp == 0) {
-              st[0] += -fminf(pl1, pl2);
-              st[2] += -ent;
-              st[3] += (fabsf(ratio - 1.0f) > a.clip) ? 1.f : 0.f;
-              st[4] += (ratio - 1.0f) - lr;
-            }
+            const PolicyRow pl = ppo_policy_row(logp, rold[hrow], adv, a.clip, a.ent_coef, inv_nb);
+            if (hcomp == 0) ppo_policy_stats(st, pl, ent);
 #pragma unroll
             for (int k = 0; k < 16; ++k)
-              if (k < nk) zrow[lo + k] = g_lp * (((k == act) ? 1.f : 0.f) - pc[k]) + g_en * (-pc[k] * (zc[k] + hc));
+              if (k < nk) zrow[lo + k] = ppo_logit_grad(pl.g_lp, pl.g_en, (k == act) ? 1.f : 0.f, pc[k], zc[k], hc);
           }
         }
         if (tid < R)
@@ -451,19 +439,9 @@ __global__ __launch_bounds__(R * 4, 2) void ppo_grad_kernel(GradArgs a) {
             ent += 1.41893853320467274178f + lsd;
           }
           const float adv = radv[tid];
-          const float lr = logp - rold[tid];
-          const float ratio = fast_exp(lr);
-          const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
-          const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-          const float pl1 = adv * ratio, pl2 = adv * rc;
-          const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-          const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);
-          const float g_lp = -inv_nb * adv * ratio * gate;
-          const float g_en = -a.ent_coef * inv_nb;
-          st[0] += -fminf(pl1, pl2);
-          st[2] += -ent;
-          st[3] += (fabsf(ratio - 1.0f) > a.clip) ? 1.f : 0.f;
-          st[4] += (ratio - 1.0f) - lr;
+          const PolicyRow pl = ppo_policy_row(logp, rold[tid], adv, a.clip, a.ent_coef, inv_nb);
+          const float g_lp = pl.g_lp, g_en = pl.g_en;
+          ppo_policy_stats(st, pl, ent);
           for (int k = nd.A; k < Lp; ++k) z[k] = 0.f;
           for (int c = 0; c < nd.A; ++c) {
             const float is = fast_exp(-ls[c]);
@@ -501,88 +479,14 @@ __global__ __launch_bounds__(R * 4, 2) void ppo_grad_kernel(GradArgs a) {
           }
           const float logp = zact - lse;
           const float adv = radv[tid];
-          const float lr = logp - rold[tid];
-          const float ratio = fast_exp(lr);
-          const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
-          const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-          const float pl1 = adv * ratio, pl2 = adv * rc;
-          const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-          const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);
-          const float g_lp = -inv_nb * adv * ratio * gate;
-          const float g_en = -a.ent_coef * inv_nb;
-          st[0] += -fminf(pl1, pl2);
-          st[2] += -ent;
-          st[3] += (fabsf(ratio - 1.0f) > a.clip) ? 1.f : 0.f;
-          st[4] += (ratio - 1.0f) - lr;
+          const PolicyRow pl = ppo_policy_row(logp, rold[tid], adv, a.clip, a.ent_coef, inv_nb);
+          ppo_policy_stats(st, pl, ent);
 #pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            if (k < nk) {
-              const float dlogp = ((k == act) ? 1.f : 0.f) - pr[k];
-              const float dent = -pr[k] * ((zr[k] - lse) + ent);
-              z[k] = g_lp * dlogp + g_en * dent;
-            }
-          }
+          for (int k = 0; k < 8; ++k)
+            if (k < nk) z[k] = ppo_logit_grad(pl.g_lp, pl.g_en, (k == act) ? 1.f : 0.f, pr[k], zr[k] - lse, ent);
           for (int k = nk; k < Lp; ++k) z[k] = 0.f;
         } else {
-          float logp = 0.f, ent = 0.f;
-          // pass 1: log-prob and entropy (MultiDiscrete: sums over components)
-          for (int c = 0; c < nd.A; ++c) {
-            const int lo = nd.act_off[c], nk = nd.act_off[c + 1] - lo;
-            float m = z[lo];
-            for (int k = 1; k < nk; ++k) m = fmaxf(m, z[lo + k]);
-            float se = 0.f;
-            for (int k = 0; k < nk; ++k) se += fast_exp(z[lo + k] - m);
-            const float lse = m + fast_log(se);
-            int act = (int)a.rb_act[(size_t)phys * nd.A + c];
-            act = act < 0 ? 0 : (act >= nk ? nk - 1 : act);
-            float e = 0.f;
-            for (int k = 0; k < nk; ++k) {
-              const float lp = z[lo + k] - lse;
-              e -= fast_exp(lp) * lp;
-            }
-            logp += z[lo + act] - lse;
-            ent += e;
-          }
-          const float adv = radv[tid];
-          const float lr = logp - rold[tid];
-          const float ratio = fast_exp(lr);
-          const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
-          const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-          const float pl1 = adv * ratio, pl2 = adv * rc;
-          // torch.min backward: the smaller branch gets the gradient, ties split 1/2 + 1/2; clamp passes the
-          // gradient iff lo <= ratio <= hi.
-          const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-          const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);
-          const float g_lp = -inv_nb * adv * ratio * gate;   // dL/dlogp
-          const float g_en = -a.ent_coef * inv_nb;            // dL/dH
-          st[0] += -fminf(pl1, pl2);
-          st[2] += -ent;
-          st[3] += (fabsf(ratio - 1.0f) > a.clip) ? 1.f : 0.f;
-          st[4] += (ratio - 1.0f) - lr;
-          // pass 2: dL/dz
-          for (int c = 0; c < nd.A; ++c) {
-            const int lo = nd.act_off[c], nk = nd.act_off[c + 1] - lo;
-            float m = z[lo];
-            for (int k = 1; k < nk; ++k) m = fmaxf(m, z[lo + k]);
-            float se = 0.f;
-            for (int k = 0; k < nk; ++k) se += fast_exp(z[lo + k] - m);
-            const float lse = m + fast_log(se);
-            int act = (int)a.rb_act[(size_t)phys * nd.A + c];
-            act = act < 0 ? 0 : (act >= nk ? nk - 1 : act);
-            float hc = 0.f;
-            for (int k = 0; k < nk; ++k) {
-              const float lp = z[lo + k] - lse;
-              hc -= fast_exp(lp) * lp;
-            }
-            for (int k = 0; k < nk; ++k) {
-              const float lp = z[lo + k] - lse;
-              const float p = fast_exp(lp);
-              const float dlogp = ((k == act) ? 1.f : 0.f) - p;
-              const float dent = -p * (lp + hc);
-              z[lo + k] = g_lp * dlogp + g_en * dent;
-            }
-          }
-          for (int k = nd.L; k < Lp; ++k) z[k] = 0.f;
+          ppo_two_pass_row(nd, z, a.rb_act, phys, radv[tid], rold[tid], a.clip, a.ent_coef, inv_nb, st, Lp);
         }
       }
       __syncthreads();
@@ -642,15 +546,9 @@ __global__ __launch_bounds__(R * 4, 2) void ppo_grad_kernel(GradArgs a) {
           v = lds_coldot<HID>(bufA + tid * LDH, 1, bos, 1, v);
           v += a.params[lay.val_b];
           const float retn = radv[tid], oldv = rold[tid];
-          float vp = v, pass = 1.f;
-          if (a.clip_vf >= 0.f) {
-            const float dlt = v - oldv;
-            pass = (dlt >= -a.clip_vf && dlt <= a.clip_vf) ? 1.f : 0.f;
-            vp = oldv + fminf(fmaxf(dlt, -a.clip_vf), a.clip_vf);
-          }
-          const float err = vp - retn;
-          st[1] += err * err;
-          dv = a.vf_coef * 2.0f * err * inv_nb * pass;
+          const ValueRow vr = ppo_value_row(v, oldv, retn, a.clip_vf, a.vf_coef, inv_nb);
+          st[1] += vr.err * vr.err;
+          dv = vr.dv();
         }
         rdv[tid] = dv;
       }

@@ -30,6 +30,7 @@
 // index arithmetic, no split, no 4-byte gathers in the 40 launches.
 // Bias gradients are MFMAs with an all-ones A operand on the B fragments already in registers; layer 1's bias rides as
 // feature 63 (FOLD) as in the f32 kernel.  3 x 24 KB of planes + 5.8 KB of head state = 79.7 KB -> two workgroups per CU.
+#include "ph_ppo_loss.h"
 #include "ph_split_tile.h"
 
 // Settled by same-box A/B (CHANGELOG round 3 / 4), no longer switches:
@@ -371,31 +372,16 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_split_kernel(GradArgs a) {
         }
         const float logp = zact - lse;
         const float adv = radv[r];
-        const float lr = logp - rold[r];
-        const float ratio = fast_exp(lr);
-        const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
-        const float rc = fminf(fmaxf(ratio, lo_c), hi_c);
-        const float pl1 = adv * ratio, pl2 = adv * rc;
-        const float inr = (ratio >= lo_c && ratio <= hi_c) ? 1.f : 0.f;
-        const float gate = (pl1 < pl2) ? 1.f : ((pl1 > pl2) ? inr : 0.5f + 0.5f * inr);
+        const PolicyRow pl = ppo_policy_row(logp, rold[r], adv, a.clip, a.ent_coef, inv_nb);
         const float live = valid ? 1.f : 0.f;
-        const float g_lp = -inv_nb * adv * ratio * gate * live;
-        const float g_en = -a.ent_coef * inv_nb * live;
-        if (valid && q == 0) {
-          st[0] += -fminf(pl1, pl2);
-          st[2] += -ent;
-          st[3] += (fabsf(ratio - 1.0f) > a.clip) ? 1.f : 0.f;
-          st[4] += (ratio - 1.0f) - lr;
-        }
+        const float g_lp = pl.g_lp * live;
+        const float g_en = pl.g_en * live;
+        if (valid && q == 0) ppo_policy_stats(st, pl, ent);
         float dz[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) dz[k] = 0.f;
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
-          const float dlogp = ((k == act) ? 1.f : 0.f) - pr[k];
-          const float dent = -pr[k] * ((z[k] - lse) + ent);
-          dz[k] = g_lp * dlogp + g_en * dent;
-        }
+        for (int k = 0; k < NK; ++k) dz[k] = ppo_logit_grad(g_lp, g_en, (k == act) ? 1.f : 0.f, pr[k], z[k] - lse, ent);
         if (q == 0) {
           float4* o = reinterpret_cast<float4*>(dzs + r * 8);
           o[0] = make_float4(dz[0], dz[1], dz[2], dz[3]);
@@ -428,15 +414,9 @@ __global__ __launch_bounds__(256, 2) void ppo_grad_split_kernel(GradArgs a) {
         }
         v = quad_sum(v) + hbs[0];
         const float retn = radv[r], oldv = rold[r];
-        float vp = v, pass = 1.f;
-        if (a.clip_vf >= 0.f) {
-          const float dlt = v - oldv;
-          pass = (dlt >= -a.clip_vf && dlt <= a.clip_vf) ? 1.f : 0.f;
-          vp = oldv + fminf(fmaxf(dlt, -a.clip_vf), a.clip_vf);
-        }
-        const float err = vp - retn;
-        const float dv = valid ? a.vf_coef * 2.0f * err * inv_nb * pass : 0.f;
-        if (valid && q == 0) st[1] += err * err;
+        const ValueRow vr = ppo_value_row(v, oldv, retn, a.clip_vf, a.vf_coef, inv_nb);
+        const float dv = valid ? vr.dv() : 0.f;
+        if (valid && q == 0) st[1] += vr.err * vr.err;
         if (q == 0) dzs[r] = dv;
 #pragma unroll
         for (int m = 0; m < 16; ++m) dzv[m] = dv * wv[m] * (1.0f - h[m] * h[m]);

@@ -28,6 +28,7 @@
 // head gradients accumulate in registers across a workgroup's tiles; dW1's NCH x 4 blocks go straight to the slab (first tile:
 // stored; later tiles: re-loaded as the accumulator -- a minibatch of this shape class is one tile per workgroup: 8 192 rows =
 // 128 tiles per net).  Slabs are in accumulator order (grad_slab_map_split_oh); 103 KB of LDS at NCH = 5: one workgroup per CU.
+#include "ph_ppo_loss.h"
 #include "ph_split_tile.h"
 
 namespace ph {
@@ -523,6 +524,9 @@ __global__ __launch_bounds__(256, 1) void ppo_grad_split_oh_kernel(GradArgs a) {
           ent += hc;
         }
         const float adv = radv[row];
+        // The surrogate of ph_ppo_loss.h's ppo_policy_row, written out: the ONE kernel that does not call it.  At 384-432 VGPRs the
+        // register allocation of this kernel moved (by 1-2 VGPRs in five instantiations) when these locals lived in the helper; a
+        // change to the loss in ph_ppo_loss.h must be repeated here (tests/test_loss_single_definition.py names this exception).
         const float lr = logp - rold[row];
         const float ratio = fast_exp(lr);
         const float lo_c = 1.0f - a.clip, hi_c = 1.0f + a.clip;
@@ -542,20 +546,14 @@ __global__ __launch_bounds__(256, 1) void ppo_grad_split_oh_kernel(GradArgs a) {
         for (int lb = 0; lb < LB; ++lb)
 #pragma unroll
           for (int r = 0; r < 4; ++r)   // logits outside every component (padding): P = isa = 0 -> dz = 0
-            dz[lb][r] = g_lp * (isa[lb][r] - P[lb][r]) + g_en * (-P[lb][r] * (lp[lb][r] + hce[lb][r]));
+            dz[lb][r] = ppo_logit_grad(g_lp, g_en, isa[lb][r], P[lb][r], lp[lb][r], hce[lb][r]);
       } else {
         // value: the one "logit" is v (lane kg == 0, register 0 of block 0)
         const float v = z[0][0];
         const float retn = radv[row], oldv = rold[row];
-        float vp = v, pass = 1.f;
-        if (a.clip_vf >= 0.f) {
-          const float dlt = v - oldv;
-          pass = (dlt >= -a.clip_vf && dlt <= a.clip_vf) ? 1.f : 0.f;
-          vp = oldv + fminf(fmaxf(dlt, -a.clip_vf), a.clip_vf);
-        }
-        const float err = vp - retn;
-        if (valid && kg == 0) st[1] += err * err;
-        dz[0][0] = (valid && kg == 0) ? a.vf_coef * 2.0f * err * inv_nb * pass : 0.f;
+        const ValueRow vr = ppo_value_row(v, oldv, retn, a.clip_vf, a.vf_coef, inv_nb);
+        if (valid && kg == 0) st[1] += vr.err * vr.err;
+        dz[0][0] = (valid && kg == 0) ? vr.dv() : 0.f;
       }
       const int sw = dzl_swz(row);
 #pragma unroll

@@ -16,11 +16,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_SOURCES = ("pantheonrl_amd/csrc/ph_ppo_split.hip", "pantheonrl_amd/csrc/ph_split_tile.h", "pantheonrl_amd/csrc/ph_split.h",
-                  "pantheonrl_amd/csrc/ph_head.h", "pantheonrl_amd/csrc/ph_device.h", "pantheonrl_amd/csrc/ph_launch.h:struct GradArgs")
+                  "pantheonrl_amd/csrc/ph_head.h", "pantheonrl_amd/csrc/ph_device.h", "pantheonrl_amd/csrc/ph_ppo_loss.h",
+                  "pantheonrl_amd/csrc/ph_launch.h:struct GradArgs")
 
 
 def kernel_source_sha256(root: str = ROOT) -> str:
-    """hash of what ppo_grad_split_kernel (the default gradient kernel of the bench workload, gemm_mode 2) is compiled from: its translation unit, the two headers with its device code, and its
+    """hash of what ppo_grad_split_kernel (the default gradient kernel of the bench workload, gemm_mode 2) is compiled from: its translation unit, the headers with its device code (the row loss of ph_ppo_loss.h among them), and its
     argument record (the rest of ph_launch.h -- other kernels' records and launcher prototypes -- does not enter)"""
     h = hashlib.sha256()
     for rel in KERNEL_SOURCES:

@@ -1,4 +1,4 @@
-"""The off-policy cases of the gradient tests: every copy of the PPO row-loss tail on a STALE buffer.
+"""The off-policy cases of the gradient tests: every caller of the row loss (ph_ppo_loss.h) on a STALE buffer.
 
 In the older single-minibatch gradient tests the policy under differentiation is the policy that filled the buffer, so ratio == 1 and
 v == old_v on every row: only the tie arm of the policy gate and only `pass = 1` of the value clip ever run.  Here a drifted copy of
@@ -22,7 +22,7 @@ counting clip_fraction with the wrong range changes the count.  Half the cases r
 the rest the defaults (Modular's loss always normalises); every case sets clip_range_vf; every second one has a minibatch that is no
 multiple of the 64-row tile.
 
-Which kernel (which copy of the tail) each case lands on -- read off launch_ppo_grad / grad_fast_eligible / select_gemm
+Which kernel (which caller of the row loss) each case lands on -- read off launch_ppo_grad / grad_fast_eligible / select_gemm
 (ph_ppo.hip, ph_ppo_fast.hip, ph_abi.hip), ph_arch.hip, ph_modular.hip, ph_adap.hip, ph_adapmult.hip -- is the `kernel` field."""
 from __future__ import annotations
 

@@ -1,4 +1,4 @@
-"""-m gpu: every copy of the PPO row-loss tail OFF-policy -- live ratio clip, live value clip -- against float32 autograd of the
+"""-m gpu: every caller of the row loss (ph_ppo_loss.h) OFF-policy -- live ratio clip, live value clip -- against float32 autograd of the
 checker's own loss, once per case of tests/offpolicy_cases.py and through the same ph_*_minibatch_grad entry points (and the same
 _grad_pair functions) as each family's on-policy gradient test.
 
