@@ -624,6 +624,53 @@ typedef struct ph_liar_pool {
  * replays against the table uploaded last, so pools that are replayed from graphs should not share a context. */
 int ph_liar_pool_step(ph_ctx *ctx, const ph_liar_pool *pool, int ego_pos, unsigned long long counter, int deal_only);
 
+/* ---- cross-play evaluation of Liar's Dice (csrc/ph_xplay.h; additions, PH_ABI_VERSION unchanged): tester.py:41-63 -- play a
+ * fixed ego against a fixed partner for a number of games and report the ego's returns -- for n tables at once.  BOTH seats are
+ * held by members of one table of 1..PH_MAX_POOL frozen / scripted members (a learner is refused): table e plays the ordered pair
+ * pairs[e % n_pairs] = (seat 0, seat 1) for the whole evaluation, exactly episodes_per_table games, and then goes idle: it is
+ * masked out of every forward and pass, and its state and logs do not change again.  A game's return is the sum of the ego rewards
+ * MultiAgentEnv.step returns over the game (the ego's own transition plus the reply's, multiagentenv.py:201-202), accumulated in
+ * f32; its length is the number of ego moves.  RNG counters of step c >= 1: seat 0's forward 3c, the reply 3c + 1, the opening
+ * 3c + 2 (each member under its own seed, row = table; the same member may hold both seats of a table, so the seats' counters are
+ * disjoint), dice c; the first deal uses dice counter 0 and opening counter 2. */
+typedef struct ph_liar_xplay {
+  int n;
+  const ph_spec *spec;
+  int *hands, *history, *nmoves;
+  unsigned char *ego_first;
+  unsigned long long dice_seed;
+  float probegostart;
+  const ph_pool_member *members;             /* host array [n_members]: PH_POOL_FROZEN / PH_POOL_SCRIPTED */
+  int n_members;
+  const int *pairs;                          /* host array [n_pairs][2]: (member at seat 0, member at seat 1) */
+  int n_pairs;                               /* 1..n */
+  int episodes_per_table;                    /* G >= 1 */
+  const int *ego_id, *alt_id;                /* (n) device: pairs[e % n_pairs][0] / [1]; a table whose index is out of range does not move */
+  int *ego_actions, *alt_actions;            /* (n,2) */
+  float *obs_ego, *obs_alt;                  /* (n,30) */
+  int *games;                                /* (n) games finished */
+  unsigned char *playing;                    /* (n) 1 while games[e] < G */
+  int *tables_left;                          /* [1] tables with budget left */
+  float *ep_return;                          /* (n) return of the game in progress */
+  int *ep_length;                            /* (n) ego moves of the game in progress */
+  float *returns;                            /* (n,G) log: ego return of game g of table e */
+  int *lengths;                              /* (n,G) log: ego moves of game g of table e */
+  float *obs_next, *rew1, *rew2;             /* scratch (n,30) (n,2) (n,2) */
+  unsigned char *done1, *done2, *running, *alt_opens, *ego_opens, *done;   /* scratch (n) */
+} ph_liar_xplay;
+/* One MultiAgentEnv.step of every playing table (tester.py:41-63): grouped forward of seat 0 by ego_id, book-keeping, grouped
+ * forward of seat 1 by alt_id where the game goes on, book-keeping (end of game: log, games += 1, then the next deal, or
+ * tables_left -= 1 when the budget is spent), grouped forward of seat 1 where it opens, book-keeping: 9 launches.  deal_only: the
+ * first deal of the tables flagged in `done` (the caller has set games = 0, playing = 1, tables_left = n and cleared ep_return /
+ * ep_length), the openings and seat 0's first observation.  No host synchronisation; capturable once it ran outside capture (the
+ * context's one member table, see ph_liar_pool_step). */
+int ph_liar_xplay_step(ph_ctx *ctx, const ph_liar_xplay *xp, unsigned long long counter, int deal_only);
+/* The statistics tester.py:41-63 prints, per pair: stats (n_pairs,4) f64 = count, sum, sum of squares, sum of lengths over the
+ * logged games (games[e] of them) of the tables p, p + n_pairs, ... in ascending table and game order, one lane per pair, no atomics:
+ * two runs give the same bits.  Mean and population standard deviation follow on the host.  stats is 16-byte aligned. */
+int ph_xplay_stats(ph_ctx *ctx, const float *returns, const int *lengths, const int *games, int n, int episodes_per_table,
+                   int n_pairs, double *stats);
+
 /* ---- the block worlds: BlockEnv-v0 (variant 0, simpleblockworld.py:36-131) and BlockEnv-v1 (variant 1, blockworld.py:34-83,
  * gridutils.py:8-64).  The planner (ego) always moves first; the constructor is the partner.  A table is PH_BLOCK_STATE_WORDS
  * int32 words, 16-byte aligned (layout: csrc/ph_block.h).  Observations are the raw integer components as f32:

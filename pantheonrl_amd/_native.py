@@ -235,6 +235,27 @@ class PhLiarPool(C.Structure):
                 ("done1", C.c_void_p), ("done2", C.c_void_p), ("running", C.c_void_p), ("can", C.c_void_p),
                 ("alt_opens", C.c_void_p), ("ego_opens", C.c_void_p), ("done", C.c_void_p)]
 
+
+XPLAY_NSTAT = 4          # count, sum, sum of squares, sum of lengths
+
+
+class PhLiarXplay(C.Structure):
+    """ph_liar_xplay: cross-play evaluation of Liar's Dice -- both seats drawn from one member table, a game budget per table"""
+    _fields_ = [("n", C.c_int), ("spec", C.POINTER(PhSpec)),
+                ("hands", C.c_void_p), ("history", C.c_void_p), ("nmoves", C.c_void_p), ("ego_first", C.c_void_p),
+                ("dice_seed", C.c_ulonglong), ("probegostart", C.c_float),
+                ("members", C.POINTER(PhPoolMember)), ("n_members", C.c_int),
+                ("pairs", C.POINTER(C.c_int)), ("n_pairs", C.c_int), ("episodes_per_table", C.c_int),
+                ("ego_id", C.c_void_p), ("alt_id", C.c_void_p),
+                ("ego_actions", C.c_void_p), ("alt_actions", C.c_void_p),
+                ("obs_ego", C.c_void_p), ("obs_alt", C.c_void_p),
+                ("games", C.c_void_p), ("playing", C.c_void_p), ("tables_left", C.c_void_p),
+                ("ep_return", C.c_void_p), ("ep_length", C.c_void_p), ("returns", C.c_void_p), ("lengths", C.c_void_p),
+                ("obs_next", C.c_void_p), ("rew1", C.c_void_p), ("rew2", C.c_void_p),
+                ("done1", C.c_void_p), ("done2", C.c_void_p), ("running", C.c_void_p),
+                ("alt_opens", C.c_void_p), ("ego_opens", C.c_void_p), ("done", C.c_void_p)]
+
+
 SIGNATURES = {
     "ph_abi_version": [],
     "ph_roundrobin_env_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, _i],
@@ -291,6 +312,8 @@ SIGNATURES = {
     "ph_pool_forward": [_vp, C.POINTER(PhSpec), C.POINTER(PhPoolMember), _i, _vp, _vp, _vp, _ull, _vp, _vp, _i],
     "ph_liar_default_actions": [_vp, _vp, _vp, _vp, _i],
     "ph_liar_pool_step": [_vp, C.POINTER(PhLiarPool), _i, _ull, _i],
+    "ph_liar_xplay_step": [_vp, C.POINTER(PhLiarXplay), _ull, _i],
+    "ph_xplay_stats": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "ph_block_reset": [_vp, _i, _vp, _vp, _ull, _ull, _i],
     "ph_block_step": [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i],
     "ph_block_obs": [_vp, _i, _vp, _i, _vp, _vp, _i],

@@ -1,0 +1,70 @@
+"""Cross-play of a population of saved agents, every table on the device (envs/crossplay.py): every agent as the ego against
+every agent as the partner -- the M x M matrix the reference reaches only as M^2 separate runs of tester.py (tester.py:41-63).
+
+    python -m pantheonrl_amd.crossplay LiarsDice-v0 --agents models/a models/b DEFAULT --n-envs 256 -t 1000 [--out x.npz]
+
+An agent is a PPO checkpoint (64-64 MlpPolicy) or DEFAULT (the game's scripted player).  `-t` is the number of games per pair:
+table e plays pair e % P, so a pair owns at least n_envs // P tables and every table plays ceil(t / (n_envs // P)) games.  Prints
+the mean and standard-deviation matrices of the ego's return (row = ego, column = partner); `--out` writes them, with the counts,
+mean lengths and the raw logs, as an .npz."""
+from __future__ import annotations
+
+import argparse
+
+import numpy as np
+
+from . import _native as nat
+from .trainer import EnvException
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Cross-play matrix of saved agents on device-resident tables")
+    p.add_argument("env")
+    p.add_argument("--agents", nargs="+", required=True, help="PPO checkpoints, or DEFAULT for the scripted player")
+    p.add_argument("--n-envs", type=int, default=256)
+    p.add_argument("--games", "-t", type=int, default=1000, help="games per pair")
+    p.add_argument("--device", "-d", default="cuda")
+    p.add_argument("--seed", "-s", type=int, default=0)
+    p.add_argument("--probegostart", type=float, default=0.5)
+    p.add_argument("--out", help="write the matrices and logs to this .npz")
+    return p
+
+
+def plan(args) -> dict:
+    """check the arguments and size the evaluation, before a device is touched"""
+    if args.env != "LiarsDice-v0":
+        raise EnvException(f"the device-resident cross-play exists for LiarsDice-v0, not {args.env}")
+    M = len(args.agents)
+    if M > nat.PH_MAX_POOL:
+        raise EnvException(f"a population holds at most {nat.PH_MAX_POOL} agents, not {M}")
+    if args.games < 1:
+        raise EnvException("-t must be at least 1")
+    P = M * M
+    if args.n_envs < P:
+        raise EnvException(f"{M} agents make {P} pairs: --n-envs must be at least {P}, not {args.n_envs}")
+    return dict(n_members=M, n_pairs=P, episodes_per_table=-(-args.games // (args.n_envs // P)))
+
+
+def run(argv=None):
+    args = build_parser().parse_args(argv)
+    size = plan(args)
+    from .envs.crossplay import VecLiarCrossPlay
+    from .tester import load_member
+    members = [load_member("DEFAULT" if a == "DEFAULT" else "PPO", {}, a, args.device) for a in args.agents]
+    xp = VecLiarCrossPlay(args.n_envs, members, episodes_per_table=size["episodes_per_table"], seed=args.seed,
+                          probegostart=args.probegostart)
+    res = xp.run()
+    with np.printoptions(precision=4, suppress=True, linewidth=160):
+        print(f"Agents: {args.agents}")
+        print(f"Games per pair: {int(res.count.min())}..{int(res.count.max())} ({args.n_envs} tables x {xp.G} games, {res.steps} steps)")
+        print(f"Average Reward (row = ego, column = partner):\n{res.matrix('mean')}")
+        print(f"Standard Deviation:\n{res.matrix('std')}")
+    if args.out:
+        np.savez(args.out, agents=np.asarray(args.agents), mean=res.matrix("mean"), std=res.matrix("std"), count=res.matrix("count"),
+                 mean_length=res.matrix("mean_length"), returns=res.returns, lengths=res.lengths, pair_of_table=res.pair_of_table,
+                 pairs=res.pairs)
+    return res
+
+
+if __name__ == "__main__":
+    run()

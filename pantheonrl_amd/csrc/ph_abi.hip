@@ -18,6 +18,7 @@
 #include "ph_block.h"
 #include "ph_arch.h"
 #include "ph_pool.h"
+#include "ph_xplay.h"
 
 namespace ph {
 
@@ -1947,6 +1948,78 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsign
                    s.alt_actions, s.es_alt, s.n))
     return 1;
   PH_HIP(ph::launch_pool_after_opening(d, st));
+  return 0;
+}
+
+// ---- cross-play evaluation of Liar's Dice (ph_xplay.h; tester.py:41-63 over n tables) ----
+int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long counter, int deal_only) {
+  DevGuard dev_guard(ctx);
+  if (!ctx || !xp) return fail("ph_liar_xplay_step: null argument");
+  const ph_liar_xplay& s = *xp;
+  if (s.n <= 0 || !s.spec) return fail("ph_liar_xplay_step: incomplete description");
+  if (!s.hands || !s.history || !s.nmoves || !s.ego_first || !s.pairs || !s.ego_id || !s.alt_id || !s.ego_actions || !s.alt_actions ||
+      !s.obs_ego || !s.obs_alt || !s.games || !s.playing || !s.tables_left || !s.ep_return || !s.ep_length || !s.returns ||
+      !s.lengths || !s.obs_next || !s.rew1 || !s.rew2 || !s.done1 || !s.done2 || !s.running || !s.alt_opens || !s.ego_opens || !s.done)
+    return fail("ph_liar_xplay_step: incomplete description");
+  if (s.episodes_per_table < 1) return fail("ph_liar_xplay_step: episodes_per_table must be at least 1");
+  if (s.n_pairs < 1 || s.n_pairs > s.n) return fail("ph_liar_xplay_step: 1..n pairs (every pair needs a table)");
+  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
+      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
+       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
+    return fail("ph_liar_xplay_step: hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
+  if (!s.members) return fail("ph_liar_xplay_step: null member array");
+  if (s.n_members < 1 || s.n_members > PH_MAX_POOL) return fail("ph_liar_xplay_step: the population holds 1..PH_MAX_POOL members");
+  for (int k = 0; k < s.n_members; ++k)
+    if (s.members[k].kind == PH_POOL_LEARNER)
+      return fail("ph_liar_xplay_step: member " + std::to_string(k) + " is a PH_POOL_LEARNER: an evaluation seats frozen and scripted members only");
+  for (int p = 0; p < 2 * s.n_pairs; ++p)
+    if (s.pairs[p] < 0 || s.pairs[p] >= s.n_members)
+      return fail("ph_liar_xplay_step: pair " + std::to_string(p / 2) + " names a member out of range");
+  if (pool_members(ctx, "ph_liar_xplay_step", s.members, s.n_members, s.n)) return 1;
+  {
+    ph::NetDims nd;
+    if (resolve(ctx, s.spec, &nd)) return 1;
+    if (!ph::pool_fwd_eligible(nd, s.n)) return fail("ph_liar_xplay_step: the spec is not the Liar's Dice 16-row one-hot class");
+  }
+  ph::XplayStep d;
+  std::memset(&d, 0, sizeof(d));
+  d.n = s.n; d.G = s.episodes_per_table;
+  d.hands = s.hands; d.history = s.history; d.nmoves = s.nmoves; d.ego_first = s.ego_first;
+  d.dice_seed = s.dice_seed; d.probegostart = s.probegostart;
+  d.ego_actions = s.ego_actions; d.alt_actions = s.alt_actions; d.obs_ego = s.obs_ego; d.obs_alt = s.obs_alt;
+  d.games = s.games; d.playing = s.playing; d.tables_left = s.tables_left; d.ep_return = s.ep_return; d.ep_length = s.ep_length;
+  d.returns = s.returns; d.lengths = s.lengths;
+  d.obs_next = s.obs_next; d.rew1 = s.rew1; d.rew2 = s.rew2;
+  d.done1 = s.done1; d.done2 = s.done2; d.running = s.running; d.alt_opens = s.alt_opens; d.ego_opens = s.ego_opens; d.done = s.done;
+  hipStream_t st = ctx->stream;
+  const char* who = "ph_liar_xplay_step";
+  if (!deal_only) {
+    // seat 0 moves in every playing table: one grouped launch over the member table, indexed by ego_id
+    if (pool_forward(ctx, who, s.spec, s.n_members, s.obs_ego, s.ego_id, s.playing, s.playing, 3 * counter, s.ego_actions, nullptr, s.n))
+      return 1;
+    PH_HIP(ph::launch_xplay_after_ego(d, st));
+    // seat 1 replies where the game goes on: the same table, indexed by alt_id
+    if (pool_forward(ctx, who, s.spec, s.n_members, s.obs_next, s.alt_id, s.running, s.running, 3 * counter + 1, s.alt_actions, nullptr,
+                     s.n))
+      return 1;
+  }
+  PH_HIP(ph::launch_xplay_after_reply(d, counter, ctx->rng_epoch, deal_only, st));
+  if (pool_forward(ctx, who, s.spec, s.n_members, s.obs_alt, s.alt_id, s.alt_opens, s.alt_opens, 3 * counter + 2, s.alt_actions, nullptr,
+                   s.n))
+    return 1;
+  PH_HIP(ph::launch_xplay_after_opening(d, st));
+  return 0;
+}
+
+int ph_xplay_stats(ph_ctx* ctx, const float* returns, const int* lengths, const int* games, int n, int episodes_per_table, int n_pairs,
+                   double* stats) {
+  DevGuard dev_guard(ctx);
+  if (!ctx) return fail("null ctx");
+  if (!returns || !lengths || !games || !stats) return fail("ph_xplay_stats: null argument");
+  if (n <= 0 || episodes_per_table < 1) return fail("ph_xplay_stats: n and episodes_per_table must be positive");
+  if (n_pairs < 1 || n_pairs > n) return fail("ph_xplay_stats: 1..n pairs (every pair needs a table)");
+  if ((uintptr_t)stats % 16) return fail("ph_xplay_stats: stats must be 16-byte aligned");
+  PH_HIP(ph::launch_xplay_stats(returns, lengths, games, n, episodes_per_table, n_pairs, stats, ctx->stream));
   return 0;
 }
 

@@ -1,0 +1,316 @@
+"""Cross-play evaluation of Liar's Dice with every table on the device: `tester.py` of the reference (tester.py:41-63 -- play a
+loaded ego against a loaded or default partner for a number of games, print the mean and standard deviation of the ego's returns)
+for a whole population at once.
+
+`VecLiarCrossPlay` seats BOTH players of E tables from one population of M <= 8 members (`FrozenVecPartner`, `VecLiarDefaultPartner`)
+and plays a list of ordered pairs (i, j) -- member i at seat 0 (the ego), member j at seat 1 (the partner).  `crossplay_stats` is the
+host statement of the per-pair reduction `ph_xplay_stats` runs on the device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch as th
+
+from .. import _native as nat
+from ..ppo import require_mlp_kernels
+from ..spaces import make_spec
+from .vec import FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice
+
+MAX_STEPS_PER_GAME = 7       # 12 bids and a call: at most 7 moves of the ego, whoever opens
+
+
+def all_pairs(n_members: int) -> List[Tuple[int, int]]:
+    """every ordered pair (ego, partner) of the population, row major -- the diagonal included"""
+    return [(i, j) for i in range(int(n_members)) for j in range(int(n_members))]
+
+
+def check_pairs(n_envs: int, n_members: int, pairs: Optional[Sequence[Sequence[int]]]) -> np.ndarray:
+    """-> (P, 2) int32.  None = all M^2 ordered pairs; more pairs than tables, or a member out of range, is refused"""
+    if not 1 <= int(n_members) <= nat.PH_MAX_POOL:
+        raise nat.NativeError(f"cross-play: the population holds 1..{nat.PH_MAX_POOL} members, not {n_members}")
+    arr = np.asarray(all_pairs(n_members) if pairs is None else [tuple(p) for p in pairs], np.int64).reshape(-1, 2)
+    if len(arr) < 1:
+        raise nat.NativeError("cross-play: the pair list is empty")
+    if len(arr) > int(n_envs):
+        raise nat.NativeError(f"cross-play: {len(arr)} pairs need at least as many tables, not n_envs = {n_envs} (table e plays "
+                              "pairs[e % P])")
+    if arr.min() < 0 or arr.max() >= int(n_members):
+        raise nat.NativeError(f"cross-play: a pair names a member outside 0..{int(n_members) - 1}")
+    return arr.astype(np.int32)
+
+
+def pair_of_tables(n_envs: int, n_pairs: int) -> np.ndarray:
+    """table e plays pair e % P for the whole evaluation"""
+    if int(n_pairs) > int(n_envs):
+        raise nat.NativeError(f"cross-play: {n_pairs} pairs need at least as many tables, not n_envs = {n_envs}")
+    return (np.arange(int(n_envs)) % int(n_pairs)).astype(np.int32)
+
+
+def crossplay_stats(returns, lengths, pair_of_table, n_pairs: int, games=None) -> dict:
+    """The per-pair reduction in plain numpy: over a pair's tables in ascending order and each table's games in ascending order,
+    float64 count / sum / sum of squares / sum of lengths (running sums, the order `ph_xplay_stats` adds in), and from them the
+    mean, the POPULATION standard deviation (np.std, what tester.py:54 prints) and the mean length.  `games` (E): how many games
+    of each table count (None = all G)."""
+    returns, lengths = np.asarray(returns), np.asarray(lengths)
+    pair_of_table = np.asarray(pair_of_table)
+    E, G = returns.shape
+    games = np.full(E, G, np.int64) if games is None else np.clip(np.asarray(games, np.int64), 0, G)
+    out = {k: np.zeros(int(n_pairs), np.float64) for k in ("count", "sum", "sumsq", "sum_length")}
+    for p in range(int(n_pairs)):
+        tables = np.nonzero(pair_of_table == p)[0]
+        r = np.concatenate([returns[e, :games[e]] for e in tables] + [np.zeros(0)]).astype(np.float64)
+        ln = np.concatenate([lengths[e, :games[e]] for e in tables] + [np.zeros(0)]).astype(np.float64)
+        out["count"][p] = float(len(r))
+        if len(r):
+            out["sum"][p] = np.cumsum(r)[-1]
+            out["sumsq"][p] = np.cumsum(r * r)[-1]
+            out["sum_length"][p] = np.cumsum(ln)[-1]
+    out.update(derived_stats(out["count"], out["sum"], out["sumsq"], out["sum_length"]))
+    return out
+
+
+def derived_stats(count, total, sumsq, sum_length) -> dict:
+    """mean, population standard deviation and mean length from the four sums (nan where nothing was played)"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = total / count
+        std = np.sqrt(np.maximum(sumsq / count - mean * mean, 0.0))
+        return dict(mean=mean, std=std, mean_length=sum_length / count)
+
+
+class CrossPlayResult:
+    """What `VecLiarCrossPlay.run` returns: the logs, the table -> pair assignment and the per-pair statistics."""
+
+    def __init__(self, n_members, pairs, pair_of_table, returns, lengths, stats, steps):
+        self.n_members, self.pairs, self.pair_of_table = int(n_members), np.asarray(pairs), np.asarray(pair_of_table)
+        self.returns, self.lengths, self.steps = returns, lengths, int(steps)
+        self.count, self.sum, self.sumsq, self.sum_length = (stats[:, i].copy() for i in range(nat.XPLAY_NSTAT))
+        for k, v in derived_stats(self.count, self.sum, self.sumsq, self.sum_length).items():
+            setattr(self, k, v)
+
+    def matrix(self, name: str = "mean") -> np.ndarray:
+        """(M, M): entry [i, j] = statistic `name` of the pair (ego i, partner j); nan where the pair was not played (a pair
+        listed twice reports its last entry)"""
+        out = np.full((self.n_members, self.n_members), np.nan)
+        for (i, j), v in zip(self.pairs, getattr(self, name)):
+            out[i, j] = v
+        return out
+
+
+class VecLiarCrossPlay:
+    """tester.py:41-63 for a population: n_envs Liar's Dice tables resident on the device, both seats held by members of ONE
+    population of M <= 8 frozen 64-64 policies (`FrozenVecPartner`) and scripted players (`VecLiarDefaultPartner`); the same object
+    may sit in either seat, or in both.
+
+    The choices this class pins:
+    * table e plays `pairs[e % P]` = (ego member, partner member) for the whole evaluation -- no resampling; P > n_envs is refused;
+      diagonal pairs are legal; `pairs=None` is all M^2 ordered pairs, row major;
+    * every table plays exactly `episodes_per_table` games and then goes idle: masked out of every forward and pass, its state and
+      logs never change again (taking "the first N games to finish" would favour short games);
+    * one step c >= 1 is one MultiAgentEnv.step of every playing table: seat 0's forward (Philox counter 3c), its move; seat 1's
+      reply where the game goes on (3c + 1), its move and the ends of games -- log the return and length at [e, games[e]], count
+      the game, then deal the next one (dice counter c) or retire the table (`tables_left` -= 1); seat 1's opening where it
+      starts the new game (3c + 2).  The constructor's deal is step 0 (dice counter 0, opening counter 2).  A member draws under
+      its own seed with row = table, so the seats' counters are disjoint even when one member holds both;
+    * a game's return is the sum of the ego rewards MultiAgentEnv.step returns over it (the ego's transition plus the reply's),
+      accumulated in float32; its length is the number of ego moves;
+    * per pair, count / sum / sum of squares / sum of lengths are float64 sums in ascending table then game order, without
+      atomics: two runs give the same bits.
+
+    native=True: one `ph_liar_xplay_step` per step -- three bucket passes, three grouped forwards, three book-keeping launches,
+    whatever M is, no host synchronisation.  native=False: the readable walk -- per-member `ph_policy_forward` /
+    `ph_liar_default_actions`, `VecLiarsDice.player_step`, torch masks, the same counters; bitwise the native step."""
+
+    def __init__(self, n_envs: int, members, pairs=None, episodes_per_table: int = 1, seed: int = 0, probegostart: float = 0.5,
+                 native: bool = True):
+        members = list(members)
+        self.pairs = check_pairs(n_envs, len(members), pairs)
+        if int(episodes_per_table) < 1:
+            raise nat.NativeError("VecLiarCrossPlay: episodes_per_table must be at least 1")
+        self.E, self.G, self.M, self.P = int(n_envs), int(episodes_per_table), len(members), len(self.pairs)
+        self.members, self.native = members, bool(native)
+        self.dev = None
+        for m in members:
+            if isinstance(m, VecLiarDefaultPartner):
+                continue
+            if not isinstance(m, FrozenVecPartner):
+                raise nat.NativeError("VecLiarCrossPlay: members are FrozenVecPartner / VecLiarDefaultPartner (learners train in "
+                                      f"VecLiarPartnerPool), not {type(m).__name__}")
+            require_mlp_kernels(m.policy, type(self).__name__)
+            lay = m.policy.layout
+            if (lay.D, lay.A, lay.L) != (30, 2, 19):
+                raise nat.NativeError("VecLiarCrossPlay: every member plays on the Liar's Dice spaces")
+            self.dev = self.dev or m.policy.device
+        self.dev = self.dev or th.device("cuda", th.cuda.current_device())
+        self.ctx = nat.Context(self.dev.index or 0)
+        self.spec = make_spec(VecLiarsDice.observation_space, VecLiarsDice.action_space)
+        self.env = VecLiarsDice(self.E, self.ctx, self.dev)
+        self.seed, self.probegostart = int(seed), float(probegostart)
+        self.pair_of_table = pair_of_tables(self.E, self.P)
+        self._seat_members = [sorted(set(self.pairs[:, s].tolist())) for s in (0, 1)]     # who can move at seat 0 / seat 1
+        E, G, dev = self.E, self.G, self.dev
+        u8 = lambda v=0: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
+        self.ego_id = th.as_tensor(self.pairs[self.pair_of_table, 0].copy()).to(dev)
+        self.alt_id = th.as_tensor(self.pairs[self.pair_of_table, 1].copy()).to(dev)
+        self.ego_first = u8()
+        self.obs_ego = th.zeros((E, 30), dtype=th.float32, device=dev)
+        self.obs_alt = th.zeros((E, 30), dtype=th.float32, device=dev)
+        self.ego_actions = th.zeros((E, 2), dtype=th.int32, device=dev)
+        self.alt_actions = th.zeros((E, 2), dtype=th.int32, device=dev)
+        self.games = th.zeros(E, dtype=th.int32, device=dev)
+        self.playing = u8(1)
+        self.tables_left = th.full((1,), E, dtype=th.int32, device=dev)
+        self.ep_return = th.zeros(E, dtype=th.float32, device=dev)
+        self.ep_length = th.zeros(E, dtype=th.int32, device=dev)
+        self.returns = th.zeros((E, G), dtype=th.float32, device=dev)
+        self.lengths = th.zeros((E, G), dtype=th.int32, device=dev)
+        self.stats = th.zeros((self.P, nat.XPLAY_NSTAT), dtype=th.float64, device=dev)
+        self.ones8, self.zeros8 = u8(1), u8(0)
+        self._rows = th.arange(E, device=dev)
+        self.steps_done = 0
+        if self.native:
+            self._build_native()
+            self._done.fill_(1)
+            self._native_call(0, deal_only=True)
+        else:
+            self._deal(self.ones8, 0)
+
+    def _bind(self):
+        stream = th.cuda.current_stream(self.dev).cuda_stream
+        self.ctx.set_stream(stream)
+        for m in self.members:
+            if isinstance(m, FrozenVecPartner):
+                m.policy.ctx.set_stream(stream)
+
+    # -- the engine-side step ------------------------------------------------------------------------------------------------------
+    def _build_native(self) -> None:
+        E, dev, env = self.E, self.dev, self.env
+        f32 = lambda *shape: th.zeros(shape, dtype=th.float32, device=dev)  # noqa: E731
+        u8 = lambda: th.zeros(E, dtype=th.uint8, device=dev)               # noqa: E731
+        self._obs_next, self._rew1, self._rew2 = f32(E, 30), f32(E, 2), f32(E, 2)
+        self._done1, self._done2, self._running = u8(), u8(), u8()
+        self._alt_opens, self._ego_opens, self._done = u8(), u8(), u8()
+        arr = (nat.PhPoolMember * self.M)()
+        for k, m in enumerate(self.members):
+            arr[k].kind = m.kind
+            if isinstance(m, FrozenVecPartner):
+                arr[k].params, arr[k].seed = m.policy.params.data_ptr(), m.policy._seed
+        self._member_arr = arr
+        self._pairs_arr = (C.c_int * (2 * self.P))(*[int(v) for v in self.pairs.reshape(-1)])
+        s = nat.PhLiarXplay()
+        s.n, s.spec = E, C.pointer(self.spec)
+        s.hands, s.history, s.nmoves = env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr()
+        s.ego_first, s.dice_seed, s.probegostart = self.ego_first.data_ptr(), self.seed, self.probegostart
+        s.members, s.n_members = arr, self.M
+        s.pairs, s.n_pairs, s.episodes_per_table = self._pairs_arr, self.P, self.G
+        s.ego_id, s.alt_id = self.ego_id.data_ptr(), self.alt_id.data_ptr()
+        s.ego_actions, s.alt_actions = self.ego_actions.data_ptr(), self.alt_actions.data_ptr()
+        s.obs_ego, s.obs_alt = self.obs_ego.data_ptr(), self.obs_alt.data_ptr()
+        s.games, s.playing, s.tables_left = self.games.data_ptr(), self.playing.data_ptr(), self.tables_left.data_ptr()
+        s.ep_return, s.ep_length = self.ep_return.data_ptr(), self.ep_length.data_ptr()
+        s.returns, s.lengths = self.returns.data_ptr(), self.lengths.data_ptr()
+        s.obs_next, s.rew1, s.rew2 = self._obs_next.data_ptr(), self._rew1.data_ptr(), self._rew2.data_ptr()
+        s.done1, s.done2, s.running = self._done1.data_ptr(), self._done2.data_ptr(), self._running.data_ptr()
+        s.alt_opens, s.ego_opens, s.done = self._alt_opens.data_ptr(), self._ego_opens.data_ptr(), self._done.data_ptr()
+        self._desc = s
+
+    def _native_call(self, counter: int, deal_only: bool = False) -> None:
+        self._bind()
+        nat.check(self.ctx.lib.ph_liar_xplay_step(self.ctx.handle, C.byref(self._desc), int(counter), int(deal_only)))
+
+    # -- the walk: per-member calls with torch masks -------------------------------------------------------------------------------
+    def _seat_act(self, seat: int, obs: th.Tensor, mask: th.Tensor, counter: int) -> th.Tensor:
+        """the forward of every member that can sit at `seat`, Philox counter `counter`; member k's move lands in the tables of
+        `mask` it holds that seat of"""
+        ids, out = (self.ego_id, self.ego_actions) if seat == 0 else (self.alt_id, self.alt_actions)
+        for k in self._seat_members[seat]:
+            m = self.members[k]
+            mk = (mask.bool() & (ids == k)).to(th.uint8)
+            if isinstance(m, VecLiarDefaultPartner):
+                m.get_action(obs, mk, out, self.ctx)
+                continue
+            m.policy._counter = counter - 1
+            a = m.get_action(obs, mk)
+            out.copy_(th.where(mk.bool()[:, None], a, out))
+        return out
+
+    def _deal(self, reset_mask: th.Tensor, c: int) -> None:
+        """deal the tables in reset_mask; where seat 1 opens, it moves once; seat 0's observation of every fresh table"""
+        env, lib, h = self.env, self.ctx.lib, self.ctx.handle
+        self._bind()
+        nat.check(lib.ph_liar_reset(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
+                                    reset_mask.data_ptr(), self.ego_first.data_ptr(), self.seed, int(c),
+                                    self.probegostart, self.E))
+        rm = reset_mask.bool()
+        alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
+        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
+                                  self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
+        a_alt = self._seat_act(1, self.obs_alt, alt_opens, 3 * c + 2)
+        env.player_step(a_alt, self.zeros8, alt_opens)              # obs_next = seat 0's observation in those tables
+        self.obs_ego.copy_(th.where(alt_opens.bool()[:, None], env.obs_next, self.obs_ego))
+        ego_opens = (rm & self.ego_first.bool()).to(th.uint8)
+        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
+                                  self.ones8.data_ptr(), ego_opens.data_ptr(), self.obs_ego.data_ptr(), self.E))
+
+    # -- one vectorised MultiAgentEnv.step of the playing tables -------------------------------------------------------------------
+    def step(self) -> None:
+        self.steps_done += 1
+        c = self.steps_done
+        if self.native:
+            self._native_call(c)
+            return
+        env, G = self.env, self.G
+        self._bind()
+        playing = self.playing.bool()
+        a_ego = self._seat_act(0, self.obs_ego, self.playing, 3 * c)
+        obs_alt, rew1, done1 = env.player_step(a_ego, self.ones8, self.playing)
+        rew1, done1 = rew1.clone(), done1.bool() & playing
+        running = playing & ~done1
+        running8 = running.to(th.uint8)
+        a_alt = self._seat_act(1, obs_alt, running8, 3 * c + 1)
+        obs_ego, rew2, done2 = env.player_step(a_alt, self.zeros8, running8)
+        done2 = done2.bool() & running
+        done = done1 | done2
+        # the ego collects both transitions of the step (multiagentenv.py:201-202)
+        step_rew = rew1[:, 0] + th.where(running, rew2[:, 0], th.zeros_like(rew2[:, 0]))
+        self.ep_return.copy_(th.where(playing, self.ep_return + step_rew, self.ep_return))
+        self.ep_length.add_(playing.to(th.int32))
+        self.obs_ego.copy_(th.where((running & ~done2)[:, None], obs_ego, self.obs_ego))
+        # ends of games: the log entry, the count, the budget
+        slot = self.games.clamp(max=G - 1).long()[:, None]
+        self.returns.scatter_(1, slot, th.where(done, self.ep_return, self.returns.gather(1, slot)[:, 0])[:, None])
+        self.lengths.scatter_(1, slot, th.where(done, self.ep_length, self.lengths.gather(1, slot)[:, 0])[:, None])
+        self.games.add_(done.to(th.int32))
+        self.ep_return.copy_(th.where(done, th.zeros_like(self.ep_return), self.ep_return))
+        self.ep_length.copy_(th.where(done, th.zeros_like(self.ep_length), self.ep_length))
+        spent = done & (self.games >= G)
+        self.playing.copy_((playing & ~spent).to(th.uint8))
+        self.tables_left.sub_(spent.sum().to(th.int32))
+        self._deal((done & ~spent).to(th.uint8), c)
+
+    def left(self) -> int:
+        """tables with budget left (synchronises)"""
+        return int(self.tables_left.item())
+
+    def compute_stats(self) -> np.ndarray:
+        """`ph_xplay_stats` over the logs so far -> (P, 4) float64: count, sum, sum of squares, sum of lengths"""
+        self._bind()
+        nat.check(self.ctx.lib.ph_xplay_stats(self.ctx.handle, self.returns.data_ptr(), self.lengths.data_ptr(), self.games.data_ptr(),
+                                              self.E, self.G, self.P, self.stats.data_ptr()))
+        return self.stats.cpu().numpy()
+
+    def run(self, chunk: int = 8) -> CrossPlayResult:
+        """play every table's budget out: `chunk` steps at a time with nothing on the host in between, then one read of
+        `tables_left`.  A game takes at most 7 steps, so more than 7 * G steps can only be a bug: that raises."""
+        limit = MAX_STEPS_PER_GAME * self.G
+        while self.left() > 0:
+            if self.steps_done >= limit:
+                raise nat.NativeError(f"VecLiarCrossPlay: {self.left()} tables still play after {limit} steps "
+                                      f"(a game takes at most {MAX_STEPS_PER_GAME})")
+            for _ in range(min(int(chunk), limit - self.steps_done)):
+                self.step()
+        stats = self.compute_stats()
+        return CrossPlayResult(self.M, self.pairs, self.pair_of_table, self.returns.cpu().numpy(), self.lengths.cpu().numpy(), stats,
+                               self.steps_done)

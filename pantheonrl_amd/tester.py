@@ -3,7 +3,12 @@
     python -m pantheonrl_amd.tester RPS-v0 PPO DEFAULT --ego-load models/ego --alt-config '{"r": 1}' -t 100 [--record FILE]
 
 Same positional arguments and flags (`--render` is accepted and ignored: the in-tree games draw nothing).  Ego types: PPO, ADAP
-(with `--ego-config '{"latent_val": [...]}'`), BC; partner types: the same plus DEFAULT."""
+(with `--ego-config '{"latent_val": [...]}'`), BC; partner types: the same plus DEFAULT.
+
+    python -m pantheonrl_amd.tester LiarsDice-v0 PPO DEFAULT --ego-load models/ego --n-envs 256 -t 10000
+
+`--n-envs E` (E > 1) plays the pair on E device-resident tables (envs/crossplay.py): LiarsDice-v0, a PPO ego against a PPO or
+DEFAULT partner, ceil(t / E) games per table; the two lines above are printed over all the games played, then their number."""
 from __future__ import annotations
 
 import argparse
@@ -55,6 +60,51 @@ def run_test(ego, env, num_episodes: int) -> List[float]:
     return rewards
 
 
+def vectorised_check(args) -> None:
+    """what `--n-envs E` cannot evaluate, by name, before a device is touched"""
+    if args.n_envs < 1:
+        raise EnvException("--n-envs must be at least 1")
+    if args.env != "LiarsDice-v0":
+        raise EnvException(f"--n-envs: the device-resident evaluation exists for LiarsDice-v0, not {args.env}")
+    if args.ego != "PPO" or args.alt not in ("PPO", "DEFAULT"):
+        raise EnvException(f"--n-envs evaluates a PPO ego against a PPO or DEFAULT partner, not {args.ego} against {args.alt}")
+    if args.framestack > 1:
+        raise EnvException("--n-envs cannot be combined with --framestack")
+    if args.record is not None:
+        raise EnvException("--n-envs cannot be combined with --record")
+    if args.alt == "DEFAULT" and args.alt_config:
+        raise EnvException("No config possible for the DEFAULT partner")
+    if set(args.env_config) - {"probegostart"}:
+        raise EnvException(f"--n-envs: LiarsDice-v0 takes probegostart only, not {sorted(set(args.env_config) - {'probegostart'})}")
+
+
+def load_member(policy_type: str, config: dict, location, device):
+    """a seat of the device-resident evaluation: the scripted player, or a frozen loaded PPO policy"""
+    from .envs.vec import FrozenVecPartner, VecLiarDefaultPartner
+    if policy_type == "DEFAULT":
+        return VecLiarDefaultPartner()
+    cfg = {k: v for k, v in config.items() if k != "verbose"}
+    cfg.setdefault("device", device)
+    return FrozenVecPartner(gen_load(cfg, "PPO", location).policy)
+
+
+def run_vectorised(args) -> List[float]:
+    """tester.py:41-63 on E tables: one (ego, partner) pair, ceil(t / E) games per table"""
+    from .envs.crossplay import VecLiarCrossPlay
+    E = args.n_envs
+    G = -(-args.total_episodes // E)
+    ego = load_member(args.ego, args.ego_config, args.ego_load, args.device)
+    alt = load_member(args.alt, args.alt_config, args.alt_load, args.device)
+    print(f"Ego: {ego}")
+    print(f"Alt: {alt}")
+    xp = VecLiarCrossPlay(E, [ego, alt], pairs=[(0, 1)], episodes_per_table=G, seed=args.seed or 0, **args.env_config)
+    res = xp.run()
+    print(f"Average Reward: {res.mean[0]}")
+    print(f"Standard Deviation: {res.std[0]}")
+    print(f"Games played: {int(res.count[0])} ({E} tables x {G} games)")
+    return res.returns.reshape(-1).tolist()
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Test ego and partner in an environment (flags as in PantheonRL's tester.py)")
     p.add_argument("env")
@@ -71,6 +121,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--render", action="store_true")
     p.add_argument("--ego-load")
     p.add_argument("--alt-load")
+    p.add_argument("--n-envs", type=int, default=1,
+                   help="E > 1: play the pair on E device-resident tables (LiarsDice-v0, PPO ego, PPO or DEFAULT partner)")
     return p
 
 
@@ -80,7 +132,11 @@ def run(argv=None) -> List[float]:
     args.tensorboard_log, args.tensorboard_name, args.verbose_partner = None, None, False
     if args.seed is not None:
         np.random.seed(args.seed)
+    if args.n_envs != 1:
+        vectorised_check(args)
     print(f"Arguments: {args}")
+    if args.n_envs != 1:
+        return run_vectorised(args)
     env, altenv = generate_env(args)
     print(f"Environment: {env}; Partner env: {altenv}")
     ego = generate_agent(env, args.ego, args.ego_config, args.ego_load, args)

@@ -1,0 +1,106 @@
+"""games per second of the cross-play evaluation of Liar's Dice (envs/crossplay.py): E = 256 tables, all M^2 ordered pairs of a
+population of M members, 40 games per table (10 240 games per run):
+  native  one ph_liar_xplay_step per step (three grouped forwards whatever M is)
+  walk    the same evaluation through per-member forwards and torch masks (native=False)
+  host    tester.run_test of ONE of those pairs on the host MultiAgentEnv -- one table, one policy round trip per move
+Median of 5 runs per variant, the variants alternating within a round; the host clock around a device synchronise; a run is
+`run()` (the steps, the reads of tables_left, the statistics kernel and the copy of the logs), not the construction.
+`--ms 1,4` / `--no-host` / `--out FILE` narrow the sweep or keep a copy of the lines."""
+import argparse
+import contextlib
+import io
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch as th  # noqa: E402
+
+from pantheonrl_amd import PPO  # noqa: E402
+from pantheonrl_amd.common import StaticPolicyAgent  # noqa: E402
+from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay  # noqa: E402
+from pantheonrl_amd.envs.liar import LiarEnv  # noqa: E402
+from pantheonrl_amd.envs.vec import FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice  # noqa: E402
+from pantheonrl_amd.tester import run_test  # noqa: E402
+
+E, G, ROUNDS = 256, 40, 5
+_p = argparse.ArgumentParser()
+_p.add_argument("--ms", default="1,4,8")
+_p.add_argument("--no-host", action="store_true")
+_p.add_argument("--host-games", type=int, default=E * G)
+_p.add_argument("--out")
+_args = _p.parse_args()
+MS = [int(m) for m in _args.ms.split(",")]
+spaces = type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
+                            _is_dummy_space_env=True))()
+lines = []
+
+
+def say(text):
+    print(text, flush=True)
+    lines.append(text)
+
+
+policies = [PPO("MlpPolicy", spaces, n_steps=2, n_envs=4, batch_size=8, n_epochs=1, seed=10 + k).policy for k in range(8)]
+
+
+def population(M):
+    """M frozen policies; from M = 4 on member 2 is the scripted player"""
+    return [VecLiarDefaultPartner() if (M >= 4 and k == 2) else FrozenVecPartner(policies[k]) for k in range(M)]
+
+
+def device_run(M, native, seed):
+    xp = VecLiarCrossPlay(E, population(M), episodes_per_table=G, seed=seed, native=native)
+    th.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = xp.run()
+    th.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert int(res.count.sum()) == E * G
+    return E * G / dt, res.steps
+
+
+def host_run(n_games):
+    env = LiarEnv()
+    env.add_partner_agent(StaticPolicyAgent(policies[1]))
+    ego = StaticPolicyAgent(policies[0])
+    th.cuda.synchronize()
+    t0 = time.perf_counter()
+    with contextlib.redirect_stdout(io.StringIO()):
+        rewards = run_test(ego, env, n_games)
+    th.cuda.synchronize()
+    return len(rewards) / (time.perf_counter() - t0)
+
+
+variants = [(f"native M={M}", lambda s, M=M: device_run(M, True, s)) for M in MS]
+variants += [(f"walk   M={M}", lambda s, M=M: device_run(M, False, s)) for M in MS]
+if not _args.no_host:
+    variants.append(("host   tester.run_test, pair (0, 1)", lambda s: (host_run(_args.host_games), 0)))
+say(f"cross-play evaluation of Liar's Dice, E = {E} tables, all M^2 pairs, {G} games per table = {E * G} games per run "
+    f"(host: {_args.host_games} games per run); median of {ROUNDS} runs, variants alternating, after one warm-up round")
+rates = {name: [] for name, _ in variants}
+steps = {}
+for rnd in range(ROUNDS + 1):
+    for name, fn in variants:
+        if rnd == 0 and name.startswith("host"):
+            host_run(64)                    # warm-up: a short run is enough for a per-move loop
+            continue
+        rate, n = fn(100 + rnd)
+        if rnd:
+            rates[name].append(rate)
+            steps.setdefault(name, []).append(n)
+med = {}
+for name, _ in variants:
+    med[name] = statistics.median(rates[name])
+    extra = "" if name.startswith("host") else f"; steps per run {min(steps[name])}..{max(steps[name])}"
+    say(f"{name}: {med[name]:,.0f} games/s (min {min(rates[name]):,.0f}, max {max(rates[name]):,.0f}){extra}")
+for M in MS:
+    say(f"M={M}: native over walk {med[f'native M={M}'] / med[f'walk   M={M}']:.2f}x")
+if not _args.no_host:
+    host = med["host   tester.run_test, pair (0, 1)"]
+    for M in MS:
+        say(f"M={M}: native over the host loop {med[f'native M={M}'] / host:,.0f}x")
+if _args.out:
+    with open(_args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
