@@ -386,6 +386,8 @@ int check_rb(const ph_rollout* rb) {
 }
 
 int fail_who(const char* who, const char* what) { return fail(std::string(who) + what); }
+// what the 16-byte accesses of a Liar's Dice table's state need, in the words of every entry point that takes one
+const char* const LIAR_ALIGN16 = ": hands/history must be 16-byte aligned";
 
 int arch_resolve(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, ph::NetDims* nd, ph::ArchDims* ad);   // with the towers, below
 
@@ -1686,7 +1688,7 @@ int ph_liar_step(ph_ctx* ctx, const int* hands, int* history, int* nmoves, const
     return fail("ph_liar_step: null argument");
   if (n <= 0) return fail("ph_liar_step: n must be positive");
   if (((uintptr_t)hands | (uintptr_t)history) % 16 || ((uintptr_t)actions | (uintptr_t)obs_next | (uintptr_t)rewards) % 8)
-    return fail("ph_liar_step: hands/history must be 16-byte aligned, actions/obs_next/rewards 8-byte aligned");
+    return fail(std::string("ph_liar_step") + LIAR_ALIGN16 + ", actions/obs_next/rewards 8-byte aligned");
   PH_HIP(ph::launch_liar_step(hands, history, nmoves, actions, is_ego, active, obs_next, rewards, done, n, ctx->stream));
   return 0;
 }
@@ -1698,7 +1700,7 @@ int ph_liar_reset(ph_ctx* ctx, int* hands, int* history, int* nmoves, const unsi
   if (!ctx) return fail("null ctx");
   if (!hands || !history || !nmoves || !ego_first) return fail("ph_liar_reset: null argument");
   if (n <= 0) return fail("ph_liar_reset: n must be positive");
-  if (((uintptr_t)hands | (uintptr_t)history) % 16) return fail("ph_liar_reset: hands/history must be 16-byte aligned");
+  if (((uintptr_t)hands | (uintptr_t)history) % 16) return fail_who("ph_liar_reset", LIAR_ALIGN16);
   PH_HIP(ph::launch_liar_reset(hands, history, nmoves, reset_mask, ego_first, seed, counter, ctx->rng_epoch, probegostart, n,
                                ctx->stream));
   return 0;
@@ -1711,7 +1713,7 @@ int ph_liar_obs(ph_ctx* ctx, const int* hands, const int* history, const int* nm
   if (!hands || !history || !nmoves || !is_ego || !obs_out) return fail("ph_liar_obs: null argument");
   if (n <= 0) return fail("ph_liar_obs: n must be positive");
   if (((uintptr_t)hands | (uintptr_t)history) % 16 || (uintptr_t)obs_out % 8)
-    return fail("ph_liar_obs: hands/history must be 16-byte aligned, obs_out 8-byte aligned");
+    return fail(std::string("ph_liar_obs") + LIAR_ALIGN16 + ", obs_out 8-byte aligned");
   PH_HIP(ph::launch_liar_obs(hands, history, nmoves, is_ego, active, obs_out, n, ctx->stream));
   return 0;
 }
@@ -1736,48 +1738,91 @@ int seat_forward_ragged(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, c
                             counter, 0, actions, values, log_probs, rb, pos_env, rec, episode_start, 0);
 }
 
-// a Liar's Dice self-play description is complete, its buffers hold one column per table, and what the kernels read in 16-byte and
-// 8-byte vectors is aligned for it
-int check_liar_selfplay(const char* who, const ph_ctx* ctx, const ph_liar_selfplay* sp) {
-  if (!ctx || !sp) return fail_who(who, ": null argument");
-  const ph_liar_selfplay& s = *sp;
-  if (s.n <= 0 || !s.spec || !s.ego_rb || !s.alt_rb) return fail_who(who, ": incomplete description");
-  if (check_rb(s.ego_rb) || check_rb(s.alt_rb)) return 1;
-  if (s.ego_rb->E != s.n || s.alt_rb->E != s.n) return fail_who(who, ": buffers must have E = n");
-  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
-      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
-       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
-    return fail_who(who, ": hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
+// The game block of a Liar's Dice step description (ph_liar_step.h's view of it) is complete, and what the kernels read in 16-byte
+// and 8-byte vectors is aligned for it.  Host validation only: nothing is launched with a bad pointer.
+int check_liar_game(const char* who, const ph::LiarGame& g) {
+  if (g.n <= 0 || !g.hands || !g.history || !g.nmoves || !g.ego_first || !g.ego_actions || !g.alt_actions || !g.obs_ego || !g.obs_alt ||
+      !g.obs_next || !g.rew1 || !g.rew2 || !g.done1 || !g.done2 || !g.running || !g.alt_opens || !g.ego_opens || !g.done)
+    return fail_who(who, ": incomplete description");
+  if (((uintptr_t)g.hands | (uintptr_t)g.history) % 16 ||
+      ((uintptr_t)g.ego_actions | (uintptr_t)g.alt_actions | (uintptr_t)g.obs_ego | (uintptr_t)g.obs_alt | (uintptr_t)g.obs_next |
+       (uintptr_t)g.rew1 | (uintptr_t)g.rew2) % 8)
+    return fail(std::string(who) + LIAR_ALIGN16 + ", actions/observations/rewards 8-byte aligned");
+  return 0;
+}
+extern "C++" {   // (templates below; the file's entry points are extern "C")
+// ... and the ego of a training step has its rectangular buffer, one column per table
+template <class Desc>
+int check_liar_ego(const char* who, const Desc& s) {
+  if (!s.spec || !s.ego_rb || !s.ego_params || !s.ego_episode_start || !s.episodes) return fail_who(who, ": incomplete description");
+  if (check_rb(s.ego_rb)) return 1;
+  if (s.ego_rb->E != s.n) return fail_who(who, ": buffers must have E = n");
+  return 0;
+}
+template <class Desc>
+ph::TrainEnd liar_train_end(const Desc& s, int ego_pos, int deal_only) {
+  return ph::TrainEnd{deal_only ? nullptr : s.ego_rb->rewards + (size_t)ego_pos * s.n, s.ego_episode_start, s.episodes};
+}
+// the grouped forward runs the Liar's Dice 16-row one-hot class only
+int check_liar_one_hot(const char* who, ph_ctx* ctx, const ph_spec* spec, int n) {
+  ph::NetDims nd;
+  if (resolve(ctx, spec, &nd)) return 1;
+  if (!ph::pool_fwd_eligible(nd, n)) return fail_who(who, ": the spec is not the Liar's Dice 16-row one-hot class");
   return 0;
 }
 
-// the launch sequence of one vectorised Liar's Dice step, written once: either seat on the 64-wide kernels (null arch) or on towers
+// a Liar's Dice self-play description is complete and its buffers hold one column per table
+int check_liar_selfplay(const char* who, const ph_ctx* ctx, const ph_liar_selfplay* sp) {
+  if (!ctx || !sp) return fail_who(who, ": null argument");
+  const ph_liar_selfplay& s = *sp;
+  if (check_liar_game(who, ph::liar_game_of(s))) return 1;
+  if (!s.alt_rb || !s.alt_params || !s.alt_pos || !s.alt_boundary || !s.alt_term || !s.alt_open || !s.alt_acted || !s.can || !s.es_alt)
+    return fail_who(who, ": incomplete description");
+  if (check_liar_ego(who, s) || check_rb(s.alt_rb)) return 1;
+  if (s.alt_rb->E != s.n) return fail_who(who, ": buffers must have E = n");
+  return 0;
+}
+
+// The launch sequence of one vectorised Liar's Dice step, written once (ph_liar_step.h):
+//   seat-0 forward | after_ego | seat-1 forward (reply) | after_reply | seat-1 forward (openers) | after_opening
+// and its re-deal half alone (deal_only: for the tables flagged in g.done).  seat0() and seat1(obs, active, counter) run a
+// seat's forward; k = the Philox counters of the three forwards; the dice (and the pool's resample) draw with `counter`.
+template <class Book, class End, class Seat0, class Seat1>
+int liar_step_run(ph_ctx* ctx, const ph::LiarGame& g, const Book& book, const End& end, unsigned long long counter, int deal_only,
+                  const unsigned long long (&k)[3], Seat0 seat0, Seat1 seat1) {
+  hipStream_t st = ctx->stream;
+  if (!deal_only) {
+    if (seat0(k[0])) return 1;                               // seat 0 moves in every table
+    PH_HIP(ph::launch_liar_pass(0, g, book, end, counter, ctx->rng_epoch, deal_only, st));
+    if (seat1(g.obs_next, g.running, k[1])) return 1;        // seat 1 replies where the game goes on (obs_next = its observation there)
+  }
+  // reply played and credited; finished tables are re-dealt; where seat 1 opens the new game it moves once
+  PH_HIP(ph::launch_liar_pass(1, g, book, end, counter, ctx->rng_epoch, deal_only, st));
+  if (seat1(g.obs_alt, g.alt_opens, k[2])) return 1;
+  PH_HIP(ph::launch_liar_pass(2, g, book, end, counter, ctx->rng_epoch, deal_only, st));
+  return 0;
+}
+
+}  // extern "C++"
+
+// self-play: either seat on the 64-wide kernels (null arch) or on towers; the partner's forwards are ragged
 int liar_selfplay_step_run(const char* who, ph_ctx* ctx, const ph_liar_selfplay* sp, const ph_arch* ego_arch, const ph_arch* alt_arch,
                            int ego_pos, unsigned long long counter, int deal_only) {
   if (check_liar_selfplay(who, ctx, sp)) return 1;
   const ph_liar_selfplay& s = *sp;
-  hipStream_t st = ctx->stream;
-  if (!deal_only) {
-    if (ego_pos < 0 || ego_pos >= s.ego_rb->T) return fail_who(who, ": ego_pos out of range (buffer full?)");
-    // ego moves in every table
-    if (seat_forward(ctx, s.spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, counter, s.ego_actions, s.ego_values,
-                     s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start))
-      return 1;
-    PH_HIP(ph::launch_liar_sp_after_ego(s, st));
-    // partner replies where the game goes on (obs_next = its observation there)
-    if (seat_forward_ragged(ctx, s.spec, alt_arch, s.alt_params, s.obs_next, s.alt_seed, 2 * counter, s.alt_actions, s.alt_values,
-                            s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
-      return 1;
-  }
-  // reply played and credited; finished tables (flagged in s.done) are re-dealt; where the partner opens the new game it
-  // moves once
-  PH_HIP(ph::launch_liar_sp_after_reply(s, deal_only ? nullptr : s.ego_rb->rewards + (size_t)ego_pos * s.n, counter,
-                                        ctx->rng_epoch, deal_only, st));
-  if (seat_forward_ragged(ctx, s.spec, alt_arch, s.alt_params, s.obs_alt, s.alt_seed, 2 * counter + 1, s.alt_actions, s.alt_values,
-                          s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt))
-    return 1;
-  PH_HIP(ph::launch_liar_sp_after_opening(s, st));
-  return 0;
+  if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail_who(who, ": ego_pos out of range (buffer full?)");
+  const ph::LearnerBook book{ph::SeatFields{s.n, s.alt_pos, s.alt_boundary, s.alt_term, s.alt_open, s.alt_acted, s.can, s.es_alt},
+                             s.alt_rb->rewards, s.alt_rb->T};
+  return liar_step_run(
+      ctx, ph::liar_game_of(s), book, liar_train_end(s, ego_pos, deal_only), counter, deal_only, {counter, 2 * counter, 2 * counter + 1},
+      [&](unsigned long long c) {
+        return seat_forward(ctx, s.spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, c, s.ego_actions, s.ego_values,
+                            s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start);
+      },
+      [&](const float* obs, const unsigned char*, unsigned long long c) {
+        return seat_forward_ragged(ctx, s.spec, alt_arch, s.alt_params, obs, s.alt_seed, c, s.alt_actions, s.alt_values, s.alt_log_probs,
+                                   s.alt_rb, s.alt_pos, s.can, s.es_alt);
+      });
 }
 }  // namespace
 
@@ -1896,119 +1941,60 @@ int ph_liar_default_actions(ph_ctx* ctx, const float* obs, const unsigned char* 
 
 int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsigned long long counter, int deal_only) {
   DevGuard dev_guard(ctx);
-  if (!ctx || !pool) return fail("ph_liar_pool_step: null argument");
+  const char* who = "ph_liar_pool_step";
+  if (!ctx || !pool) return fail_who(who, ": null argument");
   const ph_liar_pool& s = *pool;
-  if (s.n <= 0 || !s.spec || !s.ego_rb) return fail("ph_liar_pool_step: incomplete description");
-  if (!s.hands || !s.history || !s.nmoves || !s.ego_first || !s.ego_params || !s.ego_actions || !s.ego_episode_start || !s.partnerid ||
-      !s.alt_actions || !s.alt_acted || !s.obs_ego || !s.obs_alt || !s.episodes || !s.obs_next || !s.rew1 || !s.rew2 || !s.es_alt ||
-      !s.done1 || !s.done2 || !s.running || !s.can || !s.alt_opens || !s.ego_opens || !s.done)
-    return fail("ph_liar_pool_step: incomplete description");
-  if (s.resample != PH_POOL_ROBIN && s.resample != PH_POOL_RANDOM) return fail("ph_liar_pool_step: unknown resample rule");
-  if (check_rb(s.ego_rb)) return 1;
-  if (s.ego_rb->E != s.n) return fail("ph_liar_pool_step: buffers must have E = n");
-  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
-      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
-       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
-    return fail("ph_liar_pool_step: hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
-  if (pool_members(ctx, "ph_liar_pool_step", s.members, s.n_members, s.n)) return 1;
-  {
-    ph::NetDims nd;
-    if (resolve(ctx, s.spec, &nd)) return 1;
-    if (!ph::pool_fwd_eligible(nd, s.n)) return fail("ph_liar_pool_step: the spec is not the Liar's Dice 16-row one-hot class");
-  }
-  if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail("ph_liar_pool_step: ego_pos out of range (buffer full?)");
-  ph::PoolStep d;
-  std::memset(&d, 0, sizeof(d));
-  d.n = s.n; d.K = s.n_members; d.resample = s.resample;
-  d.hands = s.hands; d.history = s.history; d.nmoves = s.nmoves; d.ego_first = s.ego_first;
-  d.dice_seed = s.dice_seed; d.pool_seed = s.pool_seed; d.probegostart = s.probegostart;
-  d.ego_actions = s.ego_actions; d.ego_episode_start = s.ego_episode_start;
-  d.members = ctx->pool_dev; d.partnerid = s.partnerid; d.alt_actions = s.alt_actions; d.alt_acted = s.alt_acted;
-  d.obs_ego = s.obs_ego; d.obs_alt = s.obs_alt; d.episodes = s.episodes;
-  d.obs_next = s.obs_next; d.rew1 = s.rew1; d.rew2 = s.rew2; d.es_alt = s.es_alt;
-  d.done1 = s.done1; d.done2 = s.done2; d.running = s.running; d.can = s.can;
-  d.alt_opens = s.alt_opens; d.ego_opens = s.ego_opens; d.done = s.done;
-  hipStream_t st = ctx->stream;
-  if (!deal_only) {
-    // the ego moves in every table
-    if (ph_policy_forward(ctx, s.spec, s.ego_params, s.obs_ego, s.n, nullptr, nullptr, nullptr, s.ego_seed, counter, 0,
-                          s.ego_actions, nullptr, s.ego_values, s.ego_log_probs, nullptr, nullptr, s.ego_rb, ego_pos,
-                          s.ego_episode_start, nullptr, 0))
-      return 1;
-    PH_HIP(ph::launch_pool_after_ego(d, st));
-    // every table's member replies where the game goes on: one grouped launch
-    if (pool_forward(ctx, "ph_liar_pool_step", s.spec, s.n_members, s.obs_next, s.partnerid, s.running, s.can, 2 * counter,
-                     s.alt_actions, s.es_alt, s.n))
-      return 1;
-  }
-  PH_HIP(ph::launch_pool_after_reply(d, deal_only ? nullptr : s.ego_rb->rewards + (size_t)ego_pos * s.n, counter, ctx->rng_epoch,
-                                     deal_only, st));
-  // the freshly sampled members open the games they start
-  if (pool_forward(ctx, "ph_liar_pool_step", s.spec, s.n_members, s.obs_alt, s.partnerid, s.alt_opens, s.can, 2 * counter + 1,
-                   s.alt_actions, s.es_alt, s.n))
-    return 1;
-  PH_HIP(ph::launch_pool_after_opening(d, st));
-  return 0;
+  const ph::LiarGame g = ph::liar_game_of(s);
+  if (check_liar_game(who, g)) return 1;
+  if (!s.partnerid || !s.alt_acted || !s.can || !s.es_alt) return fail_who(who, ": incomplete description");
+  if (s.resample != PH_POOL_ROBIN && s.resample != PH_POOL_RANDOM) return fail_who(who, ": unknown resample rule");
+  if (check_liar_ego(who, s)) return 1;
+  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n)) return 1;
+  if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail_who(who, ": ego_pos out of range (buffer full?)");
+  const ph::PoolBook book{s.n, s.n_members, s.resample, s.pool_seed, ctx->pool_dev, s.partnerid, s.alt_acted, s.can, s.es_alt};
+  return liar_step_run(
+      ctx, g, book, liar_train_end(s, ego_pos, deal_only), counter, deal_only, {counter, 2 * counter, 2 * counter + 1},
+      [&](unsigned long long c) {
+        return seat_forward(ctx, s.spec, nullptr, s.ego_params, s.obs_ego, s.n, s.ego_seed, c, s.ego_actions, s.ego_values,
+                            s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start);
+      },
+      // every table's member -- behind a deal the freshly sampled one -- moves: one grouped launch
+      [&](const float* obs, const unsigned char* active, unsigned long long c) {
+        return pool_forward(ctx, who, s.spec, s.n_members, obs, s.partnerid, active, s.can, c, s.alt_actions, s.es_alt, s.n);
+      });
 }
 
 // ---- cross-play evaluation of Liar's Dice (ph_xplay.h; tester.py:41-63 over n tables) ----
 int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long counter, int deal_only) {
   DevGuard dev_guard(ctx);
-  if (!ctx || !xp) return fail("ph_liar_xplay_step: null argument");
+  const char* who = "ph_liar_xplay_step";
+  if (!ctx || !xp) return fail_who(who, ": null argument");
   const ph_liar_xplay& s = *xp;
-  if (s.n <= 0 || !s.spec) return fail("ph_liar_xplay_step: incomplete description");
-  if (!s.hands || !s.history || !s.nmoves || !s.ego_first || !s.pairs || !s.ego_id || !s.alt_id || !s.ego_actions || !s.alt_actions ||
-      !s.obs_ego || !s.obs_alt || !s.games || !s.playing || !s.tables_left || !s.ep_return || !s.ep_length || !s.returns ||
-      !s.lengths || !s.obs_next || !s.rew1 || !s.rew2 || !s.done1 || !s.done2 || !s.running || !s.alt_opens || !s.ego_opens || !s.done)
-    return fail("ph_liar_xplay_step: incomplete description");
-  if (s.episodes_per_table < 1) return fail("ph_liar_xplay_step: episodes_per_table must be at least 1");
-  if (s.n_pairs < 1 || s.n_pairs > s.n) return fail("ph_liar_xplay_step: 1..n pairs (every pair needs a table)");
-  if (((uintptr_t)s.hands | (uintptr_t)s.history) % 16 ||
-      ((uintptr_t)s.ego_actions | (uintptr_t)s.alt_actions | (uintptr_t)s.obs_ego | (uintptr_t)s.obs_alt | (uintptr_t)s.obs_next |
-       (uintptr_t)s.rew1 | (uintptr_t)s.rew2) % 8)
-    return fail("ph_liar_xplay_step: hands/history must be 16-byte aligned, actions/observations/rewards 8-byte aligned");
-  if (!s.members) return fail("ph_liar_xplay_step: null member array");
-  if (s.n_members < 1 || s.n_members > PH_MAX_POOL) return fail("ph_liar_xplay_step: the population holds 1..PH_MAX_POOL members");
+  const ph::LiarGame g = ph::liar_game_of(s);
+  if (check_liar_game(who, g)) return 1;
+  if (!s.spec || !s.pairs || !s.ego_id || !s.alt_id || !s.games || !s.playing || !s.tables_left || !s.ep_return || !s.ep_length ||
+      !s.returns || !s.lengths)
+    return fail_who(who, ": incomplete description");
+  if (s.episodes_per_table < 1) return fail_who(who, ": episodes_per_table must be at least 1");
+  if (s.n_pairs < 1 || s.n_pairs > s.n) return fail_who(who, ": 1..n pairs (every pair needs a table)");
+  if (!s.members) return fail_who(who, ": null member array");
+  if (s.n_members < 1 || s.n_members > PH_MAX_POOL) return fail_who(who, ": the population holds 1..PH_MAX_POOL members");
   for (int k = 0; k < s.n_members; ++k)
     if (s.members[k].kind == PH_POOL_LEARNER)
       return fail("ph_liar_xplay_step: member " + std::to_string(k) + " is a PH_POOL_LEARNER: an evaluation seats frozen and scripted members only");
   for (int p = 0; p < 2 * s.n_pairs; ++p)
     if (s.pairs[p] < 0 || s.pairs[p] >= s.n_members)
       return fail("ph_liar_xplay_step: pair " + std::to_string(p / 2) + " names a member out of range");
-  if (pool_members(ctx, "ph_liar_xplay_step", s.members, s.n_members, s.n)) return 1;
-  {
-    ph::NetDims nd;
-    if (resolve(ctx, s.spec, &nd)) return 1;
-    if (!ph::pool_fwd_eligible(nd, s.n)) return fail("ph_liar_xplay_step: the spec is not the Liar's Dice 16-row one-hot class");
-  }
-  ph::XplayStep d;
-  std::memset(&d, 0, sizeof(d));
-  d.n = s.n; d.G = s.episodes_per_table;
-  d.hands = s.hands; d.history = s.history; d.nmoves = s.nmoves; d.ego_first = s.ego_first;
-  d.dice_seed = s.dice_seed; d.probegostart = s.probegostart;
-  d.ego_actions = s.ego_actions; d.alt_actions = s.alt_actions; d.obs_ego = s.obs_ego; d.obs_alt = s.obs_alt;
-  d.games = s.games; d.playing = s.playing; d.tables_left = s.tables_left; d.ep_return = s.ep_return; d.ep_length = s.ep_length;
-  d.returns = s.returns; d.lengths = s.lengths;
-  d.obs_next = s.obs_next; d.rew1 = s.rew1; d.rew2 = s.rew2;
-  d.done1 = s.done1; d.done2 = s.done2; d.running = s.running; d.alt_opens = s.alt_opens; d.ego_opens = s.ego_opens; d.done = s.done;
-  hipStream_t st = ctx->stream;
-  const char* who = "ph_liar_xplay_step";
-  if (!deal_only) {
-    // seat 0 moves in every playing table: one grouped launch over the member table, indexed by ego_id
-    if (pool_forward(ctx, who, s.spec, s.n_members, s.obs_ego, s.ego_id, s.playing, s.playing, 3 * counter, s.ego_actions, nullptr, s.n))
-      return 1;
-    PH_HIP(ph::launch_xplay_after_ego(d, st));
-    // seat 1 replies where the game goes on: the same table, indexed by alt_id
-    if (pool_forward(ctx, who, s.spec, s.n_members, s.obs_next, s.alt_id, s.running, s.running, 3 * counter + 1, s.alt_actions, nullptr,
-                     s.n))
-      return 1;
-  }
-  PH_HIP(ph::launch_xplay_after_reply(d, counter, ctx->rng_epoch, deal_only, st));
-  if (pool_forward(ctx, who, s.spec, s.n_members, s.obs_alt, s.alt_id, s.alt_opens, s.alt_opens, 3 * counter + 2, s.alt_actions, nullptr,
-                   s.n))
-    return 1;
-  PH_HIP(ph::launch_xplay_after_opening(d, st));
-  return 0;
+  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n)) return 1;
+  const ph::EvalEnd end{s.episodes_per_table, s.games, s.playing, s.tables_left, s.ep_return, s.ep_length, s.returns, s.lengths};
+  // a seat's forward is one grouped launch over the member table, indexed by ego_id / alt_id; nothing is recorded
+  auto seat = [&](const float* obs, const int* id, const unsigned char* active, unsigned long long c, int* actions) {
+    return pool_forward(ctx, who, s.spec, s.n_members, obs, id, active, active, c, actions, nullptr, s.n);
+  };
+  return liar_step_run(
+      ctx, g, ph::NoBook{}, end, counter, deal_only, {3 * counter, 3 * counter + 1, 3 * counter + 2},
+      [&](unsigned long long c) { return seat(s.obs_ego, s.ego_id, s.playing, c, s.ego_actions); },
+      [&](const float* obs, const unsigned char* active, unsigned long long c) { return seat(obs, s.alt_id, active, c, s.alt_actions); });
 }
 
 int ph_xplay_stats(ph_ctx* ctx, const float* returns, const int* lengths, const int* games, int n, int episodes_per_table, int n_pairs,

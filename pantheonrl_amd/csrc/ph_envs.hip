@@ -2,7 +2,7 @@
 // rock-paper-scissors (pantheonrl/envs/rpsgym/rps.py:41-45) and Liar's Dice (pantheonrl/envs/liargym/liar.py:53-83).
 // One lane per environment; everything is integer arithmetic and must be bit-exact with the Python games.
 #include "ph_launch.h"
-#include "ph_liar.h"
+#include "ph_xplay.h"
 
 namespace ph {
 
@@ -111,37 +111,43 @@ hipError_t launch_liar_reset(int* hands, int* history, int* nmoves, const unsign
   return hipGetLastError();
 }
 
-__global__ void liar_sp_after_ego_kernel(ph_liar_selfplay s, float* alt_rewards, int alt_T) {
+// ---- the vectorised Liar's Dice step between its forwards (ph_liar_step.h): one kernel per pass and mode, one lane per table ----
+template <class Book, class End>
+__global__ void liar_after_ego_kernel(LiarGame g, Book book, End end) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= s.n) return;
-  liar_sp_after_ego_lane(s, e, alt_rewards, alt_T);
+  if (e >= g.n) return;
+  liar_after_ego_lane(g, book, end, e);
 }
-__global__ void liar_sp_after_reply_kernel(ph_liar_selfplay s, float* alt_rewards, int alt_T, float* ego_rew_row,
-                                           uint64_t counter, const unsigned long long* __restrict__ epoch, int deal_only) {
+template <class Book, class End>
+__global__ void liar_after_reply_kernel(LiarGame g, Book book, End end, uint64_t counter, const unsigned long long* __restrict__ epoch,
+                                        int deal_only) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= s.n) return;
-  liar_sp_after_reply_lane(s, e, alt_rewards, alt_T, ego_rew_row, counter, epoch, deal_only);
+  if (e >= g.n) return;
+  liar_after_reply_lane(g, book, end, e, counter, epoch, deal_only);
 }
-__global__ void liar_sp_after_opening_kernel(ph_liar_selfplay s) {
+template <class Book, class End>
+__global__ void liar_after_opening_kernel(LiarGame g, Book book, End) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= s.n) return;
-  liar_sp_after_opening_lane(s, e);
+  if (e >= g.n) return;
+  liar_after_opening_lane(g, book, e);
 }
-#define PH_SP_GRID(s) dim3(((s).n + 255) / 256), dim3(256)
-hipError_t launch_liar_sp_after_ego(const ph_liar_selfplay& s, hipStream_t st) {
-  hipLaunchKernelGGL(liar_sp_after_ego_kernel, PH_SP_GRID(s), 0, st, s, s.alt_rb->rewards, s.alt_rb->T);
+template <class Book, class End>
+hipError_t launch_liar_pass(int pass, const LiarGame& g, const Book& book, const End& end, unsigned long long counter,
+                            const unsigned long long* epoch, int deal_only, hipStream_t st) {
+  const dim3 grid((g.n + 255) / 256), block(256);
+  if (pass == 0) hipLaunchKernelGGL((liar_after_ego_kernel<Book, End>), grid, block, 0, st, g, book, end);
+  else if (pass == 1)
+    hipLaunchKernelGGL((liar_after_reply_kernel<Book, End>), grid, block, 0, st, g, book, end, (uint64_t)counter, epoch, deal_only);
+  else hipLaunchKernelGGL((liar_after_opening_kernel<Book, End>), grid, block, 0, st, g, book, end);
   return hipGetLastError();
 }
-hipError_t launch_liar_sp_after_reply(const ph_liar_selfplay& s, float* ego_rew_row, unsigned long long counter,
-                                      const unsigned long long* epoch, int deal_only, hipStream_t st) {
-  hipLaunchKernelGGL(liar_sp_after_reply_kernel, PH_SP_GRID(s), 0, st, s, s.alt_rb->rewards, s.alt_rb->T, ego_rew_row,
-                     (uint64_t)counter, epoch, deal_only);
-  return hipGetLastError();
-}
-hipError_t launch_liar_sp_after_opening(const ph_liar_selfplay& s, hipStream_t st) {
-  hipLaunchKernelGGL(liar_sp_after_opening_kernel, PH_SP_GRID(s), 0, st, s);
-  return hipGetLastError();
-}
+#define PH_LIAR_MODE(Book, End)                                                                                           \
+  template hipError_t launch_liar_pass<Book, End>(int, const LiarGame&, const Book&, const End&, unsigned long long, \
+                                                  const unsigned long long*, int, hipStream_t)
+PH_LIAR_MODE(LearnerBook, TrainEnd);   // self-play
+PH_LIAR_MODE(PoolBook, TrainEnd);      // a pool of partners at seat 1
+PH_LIAR_MODE(NoBook, EvalEnd);         // cross-play evaluation
+#undef PH_LIAR_MODE
 
 // ---- peer-to-peer action exchange over xGMI (include/pantheon_hip.h: ph_p2p) --------------------------------------------
 // push: one workgroup.  Every peer's receive slot gets this rank's `count` actions with plain (uncached, fine-grained

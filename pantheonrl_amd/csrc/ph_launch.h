@@ -337,11 +337,7 @@ hipError_t launch_liar_step(const int* hands, int* history, int* nmoves, const i
                             const unsigned char* active, float* obs_next, float* rew, unsigned char* done, int n,
                             hipStream_t s);
 hipError_t launch_ppo_grad(const GradArgs& a, int nwg, int gemm_mode, hipStream_t s);
-// device-side book-keeping of the vectorised Liar's Dice self-play step (ph_envs.hip)
-hipError_t launch_liar_sp_after_ego(const ph_liar_selfplay& s, hipStream_t st);
-hipError_t launch_liar_sp_after_reply(const ph_liar_selfplay& s, float* ego_rew_row, unsigned long long counter,
-                                      const unsigned long long* epoch, int deal_only, hipStream_t st);
-hipError_t launch_liar_sp_after_opening(const ph_liar_selfplay& s, hipStream_t st);
+// (the book-keeping launches of the vectorised Liar's Dice steps: ph_liar_step.h)
 // persistent Liar's Dice rollout (ph_policy.hip: liar_rollout_kernel)
 bool liar_rollout_eligible(const NetDims& nd, int n);
 

@@ -1,7 +1,7 @@
-// Liar's Dice on the device: a table's state, the game rules (pantheonrl/envs/liargym/liar.py:53-102) and the per-table
-// book-keeping of the vectorised self-play step as lane functions (one lane per table): what the per-step kernels run
-// (ph_envs.hip).  The persistent rollout kernel (ph_policy.hip: liar_rollout_kernel) runs the same rules with a table spread over
-// 32 lanes (ph_liar_group.h); tests hold the two forms bitwise equal.
+// Liar's Dice on the device: a table's state, the game rules (pantheonrl/envs/liargym/liar.py:53-102) and a learner's per-table
+// book-keeping at the partner seat as lane functions (one lane per table).  The step itself -- what the per-step kernels run
+// between the forwards -- is ph_liar_step.h.  The persistent rollout kernel (ph_policy.hip: liar_rollout_kernel) runs the same
+// rules with a table spread over 32 lanes (ph_liar_group.h); tests hold the two forms bitwise equal.
 #pragma once
 #include "ph_launch.h"
 
@@ -135,7 +135,7 @@ __device__ __forceinline__ bool liar_deal(LiarTable& t, int e, int* hands, int* 
   return first;   // = ego_first[e]
 }
 
-// ---- vectorised Liar's Dice self-play: the step loop's book-keeping, one lane per table ------------------------------------
+// ---- a learner at the partner seat: the step loop's book-keeping, one lane per table ----------------------------------------
 // (MultiAgentEnv._update_players / _get_actions, multiagentenv.py:149-170, and OnPolicyAgent.update, agents.py:186-203,
 // applied to n tables; the partner's rollout rows are ragged: table e writes row alt_pos[e]).  A table's state is touched
 // by its own lane only, so everything between two policy forwards is ONE launch: a vectorised step is
@@ -199,70 +199,6 @@ __device__ __forceinline__ void liar_sp_commit(const SelfPlay& s, LiarSeat& q, i
   s.alt_open[e] = can ? 1 : 0;
   q.acted = true;
   s.alt_acted[e] = 1;
-}
-
-// the ego has moved (its forward wrote ego_actions): play the move, credit the partner where it already acted this game,
-// find the tables that go on and prepare the partner's reply there
-__device__ __forceinline__ void liar_sp_after_ego_lane(const ph_liar_selfplay& s, int e, float* alt_rewards, int alt_T) {
-  LiarTable t;
-  liar_load(t, e, s.hands, s.history, s.nmoves);
-  LiarSeat q = liar_seat_load(s, e);
-  const LiarOutcome o1 = liar_move(t, e, s.history, s.nmoves, s.ego_actions, true, s.obs_next, s.rew1, s.done1);
-  liar_sp_credit(s, q, alt_rewards, alt_T, e, o1.r_alt, o1.done, q.acted);
-  s.running[e] = o1.done ? 0 : 1;
-  liar_sp_prepare(s, q, alt_T, e, !o1.done);
-}
-// the partner has replied where the game went on: play that move, credit both, the ego's reward row / episode flags /
-// next observation; then (also the whole of a deal-only call) re-deal the finished tables, find who opens the new games
-// and prepare the partner's opening forward
-__device__ __forceinline__ void liar_sp_after_reply_lane(const ph_liar_selfplay& s, int e, float* alt_rewards, int alt_T,
-                                                         float* ego_rew_row, uint64_t counter, const unsigned long long* epoch,
-                                                         int deal_only) {
-  LiarTable t;
-  liar_load(t, e, s.hands, s.history, s.nmoves);
-  LiarSeat q = liar_seat_load(s, e);
-  bool ego_first = s.ego_first[e] != 0;    // of the game in progress; a re-deal below replaces it
-  bool fresh = s.done[e] != 0;             // a deal-only call: the caller's flags
-  if (!deal_only) {
-    const bool run = s.running[e] != 0, can = s.can[e] != 0, d1 = s.done1[e] != 0;
-    const float r1_ego = s.rew1[2 * e];
-    LiarOutcome o2{0.f, 0.f, false};
-    if (run) {
-      liar_sp_commit(s, q, e, can);
-      o2 = liar_move(t, e, s.history, s.nmoves, s.alt_actions, false, s.obs_next, s.rew2, s.done2);
-    }
-    const bool d2 = run && o2.done;
-    liar_sp_credit(s, q, alt_rewards, alt_T, e, o2.r_alt, d2, run);
-    const bool done = d1 || d2;
-    liar_add_f32(ego_rew_row + e, r1_ego + (run ? o2.r_ego : 0.f));   // both transitions of the step (agents.py:44-47)
-    s.ego_episode_start[e] = done ? 1.f : 0.f;
-    if (run && !d2) liar_write_obs(t, true, s.obs_ego + (size_t)e * 30);   // = obs_next of the move just played
-    s.done[e] = done ? 1 : 0;
-    if (done) atomicAdd(s.episodes, 1ull);
-    fresh = done;
-  }
-  if (fresh) {
-    ego_first = liar_deal(t, e, s.hands, s.history, s.nmoves, s.ego_first, s.dice_seed,
-                          counter + (epoch ? (uint64_t)(*epoch) << 32 : 0ull), s.probegostart);
-    s.alt_acted[e] = 0;
-  }
-  s.alt_opens[e] = (fresh && !ego_first) ? 1 : 0;
-  s.ego_opens[e] = (fresh && ego_first) ? 1 : 0;
-  liar_sp_prepare(s, q, alt_T, e, fresh && !ego_first);
-  if (fresh && !ego_first) liar_write_obs(t, false, s.obs_alt + (size_t)e * 30);
-}
-// the partner has opened the new games it starts: play that move; the ego's observation of every fresh table
-__device__ __forceinline__ void liar_sp_after_opening_lane(const ph_liar_selfplay& s, int e) {
-  const bool alt_opens = s.alt_opens[e] != 0, ego_opens = s.ego_opens[e] != 0;
-  if (!alt_opens && !ego_opens) return;
-  LiarTable t;
-  liar_load(t, e, s.hands, s.history, s.nmoves);
-  if (alt_opens) {
-    LiarSeat q = liar_seat_load(s, e);
-    liar_sp_commit(s, q, e, s.can[e] != 0);
-    (void)liar_move(t, e, s.history, s.nmoves, s.alt_actions, false, s.obs_next, s.rew2, s.done2);
-  }
-  liar_write_obs(t, true, s.obs_ego + (size_t)e * 30);   // after the partner's opening move, or of the fresh deal
 }
 
 }  // namespace ph

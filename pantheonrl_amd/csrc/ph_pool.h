@@ -1,9 +1,9 @@
 // Liar's Dice against a pool of partners: the device-side member table, the bucket pass and the grouped forward's launch record,
-// and the per-table book-keeping of the pool step (ph_liar.h's after_ego / after_reply / after_opening with the member index).
-// Kernels: ph_pool.hip (bucket pass, scripted rule, book-keeping) and ph_policy.hip (pool_fwd16h_kernel: the grouped forward is the
+// and seat 1's book of the pool step (ph_liar_step.h's after_ego / after_reply / after_opening with the member index).
+// Kernels: ph_pool.hip (bucket pass, scripted rule), ph_envs.hip (the step's book-keeping) and ph_policy.hip (pool_fwd16h_kernel: the grouped forward is the
 // 16-row one-hot forward with its rows gathered through `order`, so it lives beside policy_fwd16h_body).
 #pragma once
-#include "ph_liar.h"
+#include "ph_liar_step.h"
 
 namespace ph {
 
@@ -37,25 +37,6 @@ struct PoolFwd {
   PoolBuckets b;
 };
 
-// the pool step's description as the book-keeping kernels take it
-struct PoolStep {
-  int n, K, resample;
-  int *hands, *history, *nmoves;
-  unsigned char* ego_first;
-  unsigned long long dice_seed, pool_seed;
-  float probegostart;
-  const int* ego_actions;
-  float* ego_episode_start;
-  const PoolMemberDev* members;     // device
-  int* partnerid;
-  const int* alt_actions;
-  unsigned char* alt_acted;
-  float *obs_ego, *obs_alt;
-  unsigned long long* episodes;
-  float *obs_next, *rew1, *rew2, *es_alt;
-  unsigned char *done1, *done2, *running, *can, *alt_opens, *ego_opens, *done;
-};
-
 // LiarDefaultAgent.get_action (envs/liar.py): bid the most frequent face (the first of equals) at its own count; call as soon as
 // the standing bid exceeds that count.  o = the row's 30 observation components.
 __device__ __forceinline__ int2 liar_default_move(const float* o) {
@@ -80,13 +61,74 @@ __device__ __forceinline__ int pool_resample(int prev, int K, int rule, unsigned
   return (prev + 1) % K;
 }
 
+// Seat 1's book of the pool step (ph_liar_step.h): table e's lane binds the member that holds (or, behind a deal, is about to hold)
+// seat 1 of table e, so a member's flags of table e are touched by that lane only.  A learner keeps LearnerBook's cursor; members
+// without a buffer record nothing (can = 0) and only mark the seat as having acted.  The index is device data: clamped.
+struct PoolBook {
+  int n, K, resample;
+  unsigned long long pool_seed;
+  const PoolMemberDev* members;     // device
+  int* partnerid;
+  unsigned char *alt_acted, *can;
+  float* es_alt;
+  struct Lane {
+    int k;
+    bool learner;
+    LearnerBook m;
+    LearnerBook::Lane s;
+  };
+  // the member at b.k: a learner's cursor addresses (members[] is device memory: a dependent load behind partnerid)
+  __device__ __forceinline__ void bind(Lane& b) const {
+    const PoolMemberDev m = members[b.k];
+    b.learner = m.kind == PH_POOL_LEARNER;
+    b.m = LearnerBook{SeatFields{n, m.pos, m.boundary, m.term, m.open, alt_acted, can, es_alt}, m.rb_rew, m.rb_T};
+    b.s.q = LiarSeat{0, false, false, false};
+  }
+  __device__ __forceinline__ Lane seat(int e) const {
+    Lane b;
+    const int k = partnerid[e];
+    b.k = k < 0 ? 0 : (k >= K ? K - 1 : k);
+    b.s.can = can[e] != 0;
+    bind(b);
+    return b;
+  }
+  __device__ __forceinline__ void cursor(Lane& b, int e) const {   // a third dependent load
+    if (b.learner) b.s.q = liar_seat_load(b.m.v, e);
+  }
+  __device__ __forceinline__ Lane load(int e) const {
+    Lane b = seat(e);
+    cursor(b, e);
+    return b;
+  }
+  __device__ __forceinline__ bool acted(const Lane& b) const { return b.s.q.acted; }
+  __device__ __forceinline__ void credit(Lane& b, int e, float r, bool done, bool credited) const {
+    if (b.learner) b.m.credit(b.s, e, r, done, credited);
+  }
+  __device__ __forceinline__ void commit(Lane& b, int e) const {
+    if (b.learner) b.m.commit(b.s, e);
+    else alt_acted[e] = 1;
+  }
+  __device__ __forceinline__ void prepare(const Lane& b, int e, bool requested) const {
+    if (b.learner) {
+      b.m.prepare(b.s, e, requested);
+    } else {
+      can[e] = 0;
+      es_alt[e] = 0.f;
+    }
+  }
+  // the member that sits at the new game: its cursor of this table is what the opening forward records at
+  __device__ __forceinline__ void on_deal(Lane& b, int e, uint64_t c) const {
+    alt_acted[e] = 0;
+    b.k = pool_resample(b.k, K, resample, pool_seed, c, e);
+    partnerid[e] = b.k;
+    bind(b);
+    cursor(b, e);
+  }
+};
+
 hipError_t launch_pool_bucket(const int* partnerid, const unsigned char* active, int n, int K, const PoolBuckets& b, hipStream_t s);
 hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s);   // ph_policy.hip
 bool pool_fwd_eligible(const NetDims& nd, int n);                     // ph_policy.hip
 hipError_t launch_liar_default_actions(const float* obs, const unsigned char* active, int* actions, int n, hipStream_t s);
-hipError_t launch_pool_after_ego(const PoolStep& s, hipStream_t st);
-hipError_t launch_pool_after_reply(const PoolStep& s, float* ego_rew_row, unsigned long long counter, const unsigned long long* epoch,
-                                   int deal_only, hipStream_t st);
-hipError_t launch_pool_after_opening(const PoolStep& s, hipStream_t st);
 
 }  // namespace ph

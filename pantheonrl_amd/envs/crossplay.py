@@ -17,7 +17,7 @@ import torch as th
 from .. import _native as nat
 from ..ppo import require_mlp_kernels
 from ..spaces import make_spec
-from .vec import FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice
+from .vec import FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice, VecLiarStep
 
 MAX_STEPS_PER_GAME = 7       # 12 bids and a call: at most 7 moves of the ego, whoever opens
 
@@ -99,7 +99,7 @@ class CrossPlayResult:
         return out
 
 
-class VecLiarCrossPlay:
+class VecLiarCrossPlay(VecLiarStep):
     """tester.py:41-63 for a population: n_envs Liar's Dice tables resident on the device, both seats held by members of ONE
     population of M <= 8 frozen 64-64 policies (`FrozenVecPartner`) and scripted players (`VecLiarDefaultPartner`); the same object
     may sit in either seat, or in both.
@@ -120,7 +120,7 @@ class VecLiarCrossPlay:
       atomics: two runs give the same bits.
 
     native=True: one `ph_liar_xplay_step` per step -- three bucket passes, three grouped forwards, three book-keeping launches,
-    whatever M is, no host synchronisation.  native=False: the readable walk -- per-member `ph_policy_forward` /
+    whatever M is, no host synchronisation.  native=False: the readable walk (VecLiarStep) -- per-member `ph_policy_forward` /
     `ph_liar_default_actions`, `VecLiarsDice.player_step`, torch masks, the same counters; bitwise the native step."""
 
     def __init__(self, n_envs: int, members, pairs=None, episodes_per_table: int = 1, seed: int = 0, probegostart: float = 0.5,
@@ -129,9 +129,9 @@ class VecLiarCrossPlay:
         self.pairs = check_pairs(n_envs, len(members), pairs)
         if int(episodes_per_table) < 1:
             raise nat.NativeError("VecLiarCrossPlay: episodes_per_table must be at least 1")
-        self.E, self.G, self.M, self.P = int(n_envs), int(episodes_per_table), len(members), len(self.pairs)
-        self.members, self.native = members, bool(native)
-        self.dev = None
+        self.G, self.M, self.P = int(episodes_per_table), len(members), len(self.pairs)
+        self.members = members
+        dev = None
         for m in members:
             if isinstance(m, VecLiarDefaultPartner):
                 continue
@@ -142,143 +142,65 @@ class VecLiarCrossPlay:
             lay = m.policy.layout
             if (lay.D, lay.A, lay.L) != (30, 2, 19):
                 raise nat.NativeError("VecLiarCrossPlay: every member plays on the Liar's Dice spaces")
-            self.dev = self.dev or m.policy.device
-        self.dev = self.dev or th.device("cuda", th.cuda.current_device())
-        self.ctx = nat.Context(self.dev.index or 0)
+            dev = dev or m.policy.device
+        dev = dev or th.device("cuda", th.cuda.current_device())
+        self.ctx = nat.Context(dev.index or 0)
         self.spec = make_spec(VecLiarsDice.observation_space, VecLiarsDice.action_space)
-        self.env = VecLiarsDice(self.E, self.ctx, self.dev)
-        self.seed, self.probegostart = int(seed), float(probegostart)
+        self._init_game(n_envs, self.ctx, dev, seed, probegostart, native)
         self.pair_of_table = pair_of_tables(self.E, self.P)
         self._seat_members = [sorted(set(self.pairs[:, s].tolist())) for s in (0, 1)]     # who can move at seat 0 / seat 1
-        E, G, dev = self.E, self.G, self.dev
-        u8 = lambda v=0: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
+        E, G = self.E, self.G
         self.ego_id = th.as_tensor(self.pairs[self.pair_of_table, 0].copy()).to(dev)
         self.alt_id = th.as_tensor(self.pairs[self.pair_of_table, 1].copy()).to(dev)
-        self.ego_first = u8()
-        self.obs_ego = th.zeros((E, 30), dtype=th.float32, device=dev)
-        self.obs_alt = th.zeros((E, 30), dtype=th.float32, device=dev)
         self.ego_actions = th.zeros((E, 2), dtype=th.int32, device=dev)
         self.alt_actions = th.zeros((E, 2), dtype=th.int32, device=dev)
         self.games = th.zeros(E, dtype=th.int32, device=dev)
-        self.playing = u8(1)
+        self.playing = th.ones(E, dtype=th.uint8, device=dev)
         self.tables_left = th.full((1,), E, dtype=th.int32, device=dev)
         self.ep_return = th.zeros(E, dtype=th.float32, device=dev)
         self.ep_length = th.zeros(E, dtype=th.int32, device=dev)
         self.returns = th.zeros((E, G), dtype=th.float32, device=dev)
         self.lengths = th.zeros((E, G), dtype=th.int32, device=dev)
         self.stats = th.zeros((self.P, nat.XPLAY_NSTAT), dtype=th.float64, device=dev)
-        self.ones8, self.zeros8 = u8(1), u8(0)
-        self._rows = th.arange(E, device=dev)
-        self.steps_done = 0
-        if self.native:
-            self._build_native()
-            self._done.fill_(1)
-            self._native_call(0, deal_only=True)
-        else:
-            self._deal(self.ones8, 0)
+        self._first_deal()
 
-    def _bind(self):
-        stream = th.cuda.current_stream(self.dev).cuda_stream
-        self.ctx.set_stream(stream)
-        for m in self.members:
-            if isinstance(m, FrozenVecPartner):
-                m.policy.ctx.set_stream(stream)
+    def _contexts(self):
+        return [self.ctx] + [m.policy.ctx for m in self.members if isinstance(m, FrozenVecPartner)]
+
+    def _counters(self, c: int):
+        return 3 * c, 3 * c + 1, 3 * c + 2
 
     # -- the engine-side step ------------------------------------------------------------------------------------------------------
     def _build_native(self) -> None:
-        E, dev, env = self.E, self.dev, self.env
-        f32 = lambda *shape: th.zeros(shape, dtype=th.float32, device=dev)  # noqa: E731
-        u8 = lambda: th.zeros(E, dtype=th.uint8, device=dev)               # noqa: E731
-        self._obs_next, self._rew1, self._rew2 = f32(E, 30), f32(E, 2), f32(E, 2)
-        self._done1, self._done2, self._running = u8(), u8(), u8()
-        self._alt_opens, self._ego_opens, self._done = u8(), u8(), u8()
-        arr = (nat.PhPoolMember * self.M)()
-        for k, m in enumerate(self.members):
-            arr[k].kind = m.kind
-            if isinstance(m, FrozenVecPartner):
-                arr[k].params, arr[k].seed = m.policy.params.data_ptr(), m.policy._seed
-        self._member_arr = arr
         self._pairs_arr = (C.c_int * (2 * self.P))(*[int(v) for v in self.pairs.reshape(-1)])
-        s = nat.PhLiarXplay()
-        s.n, s.spec = E, C.pointer(self.spec)
-        s.hands, s.history, s.nmoves = env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr()
-        s.ego_first, s.dice_seed, s.probegostart = self.ego_first.data_ptr(), self.seed, self.probegostart
-        s.members, s.n_members = arr, self.M
+        s = self._fill_game(nat.PhLiarXplay(), book=False)
+        s.spec = C.pointer(self.spec)
+        s.members, s.n_members = self._member_array(self.members), self.M
         s.pairs, s.n_pairs, s.episodes_per_table = self._pairs_arr, self.P, self.G
-        s.ego_id, s.alt_id = self.ego_id.data_ptr(), self.alt_id.data_ptr()
-        s.ego_actions, s.alt_actions = self.ego_actions.data_ptr(), self.alt_actions.data_ptr()
-        s.obs_ego, s.obs_alt = self.obs_ego.data_ptr(), self.obs_alt.data_ptr()
-        s.games, s.playing, s.tables_left = self.games.data_ptr(), self.playing.data_ptr(), self.tables_left.data_ptr()
-        s.ep_return, s.ep_length = self.ep_return.data_ptr(), self.ep_length.data_ptr()
-        s.returns, s.lengths = self.returns.data_ptr(), self.lengths.data_ptr()
-        s.obs_next, s.rew1, s.rew2 = self._obs_next.data_ptr(), self._rew1.data_ptr(), self._rew2.data_ptr()
-        s.done1, s.done2, s.running = self._done1.data_ptr(), self._done2.data_ptr(), self._running.data_ptr()
-        s.alt_opens, s.ego_opens, s.done = self._alt_opens.data_ptr(), self._ego_opens.data_ptr(), self._done.data_ptr()
+        for name in ("ego_id", "alt_id", "ego_actions", "alt_actions", "games", "playing", "tables_left", "ep_return", "ep_length",
+                     "returns", "lengths"):
+            setattr(s, name, getattr(self, name).data_ptr())
         self._desc = s
 
     def _native_call(self, counter: int, deal_only: bool = False) -> None:
         self._bind()
         nat.check(self.ctx.lib.ph_liar_xplay_step(self.ctx.handle, C.byref(self._desc), int(counter), int(deal_only)))
 
-    # -- the walk: per-member calls with torch masks -------------------------------------------------------------------------------
+    # -- the walk's hooks ----------------------------------------------------------------------------------------------------------
     def _seat_act(self, seat: int, obs: th.Tensor, mask: th.Tensor, counter: int) -> th.Tensor:
         """the forward of every member that can sit at `seat`, Philox counter `counter`; member k's move lands in the tables of
         `mask` it holds that seat of"""
         ids, out = (self.ego_id, self.ego_actions) if seat == 0 else (self.alt_id, self.alt_actions)
-        for k in self._seat_members[seat]:
-            m = self.members[k]
-            mk = (mask.bool() & (ids == k)).to(th.uint8)
-            if isinstance(m, VecLiarDefaultPartner):
-                m.get_action(obs, mk, out, self.ctx)
-                continue
-            m.policy._counter = counter - 1
-            a = m.get_action(obs, mk)
-            out.copy_(th.where(mk.bool()[:, None], a, out))
-        return out
+        return self._members_act(self._seat_members[seat], ids, obs, mask, counter, out)
 
-    def _deal(self, reset_mask: th.Tensor, c: int) -> None:
-        """deal the tables in reset_mask; where seat 1 opens, it moves once; seat 0's observation of every fresh table"""
-        env, lib, h = self.env, self.ctx.lib, self.ctx.handle
-        self._bind()
-        nat.check(lib.ph_liar_reset(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                    reset_mask.data_ptr(), self.ego_first.data_ptr(), self.seed, int(c),
-                                    self.probegostart, self.E))
-        rm = reset_mask.bool()
-        alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
-        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                  self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
-        a_alt = self._seat_act(1, self.obs_alt, alt_opens, 3 * c + 2)
-        env.player_step(a_alt, self.zeros8, alt_opens)              # obs_next = seat 0's observation in those tables
-        self.obs_ego.copy_(th.where(alt_opens.bool()[:, None], env.obs_next, self.obs_ego))
-        ego_opens = (rm & self.ego_first.bool()).to(th.uint8)
-        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                  self.ones8.data_ptr(), ego_opens.data_ptr(), self.obs_ego.data_ptr(), self.E))
+    def _live(self) -> th.Tensor:
+        return self.playing
 
-    # -- one vectorised MultiAgentEnv.step of the playing tables -------------------------------------------------------------------
-    def step(self) -> None:
-        self.steps_done += 1
-        c = self.steps_done
-        if self.native:
-            self._native_call(c)
-            return
-        env, G = self.env, self.G
-        self._bind()
-        playing = self.playing.bool()
-        a_ego = self._seat_act(0, self.obs_ego, self.playing, 3 * c)
-        obs_alt, rew1, done1 = env.player_step(a_ego, self.ones8, self.playing)
-        rew1, done1 = rew1.clone(), done1.bool() & playing
-        running = playing & ~done1
-        running8 = running.to(th.uint8)
-        a_alt = self._seat_act(1, obs_alt, running8, 3 * c + 1)
-        obs_ego, rew2, done2 = env.player_step(a_alt, self.zeros8, running8)
-        done2 = done2.bool() & running
-        done = done1 | done2
-        # the ego collects both transitions of the step (multiagentenv.py:201-202)
-        step_rew = rew1[:, 0] + th.where(running, rew2[:, 0], th.zeros_like(rew2[:, 0]))
-        self.ep_return.copy_(th.where(playing, self.ep_return + step_rew, self.ep_return))
+    def _game_end(self, reward: th.Tensor, done: th.Tensor) -> th.Tensor:
+        """the step's return and length; at the end of a game the log entry, the count, the budget -> the tables dealt again"""
+        G, playing = self.G, self.playing.bool()
+        self.ep_return.copy_(th.where(playing, self.ep_return + reward, self.ep_return))
         self.ep_length.add_(playing.to(th.int32))
-        self.obs_ego.copy_(th.where((running & ~done2)[:, None], obs_ego, self.obs_ego))
-        # ends of games: the log entry, the count, the budget
         slot = self.games.clamp(max=G - 1).long()[:, None]
         self.returns.scatter_(1, slot, th.where(done, self.ep_return, self.returns.gather(1, slot)[:, 0])[:, None])
         self.lengths.scatter_(1, slot, th.where(done, self.ep_length, self.lengths.gather(1, slot)[:, 0])[:, None])
@@ -288,7 +210,15 @@ class VecLiarCrossPlay:
         spent = done & (self.games >= G)
         self.playing.copy_((playing & ~spent).to(th.uint8))
         self.tables_left.sub_(spent.sum().to(th.int32))
-        self._deal((done & ~spent).to(th.uint8), c)
+        return (done & ~spent).to(th.uint8)
+
+    # -- one vectorised MultiAgentEnv.step of the playing tables -------------------------------------------------------------------
+    def step(self) -> None:
+        self.steps_done += 1
+        if self.native:
+            self._native_call(self.steps_done)
+        else:
+            self._walk(self.steps_done)
 
     def left(self) -> int:
         """tables with budget left (synchronises)"""

@@ -239,194 +239,6 @@ def seat_arch(agent):
     return C.pointer(pol.arch) if is_tower(pol) else None
 
 
-class VecLiarSelfPlay:
-    """`trainer.py LiarsDice-v0 PPO PPO` (BASELINE config 2) with n_envs tables resident on the device.
-
-    One vectorised step is one `MultiAgentEnv.step` of every table from the ego's point of view (multiagentenv.py:
-    172-215): the ego moves, the partner replies in the tables that are still running, finished tables are re-dealt and --
-    where the partner opens the new game -- the partner moves once more, so every table is back at the ego's turn.
-    The ego is a rectangular VecOnPolicyAgent (one row per table per step); the partner is ragged.
-
-    native=True (default): the whole step is ONE engine call (`ph_liar_selfplay_step`: the three policy forwards and ONE
-    book-keeping launch after each -- a table's state is touched by its own lane only -- every mask stays on the device, no host
-    synchronisation).  native=False walks the same step with the per-call entry points and torch masks -- the
-    readable statement of the protocol, and the bit-exact cross-check of the native step (both use the same RNG counters:
-    step c -> ego forward c, partner forwards 2c and 2c+1, dice c)."""
-
-    def __init__(self, n_envs: int, ego: VecOnPolicyAgent, alt: RaggedVecOnPolicyAgent, seed: int = 0,
-                 probegostart: float = 0.5, native: bool = True):
-        self.E, self.ego, self.alt, self.native = n_envs, ego, alt, bool(native)
-        pol = ego.model.policy
-        self.dev = pol.device
-        self.env = VecLiarsDice(n_envs, pol.ctx, self.dev)
-        self.seed, self.counter, self.probegostart = int(seed), 0, float(probegostart)
-        E, dev = n_envs, self.dev
-        u8 = lambda v=0: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
-        self.ego_first = u8()
-        self.obs_ego = th.zeros((E, 30), dtype=th.float32, device=dev)
-        self.obs_alt = th.zeros((E, 30), dtype=th.float32, device=dev)
-        self.alt_acted = u8()                                      # should_update of the partner seat, per table
-        self.ones8, self.zeros8 = u8(1), u8(0)
-        self._episodes_dev = th.zeros(1, dtype=th.int64, device=dev)
-        self.steps_done = 0
-        import os
-        self.persistent = self.native and os.environ.get("LIAR_PERSISTENT", "1") != "0"   # whole rollouts as one launch
-        self._archs = (seat_arch(ego), seat_arch(alt))        # a tower in either seat: the `_arch` step, launch by launch
-        self.towers = any(a is not None for a in self._archs)
-        if self.towers:
-            self.persistent = False                           # ph_liar_selfplay_rollout is built around the 64-wide blocks
-        if self.native:
-            self._build_native()
-            self._done.fill_(1)
-            self._native_call(0, deal_only=True)
-        else:
-            self._deal(self.ones8, 0)
-
-    @property
-    def episodes(self) -> int:
-        return int(self._episodes_dev.item())
-
-    # -- helpers -----------------------------------------------------------------------------------------------------
-    def _bind(self):
-        stream = th.cuda.current_stream(self.dev).cuda_stream
-        self.env.ctx.set_stream(stream)
-        for agent in (self.ego, self.alt):
-            agent.model.policy.ctx.set_stream(stream)
-
-    def _build_native(self) -> None:
-        E, dev, env, ego, alt = self.E, self.dev, self.env, self.ego, self.alt
-        f32 = lambda *shape: th.zeros(shape, dtype=th.float32, device=dev)  # noqa: E731
-        u8 = lambda: th.zeros(E, dtype=th.uint8, device=dev)               # noqa: E731
-        self._obs_next, self._rew1, self._rew2, self._es_alt = f32(E, 30), f32(E, 2), f32(E, 2), f32(E)
-        self._done1, self._done2, self._running, self._can = u8(), u8(), u8(), u8()
-        self._alt_opens, self._ego_opens, self._done = u8(), u8(), u8()
-        ego._last_episode_starts = ego._last_episode_starts.clone()    # updated in place by the step from here on
-        s = nat.PhLiarSelfPlay()
-        s.n, s.spec = E, C.pointer(ego.model.policy.spec)
-        s.hands, s.history, s.nmoves = env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr()
-        s.ego_first, s.dice_seed, s.probegostart = self.ego_first.data_ptr(), self.seed, self.probegostart
-        pe, pa = ego.model.policy, alt.model.policy
-        self._ego_rbc, self._alt_rbc = ego.model.rollout_buffer.c_struct(), alt.model.rollout_buffer.c_struct()
-        s.ego_params, s.ego_rb, s.ego_actions = pe.params.data_ptr(), C.pointer(self._ego_rbc), ego.actions.data_ptr()
-        s.ego_values, s.ego_log_probs = ego.values.data_ptr(), ego.log_probs.data_ptr()
-        s.ego_episode_start, s.ego_seed = ego._last_episode_starts.data_ptr(), pe._seed
-        s.alt_params, s.alt_rb, s.alt_actions = pa.params.data_ptr(), C.pointer(self._alt_rbc), alt.actions.data_ptr()
-        s.alt_values, s.alt_log_probs, s.alt_pos = alt.values.data_ptr(), alt.log_probs.data_ptr(), alt.pos.data_ptr()
-        s.alt_boundary, s.alt_term, s.alt_open = alt.boundary.data_ptr(), alt.term.data_ptr(), alt.open.data_ptr()
-        s.alt_acted, s.alt_seed = self.alt_acted.data_ptr(), pa._seed
-        s.obs_ego, s.obs_alt, s.episodes = self.obs_ego.data_ptr(), self.obs_alt.data_ptr(), self._episodes_dev.data_ptr()
-        s.obs_next, s.rew1, s.rew2, s.es_alt = (t.data_ptr() for t in (self._obs_next, self._rew1, self._rew2, self._es_alt))
-        s.done1, s.done2, s.running, s.can = (t.data_ptr() for t in (self._done1, self._done2, self._running, self._can))
-        s.alt_opens, s.ego_opens, s.done = self._alt_opens.data_ptr(), self._ego_opens.data_ptr(), self._done.data_ptr()
-        s.zeros8, s.ones8 = self.zeros8.data_ptr(), self.ones8.data_ptr()
-        self._desc = s
-
-    def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
-        self._bind()
-        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
-        pos = int(rb.pos if ego_pos < 0 else ego_pos)
-        if self.towers:
-            nat.check(ctx.lib.ph_liar_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
-                                                         int(counter), int(deal_only)))
-            return
-        nat.check(ctx.lib.ph_liar_selfplay_step(ctx.handle, C.byref(self._desc), pos, int(counter), int(deal_only)))
-
-    def rollout_persistent(self, n_steps: int, first_counter: int, ego_pos: int = 0) -> None:
-        """n_steps vectorised steps as ONE persistent launch (`ph_liar_selfplay_rollout`: one workgroup owns 16 tables for the
-        whole rollout; bitwise the result of n_steps `_native_call`s with counters first_counter, first_counter + 1, ...)"""
-        if self.towers:
-            raise nat.NativeError("VecLiarSelfPlay.rollout_persistent: a net_arch tower policy does not run on the fused MLP kernels "
-                                  "of the persistent rollout; use step()")
-        self._bind()
-        ctx = self.env.ctx
-        nat.check(ctx.lib.ph_liar_selfplay_rollout(ctx.handle, C.byref(self._desc), int(ego_pos), int(n_steps),
-                                                   int(first_counter)))
-
-    def _deal(self, reset_mask: th.Tensor, c: int) -> None:
-        """(reference path) re-deal the tables in reset_mask; where the partner opens, it moves once"""
-        env, lib, h = self.env, self.env.ctx.lib, self.env.ctx.handle
-        self._bind()
-        nat.check(lib.ph_liar_reset(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                    reset_mask.data_ptr(), self.ego_first.data_ptr(), self.seed, int(c),
-                                    self.probegostart, self.E))
-        rm = reset_mask.bool()
-        self.alt_acted.copy_(th.where(rm, self.zeros8, self.alt_acted))
-        alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
-        # partner's opening observation and move
-        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                  self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
-        self.alt.model.policy._counter = 2 * c                      # the forward below draws with counter 2c + 1
-        a_alt = self.alt.get_action(self.obs_alt, alt_opens)
-        self.alt_acted.copy_((self.alt_acted.bool() | alt_opens.bool()).to(th.uint8))
-        env.player_step(a_alt, self.zeros8, alt_opens)              # obs_next = ego's observation in those tables
-        self.obs_ego.copy_(th.where(alt_opens.bool()[:, None], env.obs_next, self.obs_ego))
-        ego_opens = (rm & self.ego_first.bool()).to(th.uint8)
-        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                  self.ones8.data_ptr(), ego_opens.data_ptr(), self.obs_ego.data_ptr(), self.E))
-
-    # -- one vectorised MultiAgentEnv.step ---------------------------------------------------------------------------------
-    def step(self):
-        """-> (E,) uint8 device tensor: tables whose game ended in this step"""
-        ego, alt = self.ego, self.alt
-        self.steps_done += 1
-        c = self.steps_done
-        if self.native:
-            model, rb = ego.model, ego.model.rollout_buffer
-            if ego.n_steps >= model.n_steps:
-                ego.learn_from_buffer()
-            self._native_call(c)
-            rb.pos += 1
-            rb.full = rb.pos == rb.buffer_size
-            ego.n_steps += 1
-            ego.num_timesteps += self.E
-            alt.num_timesteps += self.E
-            return self._done
-        env = self.env
-        self._bind()
-        ego.model.policy._counter = c - 1
-        a_ego = ego.get_action(self.obs_ego)                                   # every table is at the ego's turn
-        obs_alt, rew1, done1 = env.player_step(a_ego, self.ones8, None)
-        rew1, done1 = rew1.clone(), done1.clone()
-        running = (~done1.bool()).to(th.uint8)
-        # partners that already acted this game are credited this transition (multiagentenv.py:163-170)
-        alt.update(rew1[:, 1].contiguous(), done1, self.alt_acted)
-        self.obs_alt.copy_(th.where(running.bool()[:, None], obs_alt, self.obs_alt))
-        # partner replies where the game goes on
-        alt.model.policy._counter = 2 * c - 1
-        a_alt = alt.get_action(self.obs_alt, running)
-        self.alt_acted.copy_((self.alt_acted.bool() | running.bool()).to(th.uint8))
-        obs_ego, rew2, done2 = env.player_step(a_alt, self.zeros8, running)
-        rew2 = th.where(running.bool()[:, None], rew2, th.zeros_like(rew2))
-        done2 = (done2.bool() & running.bool())
-        alt.update(rew2[:, 1].contiguous(), done2.to(th.uint8), running)
-        done = done1.bool() | done2
-        # the ego collects both transitions of the step; the last done wins (agents.py:44-47)
-        ego.update((rew1[:, 0] + rew2[:, 0]).contiguous(), done.to(th.float32))
-        ego.flush_rewards()
-        self.obs_ego.copy_(th.where((running.bool() & ~done2)[:, None], obs_ego, self.obs_ego))
-        done8 = done.to(th.uint8)
-        self._episodes_dev += done8.sum()
-        self._deal(done8, c)
-        return done8
-
-    def rollout_and_learn(self, n_steps: int) -> None:
-        """n_steps vectorised steps, the ego's update, and the partner's whenever all its columns are full"""
-        ego, rb = self.ego, self.ego.model.rollout_buffer
-        if self.native and self.persistent and rb.pos == 0 and n_steps == rb.buffer_size and ego.n_steps == 0:
-            self.rollout_persistent(n_steps, self.steps_done + 1, 0)
-            self.steps_done += n_steps
-            rb.pos, rb.full = n_steps, True
-            ego.n_steps += n_steps
-            ego.num_timesteps += n_steps * self.E
-            self.alt.num_timesteps += n_steps * self.E
-        else:
-            for _ in range(n_steps):
-                self.step()
-        self.ego.learn_from_buffer()
-        if self.alt.full():
-            self.alt.learn_from_buffer()
-
-
 # ---- a pool of partners at seat 1 (MultiAgentEnv.add_partner_agent / resample_*, multiagentenv.py:92-147) -----------------------
 POOL_SEED_SALT = 0x9001C0DE9001C0DE          # the resample stream's own Philox key: pool seed = dice seed ^ this constant
 POOL_RESAMPLE_BLOCK = 101                    # Philox block of the resample word (the dice use blocks 0..2, the first mover 100)
@@ -501,7 +313,328 @@ class VecLiarDefaultPartner:
         return None
 
 
-class VecLiarPartnerPool:
+# ---- Liar's Dice resident on the device: self-play, a pool of partners at seat 1, cross-play evaluation ------------------------
+class VecLiarStep:
+    """What the three device-resident Liar's Dice drivers share -- VecLiarSelfPlay, VecLiarPartnerPool and (envs/crossplay.py)
+    VecLiarCrossPlay.  One vectorised step is one protocol:
+
+        seat-0 forward | after_ego | seat-1 forward (reply) | after_reply (ends of games, re-deal) | seat-1 forward (openers) |
+        after_opening
+
+    native=True runs it as ONE engine call per step; native=False walks it with the per-call entry points and torch masks -- the
+    readable statement of the protocol, written once here (`_walk` and `_deal`), and the bit-exact cross-check of the native step.
+    The base owns the game (`env`), `ego_first`, `obs_ego` / `obs_alt`, the constant masks, the native step's scratch and the part
+    of its description every mode fills the same way.  A mode supplies
+      * `_contexts()`: the engine contexts its calls run on;
+      * `_counters(c)`: the Philox counters of step c's three forwards;
+      * `_seat_act(seat, obs, mask, counter)`: who moves at a seat under a mask and a counter;
+      * `_live()`: the tables that take part (None = all);
+      * `_credit(reward, done, replied)` / `_acted(mask)`: seat 1's book (training);
+      * `_on_deal(rm, c)`: what happens at a deal besides the dice;
+      * `_game_end(reward, done)`: what the end of a game does -> the tables to deal again;
+      * `_build_native()` / `_native_call()`: its description and entry point."""
+
+    def _init_game(self, n_envs: int, ctx: nat.Context, dev, seed: int, probegostart: float, native: bool) -> None:
+        self.E, self.dev, self.native = int(n_envs), dev, bool(native)
+        self.env = VecLiarsDice(self.E, ctx, dev)
+        self.seed, self.probegostart = int(seed), float(probegostart)
+        u8 = lambda v=0: th.full((self.E,), v, dtype=th.uint8, device=dev)  # noqa: E731
+        self.ego_first = u8()
+        self.obs_ego = th.zeros((self.E, 30), dtype=th.float32, device=dev)
+        self.obs_alt = th.zeros((self.E, 30), dtype=th.float32, device=dev)
+        self.ones8, self.zeros8 = u8(1), u8(0)
+        self.steps_done = 0
+        self._ctxs = tuple(dict.fromkeys(self._contexts()))     # each engine context once: `_bind` runs in front of every step
+
+    def _first_deal(self) -> None:
+        """the constructor's deal: step 0's re-deal half for every table"""
+        if self.native:
+            self._build_native()
+            self._done.fill_(1)
+            self._native_call(0, deal_only=True)
+        else:
+            self._deal(self.ones8, 0)
+
+    def _bind(self):
+        stream = th.cuda.current_stream(self.dev).cuda_stream
+        for ctx in self._ctxs:
+            ctx.set_stream(stream)
+
+    @staticmethod
+    def _policy_of(agent):
+        """the policy a pool / population member plays with (None: the scripted player)"""
+        if isinstance(agent, VecLiarDefaultPartner):
+            return None
+        return agent.policy if isinstance(agent, FrozenVecPartner) else agent.model.policy
+
+    # -- the engine-side step: what every description holds -------------------------------------------------------------------------
+    def _fill_game(self, s, book: bool):
+        """the native step's scratch, and the game block of its description `s` (the same-named fields of PhLiarSelfPlay /
+        PhLiarPool / PhLiarXplay); `book`: seat 1 records, so the forwards need `can` / `es_alt`"""
+        E, dev, env = self.E, self.dev, self.env
+        f32 = lambda *shape: th.zeros(shape, dtype=th.float32, device=dev)  # noqa: E731
+        u8 = lambda: th.zeros(E, dtype=th.uint8, device=dev)               # noqa: E731
+        self._obs_next, self._rew1, self._rew2 = f32(E, 30), f32(E, 2), f32(E, 2)
+        self._done1, self._done2, self._running = u8(), u8(), u8()
+        self._alt_opens, self._ego_opens, self._done = u8(), u8(), u8()
+        s.n, s.dice_seed, s.probegostart = E, self.seed, self.probegostart
+        s.hands, s.history, s.nmoves, s.ego_first = (t.data_ptr() for t in (env.hands, env.history, env.nmoves, self.ego_first))
+        s.obs_ego, s.obs_alt = self.obs_ego.data_ptr(), self.obs_alt.data_ptr()
+        for name in ("obs_next", "rew1", "rew2", "done1", "done2", "running", "alt_opens", "ego_opens", "done"):
+            setattr(s, name, getattr(self, "_" + name).data_ptr())
+        if book:
+            self._es_alt, self._can = f32(E), u8()
+            s.es_alt, s.can = self._es_alt.data_ptr(), self._can.data_ptr()
+        return s
+
+    def _member_array(self, members):
+        """the PhPoolMember array of a pool / population (kept alive with the learners' buffer records in `_member_rbc`)"""
+        self._member_rbc = []
+        arr = (nat.PhPoolMember * len(members))()
+        for c, m in zip(arr, members):
+            learner = isinstance(m, RaggedVecOnPolicyAgent)
+            c.kind = nat.PH_POOL_LEARNER if learner else m.kind
+            p = self._policy_of(m)
+            if p is None:
+                continue
+            c.params, c.seed = p.params.data_ptr(), p._seed
+            if learner:
+                rbc = m.model.rollout_buffer.c_struct()
+                self._member_rbc.append(rbc)
+                c.rb = C.pointer(rbc)
+                c.pos, c.boundary, c.term, c.open = (t.data_ptr() for t in (m.pos, m.boundary, m.term, m.open))
+                c.values, c.log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
+        self._member_arr = arr
+        return arr
+
+    # -- the walk: the per-call entry points with torch masks ------------------------------------------------------------------------
+    def _members_act(self, which, ids: th.Tensor, obs: th.Tensor, mask: th.Tensor, counter: int, out: th.Tensor) -> th.Tensor:
+        """the forward of every member in `which` with Philox counter `counter`; member k's move lands in the tables of `mask`
+        where ids == k"""
+        for k in which:
+            m = self.members[k]
+            mk = (mask.bool() & (ids == k)).to(th.uint8)
+            if isinstance(m, VecLiarDefaultPartner):
+                m.get_action(obs, mk, out, self.env.ctx)
+                continue
+            self._policy_of(m)._counter = counter - 1
+            a = m.get_action(obs, mk)
+            out.copy_(th.where(mk.bool()[:, None], a, out))
+        return out
+
+    def _live(self):
+        return None
+
+    def _credit(self, reward: th.Tensor, done: th.Tensor, replied) -> None:
+        return None
+
+    def _acted(self, mask: th.Tensor) -> None:
+        return None
+
+    def _on_deal(self, rm: th.Tensor, c: int) -> None:
+        return None
+
+    def _deal(self, reset_mask: th.Tensor, c: int) -> None:
+        """deal the tables in reset_mask; where seat 1 opens, it moves once; seat 0's observation of every fresh table"""
+        env, lib, h = self.env, self.env.ctx.lib, self.env.ctx.handle
+        game = (env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr())
+        self._bind()
+        nat.check(lib.ph_liar_reset(h, *game, reset_mask.data_ptr(), self.ego_first.data_ptr(), self.seed, int(c), self.probegostart,
+                                    self.E))
+        rm = reset_mask.bool()
+        self._on_deal(rm, c)
+        alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
+        nat.check(lib.ph_liar_obs(h, *game, self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
+        a_alt = self._seat_act(1, self.obs_alt, alt_opens, self._counters(c)[2])
+        self._acted(alt_opens)
+        env.player_step(a_alt, self.zeros8, alt_opens)              # obs_next = seat 0's observation in those tables
+        self.obs_ego.copy_(th.where(alt_opens.bool()[:, None], env.obs_next, self.obs_ego))
+        ego_opens = (rm & self.ego_first.bool()).to(th.uint8)
+        nat.check(lib.ph_liar_obs(h, *game, self.ones8.data_ptr(), ego_opens.data_ptr(), self.obs_ego.data_ptr(), self.E))
+
+    def _walk(self, c: int) -> th.Tensor:
+        """one MultiAgentEnv.step of every live table -> (E,) bool: tables whose game ended in this step"""
+        env = self.env
+        self._bind()
+        k = self._counters(c)
+        live = self._live()
+        a_ego = self._seat_act(0, self.obs_ego, live, k[0])                    # every live table is at seat 0's turn
+        obs_alt, rew1, done1 = env.player_step(a_ego, self.ones8, live)
+        rew1, done1 = rew1.clone(), done1.bool() if live is None else done1.bool() & live.bool()
+        running = ~done1 if live is None else live.bool() & ~done1
+        running8 = running.to(th.uint8)
+        # a seat 1 that already acted this game is credited this transition (multiagentenv.py:163-170)
+        self._credit(rew1[:, 1].contiguous(), done1.to(th.uint8), None)
+        a_alt = self._seat_act(1, obs_alt, running8, k[1])                     # seat 1 replies where the game goes on
+        self._acted(running8)
+        obs_ego, rew2, done2 = env.player_step(a_alt, self.zeros8, running8)
+        rew2 = th.where(running[:, None], rew2, th.zeros_like(rew2))
+        done2 = done2.bool() & running
+        self._credit(rew2[:, 1].contiguous(), done2.to(th.uint8), running8)
+        done = done1 | done2
+        self.obs_ego.copy_(th.where((running & ~done2)[:, None], obs_ego, self.obs_ego))
+        # seat 0 collects both transitions of the step; the last done wins (agents.py:44-47, multiagentenv.py:201-202)
+        self._deal(self._game_end((rew1[:, 0] + rew2[:, 0]).contiguous(), done), c)
+        return done
+
+
+class VecLiarTraining(VecLiarStep):
+    """The training modes: a rectangular PPO ego (VecOnPolicyAgent) at seat 0 of every table, a book at seat 1 (`alt_acted`: seat 1
+    has moved in the table's current game -- the partner's should_update), and the end of a game adds to the ego's reward row,
+    flags its next episode start and counts `episodes`.  RNG counters of step c: ego forward c, seat-1 forwards 2c and 2c + 1,
+    dice c."""
+
+    def _init_training(self, n_envs: int, ego: VecOnPolicyAgent, seed: int, probegostart: float, native: bool) -> None:
+        self.ego = ego
+        pol = ego.model.policy
+        self._init_game(n_envs, pol.ctx, pol.device, seed, probegostart, native)
+        self.alt_acted = th.zeros(self.E, dtype=th.uint8, device=self.dev)
+        self._episodes_dev = th.zeros(1, dtype=th.int64, device=self.dev)
+
+    @property
+    def episodes(self) -> int:
+        return int(self._episodes_dev.item())
+
+    def _counters(self, c: int):
+        return c, 2 * c, 2 * c + 1
+
+    def _fill_training(self, s):
+        """the game and ego blocks of a PhLiarSelfPlay / PhLiarPool"""
+        ego, pe = self.ego, self.ego.model.policy
+        self._fill_game(s, book=True)
+        ego._last_episode_starts = ego._last_episode_starts.clone()    # updated in place by the step from here on
+        self._ego_rbc = ego.model.rollout_buffer.c_struct()
+        s.spec, s.ego_params, s.ego_rb, s.ego_seed = C.pointer(pe.spec), pe.params.data_ptr(), C.pointer(self._ego_rbc), pe._seed
+        s.ego_actions, s.ego_values, s.ego_log_probs = ego.actions.data_ptr(), ego.values.data_ptr(), ego.log_probs.data_ptr()
+        s.ego_episode_start, s.alt_acted = ego._last_episode_starts.data_ptr(), self.alt_acted.data_ptr()
+        s.episodes = self._episodes_dev.data_ptr()
+        return s
+
+    def _ego_act(self, counter: int) -> th.Tensor:
+        self.ego.model.policy._counter = counter - 1
+        return self.ego.get_action(self.obs_ego)
+
+    def _acted(self, mask: th.Tensor) -> None:
+        self.alt_acted.copy_((self.alt_acted.bool() | mask.bool()).to(th.uint8))
+
+    def _on_deal(self, rm: th.Tensor, c: int) -> None:
+        self.alt_acted.copy_(th.where(rm, self.zeros8, self.alt_acted))
+
+    def _game_end(self, reward: th.Tensor, done: th.Tensor) -> th.Tensor:
+        self.ego.update(reward, done.to(th.float32))
+        self.ego.flush_rewards()
+        done8 = done.to(th.uint8)
+        self._episodes_dev += done8.sum()
+        return done8
+
+    # -- one vectorised MultiAgentEnv.step ---------------------------------------------------------------------------------
+    def step(self):
+        """-> (E,) uint8 device tensor: tables whose game ended in this step"""
+        ego = self.ego
+        self.steps_done += 1
+        c = self.steps_done
+        if not self.native:
+            return self._walk(c).to(th.uint8)
+        model, rb = ego.model, ego.model.rollout_buffer
+        if ego.n_steps >= model.n_steps:
+            ego.learn_from_buffer()
+        self._native_call(c)
+        rb.pos += 1
+        rb.full = rb.pos == rb.buffer_size
+        ego.n_steps += 1
+        ego.num_timesteps += self.E
+        for m in self.learners:
+            m.num_timesteps += self.E
+        return self._done
+
+
+class VecLiarSelfPlay(VecLiarTraining):
+    """`trainer.py LiarsDice-v0 PPO PPO` (BASELINE config 2) with n_envs tables resident on the device.
+
+    One vectorised step is one `MultiAgentEnv.step` of every table from the ego's point of view (multiagentenv.py:
+    172-215): the ego moves, the partner replies in the tables that are still running, finished tables are re-dealt and --
+    where the partner opens the new game -- the partner moves once more, so every table is back at the ego's turn.
+    The ego is a rectangular VecOnPolicyAgent (one row per table per step); the partner is ragged.
+
+    native=True (default): the whole step is ONE engine call (`ph_liar_selfplay_step`: the three policy forwards and ONE
+    book-keeping launch after each -- a table's state is touched by its own lane only -- every mask stays on the device, no host
+    synchronisation).  native=False walks the same step with the per-call entry points and torch masks (VecLiarStep)."""
+
+    def __init__(self, n_envs: int, ego: VecOnPolicyAgent, alt: RaggedVecOnPolicyAgent, seed: int = 0,
+                 probegostart: float = 0.5, native: bool = True):
+        self.alt, self.learners, self.counter = alt, [alt], 0
+        self._init_training(n_envs, ego, seed, probegostart, native)
+        import os
+        self.persistent = self.native and os.environ.get("LIAR_PERSISTENT", "1") != "0"   # whole rollouts as one launch
+        self._archs = (seat_arch(ego), seat_arch(alt))        # a tower in either seat: the `_arch` step, launch by launch
+        self.towers = any(a is not None for a in self._archs)
+        if self.towers:
+            self.persistent = False                           # ph_liar_selfplay_rollout is built around the 64-wide blocks
+        self._first_deal()
+
+    def _contexts(self):
+        return self.env.ctx, self.ego.model.policy.ctx, self.alt.model.policy.ctx
+
+    def _build_native(self) -> None:
+        alt, pa = self.alt, self.alt.model.policy
+        s = self._fill_training(nat.PhLiarSelfPlay())
+        self._alt_rbc = alt.model.rollout_buffer.c_struct()
+        s.alt_params, s.alt_rb, s.alt_actions, s.alt_seed = pa.params.data_ptr(), C.pointer(self._alt_rbc), alt.actions.data_ptr(), pa._seed
+        s.alt_values, s.alt_log_probs, s.alt_pos = alt.values.data_ptr(), alt.log_probs.data_ptr(), alt.pos.data_ptr()
+        s.alt_boundary, s.alt_term, s.alt_open = alt.boundary.data_ptr(), alt.term.data_ptr(), alt.open.data_ptr()
+        s.zeros8, s.ones8 = self.zeros8.data_ptr(), self.ones8.data_ptr()
+        self._desc = s
+
+    def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
+        self._bind()
+        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
+        pos = int(rb.pos if ego_pos < 0 else ego_pos)
+        if self.towers:
+            nat.check(ctx.lib.ph_liar_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
+                                                         int(counter), int(deal_only)))
+            return
+        nat.check(ctx.lib.ph_liar_selfplay_step(ctx.handle, C.byref(self._desc), pos, int(counter), int(deal_only)))
+
+    def rollout_persistent(self, n_steps: int, first_counter: int, ego_pos: int = 0) -> None:
+        """n_steps vectorised steps as ONE persistent launch (`ph_liar_selfplay_rollout`: one workgroup owns 16 tables for the
+        whole rollout; bitwise the result of n_steps `_native_call`s with counters first_counter, first_counter + 1, ...)"""
+        if self.towers:
+            raise nat.NativeError("VecLiarSelfPlay.rollout_persistent: a net_arch tower policy does not run on the fused MLP kernels "
+                                  "of the persistent rollout; use step()")
+        self._bind()
+        ctx = self.env.ctx
+        nat.check(ctx.lib.ph_liar_selfplay_rollout(ctx.handle, C.byref(self._desc), int(ego_pos), int(n_steps),
+                                                   int(first_counter)))
+
+    # -- the walk's hooks -------------------------------------------------------------------------------------------------------------
+    def _seat_act(self, seat: int, obs: th.Tensor, mask, counter: int) -> th.Tensor:
+        if seat == 0:
+            return self._ego_act(counter)
+        self.alt.model.policy._counter = counter - 1
+        return self.alt.get_action(obs, mask)
+
+    def _credit(self, reward: th.Tensor, done: th.Tensor, replied) -> None:
+        self.alt.update(reward, done, self.alt_acted if replied is None else replied)
+
+    def rollout_and_learn(self, n_steps: int) -> None:
+        """n_steps vectorised steps, the ego's update, and the partner's whenever all its columns are full"""
+        ego, rb = self.ego, self.ego.model.rollout_buffer
+        if self.native and self.persistent and rb.pos == 0 and n_steps == rb.buffer_size and ego.n_steps == 0:
+            self.rollout_persistent(n_steps, self.steps_done + 1, 0)
+            self.steps_done += n_steps
+            rb.pos, rb.full = n_steps, True
+            ego.n_steps += n_steps
+            ego.num_timesteps += n_steps * self.E
+            self.alt.num_timesteps += n_steps * self.E
+        else:
+            for _ in range(n_steps):
+                self.step()
+        self.ego.learn_from_buffer()
+        if self.alt.full():
+            self.alt.learn_from_buffer()
+
+
+class VecLiarPartnerPool(VecLiarTraining):
     """`trainer.py LiarsDice-v0 PPO <alt>+ --n-envs E`: n_envs Liar's Dice tables resident on the device, seat 1 of every table
     held by one of K <= 8 pool members -- learners (RaggedVecOnPolicyAgent), frozen policies (FrozenVecPartner) or the scripted
     player (VecLiarDefaultPartner).  `partnerid[e]` names table e's member; it is resampled at that table's own re-deal
@@ -515,8 +648,8 @@ class VecLiarPartnerPool:
     max(1, E // K) unless the caller lowered it already.
 
     native=True: one `ph_liar_pool_step` per vectorised step -- a bucket pass and ONE grouped forward per partner move whatever
-    K is, no host synchronisation.  native=False: the readable walk -- per-member get_action / update calls with torch masks
-    (K full forwards per partner move), the per-call entry points only, the same counters; bitwise the native step."""
+    K is, no host synchronisation.  native=False: the readable walk (VecLiarStep) -- per-member get_action / update calls with
+    torch masks (K full forwards per partner move), the per-call entry points only, the same counters; bitwise the native step."""
 
     def __init__(self, n_envs: int, ego: VecOnPolicyAgent, members, seed: int = 0, probegostart: float = 0.5,
                  resample: str = "robin", native: bool = True):
@@ -525,10 +658,7 @@ class VecLiarPartnerPool:
             raise nat.NativeError(f"VecLiarPartnerPool: the pool holds 1..{nat.PH_MAX_POOL} members, not {len(members)}")
         if resample not in nat.POOL_RESAMPLE:
             raise nat.NativeError(f"VecLiarPartnerPool: resample must be one of {sorted(nat.POOL_RESAMPLE)}, not {resample!r}")
-        self.E, self.ego, self.members, self.native, self.resample = n_envs, ego, members, bool(native), resample
-        self.K = len(members)
-        pol = ego.model.policy
-        self.dev = pol.device
+        self.members, self.resample, self.K = members, resample, len(members)
         for who in [ego] + members:
             p = self._policy_of(who)
             if p is None:
@@ -543,87 +673,21 @@ class VecLiarPartnerPool:
                 raise nat.NativeError("VecLiarPartnerPool: a learner's rollout buffer must have n_envs columns")
             if m.min_full >= m.E:
                 m.min_full = max(1, n_envs // self.K)
-        self.env = VecLiarsDice(n_envs, pol.ctx, self.dev)
-        self.seed, self.probegostart = int(seed), float(probegostart)
+        self._init_training(n_envs, ego, seed, probegostart, native)
         self.pool_seed = (self.seed ^ POOL_SEED_SALT) & 0x7FFFFFFFFFFFFFFF
-        E, dev = n_envs, self.dev
-        u8 = lambda v=0: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
-        self.partnerid = th.zeros(E, dtype=th.int32, device=dev)
-        self.ego_first = u8()
-        self.obs_ego = th.zeros((E, 30), dtype=th.float32, device=dev)
-        self.obs_alt = th.zeros((E, 30), dtype=th.float32, device=dev)
-        self.alt_actions = th.zeros((E, 2), dtype=th.int32, device=dev)
-        self.alt_acted = u8()
-        self.ones8, self.zeros8 = u8(1), u8(0)
-        self._rows = np.arange(E)
-        self._episodes_dev = th.zeros(1, dtype=th.int64, device=dev)
-        self.steps_done = 0
-        if self.native:
-            self._build_native()
-            self._done.fill_(1)
-            self._native_call(0, deal_only=True)
-        else:
-            self._deal(self.ones8, 0)
+        self.partnerid = th.zeros(self.E, dtype=th.int32, device=self.dev)
+        self.alt_actions = th.zeros((self.E, 2), dtype=th.int32, device=self.dev)
+        self._rows = np.arange(self.E)
+        self._first_deal()
 
-    @staticmethod
-    def _policy_of(agent):
-        if isinstance(agent, VecLiarDefaultPartner):
-            return None
-        return agent.policy if isinstance(agent, FrozenVecPartner) else agent.model.policy
+    def _contexts(self):
+        return [self.env.ctx] + [p.ctx for p in map(self._policy_of, [self.ego] + self.members) if p is not None]
 
-    @property
-    def episodes(self) -> int:
-        return int(self._episodes_dev.item())
-
-    def _bind(self):
-        stream = th.cuda.current_stream(self.dev).cuda_stream
-        self.env.ctx.set_stream(stream)
-        for agent in [self.ego] + self.members:
-            p = self._policy_of(agent)
-            if p is not None:
-                p.ctx.set_stream(stream)
-
-    # -- the engine-side step ------------------------------------------------------------------------------------------------------
     def _build_native(self) -> None:
-        E, dev, env, ego = self.E, self.dev, self.env, self.ego
-        f32 = lambda *shape: th.zeros(shape, dtype=th.float32, device=dev)  # noqa: E731
-        u8 = lambda: th.zeros(E, dtype=th.uint8, device=dev)               # noqa: E731
-        self._obs_next, self._rew1, self._rew2, self._es_alt = f32(E, 30), f32(E, 2), f32(E, 2), f32(E)
-        self._done1, self._done2, self._running, self._can = u8(), u8(), u8(), u8()
-        self._alt_opens, self._ego_opens, self._done = u8(), u8(), u8()
-        ego._last_episode_starts = ego._last_episode_starts.clone()    # updated in place by the step from here on
-        self._member_rbc = []
-        arr = (nat.PhPoolMember * self.K)()
-        for k, m in enumerate(self.members):
-            c = arr[k]
-            c.kind = m.kind if not isinstance(m, RaggedVecOnPolicyAgent) else nat.PH_POOL_LEARNER
-            p = self._policy_of(m)
-            if p is None:
-                continue
-            c.params, c.seed = p.params.data_ptr(), p._seed
-            if isinstance(m, RaggedVecOnPolicyAgent):
-                rbc = m.model.rollout_buffer.c_struct()
-                self._member_rbc.append(rbc)
-                c.rb = C.pointer(rbc)
-                c.pos, c.boundary, c.term, c.open = (t.data_ptr() for t in (m.pos, m.boundary, m.term, m.open))
-                c.values, c.log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
-        self._member_arr = arr
-        s = nat.PhLiarPool()
-        s.n, s.spec = E, C.pointer(ego.model.policy.spec)
-        s.hands, s.history, s.nmoves = env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr()
-        s.ego_first, s.dice_seed, s.probegostart = self.ego_first.data_ptr(), self.seed, self.probegostart
-        pe = ego.model.policy
-        self._ego_rbc = ego.model.rollout_buffer.c_struct()
-        s.ego_params, s.ego_rb, s.ego_actions = pe.params.data_ptr(), C.pointer(self._ego_rbc), ego.actions.data_ptr()
-        s.ego_values, s.ego_log_probs = ego.values.data_ptr(), ego.log_probs.data_ptr()
-        s.ego_episode_start, s.ego_seed = ego._last_episode_starts.data_ptr(), pe._seed
-        s.members, s.n_members, s.partnerid = arr, self.K, self.partnerid.data_ptr()
+        s = self._fill_training(nat.PhLiarPool())
+        s.members, s.n_members, s.partnerid = self._member_array(self.members), self.K, self.partnerid.data_ptr()
         s.resample, s.pool_seed = nat.POOL_RESAMPLE[self.resample], self.pool_seed
-        s.alt_actions, s.alt_acted = self.alt_actions.data_ptr(), self.alt_acted.data_ptr()
-        s.obs_ego, s.obs_alt, s.episodes = self.obs_ego.data_ptr(), self.obs_alt.data_ptr(), self._episodes_dev.data_ptr()
-        s.obs_next, s.rew1, s.rew2, s.es_alt = (t.data_ptr() for t in (self._obs_next, self._rew1, self._rew2, self._es_alt))
-        s.done1, s.done2, s.running, s.can = (t.data_ptr() for t in (self._done1, self._done2, self._running, self._can))
-        s.alt_opens, s.ego_opens, s.done = self._alt_opens.data_ptr(), self._ego_opens.data_ptr(), self._done.data_ptr()
+        s.alt_actions = self.alt_actions.data_ptr()
         self._desc = s
 
     def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
@@ -632,20 +696,14 @@ class VecLiarPartnerPool:
         nat.check(ctx.lib.ph_liar_pool_step(ctx.handle, C.byref(self._desc), int(rb.pos if ego_pos < 0 else ego_pos), int(counter),
                                             int(deal_only)))
 
-    # -- the walk: per-member calls with torch masks -------------------------------------------------------------------------------
-    def _members_act(self, obs: th.Tensor, mask: th.Tensor, counter: int) -> th.Tensor:
-        """every member's forward with Philox counter `counter`; member k's move lands in the tables of `mask` it sits at"""
-        for k, m in enumerate(self.members):
-            mk = (mask.bool() & (self.partnerid == k)).to(th.uint8)
-            if isinstance(m, VecLiarDefaultPartner):
-                m.get_action(obs, mk, self.alt_actions, self.env.ctx)
-                continue
-            self._policy_of(m)._counter = counter - 1
-            a = m.get_action(obs, mk)
-            self.alt_actions.copy_(th.where(mk.bool()[:, None], a, self.alt_actions))
-        return self.alt_actions
+    # -- the walk's hooks -------------------------------------------------------------------------------------------------------------
+    def _seat_act(self, seat: int, obs: th.Tensor, mask, counter: int) -> th.Tensor:
+        if seat == 0:
+            return self._ego_act(counter)
+        return self._members_act(range(self.K), self.partnerid, obs, mask, counter, self.alt_actions)
 
-    def _members_update(self, reward: th.Tensor, done: th.Tensor, mask: th.Tensor) -> None:
+    def _credit(self, reward: th.Tensor, done: th.Tensor, replied) -> None:
+        mask = self.alt_acted if replied is None else replied
         for k, m in enumerate(self.members):
             if isinstance(m, RaggedVecOnPolicyAgent):
                 mine = self.partnerid == k
@@ -658,71 +716,9 @@ class VecLiarPartnerPool:
         ids = (words * np.uint64(self.K)) >> np.uint64(32)
         return th.as_tensor(ids.astype(np.int32)).to(self.dev)
 
-    def _deal(self, reset_mask: th.Tensor, c: int) -> None:
-        """re-deal the tables in reset_mask and seat their next members; where the member opens, it moves once"""
-        env, lib, h = self.env, self.env.ctx.lib, self.env.ctx.handle
-        self._bind()
-        nat.check(lib.ph_liar_reset(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                    reset_mask.data_ptr(), self.ego_first.data_ptr(), self.seed, int(c),
-                                    self.probegostart, self.E))
-        rm = reset_mask.bool()
-        self.alt_acted.copy_(th.where(rm, self.zeros8, self.alt_acted))
-        self.partnerid.copy_(th.where(rm, self._resampled(c).to(th.int32), self.partnerid))
-        alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
-        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                  self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
-        a_alt = self._members_act(self.obs_alt, alt_opens, 2 * c + 1)
-        self.alt_acted.copy_((self.alt_acted.bool() | alt_opens.bool()).to(th.uint8))
-        env.player_step(a_alt, self.zeros8, alt_opens)              # obs_next = ego's observation in those tables
-        self.obs_ego.copy_(th.where(alt_opens.bool()[:, None], env.obs_next, self.obs_ego))
-        ego_opens = (rm & self.ego_first.bool()).to(th.uint8)
-        nat.check(lib.ph_liar_obs(h, env.hands.data_ptr(), env.history.data_ptr(), env.nmoves.data_ptr(),
-                                  self.ones8.data_ptr(), ego_opens.data_ptr(), self.obs_ego.data_ptr(), self.E))
-
-    # -- one vectorised MultiAgentEnv.step ---------------------------------------------------------------------------------------
-    def step(self):
-        """-> (E,) uint8 device tensor: tables whose game ended in this step"""
-        ego = self.ego
-        self.steps_done += 1
-        c = self.steps_done
-        if self.native:
-            model, rb = ego.model, ego.model.rollout_buffer
-            if ego.n_steps >= model.n_steps:
-                ego.learn_from_buffer()
-            self._native_call(c)
-            rb.pos += 1
-            rb.full = rb.pos == rb.buffer_size
-            ego.n_steps += 1
-            ego.num_timesteps += self.E
-            for m in self.learners:
-                m.num_timesteps += self.E
-            return self._done
-        env = self.env
-        self._bind()
-        ego.model.policy._counter = c - 1
-        a_ego = ego.get_action(self.obs_ego)                                   # every table is at the ego's turn
-        obs_alt, rew1, done1 = env.player_step(a_ego, self.ones8, None)
-        rew1, done1 = rew1.clone(), done1.clone()
-        running = (~done1.bool()).to(th.uint8)
-        # the member that already acted this game is credited this transition (multiagentenv.py:163-170)
-        self._members_update(rew1[:, 1].contiguous(), done1, self.alt_acted)
-        self.obs_alt.copy_(th.where(running.bool()[:, None], obs_alt, self.obs_alt))
-        # every table's member replies where the game goes on
-        a_alt = self._members_act(self.obs_alt, running, 2 * c)
-        self.alt_acted.copy_((self.alt_acted.bool() | running.bool()).to(th.uint8))
-        obs_ego, rew2, done2 = env.player_step(a_alt, self.zeros8, running)
-        rew2 = th.where(running.bool()[:, None], rew2, th.zeros_like(rew2))
-        done2 = (done2.bool() & running.bool())
-        self._members_update(rew2[:, 1].contiguous(), done2.to(th.uint8), running)
-        done = done1.bool() | done2
-        # the ego collects both transitions of the step; the last done wins (agents.py:44-47)
-        ego.update((rew1[:, 0] + rew2[:, 0]).contiguous(), done.to(th.float32))
-        ego.flush_rewards()
-        self.obs_ego.copy_(th.where((running.bool() & ~done2)[:, None], obs_ego, self.obs_ego))
-        done8 = done.to(th.uint8)
-        self._episodes_dev += done8.sum()
-        self._deal(done8, c)
-        return done8
+    def _on_deal(self, rm: th.Tensor, c: int) -> None:
+        super()._on_deal(rm, c)
+        self.partnerid.copy_(th.where(rm, self._resampled(c).to(th.int32), self.partnerid))   # the member that sits at the new game
 
     def rollout_and_learn(self, n_steps: int) -> None:
         """n_steps vectorised steps, the ego's update, then the update of every learner whose full() holds"""
