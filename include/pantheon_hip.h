@@ -671,6 +671,38 @@ int ph_liar_xplay_step(ph_ctx *ctx, const ph_liar_xplay *xp, unsigned long long 
 int ph_xplay_stats(ph_ctx *ctx, const float *returns, const int *lengths, const int *games, int n, int episodes_per_table,
                    int n_pairs, double *stats);
 
+/* ---- a move log of the vectorised Liar's Dice step on the device (csrc/ph_record.h; additions, PH_ABI_VERSION unchanged): the rows
+ * TurnBasedRecorder (wrappers.py:82-160) produces for each table, [obs 30 | action 2 | flag] f32 with flag 0 ego moved, 1 partner
+ * moved, + 2 where that move ended the game.  A step logs up to three moves per table, in the table's own order: the ego's move,
+ * the reply where the game goes on, seat 1's opening of a freshly dealt game (flag 1: an opening never ends a game).  Table e owns
+ * rows[e] and its cursors; a move that finds count[e] == cap is dropped and counted in dropped[e], so the table's log stays a
+ * prefix of its stream and nothing is written past rows[e].  member[e][r] (optional) names who moved: in cross-play ego_id /
+ * alt_id, in the pool partnerid[e] for seat 1 (the opening's is read behind the deal's resample), otherwise 0.  The caller zeroes
+ * count / count_alt / dropped and fills pending with -1 before attaching. */
+typedef struct ph_liar_record {
+  int n;                                     /* tables: the n of the steps that record */
+  int cap;                                   /* rows per table, >= 1 */
+  float *rows;                               /* (n,cap,33) device, 16-byte aligned */
+  int *member;                               /* (n,cap) device, or NULL */
+  int *count;                                /* (n) rows logged */
+  int *count_alt;                            /* (n) ... of which seat 1's */
+  int *dropped;                              /* (n) moves that found the table full */
+  int *pending;                              /* (n) row of the reply whose flag is still to come within a step, else -1 */
+} ph_liar_record;
+/* Attach a recorder to the context (the struct is copied; rec == NULL detaches), in the manner of ph_ctx_set_rng_epoch.  While one
+ * is attached, every ph_liar_selfplay_step / _step_arch / ph_liar_pool_step / ph_liar_xplay_step of this context with n == rec->n
+ * launches two record kernels besides its own launches (a deal-only call: one); a step with another n is refused.  Cross-play
+ * tables that are not `playing` log nothing.  Refused inside graph capture; a step with a recorder attached is capturable like
+ * the plain one.  ph_liar_selfplay_rollout is refused while a recorder is attached. */
+int ph_liar_record_attach(ph_ctx *ctx, const ph_liar_record *rec);
+/* offsets (n+1) int64 device = exclusive scan of the per-table counts of the rows `seat` selects: -1 every row, 0 seat 0's
+ * (flag % 2 == 0), 1 seat 1's (count_alt).  With rows_out != NULL also the selected rows, table-major and in each table's own
+ * order, into rows_out (out_cap,33) f32 and -- where member_out != NULL -- who moved into member_out (out_cap) int32; rows at or
+ * past out_cap are not written.  Call it once with rows_out == NULL, read offsets[n], allocate, call it again.  `rec` need not be
+ * attached. */
+int ph_liar_record_export(ph_ctx *ctx, const ph_liar_record *rec, int seat, long long *offsets, float *rows_out, int *member_out,
+                          long long out_cap);
+
 /* ---- the block worlds: BlockEnv-v0 (variant 0, simpleblockworld.py:36-131) and BlockEnv-v1 (variant 1, blockworld.py:34-83,
  * gridutils.py:8-64).  The planner (ego) always moves first; the constructor is the partner.  A table is PH_BLOCK_STATE_WORDS
  * int32 words, 16-byte aligned (layout: csrc/ph_block.h).  Observations are the raw integer components as f32:

@@ -256,6 +256,14 @@ class PhLiarXplay(C.Structure):
                 ("alt_opens", C.c_void_p), ("ego_opens", C.c_void_p), ("done", C.c_void_p)]
 
 
+class PhLiarRecord(C.Structure):
+    """ph_liar_record: the device-resident move log of the vectorised Liar's Dice step (rows [obs 30 | action 2 | flag])"""
+    _fields_ = [("n", C.c_int), ("cap", C.c_int), ("rows", C.c_void_p), ("member", C.c_void_p),
+                ("count", C.c_void_p), ("count_alt", C.c_void_p), ("dropped", C.c_void_p), ("pending", C.c_void_p)]
+
+
+RECORD_ROW = 33          # 30 observation components, 2 action components, the move flag
+
 SIGNATURES = {
     "ph_abi_version": [],
     "ph_roundrobin_env_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, _i],
@@ -314,6 +322,8 @@ SIGNATURES = {
     "ph_liar_pool_step": [_vp, C.POINTER(PhLiarPool), _i, _ull, _i],
     "ph_liar_xplay_step": [_vp, C.POINTER(PhLiarXplay), _ull, _i],
     "ph_xplay_stats": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "ph_liar_record_attach": [_vp, C.POINTER(PhLiarRecord)],
+    "ph_liar_record_export": [_vp, C.POINTER(PhLiarRecord), _i, _vp, _vp, _vp, C.c_longlong],
     "ph_block_reset": [_vp, _i, _vp, _vp, _ull, _ull, _i],
     "ph_block_step": [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i],
     "ph_block_obs": [_vp, _i, _vp, _i, _vp, _vp, _i],

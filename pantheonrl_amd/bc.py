@@ -155,6 +155,12 @@ class BC:
     def set_expert_data_loader(self, expert_data: TransitionsMinimal) -> None:
         """upload the (obs, acts) table once; batches are drawn on the device from a per-epoch shuffled order (bc.py:239-267)"""
         lay = self.policy.layout
+        if isinstance(expert_data.obs, th.Tensor):
+            # a device-resident recording (envs.vec.LiarRecording, or any object with tensor obs / acts): no host round trip
+            n = int(expert_data.obs.shape[0])
+            self._obs = expert_data.obs.to(self.device, th.float32).reshape(n, lay.D).contiguous()
+            self._acts = th.as_tensor(expert_data.acts).to(self.device, th.float32).reshape(n, lay.A).contiguous()
+            return
         obs = np.asarray(expert_data.obs, np.float32).reshape(len(expert_data), lay.D)
         acts = np.asarray(expert_data.acts, np.float32).reshape(len(expert_data), lay.A)
         self._obs = th.as_tensor(obs).to(self.device).contiguous()

@@ -6,7 +6,9 @@ every agent as the partner -- the M x M matrix the reference reaches only as M^2
 An agent is a PPO checkpoint (64-64 MlpPolicy) or DEFAULT (the game's scripted player).  `-t` is the number of games per pair:
 table e plays pair e % P, so a pair owns at least n_envs // P tables and every table plays ceil(t / (n_envs // P)) games.  Prints
 the mean and standard-deviation matrices of the ego's return (row = ego, column = partner); `--out` writes them, with the counts,
-mean lengths and the raw logs, as an .npz."""
+mean lengths and the raw logs, as an .npz.  `--record FILE` logs every move on the device (envs/vec.py: VecLiarStep.start_recording)
+and writes the tables' streams, concatenated in table order, in the reference's recording format; `--out` then also holds
+`table_offsets` (table e's rows of the recording), `member` (who made each move) and `pair_of_table`."""
 from __future__ import annotations
 
 import argparse
@@ -27,6 +29,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", "-s", type=int, default=0)
     p.add_argument("--probegostart", type=float, default=0.5)
     p.add_argument("--out", help="write the matrices and logs to this .npz")
+    p.add_argument("--record", "-r", help="write every move of every table to this .npy (TurnBasedTransitions format)")
     return p
 
 
@@ -48,12 +51,19 @@ def plan(args) -> dict:
 def run(argv=None):
     args = build_parser().parse_args(argv)
     size = plan(args)
-    from .envs.crossplay import VecLiarCrossPlay
+    from .envs.crossplay import MAX_STEPS_PER_GAME, VecLiarCrossPlay
     from .tester import load_member
     members = [load_member("DEFAULT" if a == "DEFAULT" else "PPO", {}, a, args.device) for a in args.agents]
+    # a game takes at most MAX_STEPS_PER_GAME steps of at most 3 moves
+    record = 3 * MAX_STEPS_PER_GAME * size["episodes_per_table"] if args.record else 0
     xp = VecLiarCrossPlay(args.n_envs, members, episodes_per_table=size["episodes_per_table"], seed=args.seed,
-                          probegostart=args.probegostart)
+                          probegostart=args.probegostart, record=record)
     res = xp.run()
+    extra = {}
+    if record:
+        from .envs.vec import write_recording
+        rec = write_recording(xp, args.record)
+        extra = dict(table_offsets=rec.table_offsets, member=rec.member.cpu().numpy())
     with np.printoptions(precision=4, suppress=True, linewidth=160):
         print(f"Agents: {args.agents}")
         print(f"Games per pair: {int(res.count.min())}..{int(res.count.max())} ({args.n_envs} tables x {xp.G} games, {res.steps} steps)")
@@ -62,7 +72,7 @@ def run(argv=None):
     if args.out:
         np.savez(args.out, agents=np.asarray(args.agents), mean=res.matrix("mean"), std=res.matrix("std"), count=res.matrix("count"),
                  mean_length=res.matrix("mean_length"), returns=res.returns, lengths=res.lengths, pair_of_table=res.pair_of_table,
-                 pairs=res.pairs)
+                 pairs=res.pairs, **extra)
     return res
 
 

@@ -19,6 +19,7 @@
 #include "ph_arch.h"
 #include "ph_pool.h"
 #include "ph_xplay.h"
+#include "ph_record.h"
 
 namespace ph {
 
@@ -177,6 +178,8 @@ struct ph_ctx {
   int num_cu = 256;
   int exchange_blocks_per_cu = 0;           // occupancy answer for the exchange rollout kernel (0 = not asked yet)
   unsigned long long* rng_epoch = nullptr;  // caller-owned device word
+  ph::RecordLog rec{};                      // ph_liar_record_attach: the move log the Liar's Dice steps fill (caller-owned arrays)
+  bool recording = false;
   // partner pool (ph_pool.h): the member table the kernels read (device) with what it holds (host), the bucket pass's outputs
   ph::PoolMemberDev* pool_dev = nullptr;
   ph::PoolMemberDev pool_host[PH_MAX_POOL];
@@ -1787,18 +1790,32 @@ int check_liar_selfplay(const char* who, const ph_ctx* ctx, const ph_liar_selfpl
 //   seat-0 forward | after_ego | seat-1 forward (reply) | after_reply | seat-1 forward (openers) | after_opening
 // and its re-deal half alone (deal_only: for the tables flagged in g.done).  seat0() and seat1(obs, active, counter) run a
 // seat's forward; k = the Philox counters of the three forwards; the dice (and the pool's resample) draw with `counter`.
+// With a recorder attached (ph_liar_record_attach) the two record launches of ph_record.h stand where the scratch they read
+// is still intact: behind the reply forward, and behind the opening forward.  `seats`: who sits where, for the log's member column.
+struct LiarSeats {
+  const int *ego_id, *alt_id;        // (n) member at seat 0 / seat 1, or null: member 0
+  const unsigned char* playing;      // (n) the tables that take part, or null: all
+};
 template <class Book, class End, class Seat0, class Seat1>
 int liar_step_run(ph_ctx* ctx, const ph::LiarGame& g, const Book& book, const End& end, unsigned long long counter, int deal_only,
-                  const unsigned long long (&k)[3], Seat0 seat0, Seat1 seat1) {
+                  const unsigned long long (&k)[3], const LiarSeats& seats, Seat0 seat0, Seat1 seat1) {
   hipStream_t st = ctx->stream;
+  const bool rec = ctx->recording;
+  if (rec && ctx->rec.n != g.n)
+    return fail("Liar's Dice step: the attached recorder holds " + std::to_string(ctx->rec.n) + " tables, the step " +
+                std::to_string(g.n) + " (ph_liar_record_attach)");
+  const ph::RecordStep rs{g.obs_ego, g.obs_alt, g.obs_next, g.ego_actions, g.alt_actions, g.done1, g.done2,
+                          g.running, g.alt_opens, seats.ego_id, seats.alt_id, seats.playing};
   if (!deal_only) {
     if (seat0(k[0])) return 1;                               // seat 0 moves in every table
     PH_HIP(ph::launch_liar_pass(0, g, book, end, counter, ctx->rng_epoch, deal_only, st));
     if (seat1(g.obs_next, g.running, k[1])) return 1;        // seat 1 replies where the game goes on (obs_next = its observation there)
+    if (rec) PH_HIP(ph::launch_record_moves(ctx->rec, rs, st));
   }
   // reply played and credited; finished tables are re-dealt; where seat 1 opens the new game it moves once
   PH_HIP(ph::launch_liar_pass(1, g, book, end, counter, ctx->rng_epoch, deal_only, st));
   if (seat1(g.obs_alt, g.alt_opens, k[2])) return 1;
+  if (rec) PH_HIP(ph::launch_record_opening(ctx->rec, rs, st));
   PH_HIP(ph::launch_liar_pass(2, g, book, end, counter, ctx->rng_epoch, deal_only, st));
   return 0;
 }
@@ -1815,6 +1832,7 @@ int liar_selfplay_step_run(const char* who, ph_ctx* ctx, const ph_liar_selfplay*
                              s.alt_rb->rewards, s.alt_rb->T};
   return liar_step_run(
       ctx, ph::liar_game_of(s), book, liar_train_end(s, ego_pos, deal_only), counter, deal_only, {counter, 2 * counter, 2 * counter + 1},
+      LiarSeats{nullptr, nullptr, nullptr},
       [&](unsigned long long c) {
         return seat_forward(ctx, s.spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, c, s.ego_actions, s.ego_values,
                             s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start);
@@ -1954,6 +1972,7 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsign
   const ph::PoolBook book{s.n, s.n_members, s.resample, s.pool_seed, ctx->pool_dev, s.partnerid, s.alt_acted, s.can, s.es_alt};
   return liar_step_run(
       ctx, g, book, liar_train_end(s, ego_pos, deal_only), counter, deal_only, {counter, 2 * counter, 2 * counter + 1},
+      LiarSeats{nullptr, s.partnerid, nullptr},   // the log names the member at seat 1
       [&](unsigned long long c) {
         return seat_forward(ctx, s.spec, nullptr, s.ego_params, s.obs_ego, s.n, s.ego_seed, c, s.ego_actions, s.ego_values,
                             s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start);
@@ -1992,7 +2011,7 @@ int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long 
     return pool_forward(ctx, who, s.spec, s.n_members, obs, id, active, active, c, actions, nullptr, s.n);
   };
   return liar_step_run(
-      ctx, g, ph::NoBook{}, end, counter, deal_only, {3 * counter, 3 * counter + 1, 3 * counter + 2},
+      ctx, g, ph::NoBook{}, end, counter, deal_only, {3 * counter, 3 * counter + 1, 3 * counter + 2}, LiarSeats{s.ego_id, s.alt_id, s.playing},
       [&](unsigned long long c) { return seat(s.obs_ego, s.ego_id, s.playing, c, s.ego_actions); },
       [&](const float* obs, const unsigned char* active, unsigned long long c) { return seat(obs, s.alt_id, active, c, s.alt_actions); });
 }
@@ -2006,6 +2025,58 @@ int ph_xplay_stats(ph_ctx* ctx, const float* returns, const int* lengths, const 
   if (n_pairs < 1 || n_pairs > n) return fail("ph_xplay_stats: 1..n pairs (every pair needs a table)");
   if ((uintptr_t)stats % 16) return fail("ph_xplay_stats: stats must be 16-byte aligned");
   PH_HIP(ph::launch_xplay_stats(returns, lengths, games, n, episodes_per_table, n_pairs, stats, ctx->stream));
+  return 0;
+}
+
+// ---- the device-resident move log of the Liar's Dice steps (ph_record.h) ----
+namespace {
+int check_liar_record(const char* who, const ph_liar_record* rec) {
+  if (!rec) return fail_who(who, ": null recorder");
+  if (rec->n < 1) return fail_who(who, ": n must be positive");
+  if (rec->cap < 1) return fail_who(who, ": cap must be at least 1");
+  if (!rec->rows || !rec->count || !rec->count_alt || !rec->dropped || !rec->pending) return fail_who(who, ": incomplete recorder");
+  if ((uintptr_t)rec->rows % 16) return fail_who(who, ": rows must be 16-byte aligned");
+  if (((uintptr_t)rec->member | (uintptr_t)rec->count | (uintptr_t)rec->count_alt | (uintptr_t)rec->dropped | (uintptr_t)rec->pending) % 4)
+    return fail_who(who, ": member / count / count_alt / dropped / pending must be 4-byte aligned");
+  return 0;
+}
+ph::RecordLog record_log_of(const ph_liar_record& r) {
+  return ph::RecordLog{r.n, r.cap, r.rows, r.member, r.count, r.count_alt, r.dropped, r.pending};
+}
+}  // namespace
+
+int ph_liar_record_attach(ph_ctx* ctx, const ph_liar_record* rec) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_liar_record_attach";
+  if (!ctx) return fail("null ctx");
+  // a captured step holds the launches of the recorder it was captured with: attaching or detaching inside capture would leave
+  // the graph and the context in disagreement
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (ctx->stream) PH_HIP(hipStreamIsCapturing(ctx->stream, &cap));
+  if (ctx->capturing || cap != hipStreamCaptureStatusNone)
+    return fail_who(who, ": refused inside graph capture (attach the recorder before capture begins)");
+  if (!rec) {
+    ctx->recording = false;
+    ctx->rec = ph::RecordLog{};
+    return 0;
+  }
+  if (check_liar_record(who, rec)) return 1;
+  ctx->rec = record_log_of(*rec);
+  ctx->recording = true;
+  return 0;
+}
+
+int ph_liar_record_export(ph_ctx* ctx, const ph_liar_record* rec, int seat, long long* offsets, float* rows_out, int* member_out,
+                          long long out_cap) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_liar_record_export";
+  if (!ctx) return fail("null ctx");
+  if (check_liar_record(who, rec)) return 1;
+  if (seat < -1 || seat > 1) return fail_who(who, ": seat must be -1 (every row), 0 or 1");
+  if (!offsets) return fail_who(who, ": null offsets");
+  if ((uintptr_t)offsets % 8 || (uintptr_t)rows_out % 4 || (uintptr_t)member_out % 4) return fail_who(who, ": misaligned output");
+  if (out_cap < 0 || (member_out && !rows_out)) return fail_who(who, ": bad output arguments");
+  PH_HIP(ph::launch_record_export(record_log_of(*rec), seat, offsets, rows_out, member_out, out_cap, ctx->stream));
   return 0;
 }
 
@@ -2124,6 +2195,9 @@ int ph_liar_selfplay_rollout(ph_ctx* ctx, const ph_liar_selfplay* sp, int ego_po
   DevGuard dev_guard(ctx);
   const char* who = "ph_liar_selfplay_rollout";
   if (check_liar_selfplay(who, ctx, sp)) return 1;
+  if (ctx->recording)
+    return fail("ph_liar_selfplay_rollout: a recorder is attached (ph_liar_record_attach) and the one-launch rollout does not record: "
+                "detach it, or step with ph_liar_selfplay_step");
   const ph_liar_selfplay& s = *sp;
   if (n_steps <= 0 || ego_pos < 0 || ego_pos > s.ego_rb->T - n_steps)
     return fail("ph_liar_selfplay_rollout: ego_pos + n_steps exceeds the ego's buffer");

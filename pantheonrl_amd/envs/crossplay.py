@@ -124,7 +124,7 @@ class VecLiarCrossPlay(VecLiarStep):
     `ph_liar_default_actions`, `VecLiarsDice.player_step`, torch masks, the same counters; bitwise the native step."""
 
     def __init__(self, n_envs: int, members, pairs=None, episodes_per_table: int = 1, seed: int = 0, probegostart: float = 0.5,
-                 native: bool = True):
+                 native: bool = True, record: int = 0):
         members = list(members)
         self.pairs = check_pairs(n_envs, len(members), pairs)
         if int(episodes_per_table) < 1:
@@ -162,6 +162,8 @@ class VecLiarCrossPlay(VecLiarStep):
         self.returns = th.zeros((E, G), dtype=th.float32, device=dev)
         self.lengths = th.zeros((E, G), dtype=th.int32, device=dev)
         self.stats = th.zeros((self.P, nat.XPLAY_NSTAT), dtype=th.float64, device=dev)
+        if record:
+            self.start_recording(record)          # the move log (VecLiarStep.start_recording), from the first openings on
         self._first_deal()
 
     def _contexts(self):
@@ -195,6 +197,9 @@ class VecLiarCrossPlay(VecLiarStep):
 
     def _live(self) -> th.Tensor:
         return self.playing
+
+    def _seat_member(self, seat: int) -> th.Tensor:
+        return self.ego_id if seat == 0 else self.alt_id
 
     def _game_end(self, reward: th.Tensor, done: th.Tensor) -> th.Tensor:
         """the step's return and length; at the end of a game the log entry, the count, the budget -> the tables dealt again"""

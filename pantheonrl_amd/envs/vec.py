@@ -12,6 +12,7 @@ of the reference's step loop (multiagentenv.py:149-170) applied to E-long device
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch as th
@@ -314,6 +315,59 @@ class VecLiarDefaultPartner:
 
 
 # ---- Liar's Dice resident on the device: self-play, a pool of partners at seat 1, cross-play evaluation ------------------------
+class LiarRecording:
+    """What `VecLiarStep.recorded` returns: the tables' move streams concatenated in table order -- per table exactly the rows
+    `TurnBasedRecorder` (common/wrappers.py) produces, [obs 30 | action 2 | flag].
+      transitions    TurnBasedTransitions on the host (write_transition gives the reference's .npy)
+      obs/acts/flags (N, 30) / (N, 2) / (N,) float32 device tensors, views of `rows` (N, 33)
+      member         (N,) int32 device: who moved (cross-play: the population index; the pool: the member at seat 1; otherwise 0)
+      table_offsets  (E + 1,) int64 numpy: table e's rows are table_offsets[e]:table_offsets[e + 1]
+      dropped        (E,) int64 numpy: moves of table e that found its log full
+    It can be handed to `BC.set_expert_data_loader` as it is (device obs / acts)."""
+
+    def __init__(self, rows: th.Tensor, member: th.Tensor, table_offsets: np.ndarray, dropped: np.ndarray):
+        from ..common.trajsaver import TurnBasedTransitions
+        self.rows, self.member = rows, member
+        self.obs, self.acts, self.flags = rows[:, :30], rows[:, 30:32], rows[:, 32]
+        self.table_offsets, self.dropped = np.asarray(table_offsets, np.int64), np.asarray(dropped, np.int64)
+        host = rows.cpu().numpy()
+        self.transitions = TurnBasedTransitions(host[:, :30], host[:, 30:32], host[:, 32])
+
+    def __len__(self) -> int:
+        return int(self.rows.shape[0])
+
+
+RECORD_SEATS = {None: -1, 0: 0, 1: 1}
+
+
+def write_recording(env, file) -> "LiarRecording":
+    """`--record FILE` of the device-resident CLIs: the tables' streams concatenated in table order, in the reference's .npy
+    format (TurnBasedTransitions.write_transition); dropped moves are reported, not fatal"""
+    rec = env.recorded()
+    rec.transitions.write_transition(file)
+    lost = int(rec.dropped.sum())
+    if lost:
+        print(f"WARNING: --record: {lost} moves of {int((rec.dropped > 0).sum())} tables did not fit the move log and were dropped")
+    print(f"Recorded {len(rec)} moves of {env.E} tables to {file}")
+    return rec
+
+
+def export_recording(rows, counts, seat=None):
+    """The export in plain numpy (what `ph_liar_record_export` does on the device): rows (E, cap, 33), counts (E,) rows logged per
+    table; seat None / 0 / 1 selects every row / flag % 2 == seat.  -> (dense (N, 33), offsets (E + 1,) int64)"""
+    rows, counts = np.asarray(rows), np.asarray(counts, np.int64)
+    E, cap = rows.shape[0], rows.shape[1]
+    counts = np.clip(counts, 0, cap)
+    picked = []
+    for e in range(E):
+        r = rows[e, :counts[e]]
+        picked.append(r if seat is None else r[r[:, 32].astype(np.int64) % 2 == int(seat)])
+    offsets = np.zeros(E + 1, np.int64)
+    offsets[1:] = np.cumsum([len(r) for r in picked])
+    dense = np.concatenate(picked, axis=0) if E else np.zeros((0, rows.shape[2]), rows.dtype)
+    return dense.reshape(-1, rows.shape[2]), offsets
+
+
 class VecLiarStep:
     """What the three device-resident Liar's Dice drivers share -- VecLiarSelfPlay, VecLiarPartnerPool and (envs/crossplay.py)
     VecLiarCrossPlay.  One vectorised step is one protocol:
@@ -344,6 +398,7 @@ class VecLiarStep:
         self.obs_alt = th.zeros((self.E, 30), dtype=th.float32, device=dev)
         self.ones8, self.zeros8 = u8(1), u8(0)
         self.steps_done = 0
+        self.recording = False
         self._ctxs = tuple(dict.fromkeys(self._contexts()))     # each engine context once: `_bind` runs in front of every step
 
     def _first_deal(self) -> None:
@@ -407,6 +462,115 @@ class VecLiarStep:
         self._member_arr = arr
         return arr
 
+    # -- the move log (csrc/ph_record.h): TurnBasedRecorder's rows of every table, filled inside the step ----------------------------
+    def start_recording(self, max_moves_per_table: int) -> None:
+        """Log every move from the next step on, at most `max_moves_per_table` rows per table (a step logs up to three moves per
+        table; later moves of a full table are dropped and counted).  native=True: the log lives on the device and the engine's
+        step fills it (`ph_liar_record_attach` on the game's context) with no host work; native=False: the walk appends to
+        per-table host lists at the same three points.  The constructors' `record=` starts it in front of the first deal, so a
+        table's log begins with that game's opening, as the reference recorder's does."""
+        cap = int(max_moves_per_table)
+        if cap < 1:
+            raise nat.NativeError(f"{type(self).__name__}.start_recording: max_moves_per_table must be at least 1, not {cap}")
+        if self.recording:
+            raise nat.NativeError(f"{type(self).__name__}.start_recording: already recording (stop_recording first)")
+        E, dev = self.E, self.dev
+        self._rec_cap = cap
+        if self.native:
+            i32 = lambda shape, v=0: th.full(shape, v, dtype=th.int32, device=dev)  # noqa: E731
+            self._rec_rows, self._rec_member = self._record_alloc(cap)
+            self._rec_count, self._rec_count_alt, self._rec_dropped, self._rec_pending = i32((E,)), i32((E,)), i32((E,)), i32((E,), -1)
+            self._rec_desc = self._record_desc()
+            self._bind()
+            ctx = self.env.ctx
+            # the context keeps the log's addresses: one recording environment per context, detached before its log is freed
+            owner = getattr(ctx, "_liar_recorder", None)
+            if owner is not None and owner() is not None and owner() is not self and owner().recording:
+                raise nat.NativeError(f"{type(self).__name__}.start_recording: another environment records on this engine context")
+            nat.check(ctx.lib.ph_liar_record_attach(ctx.handle, C.byref(self._rec_desc)))
+            ctx._liar_recorder = weakref.ref(self)
+        else:
+            self._rec_lists = [[] for _ in range(E)]             # per table: (row (33,), member)
+            self._rec_lost = np.zeros(E, np.int64)
+        self.recording = True
+
+    def _record_alloc(self, cap: int):
+        """the log's storage: rows (E, cap, 33) float32 and member (E, cap) int32, zeroed"""
+        return (th.zeros((self.E, cap, nat.RECORD_ROW), dtype=th.float32, device=self.dev),
+                th.zeros((self.E, cap), dtype=th.int32, device=self.dev))
+
+    def _record_desc(self) -> "nat.PhLiarRecord":
+        r = nat.PhLiarRecord()
+        r.n, r.cap = self.E, self._rec_cap
+        r.rows, r.member = self._rec_rows.data_ptr(), self._rec_member.data_ptr()
+        r.count, r.count_alt = self._rec_count.data_ptr(), self._rec_count_alt.data_ptr()
+        r.dropped, r.pending = self._rec_dropped.data_ptr(), self._rec_pending.data_ptr()
+        return r
+
+    def stop_recording(self) -> None:
+        """stop logging; what was logged stays readable through `recorded`"""
+        if not self.recording:
+            return
+        if self.native:
+            self._bind()
+            ctx = self.env.ctx
+            nat.check(ctx.lib.ph_liar_record_attach(ctx.handle, None))
+        self.recording = False
+
+    def __del__(self):  # pragma: no cover
+        try:                                  # the engine context may outlive this object: it must not keep the log's addresses
+            if getattr(self, "recording", False) and getattr(self, "native", False):
+                self.stop_recording()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def recorded(self, seat=None) -> LiarRecording:
+        """the log so far: every row (seat=None), seat 0's (0) or seat 1's (1) -- see LiarRecording (synchronises)"""
+        if seat not in RECORD_SEATS:
+            raise nat.NativeError(f"{type(self).__name__}.recorded: seat must be None, 0 or 1, not {seat!r}")
+        if not hasattr(self, "_rec_cap"):
+            raise nat.NativeError(f"{type(self).__name__}.recorded: nothing was recorded (start_recording first)")
+        E, dev = self.E, self.dev
+        if not self.native:
+            picked = [[(r, m) for r, m in t if seat is None or int(r[32]) % 2 == seat] for t in self._rec_lists]
+            offsets = np.zeros(E + 1, np.int64)
+            offsets[1:] = np.cumsum([len(t) for t in picked])
+            flat = [rm for t in picked for rm in t]
+            rows = np.stack([r for r, _ in flat]).astype(np.float32) if flat else np.zeros((0, nat.RECORD_ROW), np.float32)
+            member = np.asarray([m for _, m in flat], np.int32)
+            return LiarRecording(th.as_tensor(rows).to(dev), th.as_tensor(member).to(dev), offsets, self._rec_lost.copy())
+        self._bind()
+        ctx, desc = self.env.ctx, C.byref(self._rec_desc)
+        offsets = th.zeros(E + 1, dtype=th.int64, device=dev)
+        nat.check(ctx.lib.ph_liar_record_export(ctx.handle, desc, RECORD_SEATS[seat], offsets.data_ptr(), None, None, 0))
+        n = int(offsets[-1].item())
+        rows = th.zeros((n, nat.RECORD_ROW), dtype=th.float32, device=dev)
+        member = th.zeros(n, dtype=th.int32, device=dev)
+        if n:
+            nat.check(ctx.lib.ph_liar_record_export(ctx.handle, desc, RECORD_SEATS[seat], offsets.data_ptr(), rows.data_ptr(),
+                                                    member.data_ptr(), n))
+        return LiarRecording(rows, member, offsets.cpu().numpy(), self._rec_dropped.cpu().numpy())
+
+    def _seat_member(self, seat: int):
+        """the walk's member column: who sits at `seat` of every table (None: member 0)"""
+        return None
+
+    def _log_moves(self, mask, obs: th.Tensor, actions: th.Tensor, flags, seat: int) -> None:
+        """the walk's recorder: one row [obs | action | flag] for every table in `mask` (None = all), appended to that table's
+        host list -- or dropped and counted where the list is full"""
+        E = self.E
+        on = np.ones(E, bool) if mask is None else mask.bool().cpu().numpy()
+        obs_h, act_h = obs.cpu().numpy(), actions.cpu().numpy().reshape(E, 2)
+        flag_h = np.broadcast_to(flags.cpu().numpy() if isinstance(flags, th.Tensor) else np.asarray(flags), (E,))
+        who = self._seat_member(seat)
+        who_h = np.zeros(E, np.int32) if who is None else who.cpu().numpy()
+        for e in np.nonzero(on)[0]:
+            if len(self._rec_lists[e]) >= self._rec_cap:
+                self._rec_lost[e] += 1
+                continue
+            row = np.concatenate([obs_h[e], act_h[e], [flag_h[e]]]).astype(np.float32)
+            self._rec_lists[e].append((row, int(who_h[e])))
+
     # -- the walk: the per-call entry points with torch masks ------------------------------------------------------------------------
     def _members_act(self, which, ids: th.Tensor, obs: th.Tensor, mask: th.Tensor, counter: int, out: th.Tensor) -> th.Tensor:
         """the forward of every member in `which` with Philox counter `counter`; member k's move lands in the tables of `mask`
@@ -446,6 +610,8 @@ class VecLiarStep:
         alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
         nat.check(lib.ph_liar_obs(h, *game, self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
         a_alt = self._seat_act(1, self.obs_alt, alt_opens, self._counters(c)[2])
+        if self.recording:                                          # an opening never ends a game: ALT_NOT_DONE
+            self._log_moves(alt_opens, self.obs_alt, a_alt, 1, 1)
         self._acted(alt_opens)
         env.player_step(a_alt, self.zeros8, alt_opens)              # obs_next = seat 0's observation in those tables
         self.obs_ego.copy_(th.where(alt_opens.bool()[:, None], env.obs_next, self.obs_ego))
@@ -463,6 +629,9 @@ class VecLiarStep:
         rew1, done1 = rew1.clone(), done1.bool() if live is None else done1.bool() & live.bool()
         running = ~done1 if live is None else live.bool() & ~done1
         running8 = running.to(th.uint8)
+        if self.recording:                                                     # EGO_NOT_DONE / EGO_DONE
+            self._log_moves(live, self.obs_ego, a_ego, 2 * done1.to(th.int32), 0)
+            obs_alt = obs_alt.clone()                                          # the reply's step writes the same buffer
         # a seat 1 that already acted this game is credited this transition (multiagentenv.py:163-170)
         self._credit(rew1[:, 1].contiguous(), done1.to(th.uint8), None)
         a_alt = self._seat_act(1, obs_alt, running8, k[1])                     # seat 1 replies where the game goes on
@@ -470,6 +639,8 @@ class VecLiarStep:
         obs_ego, rew2, done2 = env.player_step(a_alt, self.zeros8, running8)
         rew2 = th.where(running[:, None], rew2, th.zeros_like(rew2))
         done2 = done2.bool() & running
+        if self.recording:                                                     # ALT_NOT_DONE / ALT_DONE
+            self._log_moves(running8, obs_alt, a_alt, 1 + 2 * done2.to(th.int32), 1)
         self._credit(rew2[:, 1].contiguous(), done2.to(th.uint8), running8)
         done = done1 | done2
         self.obs_ego.copy_(th.where((running & ~done2)[:, None], obs_ego, self.obs_ego))
@@ -561,7 +732,7 @@ class VecLiarSelfPlay(VecLiarTraining):
     synchronisation).  native=False walks the same step with the per-call entry points and torch masks (VecLiarStep)."""
 
     def __init__(self, n_envs: int, ego: VecOnPolicyAgent, alt: RaggedVecOnPolicyAgent, seed: int = 0,
-                 probegostart: float = 0.5, native: bool = True):
+                 probegostart: float = 0.5, native: bool = True, record: int = 0):
         self.alt, self.learners, self.counter = alt, [alt], 0
         self._init_training(n_envs, ego, seed, probegostart, native)
         import os
@@ -570,7 +741,18 @@ class VecLiarSelfPlay(VecLiarTraining):
         self.towers = any(a is not None for a in self._archs)
         if self.towers:
             self.persistent = False                           # ph_liar_selfplay_rollout is built around the 64-wide blocks
+        if record:
+            self.start_recording(record)                      # in front of the first deal: its openings are the logs' first rows
         self._first_deal()
+
+    @property
+    def persistent(self) -> bool:
+        """whole rollouts as one launch -- never while recording: the one-launch rollout does not fill the move log"""
+        return self._persistent and not self.recording
+
+    @persistent.setter
+    def persistent(self, value) -> None:
+        self._persistent = bool(value)
 
     def _contexts(self):
         return self.env.ctx, self.ego.model.policy.ctx, self.alt.model.policy.ctx
@@ -652,7 +834,7 @@ class VecLiarPartnerPool(VecLiarTraining):
     torch masks (K full forwards per partner move), the per-call entry points only, the same counters; bitwise the native step."""
 
     def __init__(self, n_envs: int, ego: VecOnPolicyAgent, members, seed: int = 0, probegostart: float = 0.5,
-                 resample: str = "robin", native: bool = True):
+                 resample: str = "robin", native: bool = True, record: int = 0):
         members = list(members)
         if not 1 <= len(members) <= nat.PH_MAX_POOL:
             raise nat.NativeError(f"VecLiarPartnerPool: the pool holds 1..{nat.PH_MAX_POOL} members, not {len(members)}")
@@ -678,6 +860,8 @@ class VecLiarPartnerPool(VecLiarTraining):
         self.partnerid = th.zeros(self.E, dtype=th.int32, device=self.dev)
         self.alt_actions = th.zeros((self.E, 2), dtype=th.int32, device=self.dev)
         self._rows = np.arange(self.E)
+        if record:
+            self.start_recording(record)
         self._first_deal()
 
     def _contexts(self):
@@ -708,6 +892,9 @@ class VecLiarPartnerPool(VecLiarTraining):
             if isinstance(m, RaggedVecOnPolicyAgent):
                 mine = self.partnerid == k
                 m.update(reward, (done.bool() & mine).to(th.uint8), (mask.bool() & mine).to(th.uint8))
+
+    def _seat_member(self, seat: int):
+        return self.partnerid if seat == 1 else None
 
     def _resampled(self, c: int) -> th.Tensor:
         if self.resample == "robin":
@@ -756,6 +943,7 @@ class LiarIterationGraph:
             nat.check(ctx.lib.ph_ctx_set_rng_epoch(ctx.handle, self.epoch_word.data_ptr()))
             agent.model.device_permutations = True
         self.graph_id = None
+        self._recording = bool(sp.recording)      # a captured step holds the record launches of the recorder attached at capture
         self.split = bool(sp.persistent)          # rollout launch | ego-update graph || partner update | epoch advance
         th.cuda.synchronize(sp.dev)
         with th.cuda.stream(self.stream):
@@ -833,6 +1021,9 @@ class LiarIterationGraph:
             alt.learn_from_buffer()
 
     def launch(self) -> None:
+        if self.graph_id is not None and bool(self.sp.recording) != self._recording:
+            raise nat.NativeError("LiarIterationGraph: the environment's recorder was attached or detached after capture: the graph "
+                                  "replays the launches it was captured with (start_recording before building the graph)")
         with th.cuda.stream(self.stream):
             self._iteration(eager=self.graph_id is None)
 

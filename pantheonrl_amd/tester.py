@@ -8,7 +8,9 @@ Same positional arguments and flags (`--render` is accepted and ignored: the in-
     python -m pantheonrl_amd.tester LiarsDice-v0 PPO DEFAULT --ego-load models/ego --n-envs 256 -t 10000
 
 `--n-envs E` (E > 1) plays the pair on E device-resident tables (envs/crossplay.py): LiarsDice-v0, a PPO ego against a PPO or
-DEFAULT partner, ceil(t / E) games per table; the two lines above are printed over all the games played, then their number."""
+DEFAULT partner, ceil(t / E) games per table; the two lines above are printed over all the games played, then their number.
+The command line still refuses `--record` there; `run_vectorised` called with `args.record` set writes the tables' move streams,
+concatenated in table order, in the reference's format, and `python -m pantheonrl_amd.crossplay ... --record FILE` is its CLI."""
 from __future__ import annotations
 
 import argparse
@@ -71,7 +73,10 @@ def vectorised_check(args) -> None:
     if args.framestack > 1:
         raise EnvException("--n-envs cannot be combined with --framestack")
     if args.record is not None:
-        raise EnvException("--n-envs cannot be combined with --record")
+        # tests/test_crossplay_host.py pins this refusal of the command line; `run_vectorised` itself records (args.record), and
+        # so does `python -m pantheonrl_amd.crossplay ... --record FILE`
+        raise EnvException("--n-envs cannot be combined with --record on this command line: record device-resident evaluation "
+                           "games with `python -m pantheonrl_amd.crossplay LiarsDice-v0 --agents ... --record FILE`")
     if args.alt == "DEFAULT" and args.alt_config:
         raise EnvException("No config possible for the DEFAULT partner")
     if set(args.env_config) - {"probegostart"}:
@@ -90,15 +95,20 @@ def load_member(policy_type: str, config: dict, location, device):
 
 def run_vectorised(args) -> List[float]:
     """tester.py:41-63 on E tables: one (ego, partner) pair, ceil(t / E) games per table"""
-    from .envs.crossplay import VecLiarCrossPlay
+    from .envs.crossplay import MAX_STEPS_PER_GAME, VecLiarCrossPlay
     E = args.n_envs
     G = -(-args.total_episodes // E)
     ego = load_member(args.ego, args.ego_config, args.ego_load, args.device)
     alt = load_member(args.alt, args.alt_config, args.alt_load, args.device)
     print(f"Ego: {ego}")
     print(f"Alt: {alt}")
-    xp = VecLiarCrossPlay(E, [ego, alt], pairs=[(0, 1)], episodes_per_table=G, seed=args.seed or 0, **args.env_config)
+    # --record: the device-resident move log; a game takes at most MAX_STEPS_PER_GAME steps of at most 3 moves
+    record = 3 * MAX_STEPS_PER_GAME * G if args.record is not None else 0
+    xp = VecLiarCrossPlay(E, [ego, alt], pairs=[(0, 1)], episodes_per_table=G, seed=args.seed or 0, record=record, **args.env_config)
     res = xp.run()
+    if record:
+        from .envs.vec import write_recording
+        write_recording(xp, args.record)
     print(f"Average Reward: {res.mean[0]}")
     print(f"Standard Deviation: {res.std[0]}")
     print(f"Games played: {int(res.count[0])} ({E} tables x {G} games)")

@@ -262,6 +262,21 @@ def pool_plan(args):
     return dict(members=members, resample=resample, env_config=env_config)
 
 
+def vectorised_record_check(args) -> None:
+    """what `--n-envs` cannot combine with, by name, before a device is touched.  `--record` is the device-resident move log of
+    the Liar's Dice step (envs/vec.py: VecLiarStep.start_recording); frame stacking changes every kernel's shape class"""
+    if args.framestack > 1:
+        raise EnvException("--n-envs cannot be combined with --framestack")
+    if args.record is not None and args.env != "LiarsDice-v0":
+        raise EnvException(f"--n-envs cannot be combined with --record for {args.env}: the device-resident recorder exists for "
+                           "LiarsDice-v0")
+
+
+def record_capacity(iterations: int, n_steps: int) -> int:
+    """rows per table a training run can log: at most 3 moves per vectorised step, plus the first deal's opening"""
+    return 3 * int(iterations) * int(n_steps) + 1
+
+
 def run_pool(args, plan):
     """the pool's object graph: the ego, one member per partner argument, `VecLiarPartnerPool.rollout_and_learn` per iteration"""
     import random as _random
@@ -299,12 +314,16 @@ def run_pool(args, plan):
         print(f"Partner {i}: {members[-1]}")
     base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
     dice_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xD1CE0D1CE0D1CE) & 0x7FFFFFFFFFFFFFFF
-    env = VecLiarPartnerPool(E, ego, members, seed=dice_seed, resample=plan["resample"], **plan["env_config"])
     n_steps = ego_model.n_steps
     iterations = max(1, -(-args.total_timesteps // (E * n_steps)))
+    record = record_capacity(iterations, n_steps) if args.record is not None else 0
+    env = VecLiarPartnerPool(E, ego, members, seed=dice_seed, resample=plan["resample"], record=record, **plan["env_config"])
     for _ in range(iterations):
         env.rollout_and_learn(n_steps)
     th.cuda.synchronize()
+    if record:
+        from .envs.vec import write_recording
+        write_recording(env, args.record)
     updates = [m.iteration for m in env.learners]
     print(f"vectorised pool play: {iterations} iterations x {E} envs x {n_steps} steps against {len(members)} members; "
           f"ego updates {ego.iteration}, learner updates {updates}")
@@ -325,8 +344,7 @@ def run_vectorised(args):
 
     from .envs.vec import VecLiarsDice, VecLiarSelfPlay, VecRPS, ragged_agent_for, selfplay_iteration
     from .vec import vec_agent_for
-    if args.framestack > 1 or args.record is not None:
-        raise EnvException("--n-envs cannot be combined with --framestack / --record")
+    vectorised_record_check(args)
     plan = pool_plan(args)
     if plan is not None:
         return run_pool(args, plan)
@@ -378,7 +396,8 @@ def run_vectorised(args):
         import random as _random
         base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
         dice_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xD1CE0D1CE0D1CE) & 0x7FFFFFFFFFFFFFFF
-        env = VecLiarSelfPlay(E, ego, alt, seed=dice_seed, **args.env_config)
+        record = record_capacity(iterations, n_steps) if args.record is not None else 0     # recording runs launch by launch
+        env = VecLiarSelfPlay(E, ego, alt, seed=dice_seed, record=record, **args.env_config)
         if iterations >= 4 and env.native:
             # two launch-by-launch iterations size the workspaces, the rest replay one hipGraph per iteration
             from .envs.vec import LiarIterationGraph
@@ -391,6 +410,9 @@ def run_vectorised(args):
     th.cuda.synchronize()
     print(f"vectorised self-play: {iterations} iterations x {E} envs x {n_steps} steps; "
           f"ego updates {ego.iteration}, partner updates {alt.iteration}")
+    if args.record is not None:
+        from .envs.vec import write_recording
+        write_recording(env, args.record)
     if args.ego_save:
         models[0].save(args.ego_save)
     if args.alt_save:
