@@ -286,7 +286,35 @@ bool fwd_args_lean(const FwdArgs& a, bool joint_ok = false) {
 
 constexpr int ZS_FLOATS = 4 * 16 * 8;   // the head's four partial output tiles in LDS (one per wave)
 
-template <bool VALU, int LEAN = 0>
+// The tail wave's hook into discrete8_row_tail (TW = 4 below): its arrival at the layer-1 barrier of the step the other waves are
+// in, between the two halves of the tail, and the predicate of a lane whose row does not exist.
+struct TailWaveHook {
+  bool arrive, alive;   // arrive: wave-uniform
+  long long* stamp;     // debug builds: the workgroup's stamp record in this wave's lane 0 for the stamped tail, else null
+  // act, lse: operands of the arrival.  Everything the first half computes feeds stores that only a live lane executes, and left
+  // alone the compiler sinks that arithmetic behind the barrier, into the predicated block -- the whole tail then ran under layer 2.
+  __device__ __forceinline__ void split(int act, float lse) const {
+    if (stamp) stamp[4] = (long long)clock64();
+    if (arrive) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::"v"(act), "v"(lse) : "memory");
+    else asm volatile("" ::"v"(act), "v"(lse));
+  }
+  __device__ __forceinline__ bool live() const { return alive; }
+};
+
+// TW: the wave that owns the row tail.  0: wave 0, behind the head barrier, with waves 1..3 waiting for it at the top of the next
+// step (per-step launches, where there is no next step, and the exchange rollout, whose value tail polls).  4 (the one-launch
+// rollout, 320 threads): a fifth wave that holds no weights and takes no part in the layers.  Nothing in step t + 1 consumes what
+// the tail of step t produces -- the rows come from the script -- so wave 4 runs the tail of step t UNDER the layers of step t + 1:
+//
+//   waves 0..3:  top(t+1) | layer 1       | layer 2          | head product -> zs(t+1) | rows of t+2 -> xs | top(t+2) ...
+//   wave 4:      top(t+1) | fold zs(t),   | log-prob, stores,| uniform of t+1          |                  | top(t+2) ...   (tail of step t)
+//                         | softmax, act  | preloads of t+1  |                         |
+//
+// gfx950 has ONE workgroup barrier and every live wave counts towards it: wave 4 arrives at every barrier of the step, the same
+// number of times as the others, and does its work between arrivals (a barrier does not care where in the program a wave stands).
+// It folds zs into registers before it arrives at the layer-1 barrier of step t + 1, and waves 0..3 write zs again only behind the
+// layer-2 barrier of that step: one buffer.  After the last step the other waves leave; wave 4 runs the last tail alone.
+template <bool VALU, int LEAN = 0, int TW = 0>
 __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2p* px = nullptr, int px_t = 0, int px_a_local = 0,
                                                   int agent = 0, const ScriptedSteps* sc = nullptr, int px_persistent = 0) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -295,6 +323,16 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   FwdArgs a = a0;
   if constexpr (LEAN == 1) fwd_args_pin_lean<false>(a);
   if constexpr (LEAN == 2) fwd_args_pin_lean<true>(a);
+  // Beside a tail wave no form of the kernel takes action masks, teacher-forced uniforms or actions, or `deterministic`: the one-launch
+  // entry point has no argument that could carry them, launch_policy_fwd16_rollout refuses a record that does, and the fields are
+  // constants here, so that no path of the tails that nothing can reach is compiled into the 320-thread schedule.
+  if constexpr (TW != 0) {
+    a.mask = nullptr;
+    a.env_mask = nullptr;
+    a.uniforms = nullptr;
+    a.given_actions = nullptr;
+    a.deterministic = 0;
+  }
 #ifdef PH_LEAN_PROF
   long long* const prof0 = a0.prof;
 #else
@@ -309,7 +347,10 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   unsigned long long** pxll = (unsigned long long**)(upre + 32);   // [PH_MAX_RANKS] every rank's receive area (exchange forms)
 
   const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
+  const int wave = TW ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
+  // lw: a layer wave -- every wave where wave 0 owns the tail.  (wave is scalar beside a tail wave, so a branch on it is the wave's.)
+  // A tail wave holds no weights and stages no rows; it arrives at the prologue's barriers and leaves for its own loop in front of the step loop.
+  const bool lw = TW == 0 || wave < 4;
   const int net = blockIdx.y;
   const int row0 = blockIdx.x * R;
   const ph_layout& lay = nd.lay;
@@ -346,20 +387,21 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
 #pragma unroll
   for (int s = 0; s < 16; ++s) {
     const int k = g + 4 * s;
-    bw1[s] = (k < nd.F) ? W1[k * HID + col] : 0.f;
-    bw2[s] = W2[k * HID + col];
+    bw1[s] = (lw && k < nd.F) ? W1[k * HID + col] : 0.f;
+    bw2[s] = lw ? W2[k * HID + col] : 0.f;
   }
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     const int k = g + 4 * (4 * wave + s);
     bwh[s] = 0.f;
+    if (!lw) continue;
     if (net == 0) {
       if (c < nk) bwh[s] = a.params[lay.act_W + k * nk + c];
     } else if (c == 0) {
       bwh[s] = a.params[lay.val_W + k];
     }
   }
-  const float bias1 = B1[col], bias2 = B2[col];
+  const float bias1 = lw ? B1[col] : 0.f, bias2 = lw ? B2[col] : 0.f;
   float hbias = 0.f;
   if (wave == 0) {
     if (net == 0) hbias = (c < nk) ? a.params[lay.act_b + c] : 0.f;
@@ -368,7 +410,8 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   XStage<R, NT> xr;
   lds_only_barrier();  // rowphys visible
   if (sc) a.obs = sc->obs_seq;
-  xr.issue(rowphys, a.obs, nd, 0);
+  const bool xsync = nd.obs_kind != PH_SPACE_BOX;   // XStage's commit of one-hot rows has a barrier of its own in the middle: a tail wave counts it
+  if (lw) xr.issue(rowphys, a.obs, nd, 0);
   // (one-launch rollouts, Box rows) steps t > 0 take their rows from waves 1..3 (RowStage3): the policy workgroup's behind the head
   // barrier, under wave 0's row tail; the value workgroup's, which has no action to wait for, at the start of the head phase.  The
   // value workgroup's waves 1..3 also issue RolloutBuffer.add's observation copy of a step straight from those registers, right
@@ -376,12 +419,14 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   // (one counter for loads and stores on gfx950), and with no second register set: the rows are dead once stored.  Step 0's rows
   // are fetched into the same registers here, once per launch, so that the copy has ONE form for every step.
   // (Per-step launches: one step, the prologue's rows, the copy at the end of the step from XStage's registers.)
+  // (Beside a tail wave both workgroups request the rows of step t + 1 at the top of step t and commit them behind its head barrier.)
   const bool staged = sc != nullptr && nd.obs_kind == PH_SPACE_BOX;
-  const bool copy_staged = staged && net == 1 && a.rb_obs && !a.pos_env && wave != 0;
+  const bool copy_staged = staged && net == 1 && a.rb_obs && !a.pos_env && (TW ? wave != 0 && wave < 4 : wave != 0);
   const unsigned roff = RowStage3::base_offset(row0, nd, tid);
   RowStage3 rows;
   if (copy_staged) rows.issue(a.obs, a0.n, nd, roff, tid);
-  xr.commit(xs, rowphys, a.obs, nd, 0);
+  if (lw) xr.commit(xs, rowphys, a.obs, nd, 0);
+  if (TW != 0 && !lw && xsync) lds_only_barrier();
   // Every load issued so far (weights, biases, the first rows) is waited for HERE, once, as an instruction the compiler's wait
   // insertion can see: otherwise the registers loaded ahead of the step loop stay "pending" at its header, and every step waits
   // `vmcnt(k)` inside layer 1 and `vmcnt(0)` before the bias adds -- which, with ONE counter for loads and stores on gfx950, drains
@@ -407,7 +452,8 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
     if (lane < R && row0 + lane < a0.n)
       upre[(t1 & 1) * R + lane] = philox_uniform(a0.seed, a0.counter + (unsigned long long)t1 + epoch_hi, (uint32_t)(row0 + lane), 0u);
   };
-  if (draw_ahead && wave == 1) draw_uniforms(0);   // visible to wave 0 after the barriers of step 0's layers
+  // (a tail wave draws its own, in the part of a step where it has nothing else to do)
+  if (TW == 0 && draw_ahead && wave == 1) draw_uniforms(0);   // visible to wave 0 after the barriers of step 0's layers
 
   // one 16x16 output tile per wave: D[row 4g+r][this lane's column] = sum_k A[row][k] B[k][column]; two accumulator chains
   auto product = [&](const float* A, const float (&bw)[16]) -> f32x4 {
@@ -428,11 +474,8 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
     return e + o;
   };
 
-  for (int t = 0; t < n_steps; ++t) {
-  // debug stamps of ONE step in the middle of a scripted rollout (slots 8..15: scripts/rollout_phase.py)
-  long long* const pstep = (sc && t == 8) ? prof0 : nullptr;
-  PH_STAMP(pstep, 8);
-  if (t > 0) {   // (scripted rollout) the next step's argument record and observation rows; the weights stay where they are
+  // (scripted rollout) the argument record of step t > 0; the weights stay where they are
+  auto step_record = [&](FwdArgs& a, int t) {
     const size_t row = (size_t)t * a0.n;
     a.obs = sc->obs_seq + row * nd.D;
     a.counter = a0.counter + (unsigned long long)t + epoch_hi;
@@ -445,7 +488,7 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
     a.es_in = sc->done_seq + (row - a0.n);          // Agent.update(reward, done) of the previous step:
     a.pending_reward = sc->rew_seq + (row - a0.n);  //   last_episode_starts = done, rewards[pos - 1] += reward
     a.prev_rew = a0.rb_rew + (row - a0.n);
-    if constexpr (!LEAN) {
+    if constexpr (!LEAN && TW == 0) {
       a.mask = (sc->mask_seq && sc->mask_policy) ? sc->mask_seq + row * nd.L : nullptr;
       a.env_mask = (sc->mask_seq && sc->mask_env) ? sc->mask_seq + row * nd.L : nullptr;
     }
@@ -455,6 +498,133 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
       a.ll_t = t - 1;
     }
     a.prof = nullptr;
+  };
+
+  // The row tail of step t: the lane owns row r of the tile (global row grow) and reads the head's four partial tiles from zs.
+  // Wave 0 calls it behind the head barrier for the lanes that have a row; a tail wave calls it with EVERY lane, in uniform control
+  // flow (its hook holds a barrier arrival), a lane without a row on the clamped last row of the tile and with its stores off.
+  auto row_tail = [&](const FwdArgs& a, int t, int r, int grow, const ValuePre& vpre, const float* up, long long* pstep, auto hook) {
+    // the row's logits: (partial 0 + partial 1) + (partial 2 + partial 3), the same tree in every form of this kernel
+    float z[8];
+    {
+      float4 q[4][2];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        q[w][0] = *reinterpret_cast<const float4*>(zs + (w * R + r) * 8);
+        q[w][1] = *reinterpret_cast<const float4*>(zs + (w * R + r) * 8 + 4);
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        z[4 * h + 0] = (q[0][h].x + q[1][h].x) + (q[2][h].x + q[3][h].x);
+        z[4 * h + 1] = (q[0][h].y + q[1][h].y) + (q[2][h].y + q[3][h].y);
+        z[4 * h + 2] = (q[0][h].z + q[1][h].z) + (q[2][h].z + q[3][h].z);
+        z[4 * h + 3] = (q[0][h].w + q[1][h].w) + (q[2][h].w + q[3][h].w);
+      }
+    }
+    if (net == 0) {
+      const uint64_t ctr = fwd_counter(a);
+      int act;
+      switch (nk) {   // the logit count as a compile-time constant: the tail's loops shrink to the logits that exist
+        case 1: act = discrete8_row_tail<1>(a, nd, grow, z, ctr, up, pstep, hook); break;
+        case 2: act = discrete8_row_tail<2>(a, nd, grow, z, ctr, up, pstep, hook); break;
+        case 3: act = discrete8_row_tail<3>(a, nd, grow, z, ctr, up, pstep, hook); break;
+        case 4: act = discrete8_row_tail<4>(a, nd, grow, z, ctr, up, pstep, hook); break;
+        case 5: act = discrete8_row_tail<5>(a, nd, grow, z, ctr, up, pstep, hook); break;
+        case 6: act = discrete8_row_tail<6>(a, nd, grow, z, ctr, up, pstep, hook); break;
+        case 7: act = discrete8_row_tail<7>(a, nd, grow, z, ctr, up, pstep, hook); break;
+        default: act = discrete8_row_tail<8>(a, nd, grow, z, ctr, up, pstep, hook); break;
+      }
+      if (px && hook.live()) {  // push: (stamp << 32 | action) as one 8-byte store into every rank's receive area, slot t mod ll_slots
+        const int pt = px_t + t;
+        const int slot = px_persistent ? p2p_persistent_slot(px_epoch, pxT, pt) : pt % pxslots;
+        const size_t off = (size_t)slot * pxw * pxc + (size_t)(pxr * px_a_local + agent) * a.n + grow;
+        const unsigned long long w =
+            ((unsigned long long)p2p_stamp32(px_persistent ? px_epoch : *px->epoch, pxT, pt) << 32) | (unsigned long long)(unsigned)act;
+        for (int p = 0; p < pxw; ++p)
+          __hip_atomic_store(PXLL(p) + off, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    } else {
+      if (hook.live()) {
+        // (for a live row the preload condition IS its last two terms: said so, the lean forms see a constant, the tail's own loads -- the
+        // arms without a preload, each a branch that may leave a load pending up to the loop's header -- fold away)
+        value_row_tail(a, grow, z[0], !a.pos_env && a.rb_val, vpre);
+        // (scripted rollout) the last step's own reward: the flush that precedes GAE on the launch-by-launch path
+        if (sc && t == n_steps - 1) {
+          float add = sc->rew_seq[(size_t)t * a0.n + grow];
+          if (px_persistent && a0.joint) {   // ph_buffer_add_reward_joint of the launch-by-launch walk: base + bonus * [own == partner's]
+            FwdArgs b = a;
+            b.joint_ll = ll_self + (size_t)p2p_persistent_slot(px_epoch, pxT, t) * pxw * pxc;
+            b.ll_t = t;
+            int p = *a0.partner_seat;
+            p = p < 0 ? 0 : (p >= a0.n_seats ? a0.n_seats - 1 : p);
+            const int mine = ll_read(b, b.joint_ll + (size_t)a0.seat * a0.n + grow);
+            const int theirs = ll_read(b, b.joint_ll + (size_t)p * a0.n + grow);
+            add += joint_reward(mine, theirs, a0.bonus, a0.reward_rule);
+          }
+          a.rb_rew[grow] += add;
+        }
+      }
+      hook.split(0, z[0]);
+    }
+  };
+
+  if constexpr (TW != 0) {
+    if (!lw) {
+      // ---- the tail wave: the tail of step s between its arrivals at the barriers of step s + 1 (see the head of the body) ----
+      const int nlive = (a0.n - row0 < R) ? a0.n - row0 : R;       // >= 1: the tile exists
+      const int r = lane < nlive ? lane : nlive - 1, grow = row0 + r;   // a lane without a row walks the tile's last one, stores off
+      const bool live = lane < nlive;
+#ifdef PH_LEAN_PROF   // (slots 2 / 4 / 6 are PH_TAIL_STAMPS' in every other build: only scripts/rollout_phase.py's build writes them here)
+      long long* const wstamp = (prof0 && lane == 0) ? prof0 + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 : nullptr;
+#else
+      long long* const wstamp = nullptr;
+#endif
+      auto draw = [&](int t) { return philox_uniform(a0.seed, a0.counter + (unsigned long long)t + epoch_hi, (uint32_t)grow, 0u); };
+      // what the value tail reads, one step ahead and behind the previous tail's stores (it reads the reward row that tail zeroed);
+      // every lane, on its clamped row: no branch between the loads and their use
+      auto preload = [&](const FwdArgs& a) {
+        return (net == 1 && !a.pos_env && a.rb_val) ? value_row_preload(a, grow) : ValuePre{0.f, 0.f, 0.f, 0ull, 0ull, 0u, 0, 0};
+      };
+      // (its own uniform goes through the row's word of upre, which nobody else uses here: a pointer to a local that may also be
+      // null would put the local in scratch)
+      if (draw_ahead) upre[r] = draw(0);
+      ValuePre vpre = preload(a);
+      lds_only_barrier();   // step 0: layer 1
+      lds_only_barrier();   //         layer 2
+      lds_only_barrier();   //         head: zs holds step 0
+      for (int s = 0; s < n_steps; ++s) {
+        const bool more = s + 1 < n_steps;   // the other waves run step s + 1 beside this tail; after the last step they are gone
+        if (more) {
+          if (xsync) lds_only_barrier();   // XStage's own, in the commit of the one-hot rows of step s + 1 (the arrival alone: no drain of this wave's stores)
+          lds_only_barrier();           // top of step s + 1: nothing in front of it
+        }
+        // debug stamps of ONE tail, the one under the step the layer waves stamp (slots 2 / 4 / 6: scripts/rollout_phase.py)
+        long long* const ws = (s == 7) ? wstamp : nullptr;
+        if (ws) ws[2] = (long long)clock64();
+        // zs(s) goes into registers first thing.  The arrival below (the hook's, where the action is known) is at the LAYER-1 barrier
+        // of step s + 1; the layer waves write zs(s + 1) behind its LAYER-2 barrier, which they cannot pass before this wave has
+        // arrived there too, further down: one zs buffer is enough.
+        row_tail(a, s, r, grow, vpre, draw_ahead ? upre + r : nullptr, nullptr, TailWaveHook{more, live, ws});
+        if (ws) ws[6] = (long long)clock64();
+        if (more) {
+          step_record(a, s + 1);
+          vpre = preload(a);
+          lds_only_barrier();   // layer 2 of step s + 1
+          if (draw_ahead) upre[r] = draw(s + 1);
+          lds_only_barrier();   // head of step s + 1: zs holds step s + 1
+        }
+      }
+      return;
+    }
+    __builtin_amdgcn_s_setprio(1);   // the layer waves are the chain: wave 0 shares its SIMD with the tail wave and goes first
+  }
+
+  for (int t = 0; t < n_steps; ++t) {
+  // debug stamps of ONE step in the middle of a scripted rollout (slots 8..15: scripts/rollout_phase.py)
+  long long* const pstep = (sc && t == 8) ? prof0 : nullptr;
+  PH_STAMP(pstep, 8);
+  if (t > 0) {   // (scripted rollout) the next step's argument record and observation rows; the weights stay where they are
+    step_record(a, t);
     // Box rows of this step: waves 1..3 put them into xs behind the previous step's head barrier (below).  One-hot rows are built
     // here by the whole workgroup.  (No barrier before xs is overwritten: every wave read its part of H2 before the head phase's
     // own barrier.)
@@ -469,11 +639,16 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   PH_STAMP(pstep, 9);
   const bool more = t + 1 < n_steps;   // (one-launch rollouts) waves 1..3 stage the rows of step t + 1 inside this step
   const float* const obs_next = sc ? sc->obs_seq + (size_t)(t + 1) * a0.n * nd.D : nullptr;
+  // (beside a tail wave) the rows of step t + 1 are requested HERE, a whole step ahead of their commit behind the head barrier: the
+  // window under wave 0's tail, where the policy workgroup's waves 1..3 used to fetch them, is gone, and a request at the start of
+  // the head phase left a third of an HBM round trip in front of the next top-of-step barrier (the stamps' "X rows" phase).  The
+  // registers are free: the previous rows were committed, and copied out, before that barrier.
+  if (TW != 0 && staged && more && wave != 0) rows.issue(obs_next, a0.n, nd, roff, tid);
 
   // value workgroup, rectangular rollout: what the row tail reads (previous done, pending reward, the reward row it adds to) is
   // fetched here, under the layers; RolloutBuffer.add's observation copy of Box rows goes out straight from the staged registers
   // (the row was read once: no second trip to the observation)
-  const bool pre_ok = net == 1 && wave == 0 && lane < R && row0 + lane < a.n && !a.pos_env && a.rb_val;
+  const bool pre_ok = TW == 0 && net == 1 && wave == 0 && lane < R && row0 + lane < a.n && !a.pos_env && a.rb_val;
   ValuePre vpre = {0.f, 0.f, 0.f, 0ull, 0ull, 0u, 0, 0};
   if (pre_ok) vpre = value_row_preload(a, row0 + lane);
   const bool copy_from_regs = net == 1 && a.rb_obs && !a.pos_env && nd.obs_kind == PH_SPACE_BOX;
@@ -495,7 +670,7 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   PH_STAMP(pstep, 11);
 
   // value workgroup of a one-launch rollout: the rows of step t + 1 are requested HERE (nothing of it waits for an action)
-  if (staged && net == 1 && more && wave != 0) rows.issue(obs_next, a0.n, nd, roff, tid);
+  if (TW == 0 && staged && net == 1 && more && wave != 0) rows.issue(obs_next, a0.n, nd, roff, tid);
 
   // ---- head: a third product (columns = logits, or the value in column 0) ----
   {   // every wave: its K quarter (four MFMAs, two chains), the partial tile to zs[wave]; wave 0's partial carries the bias
@@ -523,84 +698,24 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
   // another consumes, stay "pending" on the paths that skip the tail, and the compiler drains the counter at the loop's header
   // instead -- behind the top-of-step barrier, where wave 0 has just issued the row tail's stores and waves 1..3 the copy's.
   if (sc) vm_drain();
-  if (staged && more && wave != 0) {
-    if (net == 1) {   // value workgroup: in by now, or nearly; step t + 1's observation copy leaves with them (stores only, no drain)
+  if (staged && more && wave != 0 && lw) {
+    if (net == 1 || TW != 0) {   // value workgroup: in by now, or nearly; step t + 1's observation copy leaves with them (stores only, no drain)
       rows.commit(xs, tid);
       if (copy_staged) rows.copy_out(a0.rb_obs + (size_t)(t + 1) * a0.n * nd.D, a0.n, nd.D, roff, tid);
     }
   }
-  if (wave == 0) {
+  if (TW != 0) PH_STAMP(pstep, 13);
+  if (TW == 0 && wave == 0) {
     PH_STAMP(pstep, 13);
     const int r = lane, grow = row0 + lane;   // lane r < 16 owns row r
-    if (r < R && grow < a.n) {
-      // the row's logits: (partial 0 + partial 1) + (partial 2 + partial 3), the same tree in every form of this kernel
-      float z[8];
-      {
-        float4 q[4][2];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          q[w][0] = *reinterpret_cast<const float4*>(zs + (w * R + r) * 8);
-          q[w][1] = *reinterpret_cast<const float4*>(zs + (w * R + r) * 8 + 4);
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          z[4 * h + 0] = (q[0][h].x + q[1][h].x) + (q[2][h].x + q[3][h].x);
-          z[4 * h + 1] = (q[0][h].y + q[1][h].y) + (q[2][h].y + q[3][h].y);
-          z[4 * h + 2] = (q[0][h].z + q[1][h].z) + (q[2][h].z + q[3][h].z);
-          z[4 * h + 3] = (q[0][h].w + q[1][h].w) + (q[2][h].w + q[3][h].w);
-        }
-      }
-      if (net == 0) {
-        const float* up = draw_ahead ? upre + (t & 1) * R + r : nullptr;
-        const uint64_t ctr = fwd_counter(a);
-        int act;
-        switch (nk) {   // the logit count as a compile-time constant: the tail's loops shrink to the logits that exist
-          case 1: act = discrete8_row_tail<1>(a, nd, grow, z, ctr, up, pstep); break;
-          case 2: act = discrete8_row_tail<2>(a, nd, grow, z, ctr, up, pstep); break;
-          case 3: act = discrete8_row_tail<3>(a, nd, grow, z, ctr, up, pstep); break;
-          case 4: act = discrete8_row_tail<4>(a, nd, grow, z, ctr, up, pstep); break;
-          case 5: act = discrete8_row_tail<5>(a, nd, grow, z, ctr, up, pstep); break;
-          case 6: act = discrete8_row_tail<6>(a, nd, grow, z, ctr, up, pstep); break;
-          case 7: act = discrete8_row_tail<7>(a, nd, grow, z, ctr, up, pstep); break;
-          default: act = discrete8_row_tail<8>(a, nd, grow, z, ctr, up, pstep); break;
-        }
-        if (px) {  // push: (stamp << 32 | action) as one 8-byte store into every rank's receive area, slot t mod ll_slots
-          const int pt = px_t + t;
-          const int slot = px_persistent ? p2p_persistent_slot(px_epoch, pxT, pt) : pt % pxslots;
-          const size_t off = (size_t)slot * pxw * pxc + (size_t)(pxr * px_a_local + agent) * a.n + grow;
-          const unsigned long long w =
-              ((unsigned long long)p2p_stamp32(px_persistent ? px_epoch : *px->epoch, pxT, pt) << 32) | (unsigned long long)(unsigned)act;
-          for (int p = 0; p < pxw; ++p)
-            __hip_atomic_store(PXLL(p) + off, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      } else {
-        // (inside this block pre_ok IS its last two terms: said so, the lean forms see a constant, the tail's own loads -- the arms
-        // without a preload, each a branch that may leave a load pending up to the loop's header -- fold away)
-        value_row_tail(a, grow, z[0], !a.pos_env && a.rb_val, vpre);
-        // (scripted rollout) the last step's own reward: the flush that precedes GAE on the launch-by-launch path
-        if (sc && t == n_steps - 1) {
-          float add = sc->rew_seq[(size_t)t * a0.n + grow];
-          if (px_persistent && a0.joint) {   // ph_buffer_add_reward_joint of the launch-by-launch walk: base + bonus * [own == partner's]
-            FwdArgs b = a;
-            b.joint_ll = ll_self + (size_t)p2p_persistent_slot(px_epoch, pxT, t) * pxw * pxc;
-            b.ll_t = t;
-            int p = *a0.partner_seat;
-            p = p < 0 ? 0 : (p >= a0.n_seats ? a0.n_seats - 1 : p);
-            const int mine = ll_read(b, b.joint_ll + (size_t)a0.seat * a0.n + grow);
-            const int theirs = ll_read(b, b.joint_ll + (size_t)p * a0.n + grow);
-            add += joint_reward(mine, theirs, a0.bonus, a0.reward_rule);
-          }
-          a.rb_rew[grow] += add;
-        }
-      }
-    }
+    if (r < R && grow < a.n) row_tail(a, t, r, grow, vpre, draw_ahead ? upre + (t & 1) * R + r : nullptr, pstep, TailNoHook{});
   }
   PH_STAMP(pstep, 14);
   // policy workgroup: waves 1..3 come here straight from the head barrier (the tail above is wave 0's) and request the rows where
   // they always did -- but all sixteen of them, and in under the row tail; the registers are not live across the tail's code
-  const bool stage_here = staged && net == 0 && more && wave != 0;
+  const bool stage_here = TW == 0 && staged && net == 0 && more && wave != 0;
   if (stage_here) rows.issue(obs_next, a0.n, nd, roff, tid);
-  if (draw_ahead && wave == 1 && more) draw_uniforms(t + 1);
+  if (TW == 0 && draw_ahead && wave == 1 && more) draw_uniforms(t + 1);
   if (stage_here) {
     rows.commit(xs, tid);
     vm_drain();   // the rows are in (the commit waited for them): say so, or the loop's header keeps them pending
@@ -615,7 +730,7 @@ __device__ __forceinline__ void policy_fwd16_body(const FwdArgs& a0, const ph_p2
       }
     }
   } else if (net == 1) {
-    copy_obs_rows(a, row0, (a.n - row0 < R) ? a.n - row0 : R, nd.D);
+    copy_obs_rows(a, row0, (a.n - row0 < R) ? a.n - row0 : R, nd.D, TW ? tid : -1, NT);
   }
   PH_STAMP(a.prof, 7);
   PH_STAMP(pstep, 15);
@@ -644,9 +759,13 @@ __global__ __launch_bounds__(256) void policy_fwd16_kernel(FwdArgs a) {
     }
   }
 }
+// 320 threads: four layer waves and the tail wave (policy_fwd16_body, TW = 4).  Two waves then share a SIMD (taken to be SIMD 0, wave 0's: inferred from the stamps, not read back) and with it its 512
+// registers; the VALU cross-check (gemm_mode 1) needs 368 for its ds_bpermute restatement of the products, so it keeps the
+// 256-thread form with wave 0's tail: the same arithmetic in the other schedule, bitwise the same rollout.
+constexpr int ROLLOUT_THREADS = 320;
 template <bool VALU, bool LEAN>
-__global__ __launch_bounds__(256) void policy_fwd16_rollout_kernel(FwdArgs a, ScriptedSteps sc) {
-  policy_fwd16_body<VALU, LEAN ? 1 : 0>(a, nullptr, 0, 0, 0, &sc);
+__global__ __launch_bounds__(VALU ? 256 : ROLLOUT_THREADS) void policy_fwd16_rollout_kernel(FwdArgs a, ScriptedSteps sc) {
+  policy_fwd16_body<VALU, LEAN ? 1 : 0, VALU ? 0 : 4>(a, nullptr, 0, 0, 0, &sc);
 }
 template <bool LEAN>
 __global__ __launch_bounds__(256) void policy_fwd16_multi_kernel(FwdMulti m) {
@@ -702,9 +821,11 @@ static size_t rollout_lds_bytes(int nwg_total) {
   return (cu > 0 && 2 * nwg_total <= cu) ? (size_t)81 * 1024 + 512 : fwd16_lds_bytes();
 }
 hipError_t launch_policy_fwd16_rollout(const FwdArgs& a, const ScriptedSteps& sc, int gemm_mode, hipStream_t s) {
-  dim3 grid((a.n + 15) / 16, 2), block(256);
+  // (ph_scripted_rollout hands over none of these; the tail-wave forms are built without them -- an error, not another path)
+  if (a.mask || a.env_mask || a.uniforms || a.given_actions || a.deterministic || sc.mask_seq) return hipErrorInvalidValue;
+  const int variant = gemm_mode == 1 ? 1 : (fwd_args_lean(a) ? 2 : 0);   // 1: VALU cross-check, 2: lean, 0: general (debug stamps)
+  dim3 grid((a.n + 15) / 16, 2), block(variant == 1 ? 256 : ROLLOUT_THREADS);
   const size_t lds = rollout_lds_bytes((int)(grid.x * grid.y));
-  const int variant = gemm_mode == 1 ? 1 : ((fwd_args_lean(a) && !sc.mask_seq) ? 2 : 0);   // 1: VALU cross-check, 2: lean, 0: general
   const void* fn = variant == 1 ? (const void*)policy_fwd16_rollout_kernel<true, false>
                                 : (variant == 2 ? (const void*)policy_fwd16_rollout_kernel<false, true> : (const void*)policy_fwd16_rollout_kernel<false, false>);
   if (const hipError_t e = allow_dynamic_lds(fn, lds); e != hipSuccess) return e;

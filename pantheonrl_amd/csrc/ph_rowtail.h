@@ -164,16 +164,26 @@ __device__ __forceinline__ uint64_t fwd_counter(const FwdArgs& a) {
 #else
 #define PH_TAIL_STAMP(slot) do { } while (0)
 #endif
-template <int NK = 8>
+// hook: what a caller that runs the tail on a wave of its own, beside other waves' work, needs from it (the one-launch rollout's
+// tail wave).  `split()` runs once, in uniform control flow, where the action is known and nothing of the row is stored yet -- the
+// caller's barrier arrival between the two halves of the tail, handed what the first half computed (the action and the log-sum-exp:
+// a hook that names them as operands of its barrier keeps the first half in front of it); `live()` predicates every store, so that
+// a lane without a row can walk the tail on a clamped row instead of branching round it.  TailNoHook: nothing, and every lane
+// live -- the code without a hook.
+struct TailNoHook {
+  __device__ __forceinline__ void split(int, float) const {}
+  __device__ __forceinline__ constexpr bool live() const { return true; }
+};
+template <int NK = 8, class Hook = TailNoHook>
 __device__ __forceinline__ int discrete8_row_tail(const FwdArgs& a, const NetDims& nd, int g, float (&zr)[8], uint64_t ctr,
-                                                  const float* u_pre = nullptr, long long* tail_dbg = nullptr) {
+                                                  const float* u_pre = nullptr, long long* tail_dbg = nullptr, const Hook hook = Hook{}) {
   const int nk = NK < 8 ? NK : nd.L;
   if (a.mask) {  // modular/policies.py:330-333 : logits - 30*(~mask)
 #pragma unroll
     for (int k = 0; k < 8; ++k)
       if (k < nk) zr[k] = zr[k] - 30.0f * (1.0f - (float)(a.mask[(size_t)g * nk + k] != 0));
   }
-  if (a.logits) {
+  if (a.logits && hook.live()) {
 #pragma unroll
     for (int k = 0; k < 8; ++k)
       if (k < nk) a.logits[(size_t)g * nk + k] = zr[k];
@@ -216,6 +226,7 @@ __device__ __forceinline__ int discrete8_row_tail(const FwdArgs& a, const NetDim
     }
   }
   PH_TAIL_STAMP(4);
+  hook.split(act, lse);
   float zact = 0.f, ent = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -235,6 +246,7 @@ __device__ __forceinline__ int discrete8_row_tail(const FwdArgs& a, const NetDim
       if (k < nk && a.env_mask[(size_t)g * nk + k] != 0) env_act = k;
   }
   PH_TAIL_STAMP(6);
+  if (!hook.live()) return env_act;
   if (a.act_i32) a.act_i32[g] = env_act;
   if (a.act_f32) a.act_f32[g] = (float)act;
   if (a.logp) a.logp[g] = logp;

@@ -43,6 +43,17 @@ for net in range(2):
     print(f"net {net}: step 8 of {len(blk)} workgroups, {np.median(blk[:, -1] - blk[:, 0]):.0f} cycles (median)")
     for lab, colv in zip(labels, d.T):
         print(f"    {lab:<58} median {np.median(colv):>7.0f}   max {colv.max():>7.0f}")
+    # the tail wave's own stamps (slots 2 / 4 / 6, written by its lane 0): the tail of step 7, which runs beside step 8's layers --
+    # its two halves against the phases they run under (slot 9: behind the top barrier, 10: behind layer 1's, 11: behind layer 2's)
+    raw = st[net * nwg:(net + 1) * nwg].astype(np.float64)
+    raw = raw[raw[:, 8] > 0]
+    if len(raw) and (raw[:, [2, 4, 6]] > 0).all() and not os.environ.get("TAIL_STAMPS"):
+        for lab, colv in (("tail wave: fold, softmax, sample (from the top barrier)", raw[:, 4] - raw[:, 2]),
+                          ("tail wave: its start behind wave 0's layer-1 start", raw[:, 2] - raw[:, 9]),
+                          ("tail wave: first half done, relative to the layer-1 barrier opening (about 0: the barrier waited for it)", raw[:, 4] - raw[:, 10]),
+                          ("tail wave: second half (log-prob, stores | value, reward), from its layer-1 arrival", raw[:, 6] - raw[:, 4]),
+                          ("tail wave: second half done, relative to the layer-2 barrier opening (about 0: the barrier waited for it)", raw[:, 6] - raw[:, 11])):
+            print(f"        {lab:<104} median {np.median(colv):>7.0f}   max {colv.max():>7.0f}")
     if net == 0 and os.environ.get("TAIL_STAMPS"):   # library built with -DPH_TAIL_STAMPS: slots 2 / 4 / 6 inside the row tail
         raw = st[:nwg].astype(np.float64)
         raw = raw[raw[:, 8] > 0]
