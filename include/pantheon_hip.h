@@ -562,28 +562,36 @@ int ph_liar_selfplay_rollout(ph_ctx *ctx, const ph_liar_selfplay *s, int ego_pos
  * PH_MAX_POOL members, resampled at that table's own re-deal (MultiAgentEnv.add_partner_agent / resample_round_robin /
  * resample_random, multiagentenv.py:92-147).  A member is a learner (its own ragged rollout buffer and per-table book-keeping
  * vectors, as the partner block of ph_liar_selfplay), a frozen policy (samples like any forward, records nothing) or the
- * scripted player (LiarDefaultAgent, integer rule).  All members share the Liar's Dice spaces and the 64-64 policy. */
+ * scripted player (LiarDefaultAgent, integer rule).  All members share the Liar's Dice spaces; learners and frozen members play
+ * the 64-64 policy.  A clone (PH_POOL_CLONE; an addition, PH_ABI_VERSION unchanged) plays the shared-trunk FeedForward32Policy of
+ * behavioural cloning: `params` is a ph_bc_layout vector for the step's spec (ph_bc_layout_of must succeed for it) and `seed` its
+ * Philox key; rb, pos, boundary, term, open, values and log_probs are ignored and may be NULL.  Like a frozen member it records
+ * nothing.  ph_pool_forward, ph_liar_pool_step and ph_liar_xplay_step accept it. */
 #define PH_MAX_POOL 8
 #define PH_POOL_LEARNER 0
 #define PH_POOL_FROZEN 1
 #define PH_POOL_SCRIPTED 2
+#define PH_POOL_CLONE 3
 #define PH_POOL_ROBIN 0    /* partnerid <- (partnerid + 1) % K at every deal of the table */
 #define PH_POOL_RANDOM 1   /* partnerid <- (uint64(w) * K) >> 32, w = word 0 of Philox block 101 keyed (pool_seed, deal counter, table) */
 typedef struct ph_pool_member {
   int kind;                                  /* PH_POOL_* */
-  const float *params;                       /* learner, frozen */
+  const float *params;                       /* learner, frozen: ph_layout vector; clone: ph_bc_layout vector */
   const ph_rollout *rb;                      /* learner: (T, n) ragged buffer; NULL otherwise */
   int *pos;                                  /* (n) learner: per-table write row */
   unsigned char *boundary, *term, *open;     /* (n) learner: OnPolicyAgent book-keeping per table */
   float *values, *log_probs;                 /* (n) learner: caches of the last recorded forward; frozen: optional */
-  unsigned long long seed;                   /* learner, frozen: Philox key of its forwards */
+  unsigned long long seed;                   /* learner, frozen, clone: Philox key of its forwards */
 } ph_pool_member;
 /* The grouped forward on its own: ONE launch behind a bucket pass (stable counting sort of the tables with active[e] != 0 by
  * partnerid[e], 16-row tiles per member).  A workgroup runs one tile with its member's weights: rows of a learner are recorded
  * at pos[e] of its buffer where the column has room (episode_start_in[e] goes into the row; values cached for recorded rows
  * only), rows of a frozen member write actions only, rows of the scripted member follow ph_liar_default_actions.  Row e draws
  * with the Philox key (member seed, counter, e) -- what ph_policy_forward_ragged / ph_policy_forward use -- and stores its
- * action into actions (n, 2); rows that are not active are not touched.  The spec must run on the 16-row one-hot forward
+ * action into actions (n, 2); rows that are not active are not touched.  A clone's row e draws philox_uniform(member seed,
+ * counter, e, component) -- exactly what ph_bc_forward draws for row e -- and its action is bitwise the one ph_bc_forward(params,
+ * obs, n, seed, counter) samples for that row; it writes actions only.  Clone tiles run in a launch of their own behind the grouped
+ * one, made only when the member table holds a clone (and alone when it holds nothing else).  The spec must run on the 16-row one-hot forward
  * (<= 64 observation components, <= 32 logits). */
 int ph_pool_forward(ph_ctx *ctx, const ph_spec *spec, const ph_pool_member *members, int n_members, const float *obs,
                     const int *partnerid, const unsigned char *active, unsigned long long counter, int *actions,
@@ -619,14 +627,14 @@ typedef struct ph_liar_pool {
 } ph_liar_pool;
 /* One vectorised step (deal_only: only the re-deal half, for the tables flagged in `done`): ego forward, book-keeping, bucket
  * pass + ONE grouped forward for the replies, book-keeping + re-deal + resample, bucket pass + ONE grouped forward for the
- * openers, book-keeping: 8 launches.  No host synchronisation; capturable once it ran outside capture.  The context keeps ONE
+ * openers, book-keeping: 8 launches (10 when the members are clones and others).  No host synchronisation; capturable once it ran outside capture.  The context keeps ONE
  * device-side member table, uploaded (with a stream synchronisation) whenever the members passed in differ from it: a captured step
  * replays against the table uploaded last, so pools that are replayed from graphs should not share a context. */
 int ph_liar_pool_step(ph_ctx *ctx, const ph_liar_pool *pool, int ego_pos, unsigned long long counter, int deal_only);
 
 /* ---- cross-play evaluation of Liar's Dice (csrc/ph_xplay.h; additions, PH_ABI_VERSION unchanged): tester.py:41-63 -- play a
  * fixed ego against a fixed partner for a number of games and report the ego's returns -- for n tables at once.  BOTH seats are
- * held by members of one table of 1..PH_MAX_POOL frozen / scripted members (a learner is refused): table e plays the ordered pair
+ * held by members of one table of 1..PH_MAX_POOL frozen / cloned / scripted members (a learner is refused): table e plays the ordered pair
  * pairs[e % n_pairs] = (seat 0, seat 1) for the whole evaluation, exactly episodes_per_table games, and then goes idle: it is
  * masked out of every forward and pass, and its state and logs do not change again.  A game's return is the sum of the ego rewards
  * MultiAgentEnv.step returns over the game (the ego's own transition plus the reply's, multiagentenv.py:201-202), accumulated in
@@ -640,7 +648,7 @@ typedef struct ph_liar_xplay {
   unsigned char *ego_first;
   unsigned long long dice_seed;
   float probegostart;
-  const ph_pool_member *members;             /* host array [n_members]: PH_POOL_FROZEN / PH_POOL_SCRIPTED */
+  const ph_pool_member *members;             /* host array [n_members]: PH_POOL_FROZEN / PH_POOL_CLONE / PH_POOL_SCRIPTED */
   int n_members;
   const int *pairs;                          /* host array [n_pairs][2]: (member at seat 0, member at seat 1) */
   int n_pairs;                               /* 1..n */
@@ -660,7 +668,8 @@ typedef struct ph_liar_xplay {
 } ph_liar_xplay;
 /* One MultiAgentEnv.step of every playing table (tester.py:41-63): grouped forward of seat 0 by ego_id, book-keeping, grouped
  * forward of seat 1 by alt_id where the game goes on, book-keeping (end of game: log, games += 1, then the next deal, or
- * tables_left -= 1 when the budget is spent), grouped forward of seat 1 where it opens, book-keeping: 9 launches.  deal_only: the
+ * tables_left -= 1 when the budget is spent), grouped forward of seat 1 where it opens, book-keeping: 9 launches (12 when the members
+ * are clones and others).  deal_only: the
  * first deal of the tables flagged in `done` (the caller has set games = 0, playing = 1, tables_left = n and cleared ep_return /
  * ep_length), the openings and seat 0's first observation.  No host synchronisation; capturable once it ran outside capture (the
  * context's one member table, see ph_liar_pool_step). */

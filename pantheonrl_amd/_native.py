@@ -208,7 +208,7 @@ class PhBlockSelfPlay(C.Structure):
 PH_BLOCK_STATE_WORDS = 12
 
 PH_MAX_POOL = 8
-PH_POOL_LEARNER, PH_POOL_FROZEN, PH_POOL_SCRIPTED = 0, 1, 2
+PH_POOL_LEARNER, PH_POOL_FROZEN, PH_POOL_SCRIPTED, PH_POOL_CLONE = 0, 1, 2, 3
 POOL_RESAMPLE = {"robin": 0, "random": 1}
 
 

@@ -1,9 +1,10 @@
 """Cross-play of a population of saved agents, every table on the device (envs/crossplay.py): every agent as the ego against
 every agent as the partner -- the M x M matrix the reference reaches only as M^2 separate runs of tester.py (tester.py:41-63).
 
-    python -m pantheonrl_amd.crossplay LiarsDice-v0 --agents models/a models/b DEFAULT --n-envs 256 -t 1000 [--out x.npz]
+    python -m pantheonrl_amd.crossplay LiarsDice-v0 --agents models/a BC:models/clone.pt DEFAULT --n-envs 256 -t 1000 [--out x.npz]
 
-An agent is a PPO checkpoint (64-64 MlpPolicy) or DEFAULT (the game's scripted player).  `-t` is the number of games per pair:
+An agent is a PPO checkpoint (64-64 MlpPolicy), BC:<path> (a FeedForward32Policy saved by bctrainer: the cloned "human proxy") or
+DEFAULT (the game's scripted player).  `-t` is the number of games per pair:
 table e plays pair e % P, so a pair owns at least n_envs // P tables and every table plays ceil(t / (n_envs // P)) games.  Prints
 the mean and standard-deviation matrices of the ego's return (row = ego, column = partner); `--out` writes them, with the counts,
 mean lengths and the raw logs, as an .npz.  `--record FILE` logs every move on the device (envs/vec.py: VecLiarStep.start_recording)
@@ -22,7 +23,7 @@ from .trainer import EnvException
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Cross-play matrix of saved agents on device-resident tables")
     p.add_argument("env")
-    p.add_argument("--agents", nargs="+", required=True, help="PPO checkpoints, or DEFAULT for the scripted player")
+    p.add_argument("--agents", nargs="+", required=True, help="PPO checkpoints, BC:<path> for a policy saved by bctrainer, or DEFAULT for the scripted player")
     p.add_argument("--n-envs", type=int, default=256)
     p.add_argument("--games", "-t", type=int, default=1000, help="games per pair")
     p.add_argument("--device", "-d", default="cuda")
@@ -31,6 +32,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--out", help="write the matrices and logs to this .npz")
     p.add_argument("--record", "-r", help="write every move of every table to this .npy (TurnBasedTransitions format)")
     return p
+
+
+def parse_agent(agent: str):
+    """one --agents entry -> (type, location): DEFAULT -> ("DEFAULT", None), BC:<path> -> ("BC", path), anything else a PPO
+    checkpoint -> ("PPO", path).  No file is touched."""
+    if agent == "DEFAULT":
+        return "DEFAULT", None
+    if agent.startswith("BC:"):
+        if len(agent) == 3:
+            raise EnvException("--agents BC: needs the path of a policy saved by bctrainer (BC:<path>)")
+        return "BC", agent[3:]
+    return "PPO", agent
 
 
 def plan(args) -> dict:
@@ -42,6 +55,8 @@ def plan(args) -> dict:
         raise EnvException(f"a population holds at most {nat.PH_MAX_POOL} agents, not {M}")
     if args.games < 1:
         raise EnvException("-t must be at least 1")
+    for a in args.agents:
+        parse_agent(a)
     P = M * M
     if args.n_envs < P:
         raise EnvException(f"{M} agents make {P} pairs: --n-envs must be at least {P}, not {args.n_envs}")
@@ -53,7 +68,7 @@ def run(argv=None):
     size = plan(args)
     from .envs.crossplay import MAX_STEPS_PER_GAME, VecLiarCrossPlay
     from .tester import load_member
-    members = [load_member("DEFAULT" if a == "DEFAULT" else "PPO", {}, a, args.device) for a in args.agents]
+    members = [load_member(kind, {}, location, args.device) for kind, location in map(parse_agent, args.agents)]
     # a game takes at most MAX_STEPS_PER_GAME steps of at most 3 moves
     record = 3 * MAX_STEPS_PER_GAME * size["episodes_per_table"] if args.record else 0
     xp = VecLiarCrossPlay(args.n_envs, members, episodes_per_table=size["episodes_per_table"], seed=args.seed,

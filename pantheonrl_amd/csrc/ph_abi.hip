@@ -1868,13 +1868,15 @@ int pool_members(ph_ctx* ctx, const char* who, const ph_pool_member* members, in
     const ph_pool_member& m = members[k];
     ph::PoolMemberDev& d = tab[k];
     const std::string wk = w + ": member " + std::to_string(k);
-    if (m.kind != PH_POOL_LEARNER && m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED) return fail(wk + ": unknown kind");
+    if (m.kind != PH_POOL_LEARNER && m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED && m.kind != PH_POOL_CLONE)
+      return fail(wk + ": unknown kind");
     d.kind = m.kind;
     if (m.kind == PH_POOL_SCRIPTED) continue;
     if (!m.params) return fail(wk + ": null params");
     if ((uintptr_t)m.params % 16 != 0) return fail(wk + ": params must be 16-byte aligned");
     d.params = m.params;
     d.seed = m.seed;
+    if (m.kind == PH_POOL_CLONE) continue;   // a ph_bc_layout vector and its key: every other field is ignored
     d.values = m.values;
     d.log_probs = m.log_probs;
     if (m.kind == PH_POOL_FROZEN) continue;
@@ -1908,6 +1910,25 @@ int pool_members(ph_ctx* ctx, const char* who, const ph_pool_member* members, in
   return 0;
 }
 
+// the shared-trunk layout of the spec when the context's member table holds a clone (checked against the clone tile), else P = 0
+int pool_clone_layout(const char* who, ph_ctx* ctx, const ph_spec* spec, const ph::NetDims& nd, ph_bc_layout* out) {
+  std::memset(out, 0, sizeof(*out));
+  bool clone = false;
+  for (int k = 0; k < ctx->pool_count; ++k) clone = clone || ctx->pool_host[k].kind == PH_POOL_CLONE;
+  if (!clone) return 0;
+  if (ph_bc_layout_of(spec, out)) return 1;
+  if (!ph::pool_clone_eligible(nd, *out))
+    return fail(std::string(who) + ": a PH_POOL_CLONE member needs one-hot observations of at most 32 components and at most 32 logits");
+  return 0;
+}
+// the same check in front of a step's first launch
+int check_pool_clones(const char* who, ph_ctx* ctx, const ph_spec* spec) {
+  ph::NetDims nd;
+  ph_bc_layout lay;
+  if (resolve(ctx, spec, &nd)) return 1;
+  return pool_clone_layout(who, ctx, spec, nd, &lay);
+}
+
 // bucket pass + the grouped forward over the tables with active[e] != 0
 int pool_forward(ph_ctx* ctx, const char* who, const ph_spec* spec, int K, const float* obs, const int* partnerid,
                  const unsigned char* active, const unsigned char* rec_mask, unsigned long long counter, int* actions,
@@ -1918,6 +1939,7 @@ int pool_forward(ph_ctx* ctx, const char* who, const ph_spec* spec, int K, const
   if (!ph::pool_fwd_eligible(p.a.nd, n))
     return fail(std::string(who) + ": the spec is not the Liar's Dice 16-row one-hot class (30 observation components, <= 32 logits, "
                                    "two action components, n < 16384)");
+  if (pool_clone_layout(who, ctx, spec, p.a.nd, &p.bc)) return 1;
   p.a.rec_mask = rec_mask;
   p.a.es_in = es_in;
   if (ensure(ctx, ctx->pool_order, ctx->pool_order_cap, (size_t)n)) return 1;
@@ -1928,7 +1950,9 @@ int pool_forward(ph_ctx* ctx, const char* who, const ph_spec* spec, int K, const
   p.b.tiles = ctx->pool_tiles;
   p.b.ntiles = ctx->pool_tiles + 3 * ntile;
   PH_HIP(ph::launch_pool_bucket(partnerid, active, n, K, p.b, ctx->stream));
-  PH_HIP(ph::launch_pool_fwd(p, K, ctx->stream));
+  bool clones_only = p.bc.P != 0;
+  for (int k = 0; k < ctx->pool_count; ++k) clones_only = clones_only && ctx->pool_host[k].kind == PH_POOL_CLONE;
+  PH_HIP(ph::launch_pool_fwd(p, K, ctx->stream, clones_only));
   return 0;
 }
 }  // namespace
@@ -1941,7 +1965,7 @@ int ph_pool_forward(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* memb
   if (!spec || !obs || !partnerid || !active || !actions) return fail("ph_pool_forward: null argument");
   if (n <= 0) return fail("ph_pool_forward: n must be positive");
   if ((uintptr_t)actions % 8) return fail("ph_pool_forward: actions must be 8-byte aligned");
-  if (pool_members(ctx, "ph_pool_forward", members, n_members, n)) return 1;
+  if (pool_members(ctx, "ph_pool_forward", members, n_members, n) || check_pool_clones("ph_pool_forward", ctx, spec)) return 1;
   for (int k = 0; k < n_members; ++k)
     if (members[k].kind == PH_POOL_LEARNER && !episode_start_in) return fail("ph_pool_forward: learners need episode_start_in");
   return pool_forward(ctx, "ph_pool_forward", spec, n_members, obs, partnerid, active, active, counter, actions, episode_start_in, n);
@@ -1967,7 +1991,8 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsign
   if (!s.partnerid || !s.alt_acted || !s.can || !s.es_alt) return fail_who(who, ": incomplete description");
   if (s.resample != PH_POOL_ROBIN && s.resample != PH_POOL_RANDOM) return fail_who(who, ": unknown resample rule");
   if (check_liar_ego(who, s)) return 1;
-  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n)) return 1;
+  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) || check_pool_clones(who, ctx, s.spec))
+    return 1;
   if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail_who(who, ": ego_pos out of range (buffer full?)");
   const ph::PoolBook book{s.n, s.n_members, s.resample, s.pool_seed, ctx->pool_dev, s.partnerid, s.alt_acted, s.can, s.es_alt};
   return liar_step_run(
@@ -2000,11 +2025,12 @@ int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long 
   if (s.n_members < 1 || s.n_members > PH_MAX_POOL) return fail_who(who, ": the population holds 1..PH_MAX_POOL members");
   for (int k = 0; k < s.n_members; ++k)
     if (s.members[k].kind == PH_POOL_LEARNER)
-      return fail("ph_liar_xplay_step: member " + std::to_string(k) + " is a PH_POOL_LEARNER: an evaluation seats frozen and scripted members only");
+      return fail("ph_liar_xplay_step: member " + std::to_string(k) + " is a PH_POOL_LEARNER: an evaluation seats frozen, cloned and scripted members only");
   for (int p = 0; p < 2 * s.n_pairs; ++p)
     if (s.pairs[p] < 0 || s.pairs[p] >= s.n_members)
       return fail("ph_liar_xplay_step: pair " + std::to_string(p / 2) + " names a member out of range");
-  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n)) return 1;
+  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) || check_pool_clones(who, ctx, s.spec))
+    return 1;
   const ph::EvalEnd end{s.episodes_per_table, s.games, s.playing, s.tables_left, s.ep_return, s.ep_length, s.returns, s.lengths};
   // a seat's forward is one grouped launch over the member table, indexed by ego_id / alt_id; nothing is recorded
   auto seat = [&](const float* obs, const int* id, const unsigned char* active, unsigned long long c, int* actions) {

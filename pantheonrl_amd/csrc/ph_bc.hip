@@ -12,10 +12,10 @@
 // occupy one wave for 2 K cycles at the VALU's own f32 rate (guide section 3); the same tile as plain FMAs is spread over all
 // four SIMDs of the CU, so the products here are VALU loops on LDS operands.
 #include "ph_launch.h"
+#include "ph_bc_row.h"
 
 namespace ph {
 
-constexpr int BH = PH_BC_HIDDEN;       // hidden width of the shared trunk
 constexpr int BR = 32;                 // rows per tile (the reference's batch size)
 constexpr int BLD = BH + 1;            // padded leading dimension of the 32-wide activation tiles
 
@@ -33,8 +33,6 @@ struct BcArgs {
   float lr, beta1, beta2, eps, ent_weight, l2_weight;
   float* stats;          // (total minibatches, PH_BC_NSTAT) or null
 };
-
-__device__ __forceinline__ float bc_tanh(float x) { return fast_tanh(x); }
 
 // debug: -DPH_BC_PROF makes thread 0 accumulate the shader clock per phase (scripts/bc_phase_profile.py)
 #if defined(PH_BC_PROF)
@@ -832,6 +830,7 @@ hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* pa
 }
 
 // ---- forward of the shared-trunk policy: one lane per row, weights staged per workgroup ------------------------------------------
+// (the row arithmetic is ph_bc_row.h's: the clone tile of the pool's grouped forward computes the same bits from the same text)
 struct BcFwdArgs {
   NetDims nd;
   ph_bc_layout lay;
@@ -872,65 +871,39 @@ __global__ __launch_bounds__(64) void bc_forward_kernel(BcFwdArgs a) {
     }
   } else {   // one-hot rows: the dense layer's k-ordered sum with the zero terms left out
     for (int comp = 0; comp < nd.D; ++comp) {
-      const int lo = nd.obs_off[comp], n = nd.obs_off[comp + 1] - lo;
-      int x = (int)a.obs[(size_t)row * nd.D + comp];
-      x = x < 0 ? 0 : (x >= n ? n - 1 : x);
+      const float* w = ps + lay.W1 + bc_hot_feature(nd.obs_off, a.obs + (size_t)row * nd.D, comp) * BH;
 #pragma unroll
-      for (int j = 0; j < BH; ++j) h1[j] += ps[lay.W1 + (lo + x) * BH + j];
+      for (int j = 0; j < BH; ++j) h1[j] = bc_h1_add(h1[j], w[j]);
     }
   }
 #pragma unroll
   for (int j = 0; j < BH; ++j) h1[j] = bc_tanh(h1[j]);
 #pragma unroll
-  for (int j = 0; j < BH; ++j) h2[j] = ps[lay.b2 + j];
-#pragma unroll
-  for (int k = 0; k < BH; ++k) {
-#pragma unroll
-    for (int j = 0; j < BH; ++j) h2[j] = __builtin_fmaf(h1[k], ps[lay.W2 + k * BH + j], h2[j]);
-  }
-  float v = ps[lay.val_b];
-#pragma unroll
-  for (int j = 0; j < BH; ++j) {
-    h2[j] = bc_tanh(h2[j]);
-    v = __builtin_fmaf(h2[j], ps[lay.val_W + j], v);
-  }
+  for (int j = 0; j < BH; ++j)
+    h2[j] = bc_tanh(bc_chain(ps[lay.b2 + j], [&](int k) { return h1[k]; }, [&](int k) { return ps[lay.W2 + k * BH + j]; }));
+  const float v = bc_chain(ps[lay.val_b], [&](int k) { return h2[k]; }, [&](int k) { return ps[lay.val_W + k]; });
   if (a.values) a.values[row] = v;
   float lp_sum = 0.f, ent_sum = 0.f;
   for (int comp = 0; comp < nd.A; ++comp) {
     const int lo = nd.act_off[comp], n = nd.act_off[comp + 1] - lo;
     auto z = [&](int c) -> float& { return zs[c * 64]; };
-    float mx = -3.0e38f;
+    float mx = BC_MAX_INIT;
     int arg = 0;
     for (int c = 0; c < n; ++c) {
-      float s = ps[lay.act_b + lo + c];
-#pragma unroll
-      for (int k = 0; k < BH; ++k) s = __builtin_fmaf(h2[k], ps[lay.act_W + k * L + lo + c], s);
+      float s = bc_chain(ps[lay.act_b + lo + c], [&](int k) { return h2[k]; }, [&](int k) { return ps[lay.act_W + k * L + lo + c]; });
       if (a.mask && a.mask[(size_t)row * L + lo + c] == 0) s -= 30.0f;   // modular/policies.py:330-333
       if (a.logits) a.logits[(size_t)row * L + lo + c] = s;
       z(c) = s;
-      if (s > mx) {
-        mx = s;
-        arg = c;
-      }
+      bc_max_step(s, c, mx, arg);
     }
-    float se = 0.f;
-    for (int c = 0; c < n; ++c) se += __expf(z(c) - mx);
-    const float lse = mx + __logf(se);
+    const float lse = bc_lse(z, n, mx);
     int act = arg;
     if (a.given) {
       act = (int)a.given[(size_t)row * nd.A + comp];
       act = act < 0 ? 0 : (act >= n ? n - 1 : act);
     } else if (!a.deterministic) {
       const float u = a.uniforms ? a.uniforms[(size_t)row * nd.A + comp] : philox_uniform(a.seed, a.counter, (uint32_t)row, (uint32_t)comp);
-      float cdf = 0.f;
-      act = n - 1;
-      for (int c = 0; c < n; ++c) {
-        cdf += __expf(z(c) - lse);
-        if (u < cdf) {
-          act = c;
-          break;
-        }
-      }
+      act = bc_sample_cdf(z, n, lse, u);
     }
     float h = 0.f;
     for (int c = 0; c < n; ++c) {

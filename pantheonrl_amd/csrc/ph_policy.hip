@@ -11,6 +11,7 @@
 #include "ph_rowtail.h"
 #include "ph_liar_group.h"
 #include "ph_pool.h"
+#include "ph_bc_row.h"
 
 namespace ph {
 
@@ -1313,7 +1314,11 @@ static size_t fwd16h_lds_bytes() {
 // The tile names a member and <= 16 sorted positions; the workgroup patches that member's weights, seed, caches and ragged buffer
 // into its copy of the shared record (uniform loads from the device-side member table) and runs the 16-row one-hot forward over
 // the tables order[first .. first + rows).  A frozen member has no buffer and no caches: its value net has nothing to write and is
-// skipped.  A scripted member's tile applies the integer rule instead of the net.
+// skipped.  A scripted member's tile applies the integer rule instead of the net.  A clone's tile (PH_POOL_CLONE: the shared 32-32
+// trunk, params in ph_bc_layout) is left to pool_clone16_kernel below, launched behind this kernel only when the member table holds
+// a clone: the tile needed 74 VGPRs on its own when this was tried, but inside this kernel -- inlined, or behind a call -- it moved the register
+// allocation of the 64-64 path (179 -> 189 VGPRs inlined; 191 and 112 bytes of scratch behind a call), which every population
+// without a clone would have paid for.
 template <bool VALU>
 __global__ __launch_bounds__(256) void pool_fwd16h_kernel(PoolFwd p) {
   const int tile = blockIdx.x;
@@ -1329,6 +1334,7 @@ __global__ __launch_bounds__(256) void pool_fwd16h_kernel(PoolFwd p) {
     }
     return;
   }
+  if (kind == PH_POOL_CLONE) return;   // pool_clone16_kernel's
   const bool learner = kind == PH_POOL_LEARNER;
   if (blockIdx.y == 1 && !learner && !m.values) return;
   FwdArgs a = p.a;
@@ -1352,6 +1358,18 @@ __global__ __launch_bounds__(256) void pool_fwd16h_kernel(PoolFwd p) {
   }
   policy_fwd16h_body<VALU, false, false, true>(a, 0, 0, 0, nullptr, 0, ResidentNet{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr,
                                                map, rows);
+}
+
+// the clone tiles of the bucket pass (ph_bc_row.h): one workgroup per tile; tiles of the other kinds are pool_fwd16h_kernel's.  No value
+// half: a clone has no separate value net and nothing caches a value.
+__global__ __launch_bounds__(256) void pool_clone16_kernel(PoolFwd p) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dyn[];
+  const int tile = blockIdx.x;
+  if (tile >= p.b.ntiles[0]) return;
+  const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1], rows = p.b.tiles[3 * tile + 2];
+  const PoolMemberDev& m = p.members[member];
+  if (m.kind != PH_POOL_CLONE) return;
+  bc_clone_tile(bc_clone_args(p.a.nd, p.bc, m.params, p.a.obs, p.b.order + first, rows, m.seed, fwd_counter(p.a), p.a.act_i32), smem_dyn);
 }
 
 // one net (policy: net 0, value: net 1) of `params` into a resident set, by the 256 lanes of the half that runs that net -- the very
@@ -1962,9 +1980,20 @@ static hipError_t launch_fwd16h_variant(const FwdArgs& a, hipStream_t s) {
 }
 
 bool pool_fwd_eligible(const NetDims& nd, int n) { return fwd16h_eligible(nd, n) && !fwd16_eligible(nd, n) && nd.D == 30 && nd.A == 2; }
-hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s) {
+bool pool_clone_eligible(const NetDims& nd, const ph_bc_layout& lay) {
+  return bc_clone_eligible(nd.obs_kind, nd.D, nd.L) && lay.P > lay.b1 && lay.P - lay.b1 <= BC_CLONE_SMALL_MAX && lay.b1 == lay.W1 + lay.F * BH &&
+         sizeof(float) * (size_t)bc_clone_lds_floats(lay.P - lay.b1) <= fwd16h_lds_bytes();
+}
+hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool clones_only) {
   if (!pool_fwd_eligible(p.a.nd, p.a.n)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((pool_fwd16h_kernel<false>), dim3(pool_max_tiles(p.a.n, K), 2), dim3(256), fwd16h_lds_bytes(), s, p);
+  if (p.bc.P != 0 && !pool_clone_eligible(p.a.nd, p.bc)) return hipErrorInvalidValue;
+  if (clones_only && p.bc.P == 0) return hipErrorInvalidValue;
+  if (!clones_only)   // (a table of clones alone has no tile for this kernel: every workgroup would return at its tile's kind)
+    hipLaunchKernelGGL((pool_fwd16h_kernel<false>), dim3(pool_max_tiles(p.a.n, K), 2), dim3(256), fwd16h_lds_bytes(), s, p);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (p.bc.P != 0)   // the member table holds a clone: its tiles (the two kernels write disjoint rows of the actions)
+    hipLaunchKernelGGL(pool_clone16_kernel, dim3(pool_max_tiles(p.a.n, K)), dim3(256), sizeof(float) * (size_t)bc_clone_lds_floats(p.bc.P - p.bc.b1),
+                       s, p);
   return hipGetLastError();
 }
 

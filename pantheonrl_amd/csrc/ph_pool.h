@@ -1,7 +1,9 @@
 // Liar's Dice against a pool of partners: the device-side member table, the bucket pass and the grouped forward's launch record,
 // and seat 1's book of the pool step (ph_liar_step.h's after_ego / after_reply / after_opening with the member index).
 // Kernels: ph_pool.hip (bucket pass, scripted rule), ph_envs.hip (the step's book-keeping) and ph_policy.hip (pool_fwd16h_kernel: the grouped forward is the
-// 16-row one-hot forward with its rows gathered through `order`, so it lives beside policy_fwd16h_body).
+// 16-row one-hot forward with its rows gathered through `order`, so it lives beside policy_fwd16h_body).  A PH_POOL_CLONE member
+// (the shared-trunk FeedForward32Policy, params in ph_bc_layout) is a non-learner like a frozen one -- PoolBook below asks for
+// `kind == PH_POOL_LEARNER` only -- and its tile of the grouped forward is ph_bc_row.h's bc_clone_tile.
 #pragma once
 #include "ph_liar_step.h"
 
@@ -35,6 +37,7 @@ struct PoolFwd {
   FwdArgs a;                        // the shared part: spec, obs, n, counter, epoch, act_i32, es_in, rec_mask; the member's part is patched in
   const PoolMemberDev* members;     // device
   PoolBuckets b;
+  ph_bc_layout bc;                  // the spec's shared-trunk layout: what a PH_POOL_CLONE member's params are (P = 0: no clone in the table)
 };
 
 // LiarDefaultAgent.get_action (envs/liar.py): bid the most frequent face (the first of equals) at its own count; call as soon as
@@ -127,8 +130,10 @@ struct PoolBook {
 };
 
 hipError_t launch_pool_bucket(const int* partnerid, const unsigned char* active, int n, int K, const PoolBuckets& b, hipStream_t s);
-hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s);   // ph_policy.hip
+// ph_policy.hip; p.bc.P != 0: the member table holds a clone (its tiles' kernel follows); clones_only: it holds nothing else (no 64-64 launch)
+hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool clones_only = false);
 bool pool_fwd_eligible(const NetDims& nd, int n);                     // ph_policy.hip
+bool pool_clone_eligible(const NetDims& nd, const ph_bc_layout& lay); // ph_policy.hip: the clone tile's shapes and LDS inside the grouped launch
 hipError_t launch_liar_default_actions(const float* obs, const unsigned char* active, int* actions, int n, hipStream_t s);
 
 }  // namespace ph

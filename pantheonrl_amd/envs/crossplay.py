@@ -2,7 +2,8 @@
 loaded ego against a loaded or default partner for a number of games, print the mean and standard deviation of the ego's returns)
 for a whole population at once.
 
-`VecLiarCrossPlay` seats BOTH players of E tables from one population of M <= 8 members (`FrozenVecPartner`, `VecLiarDefaultPartner`)
+`VecLiarCrossPlay` seats BOTH players of E tables from one population of M <= 8 members (`FrozenVecPartner`, `ClonedVecPartner`,
+`VecLiarDefaultPartner`)
 and plays a list of ordered pairs (i, j) -- member i at seat 0 (the ego), member j at seat 1 (the partner).  `crossplay_stats` is the
 host statement of the per-pair reduction `ph_xplay_stats` runs on the device.
 """
@@ -15,9 +16,8 @@ import numpy as np
 import torch as th
 
 from .. import _native as nat
-from ..ppo import require_mlp_kernels
 from ..spaces import make_spec
-from .vec import FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice, VecLiarStep
+from .vec import (ClonedVecPartner, FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice, VecLiarStep, check_liar_member_policy)
 
 MAX_STEPS_PER_GAME = 7       # 12 bids and a call: at most 7 moves of the ego, whoever opens
 
@@ -101,7 +101,8 @@ class CrossPlayResult:
 
 class VecLiarCrossPlay(VecLiarStep):
     """tester.py:41-63 for a population: n_envs Liar's Dice tables resident on the device, both seats held by members of ONE
-    population of M <= 8 frozen 64-64 policies (`FrozenVecPartner`) and scripted players (`VecLiarDefaultPartner`); the same object
+    population of M <= 8 frozen 64-64 policies (`FrozenVecPartner`), behavioural clones (`ClonedVecPartner`: the shared 32-32 trunk of
+    bc.py) and scripted players (`VecLiarDefaultPartner`); the same object
     may sit in either seat, or in both.
 
     The choices this class pins:
@@ -120,7 +121,7 @@ class VecLiarCrossPlay(VecLiarStep):
       atomics: two runs give the same bits.
 
     native=True: one `ph_liar_xplay_step` per step -- three bucket passes, three grouped forwards, three book-keeping launches,
-    whatever M is, no host synchronisation.  native=False: the readable walk (VecLiarStep) -- per-member `ph_policy_forward` /
+    whatever M is, no host synchronisation.  native=False: the readable walk (VecLiarStep) -- per-member `ph_policy_forward` / `ph_bc_forward` /
     `ph_liar_default_actions`, `VecLiarsDice.player_step`, torch masks, the same counters; bitwise the native step."""
 
     def __init__(self, n_envs: int, members, pairs=None, episodes_per_table: int = 1, seed: int = 0, probegostart: float = 0.5,
@@ -135,13 +136,10 @@ class VecLiarCrossPlay(VecLiarStep):
         for m in members:
             if isinstance(m, VecLiarDefaultPartner):
                 continue
-            if not isinstance(m, FrozenVecPartner):
-                raise nat.NativeError("VecLiarCrossPlay: members are FrozenVecPartner / VecLiarDefaultPartner (learners train in "
-                                      f"VecLiarPartnerPool), not {type(m).__name__}")
-            require_mlp_kernels(m.policy, type(self).__name__)
-            lay = m.policy.layout
-            if (lay.D, lay.A, lay.L) != (30, 2, 19):
-                raise nat.NativeError("VecLiarCrossPlay: every member plays on the Liar's Dice spaces")
+            if not isinstance(m, (FrozenVecPartner, ClonedVecPartner)):
+                raise nat.NativeError("VecLiarCrossPlay: members are FrozenVecPartner / ClonedVecPartner / VecLiarDefaultPartner "
+                                      f"(learners train in VecLiarPartnerPool), not {type(m).__name__}")
+            check_liar_member_policy(m.policy, type(self).__name__)
             dev = dev or m.policy.device
         dev = dev or th.device("cuda", th.cuda.current_device())
         self.ctx = nat.Context(dev.index or 0)
@@ -167,7 +165,7 @@ class VecLiarCrossPlay(VecLiarStep):
         self._first_deal()
 
     def _contexts(self):
-        return [self.ctx] + [m.policy.ctx for m in self.members if isinstance(m, FrozenVecPartner)]
+        return [self.ctx] + [m.policy.ctx for m in self.members if isinstance(m, (FrozenVecPartner, ClonedVecPartner))]
 
     def _counters(self, c: int):
         return 3 * c, 3 * c + 1, 3 * c + 2

@@ -19,6 +19,7 @@ import torch as th
 
 from .. import _native as nat
 from ..spaces import Discrete, MultiDiscrete
+from ..bc import FeedForward32Policy
 from ..ppo import require_mlp_kernels
 from ..vec import VecOnPolicyAgent, is_tower, require_tower_lds
 
@@ -279,6 +280,10 @@ class FrozenVecPartner:
     kind = nat.PH_POOL_FROZEN
 
     def __init__(self, policy):
+        if isinstance(policy, FeedForward32Policy):
+            # its ph_bc_layout vector (one shared 32-32 trunk) is a sixth of the 64-64 ph_layout vector the frozen forward reads
+            raise nat.NativeError(f"{type(self).__name__}: a FeedForward32Policy (the shared 32-32 trunk of behavioural cloning) is "
+                                  "not a 64-64 policy; seat it as ClonedVecPartner(policy)")
         require_mlp_kernels(policy, type(self).__name__)
         self.policy = policy
         self._out = {}
@@ -299,6 +304,52 @@ class FrozenVecPartner:
 
     def update(self, reward, done, mask=None) -> None:
         return None
+
+
+class ClonedVecPartner:
+    """A pool / population member that plays a behavioural clone: a `FeedForward32Policy` (bc.py: one shared 32-32 tanh trunk,
+    parameters in ph_bc_layout) on the Liar's Dice spaces -- the "human proxy" partner of the reference's workflow (train, record,
+    bctrainer, play the clone).  Like FrozenVecPartner it samples under its own Philox key and counter, records nothing, and `update`
+    is a no-op.  In the native steps its rows run the clone tile of the grouped forward; `get_action` is the walk's form, one
+    `ph_bc_forward` over all rows -- the same bits row by row."""
+    kind = nat.PH_POOL_CLONE
+
+    def __init__(self, policy):
+        who = type(self).__name__
+        if not isinstance(policy, FeedForward32Policy):
+            raise nat.NativeError(f"{who}: takes a FeedForward32Policy (bc.reconstruct_policy), not {type(policy).__name__}; a 64-64 "
+                                  "ActorCriticPolicy is seated as FrozenVecPartner")
+        lay = policy.layout
+        if (lay.D, lay.A, lay.L) != (30, 2, 19) or policy.spec.obs.kind == nat.PH_SPACE_BOX:
+            raise nat.NativeError(f"{who}: the clone must play on the Liar's Dice spaces (30 one-hot observation components, 2 action "
+                                  f"components, 19 logits), not (D, A, L) = {(lay.D, lay.A, lay.L)}")
+        self.policy = policy
+        self._out = {}
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
+        pol = self.policy
+        n = int(obs.shape[0])
+        out = self._out.get(n)
+        if out is None:
+            out = self._out[n] = th.zeros((n, pol.layout.A), dtype=th.int32, device=pol.device)
+        pol.ctx.set_stream(th.cuda.current_stream(pol.device).cuda_stream)
+        pol._counter += 1
+        nat.check(pol.ctx.lib.ph_bc_forward(pol.ctx.handle, C.byref(pol.spec), pol.params.data_ptr(), obs.data_ptr(), n, None, None, None,
+                                            pol._seed, pol._counter, 0, out.data_ptr(), None, None, None, None))
+        return out
+
+    def update(self, reward, done, mask=None) -> None:
+        return None
+
+
+def check_liar_member_policy(policy, who: str) -> None:
+    """a pool / population member's policy runs on the grouped forward's kernels and plays on the Liar's Dice spaces: the 64-64
+    layout through `require_mlp_kernels`, a clone's through its BC layout (ClonedVecPartner has checked the one-hot observation)"""
+    if not isinstance(policy, FeedForward32Policy):
+        require_mlp_kernels(policy, who)
+    lay = policy.layout
+    if (lay.D, lay.A, lay.L) != (30, 2, 19):
+        raise nat.NativeError(f"{who}: every member plays on the Liar's Dice spaces")
 
 
 class VecLiarDefaultPartner:
@@ -420,7 +471,7 @@ class VecLiarStep:
         """the policy a pool / population member plays with (None: the scripted player)"""
         if isinstance(agent, VecLiarDefaultPartner):
             return None
-        return agent.policy if isinstance(agent, FrozenVecPartner) else agent.model.policy
+        return agent.policy if isinstance(agent, (FrozenVecPartner, ClonedVecPartner)) else agent.model.policy
 
     # -- the engine-side step: what every description holds -------------------------------------------------------------------------
     def _fill_game(self, s, book: bool):
@@ -452,7 +503,7 @@ class VecLiarStep:
             p = self._policy_of(m)
             if p is None:
                 continue
-            c.params, c.seed = p.params.data_ptr(), p._seed
+            c.params, c.seed = p.params.data_ptr(), p._seed       # (a clone: its ph_bc_layout vector and key, nothing else)
             if learner:
                 rbc = m.model.rollout_buffer.c_struct()
                 self._member_rbc.append(rbc)
@@ -818,8 +869,8 @@ class VecLiarSelfPlay(VecLiarTraining):
 
 class VecLiarPartnerPool(VecLiarTraining):
     """`trainer.py LiarsDice-v0 PPO <alt>+ --n-envs E`: n_envs Liar's Dice tables resident on the device, seat 1 of every table
-    held by one of K <= 8 pool members -- learners (RaggedVecOnPolicyAgent), frozen policies (FrozenVecPartner) or the scripted
-    player (VecLiarDefaultPartner).  `partnerid[e]` names table e's member; it is resampled at that table's own re-deal
+    held by one of K <= 8 pool members -- learners (RaggedVecOnPolicyAgent), frozen policies (FrozenVecPartner), behavioural
+    clones (ClonedVecPartner) or the scripted player (VecLiarDefaultPartner).  `partnerid[e]` names table e's member; it is resampled at that table's own re-deal
     (`pool_resample`), the first deal included.
 
     Per table the callbacks are VecLiarSelfPlay's, with every partner-side mask ANDed with `partnerid == k`: credit goes to the
@@ -845,10 +896,9 @@ class VecLiarPartnerPool(VecLiarTraining):
             p = self._policy_of(who)
             if p is None:
                 continue
-            require_mlp_kernels(p, type(self).__name__)
-            lay = p.layout
-            if (lay.D, lay.A, lay.L) != (30, 2, 19):
-                raise nat.NativeError("VecLiarPartnerPool: every member plays on the Liar's Dice spaces")
+            if isinstance(p, FeedForward32Policy) and not isinstance(who, ClonedVecPartner):
+                raise nat.NativeError("VecLiarPartnerPool: a FeedForward32Policy is seated as ClonedVecPartner(policy)")
+            check_liar_member_policy(p, type(self).__name__)
         self.learners = [m for m in members if isinstance(m, RaggedVecOnPolicyAgent)]
         for m in self.learners:
             if m.E != n_envs:

@@ -84,10 +84,15 @@ def vectorised_check(args) -> None:
 
 
 def load_member(policy_type: str, config: dict, location, device):
-    """a seat of the device-resident evaluation: the scripted player, or a frozen loaded PPO policy"""
-    from .envs.vec import FrozenVecPartner, VecLiarDefaultPartner
+    """a seat of the device-resident evaluation: the scripted player, a behavioural clone saved by bctrainer ("BC": reached
+    through `python -m pantheonrl_amd.crossplay ... --agents BC:<path>`; `tester ... BC ... --n-envs` stays refused on this command
+    line), or a frozen loaded PPO policy"""
+    from .envs.vec import ClonedVecPartner, FrozenVecPartner, VecLiarDefaultPartner
     if policy_type == "DEFAULT":
         return VecLiarDefaultPartner()
+    if policy_type == "BC":
+        from .bc import reconstruct_policy
+        return ClonedVecPartner(reconstruct_policy(location, device))
     cfg = {k: v for k, v in config.items() if k != "verbose"}
     cfg.setdefault("device", device)
     return FrozenVecPartner(gen_load(cfg, "PPO", location).policy)

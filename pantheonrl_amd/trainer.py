@@ -254,8 +254,9 @@ def pool_plan(args):
         if kind == "FIXED":
             if "type" not in config or "location" not in config:
                 raise EnvException("a FIXED partner needs 'type' and 'location' in its --alt-config")
-            if config["type"] != "PPO":
-                raise EnvException("pool members play the 64-64 MlpPolicy: a FIXED member must be a PPO checkpoint")
+            if config["type"] not in ("PPO", "BC"):
+                raise EnvException("a FIXED member must be a PPO checkpoint (the 64-64 MlpPolicy) or a BC policy (bctrainer's "
+                                   f"shared 32-32 trunk), not {config['type']}")
         elif kind == "DEFAULT" and config:
             raise EnvException("No config possible for this default agent")
         members.append((kind, config))
@@ -283,7 +284,8 @@ def run_pool(args, plan):
 
     import torch as th
 
-    from .envs.vec import (FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner, VecLiarPartnerPool, VecLiarsDice)
+    from .envs.vec import (ClonedVecPartner, FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner, VecLiarPartnerPool,
+                           VecLiarsDice)
     from .vec import VecOnPolicyAgent
     E = int(args.n_envs)
     spaces = type("Spaces", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
@@ -308,7 +310,8 @@ def run_pool(args, plan):
             models.append(learner(config, i + 1))
             members.append(RaggedVecOnPolicyAgent(models[-1]))
         elif kind == "FIXED":
-            members.append(FrozenVecPartner(gen_load(config, config["type"], config["location"]).policy))
+            seat = ClonedVecPartner if config["type"] == "BC" else FrozenVecPartner
+            members.append(seat(gen_load(config, config["type"], config["location"]).policy))
         else:
             members.append(VecLiarDefaultPartner())
         print(f"Partner {i}: {members[-1]}")

@@ -5,7 +5,10 @@ population of M members, 40 games per table (10 240 games per run):
   host    tester.run_test of ONE of those pairs on the host MultiAgentEnv -- one table, one policy round trip per move
 Median of 5 runs per variant, the variants alternating within a round; the host clock around a device synchronise; a run is
 `run()` (the steps, the reads of tables_left, the statistics kernel and the copy of the logs), not the construction.
-`--ms 1,4` / `--no-host` / `--out FILE` narrow the sweep or keep a copy of the lines."""
+`--ms 1,4` / `--no-host` / `--out FILE` narrow the sweep or keep a copy of the lines.
+`--clones` times instead the native evaluation of three populations of M = 4 -- four frozen 64-64 members (the yardstick), four
+behavioural clones (ClonedVecPartner: the shared 32-32 trunk), two of each -- and reports games/s and microseconds per vectorised
+step for each, with the spread over the runs."""
 import argparse
 import contextlib
 import io
@@ -21,7 +24,8 @@ from pantheonrl_amd import PPO  # noqa: E402
 from pantheonrl_amd.common import StaticPolicyAgent  # noqa: E402
 from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay  # noqa: E402
 from pantheonrl_amd.envs.liar import LiarEnv  # noqa: E402
-from pantheonrl_amd.envs.vec import FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice  # noqa: E402
+from pantheonrl_amd.bc import FeedForward32Policy  # noqa: E402
+from pantheonrl_amd.envs.vec import ClonedVecPartner, FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice  # noqa: E402
 from pantheonrl_amd.tester import run_test  # noqa: E402
 
 E, G, ROUNDS = 256, 40, 5
@@ -30,6 +34,7 @@ _p.add_argument("--ms", default="1,4,8")
 _p.add_argument("--no-host", action="store_true")
 _p.add_argument("--host-games", type=int, default=E * G)
 _p.add_argument("--out")
+_p.add_argument("--clones", action="store_true")
 _args = _p.parse_args()
 MS = [int(m) for m in _args.ms.split(",")]
 spaces = type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
@@ -50,8 +55,8 @@ def population(M):
     return [VecLiarDefaultPartner() if (M >= 4 and k == 2) else FrozenVecPartner(policies[k]) for k in range(M)]
 
 
-def device_run(M, native, seed):
-    xp = VecLiarCrossPlay(E, population(M), episodes_per_table=G, seed=seed, native=native)
+def device_run(M, native, seed, members=None):
+    xp = VecLiarCrossPlay(E, population(M) if members is None else members, episodes_per_table=G, seed=seed, native=native)
     th.cuda.synchronize()
     t0 = time.perf_counter()
     res = xp.run()
@@ -59,6 +64,44 @@ def device_run(M, native, seed):
     dt = time.perf_counter() - t0
     assert int(res.count.sum()) == E * G
     return E * G / dt, res.steps
+
+
+def clone_sweep():
+    """M = 4, native: frozen x 4 | clone x 4 | frozen x 2 + clone x 2"""
+    import numpy as np
+    clones = []
+    for k in range(4):
+        pol = FeedForward32Policy(spaces.observation_space, spaces.action_space, seed=50 + k)
+        pol.set_flat_params(0.4 * np.random.default_rng(50 + k).standard_normal(pol.layout.P).astype(np.float32))
+        clones.append(pol)
+    pops = {"frozen x4 (yardstick)": lambda: [FrozenVecPartner(policies[k]) for k in range(4)],
+            "clone x4": lambda: [ClonedVecPartner(clones[k]) for k in range(4)],
+            "frozen x2 + clone x2": lambda: [FrozenVecPartner(policies[0]), ClonedVecPartner(clones[0]), FrozenVecPartner(policies[1]),
+                                             ClonedVecPartner(clones[1])]}
+    say(f"cross-play of Liar's Dice with behavioural clones, native step, E = {E} tables, M = 4, all 16 pairs, {G} games per table = "
+        f"{E * G} games per run; median of {ROUNDS} runs, populations alternating, after one warm-up round")
+    rate, us = {n: [] for n in pops}, {n: [] for n in pops}
+    for rnd in range(ROUNDS + 1):
+        for name, make in pops.items():
+            r, n = device_run(4, True, 100 + rnd, make())
+            if rnd:
+                rate[name].append(r)
+                us[name].append(1e6 * E * G / r / n)
+    for name in pops:
+        say(f"{name}: {statistics.median(rate[name]):,.0f} games/s (min {min(rate[name]):,.0f}, max {max(rate[name]):,.0f}); "
+            f"{statistics.median(us[name]):.1f} us per vectorised step (min {min(us[name]):.1f}, max {max(us[name]):.1f})")
+    base = statistics.median(us["frozen x4 (yardstick)"])
+    for name in list(pops)[1:]:
+        say(f"{name}: {statistics.median(us[name]) / base:.3f}x the yardstick's time per step "
+            f"(the yardstick's own runs span {min(us['frozen x4 (yardstick)']) / base:.3f}..{max(us['frozen x4 (yardstick)']) / base:.3f})")
+    if _args.out:
+        with open(_args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if _args.clones:
+    clone_sweep()
+    sys.exit(0)
 
 
 def host_run(n_games):

@@ -1,0 +1,453 @@
+"""gpu: behavioural clones (FeedForward32Policy, the shared 32-32 trunk of bc.py) as members of the device-resident Liar's Dice
+pool and cross-play -- the clone tile of the grouped forward against `ph_bc_forward`, the native steps against the walk, recorded
+games replayed through the host LiarEnv, graph capture, misuse, and the command lines end to end.  Every comparison is exact."""
+import ctypes as C
+import json
+
+import numpy as np
+import pytest
+import torch as th
+
+from pantheonrl_amd import _native as nat
+
+pytestmark = pytest.mark.gpu
+
+RB_KEYS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs")
+XSTATE = ("hands", "history", "nmoves", "obs_ego", "obs_alt", "games", "playing", "tables_left", "returns", "lengths", "ep_return",
+          "ep_length")
+KIND = dict(learner=nat.PH_POOL_LEARNER, frozen=nat.PH_POOL_FROZEN, scripted=nat.PH_POOL_SCRIPTED, clone=nat.PH_POOL_CLONE)
+
+
+def _spaces():
+    from pantheonrl_amd.envs.vec import VecLiarsDice
+    return type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
+                              _is_dummy_space_env=True))()
+
+
+def _ppo(E, T, seed):
+    from pantheonrl_amd import PPO
+    model = PPO("MlpPolicy", _spaces(), n_steps=T, n_envs=E, batch_size=max(8, E * T // 2), n_epochs=2, seed=seed)
+    model.device_permutations = True
+    model.rollout_buffer.gae_mode = 1
+    return model
+
+
+def _clone_policy(seed):
+    """a FeedForward32Policy on the Liar's Dice spaces with parameters of order one (sharp enough that a wrong bit moves a sample);
+    the same seed gives the same parameters and the same Philox key"""
+    from pantheonrl_amd.bc import FeedForward32Policy
+    s = _spaces()
+    pol = FeedForward32Policy(s.observation_space, s.action_space, seed=1000 + seed)
+    pol.set_flat_params(0.4 * np.random.default_rng(seed).standard_normal(pol.layout.P).astype(np.float32))
+    return pol
+
+
+def _member(kind, E, T_alt, seed):
+    from pantheonrl_amd.envs.vec import ClonedVecPartner, FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner
+    if kind == "learner":
+        return RaggedVecOnPolicyAgent(_ppo(E, T_alt, seed))
+    if kind == "frozen":
+        return FrozenVecPartner(_ppo(E, 2, seed).policy)
+    if kind == "clone":
+        return ClonedVecPartner(_clone_policy(seed))
+    return VecLiarDefaultPartner()
+
+
+def _pool(E, T_ego, T_alt, kinds, seed=0, native=True, resample="robin", record=0):
+    from pantheonrl_amd.envs.vec import VecLiarPartnerPool
+    from pantheonrl_amd.vec import VecOnPolicyAgent
+    ego = VecOnPolicyAgent(_ppo(E, T_ego, seed))
+    members = [_member(kind, E, T_alt, seed + 1 + k) for k, kind in enumerate(kinds)]
+    return VecLiarPartnerPool(E, ego, members, seed=seed + 7, resample=resample, native=native, record=record), ego, members
+
+
+def _xplay(E, kinds, G, pairs=None, seed=5, native=True, record=0):
+    from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
+    members = [_member(kind, 4, 2, 20 + k) for k, kind in enumerate(kinds)]
+    return VecLiarCrossPlay(E, members, pairs=pairs, episodes_per_table=G, seed=seed, native=native, record=record)
+
+
+def _ctx_of(agent):
+    ctx = agent.model.policy.ctx
+    ctx.set_stream(th.cuda.current_stream(agent.model.policy.device).cuda_stream)
+    return ctx
+
+
+# ---- 1. the grouped forward on its own -------------------------------------------------------------------------------------------
+def _interleave(counts):
+    """member ids with the given counts, interleaved by table index (round robin over the members that still have rows left)"""
+    left, out = list(counts), []
+    while any(left):
+        for k in range(len(left)):
+            if left[k]:
+                out.append(k)
+                left[k] -= 1
+    return np.asarray(out, np.int32)
+
+
+def _forward_case(name):
+    """-> (kinds, partnerid, active).  The mixed case has active-row counts [17, 16, 1, 0, 16] per member, interleaved by table
+    index: a full tile plus one row, a one-row tile, a member with no rows, clone tiles beside tiles of every other kind, two clones
+    with different parameters and keys.  Those counts sum to 50, so `mixed50` is n = 50 with every row active and `mixed54` the same
+    active rows with four inactive ones in between (one of them naming the member that has no row)."""
+    mixed = ["clone", "frozen", "clone", "scripted", "learner"]
+    if name == "mixed50":
+        pid = _interleave([17, 16, 1, 0, 16])
+        return mixed, pid, np.ones(50, np.uint8)
+    if name == "mixed54":
+        pid, active = _interleave([17, 16, 1, 0, 16]).tolist(), [1] * 50
+        for at, k in ((3, 0), (17, 3), (30, 2), (41, 4)):
+            pid.insert(at, k)
+            active.insert(at, 0)
+        pid, active = np.asarray(pid, np.int32), np.asarray(active, np.uint8)
+        assert np.bincount(pid[active != 0], minlength=5).tolist() == [17, 16, 1, 0, 16] and len(pid) == 54
+        return mixed, pid, active
+    if name == "seven":
+        return ["clone", "frozen", "scripted"], np.array([0, 1, 2, 0, 1, 2, 0], np.int32), np.array([1, 1, 1, 0, 1, 0, 1], np.uint8)
+    if name == "clones23":     # every row at member 0: member 1 has no tile
+        return ["clone", "clone"], np.zeros(23, np.int32), (np.arange(23) % 5 != 0).astype(np.uint8)
+    assert name == "tile16"    # exactly one full tile
+    return ["clone"], np.zeros(16, np.int32), np.ones(16, np.uint8)
+
+
+@pytest.mark.parametrize("case", ["mixed50", "mixed54", "seven", "clones23", "tile16"])
+def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
+    from pantheonrl_amd.vec import VecOnPolicyAgent
+    kinds, pid_h, active_h = _forward_case(case)
+    n, K, T, counter = len(pid_h), len(kinds), 4, 9
+    rng = np.random.default_rng(5)
+    obs_space = _spaces().observation_space
+    obs = th.as_tensor((rng.random((n, 30)) * np.asarray(obs_space.nvec)).astype(np.int64).astype(np.float32)).cuda()
+    pid, active = th.as_tensor(pid_h).cuda(), th.as_tensor(active_h).cuda()
+    host = VecOnPolicyAgent(_ppo(n, 2, 0))
+    ctx = _ctx_of(host)
+    lib, h, spec = ctx.lib, ctx.handle, C.byref(host.model.policy.spec)
+    sets = []
+    for _ in range(2):                                    # two identical sets: one for the grouped launch, one for the yardstick
+        members = [_member(kind, n, T, 20 + k) for k, kind in enumerate(kinds)]
+        fill = np.random.default_rng(6)
+        for k, m in enumerate(members):
+            if kinds[k] != "learner":
+                continue
+            rb = m.model.rollout_buffer
+            for key in RB_KEYS:
+                t = getattr(rb, key)
+                t.copy_(th.as_tensor(fill.standard_normal(tuple(t.shape)).astype(np.float32)))
+            m.pos.copy_(th.as_tensor(((2 * np.arange(n) + k) % (T + 1)).astype(np.int32)))   # every fill level, full columns included
+            m.boundary.copy_(th.as_tensor(fill.integers(0, 2, n).astype(np.uint8)))
+            m.values.fill_(-3.0)
+            m.log_probs.fill_(-5.0)
+        sets.append(members)
+    grouped, plain = sets
+    clones = [k for k in range(K) if kinds[k] == "clone"]
+    if len(clones) > 1:                                   # two clones differ in parameters and in key
+        a, b = (grouped[k].policy for k in clones[:2])
+        assert a._seed != b._seed and not np.array_equal(a.get_flat_params(), b.get_flat_params())
+    es = th.zeros(n, dtype=th.float32, device="cuda")
+    for k, m in enumerate(grouped):
+        if kinds[k] == "learner":
+            es = th.where(pid == k, m.boundary.to(th.float32), es)
+    es = es.contiguous()
+    arr = (nat.PhPoolMember * K)()
+    keep = []
+    for k, m in enumerate(grouped):
+        arr[k].kind = KIND[kinds[k]]
+        if kinds[k] == "scripted":
+            continue
+        pol = m.model.policy if kinds[k] == "learner" else m.policy
+        arr[k].params, arr[k].seed = pol.params.data_ptr(), pol._seed
+        if kinds[k] == "learner":
+            keep.append(m.model.rollout_buffer.c_struct())
+            arr[k].rb = C.pointer(keep[-1])
+            arr[k].pos, arr[k].boundary, arr[k].term, arr[k].open = (t.data_ptr() for t in (m.pos, m.boundary, m.term, m.open))
+            arr[k].values, arr[k].log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
+    actions = th.full((n, 2), -7, dtype=th.int32, device="cuda")
+    nat.check(lib.ph_pool_forward(h, spec, arr, K, obs.data_ptr(), pid.data_ptr(), active.data_ptr(), counter, actions.data_ptr(),
+                                  es.data_ptr(), n))
+    th.cuda.synchronize()
+    got = actions.cpu().numpy()
+    act = active_h.astype(bool)
+    assert (got[~act] == -7).all()
+    for k, (g, p) in enumerate(zip(grouped, plain)):
+        mine = act & (pid_h == k)
+        if kinds[k] == "scripted":
+            want = th.full((n, 2), -7, dtype=th.int32, device="cuda")
+            rows = th.as_tensor(mine.astype(np.uint8)).cuda()
+            nat.check(lib.ph_liar_default_actions(h, obs.data_ptr(), rows.data_ptr(), want.data_ptr(), n))
+            assert np.array_equal(got[mine], want.cpu().numpy()[mine])
+            continue
+        if kinds[k] == "clone":
+            # ONE ph_bc_forward over all n rows (row index = table) on the identical second policy
+            pol = p.policy
+            want = th.full((n, 2), -9, dtype=th.int32, device="cuda")
+            pol.ctx.set_stream(th.cuda.current_stream(pol.device).cuda_stream)
+            nat.check(pol.ctx.lib.ph_bc_forward(pol.ctx.handle, C.byref(pol.spec), pol.params.data_ptr(), obs.data_ptr(), n, None, None,
+                                                None, pol._seed, counter, 0, want.data_ptr(), None, None, None, None))
+            th.cuda.synchronize()
+            want = want.cpu().numpy()
+            assert (want >= 0).all() and np.array_equal(got[mine], want[mine]), k
+            if mine.sum() >= 10:
+                assert len(np.unique(want[mine], axis=0)) > 3          # a spread of moves: nothing vacuous
+            p.policy._counter = counter - 1
+            assert np.array_equal(p.get_action(obs).cpu().numpy(), want)        # the walk's form is the same call
+            continue
+        if kinds[k] == "frozen":
+            p.policy._counter = counter - 1
+            want = p.get_action(obs).cpu().numpy()            # ph_policy_forward without a buffer
+            assert np.array_equal(got[mine], want[mine])
+            continue
+        pol, rb = p.model.policy, p.model.rollout_buffer
+        want = th.zeros((n, 2), dtype=th.int32, device="cuda")
+        mask = th.as_tensor(mine.astype(np.uint8)).cuda()
+        nat.check(lib.ph_policy_forward_ragged(h, spec, pol.params.data_ptr(), obs.data_ptr(), None, pol._seed, counter, 0,
+                                               want.data_ptr(), p.values.data_ptr(), p.log_probs.data_ptr(),
+                                               C.byref(rb.c_struct()), p.pos.data_ptr(), mask.data_ptr(), es.data_ptr()))
+        th.cuda.synchronize()
+        assert np.array_equal(got[mine], want.cpu().numpy()[mine]), k
+        assert np.array_equal(g.values.cpu().numpy(), p.values.cpu().numpy()), k               # cached for recorded rows only
+        glp, plp = g.log_probs.cpu().numpy(), p.log_probs.cpu().numpy()
+        assert np.array_equal(glp[mine], plp[mine]) and (glp[~mine] == -5.0).all(), k
+        recorded = mine & (p.pos.cpu().numpy() < T)
+        assert (g.values.cpu().numpy()[~recorded] == -3.0).all()
+        if mine.sum() >= 10:
+            assert recorded.any() and (mine & ~recorded).any()
+        gb, pb = g.model.rollout_buffer.host(), rb.host()
+        for key in gb:                                        # every recorded row, and nothing else anywhere in the buffer
+            assert np.array_equal(gb[key], pb[key]), (k, key)
+        assert np.array_equal(g.pos.cpu().numpy(), p.pos.cpu().numpy())                        # the forward does not advance
+
+
+# ---- 2. the native step is bitwise the walk --------------------------------------------------------------------------------------
+def _pool_state(sp, ego):
+    th.cuda.synchronize()
+    out = dict(hands=sp.env.hands.cpu().numpy(), hist=sp.env.history.cpu().numpy(), nmoves=sp.env.nmoves.cpu().numpy(),
+               obs=sp.obs_ego.cpu().numpy(), pid_now=sp.partnerid.cpu().numpy(), acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes,
+               ego_it=ego.iteration, pe=ego.model.policy.get_flat_params())
+    be = ego.model.rollout_buffer.host()
+    out.update({"e_" + k: v for k, v in be.items() if k in ("observations", "actions", "rewards", "episode_starts")})
+    for i, m in enumerate(sp.learners):
+        out[f"pos{i}"] = m.pos.cpu().numpy()
+        out[f"flags{i}"] = np.stack([t.cpu().numpy() for t in (m.boundary, m.term, m.open)])
+        out[f"values{i}"] = m.values.cpu().numpy()
+        out[f"p{i}"] = m.model.policy.get_flat_params()
+        out.update({f"a{i}_" + k: v for k, v in m.model.rollout_buffer.host().items() if k in RB_KEYS})
+    return out
+
+
+def _run_pool(native, resample, kinds, E, T_ego, T_alt, steps, seed=11):
+    sp, ego, members = _pool(E, T_ego, T_alt, kinds, seed=seed, native=native, resample=resample)
+    trained = [0] * len(sp.learners)
+    pids = []
+    for _ in range(steps):
+        sp.step()
+        pids.append(sp.partnerid.cpu().numpy().copy())
+        for i, m in enumerate(sp.learners):
+            if m.full():
+                m.learn_from_buffer()
+                trained[i] += 1
+    out = _pool_state(sp, ego)
+    out.update(pid=np.stack(pids), trained=trained)
+    return out
+
+
+@pytest.mark.parametrize("resample", ["robin", "random"])
+def test_native_pool_step_with_clones_is_bitwise_the_walk(resample):
+    kinds = ["learner", "clone", "scripted", "clone"]
+    a, b = (_run_pool(native, resample, kinds, E=50, T_ego=8, T_alt=4, steps=24) for native in (True, False))
+    assert min(a["trained"]) >= 1 and a["trained"] == b["trained"], a["trained"]
+    assert a["ego_it"] >= 2 and a["episodes"] > 50
+    assert len(np.unique(a["pid"])) == 4                   # every member sat somewhere, both clones included
+    for key in a:
+        x, y = a[key], b[key]
+        if key[0] == "a" and key[1].isdigit() and getattr(x, "ndim", 0) >= 2:       # only the recorded rows of a ragged buffer are defined
+            pos = a["pos" + key[1]]
+            rows = np.arange(x.shape[0])[:, None] < pos[None, :]
+            x, y = x[rows], y[rows]
+        assert np.array_equal(x, y), key
+
+
+def _xstate(xp):
+    th.cuda.synchronize()
+    out = {k: getattr(xp.env if k in ("hands", "history", "nmoves") else xp, k).cpu().numpy().copy() for k in XSTATE}
+    out["ego_first"] = xp.ego_first.cpu().numpy().copy()
+    return out
+
+
+def test_native_crossplay_step_with_clones_is_bitwise_the_walk_after_every_step():
+    E, G, kinds = 50, 3, ["clone", "frozen", "scripted", "clone"]          # all 16 pairs on 50 tables
+    a, b = (_xplay(E, kinds, G, native=native) for native in (True, False))
+    assert a.P == 16
+    steps = 0
+    while True:
+        sa, sb = _xstate(a), _xstate(b)
+        for key in sa:
+            assert np.array_equal(sa[key], sb[key]), (steps, key)
+        if sb["tables_left"][0] == 0:
+            break
+        assert steps < 7 * G
+        a.step()
+        b.step()
+        steps += 1
+    assert (sb["games"] == G).all() and sb["lengths"].min() >= 1 and sb["lengths"].max() >= 2
+    ra, rb = a.run(), b.run()
+    assert a.left() == 0 and b.left() == 0 and ra.steps == rb.steps == steps
+    for name in ("count", "sum", "sumsq", "sum_length", "mean", "std", "mean_length"):
+        assert np.array_equal(getattr(ra, name), getattr(rb, name)), name
+    assert (ra.count >= 3 * G).all()
+    assert set(np.unique(ra.returns).tolist()) == {-1.0, 1.0}
+
+
+# ---- 3. the games are real games ---------------------------------------------------------------------------------------------------
+def test_recorded_clone_games_replay_through_the_host_game():
+    from pantheonrl_amd.envs.crossplay import MAX_STEPS_PER_GAME
+    from pantheonrl_amd.envs.liar import LiarEnv
+    E, G = 12, 2
+    pairs = [(0, 0), (0, 1), (1, 0)]                        # (clone, clone), (clone, scripted), (scripted, clone)
+    xp = _xplay(E, ["clone", "scripted"], G, pairs=pairs, record=3 * MAX_STEPS_PER_GAME * G)
+    # the deals: hands and who opens, game by game, read from the device between steps
+    deals = [[None] * G for _ in range(E)]
+
+    def snapshot():
+        th.cuda.synchronize()
+        games, hands, first = xp.games.cpu().numpy(), xp.env.hands.cpu().numpy(), xp.ego_first.cpu().numpy()
+        for e in range(E):
+            if games[e] < G and deals[e][games[e]] is None:
+                deals[e][games[e]] = (hands[e].copy(), bool(first[e]))
+    snapshot()
+    while xp.left() > 0:
+        assert xp.steps_done < MAX_STEPS_PER_GAME * G
+        xp.step()
+        snapshot()
+    rec = xp.recorded()
+    rows, member, off = rec.rows.cpu().numpy(), rec.member.cpu().numpy(), rec.table_offsets
+    returns, lengths = xp.returns.cpu().numpy(), xp.lengths.cpu().numpy()
+    assert not rec.dropped.any() and off[-1] == len(rows)
+    clone_moves = 0
+    for e in range(E):
+        mine, who = rows[off[e]:off[e + 1]], member[off[e]:off[e + 1]]
+        pair = pairs[e % 3]
+        at = 0
+        for g in range(G):
+            hands, ego_first = deals[e][g]
+            env = LiarEnv()
+            env.history, env.egohand, env.althand = [], [int(x) for x in hands[:6]], [int(x) for x in hands[6:]]
+            isego, done, ret, length = ego_first, False, 0.0, 0
+            while not done:
+                row = mine[at]
+                flag = int(row[32])
+                assert flag % 2 == (0 if isego else 1), (e, g, at)
+                assert who[at] == pair[0 if isego else 1], (e, g, at)
+                assert np.array_equal(row[:30], env.getObs(isego).astype(np.float32)), (e, g, at)
+                _, payoff, done, _ = env.player_step(row[30:32].astype(np.int64), isego)
+                assert (flag >= 2) == bool(done), (e, g, at)
+                ret += float(payoff[0])
+                length += int(isego)
+                clone_moves += int(who[at] == 0)
+                isego = not isego
+                at += 1
+            assert returns[e, g] == np.float32(ret) and lengths[e, g] == length, (e, g)
+        assert at == len(mine), e
+    assert clone_moves > E * G
+
+
+# ---- 4. no host work ---------------------------------------------------------------------------------------------------------------
+def test_native_pool_step_with_clones_does_no_host_work_and_captures():
+    kinds = ["learner", "clone", "scripted", "clone"]
+    (eager, ego_e, _), (sp, ego, _) = (_pool(32, 8, 8, kinds, seed=3) for _ in range(2))
+    for c in range(1, 7):
+        eager._native_call(c, ego_pos=c - 1)
+    stream = th.cuda.Stream(device=sp.dev)
+    th.cuda.synchronize()
+    with th.cuda.stream(stream):
+        for c in (1, 2):
+            sp._native_call(c, ego_pos=c - 1)
+        stream.synchronize()
+        ctx = sp.env.ctx
+        sp._bind()
+        nat.check(ctx.lib.ph_graph_begin(ctx.handle))
+        try:
+            for c in (3, 4, 5, 6):
+                sp._native_call(c, ego_pos=c - 1)
+        finally:
+            gid = C.c_int(-1)
+            nat.check(ctx.lib.ph_graph_end(ctx.handle, C.byref(gid)))
+        assert gid.value >= 0
+        episodes = sp.episodes
+        nat.check(ctx.lib.ph_graph_launch(ctx.handle, gid.value))
+        stream.synchronize()
+    th.cuda.synchronize()
+    assert sp.episodes > episodes
+    a, b = _pool_state(sp, ego), _pool_state(eager, ego_e)
+    for key in a:
+        x, y = a[key], b[key]
+        if key[0] == "a" and key[1].isdigit() and getattr(x, "ndim", 0) >= 2:
+            rows = np.arange(x.shape[0])[:, None] < a["pos" + key[1]][None, :]
+            x, y = x[rows], y[rows]
+        if key.startswith("e_"):
+            x, y = x[:6], y[:6]
+        assert np.array_equal(x, y), key
+
+
+# ---- 5. misuse ---------------------------------------------------------------------------------------------------------------------
+def test_clone_misuse_is_an_error_string_and_nothing_is_launched():
+    from pantheonrl_amd import spaces as sps
+    from pantheonrl_amd.bc import FeedForward32Policy
+    from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
+    from pantheonrl_amd.envs.vec import ClonedVecPartner, FrozenVecPartner, RaggedVecOnPolicyAgent
+    sp, ego, members = _pool(16, 4, 4, ["clone", "frozen", "scripted"], seed=1)
+    ctx = sp.env.ctx
+    sp._bind()
+    lib, h, d = ctx.lib, ctx.handle, sp._desc
+    err = lambda: lib.ph_last_error()  # noqa: E731
+    th.cuda.synchronize()
+    before = {k: getattr(sp.env, k).cpu().numpy().copy() for k in ("hands", "history", "nmoves")}
+    arr = sp._member_arr
+    assert arr[0].kind == nat.PH_POOL_CLONE and not arr[0].values and not arr[0].rb
+    good = arr[0].params
+    arr[0].params = None
+    assert lib.ph_liar_pool_step(h, C.byref(d), 0, 1, 0) != 0 and b"member 0: null params" in err()
+    arr[0].params = good
+    for bad in (4, 7):
+        arr[0].kind = bad
+        assert lib.ph_liar_pool_step(h, C.byref(d), 0, 1, 0) != 0 and b"unknown kind" in err()
+    arr[0].kind = nat.PH_POOL_CLONE
+    th.cuda.synchronize()
+    for k, v in before.items():                              # refused in front of the first launch: the game did not move
+        assert np.array_equal(getattr(sp.env, k).cpu().numpy(), v), k
+    s = _spaces()
+    with pytest.raises(nat.NativeError, match="ClonedVecPartner"):
+        FrozenVecPartner(FeedForward32Policy(s.observation_space, s.action_space, seed=1))
+    with pytest.raises(nat.NativeError, match="Liar's Dice spaces"):
+        ClonedVecPartner(FeedForward32Policy(sps.Discrete(1), sps.Discrete(3), seed=1))          # RPS
+    with pytest.raises(nat.NativeError, match="FeedForward32Policy"):
+        ClonedVecPartner(_ppo(4, 2, 3).policy)                                                   # a 64-64 ActorCriticPolicy
+    with pytest.raises(nat.NativeError, match="learners train in VecLiarPartnerPool"):
+        VecLiarCrossPlay(8, [RaggedVecOnPolicyAgent(_ppo(8, 2, 3))])
+    # ... and the context still steps
+    sp.step()
+    th.cuda.synchronize()
+    assert np.isfinite(ego.model.rollout_buffer.host()["values"][0]).all()
+    assert not np.array_equal(sp.env.nmoves.cpu().numpy(), before["nmoves"]) or sp.episodes > 0
+
+
+# ---- 6. end to end -------------------------------------------------------------------------------------------------------------------
+def test_train_record_clone_crossplay_and_train_against_the_clone(tmp_path, monkeypatch):
+    from pantheonrl_amd import bctrainer, crossplay, trainer
+    from pantheonrl_amd.envs.vec import ClonedVecPartner, VecLiarDefaultPartner, VecLiarPartnerPool
+    monkeypatch.chdir(tmp_path)
+    trainer.run(["LiarsDice-v0", "PPO", "PPO", "--n-envs", "32", "-t", "2048", "--seed", "1", "--record", "demo.npy",
+                 "--ego-save", "m/ego"])
+    bctrainer.run(["LiarsDice-v0", "demo.npy", "--total-epochs", "2", "--save", "m/clone.pt"])
+    res = crossplay.run(["LiarsDice-v0", "--agents", "m/ego", "BC:m/clone.pt", "DEFAULT", "--n-envs", "32", "-t", "6", "--seed", "0",
+                         "--record", "x.npy", "--out", "x.npz"])
+    z = np.load("x.npz")
+    assert z["mean"].shape == z["std"].shape == z["count"].shape == (3, 3)
+    assert np.isfinite(z["mean"]).all() and np.isfinite(z["std"]).all() and (z["count"] >= 6).all()
+    assert np.array_equal(z["mean"], res.matrix("mean"))
+    assert (z["member"] == 1).any() and len(z["member"]) == len(np.load("x.npy"))
+    fixed = json.dumps({"type": "BC", "location": "m/clone.pt"})
+    ego, partners, env = trainer.run(["LiarsDice-v0", "PPO", "FIXED", "DEFAULT", "--alt-config", fixed, "{}", "--n-envs", "32",
+                                      "-t", "2048", "--seed", "2"])
+    assert isinstance(env, VecLiarPartnerPool) and env.native and env.K == 2
+    assert isinstance(partners[0], ClonedVecPartner) and isinstance(partners[1], VecLiarDefaultPartner)
+    assert env.ego.iteration >= 1 and env.episodes > 0
