@@ -566,7 +566,9 @@ int ph_liar_selfplay_rollout(ph_ctx *ctx, const ph_liar_selfplay *s, int ego_pos
  * the 64-64 policy.  A clone (PH_POOL_CLONE; an addition, PH_ABI_VERSION unchanged) plays the shared-trunk FeedForward32Policy of
  * behavioural cloning: `params` is a ph_bc_layout vector for the step's spec (ph_bc_layout_of must succeed for it) and `seed` its
  * Philox key; rb, pos, boundary, term, open, values and log_probs are ignored and may be NULL.  Like a frozen member it records
- * nothing.  ph_pool_forward, ph_liar_pool_step and ph_liar_xplay_step accept it. */
+ * nothing.  ph_pool_forward, ph_liar_pool_step and ph_liar_xplay_step accept it.  A learner or a frozen member -- and the pool's
+ * ego -- may instead play the towers of a run-time shape (ph_arch): through ph_pool_forward_arch, ph_liar_pool_step_arch and
+ * ph_liar_xplay_step_arch, declared with the towers below. */
 #define PH_MAX_POOL 8
 #define PH_POOL_LEARNER 0
 #define PH_POOL_FROZEN 1
@@ -1095,6 +1097,32 @@ int ph_liar_selfplay_step_arch(ph_ctx *ctx, const ph_liar_selfplay *s, const ph_
  *      multiagentenv.py:149-215); both forwards and the worlds draw with `counter`. */
 int ph_block_selfplay_step_arch(ph_ctx *ctx, const ph_block_selfplay *s, const ph_arch *ego_arch /* host or NULL */,
                                 const ph_arch *alt_arch /* host or NULL */, int ego_pos, unsigned long long counter);
+/*  Towers as members of the Liar's Dice pool and of cross-play (additions; PH_ABI_VERSION unchanged; ph_pool_member, ph_liar_pool
+ *      and ph_liar_xplay keep their layouts: the archs travel beside them).  member_archs: NULL, or a host array [n_members] whose
+ *      entry k is NULL -- member k stays what its kind says, on today's kernels -- or the arch of the towers that a PH_POOL_LEARNER
+ *      or PH_POOL_FROZEN member's `params` (a ph_arch_layout vector, 16-byte aligned) describe.  With every arch NULL each entry
+ *      point is bit for bit the one it extends (which is that call).  Refused with nothing launched: an arch on a scripted member
+ *      or a clone, an arch ph_arch_fits refuses for the spec, misaligned params.
+ *  ph_pool_forward_arch: a tower member's tiles of the bucket pass run in ONE launch of their own behind the grouped one
+ *      (pool_tower_kernel: one workgroup per (tile, net), the 32-row tower forward over the tile's <= 16 tables, dynamic LDS the
+ *      largest carve over the table's tower members), made only when the member table holds a tower; the 64-wide launch is left out
+ *      when the table holds neither a 64-wide nor a scripted member.  Row e of a frozen tower is bitwise ph_arch_forward's row e
+ *      for (member seed, counter), row e of a learner tower ph_arch_forward_ragged's with the member's rows as record mask.  Only
+ *      the MFMA instantiation (gemm_mode 0) is built: the grouped forward takes no gemm_mode.
+ *  ph_liar_pool_step_arch: ph_liar_pool_step with tower members and / or a tower ego (ego_arch describes pool->ego_params; NULL: the
+ *      64-wide ego).  8 launches as ph_liar_pool_step when every member is a tower or none is; a table that holds towers beside
+ *      other members adds one launch per grouped forward: 10 (12 with clones as well).
+ *  ph_liar_xplay_step_arch: ph_liar_xplay_step with tower members.  9 launches when every member is a tower or none is, else one
+ *      more per grouped forward: 12 (15 with clones as well).
+ *  A recorder logs a tower member's moves like any member's. */
+int ph_pool_forward_arch(ph_ctx *ctx, const ph_spec *spec, const ph_pool_member *members, int n_members, const float *obs,
+                         const int *partnerid, const unsigned char *active, unsigned long long counter, int *actions,
+                         const float *episode_start_in, int n, const ph_arch *const *member_archs /* host or NULL */);
+int ph_liar_pool_step_arch(ph_ctx *ctx, const ph_liar_pool *pool, const ph_arch *ego_arch /* host or NULL */,
+                           const ph_arch *const *member_archs /* host or NULL */, int ego_pos, unsigned long long counter,
+                           int deal_only);
+int ph_liar_xplay_step_arch(ph_ctx *ctx, const ph_liar_xplay *xp, const ph_arch *const *member_archs /* host or NULL */,
+                            unsigned long long counter, int deal_only);
 /*  ph_arch_scripted_rollout: ph_scripted_rollout for towers -- OnPolicyAgent.get_action / update per step (agents.py:111-203)
  *      against a scripted environment with the launch boundaries removed: ONE launch in which a workgroup owns 32 rows of one net
  *      for all n_steps.  Exactly, bit for bit,

@@ -385,6 +385,10 @@ SIGNATURES = {
     "ph_arch_forward_ragged": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp,
                                C.POINTER(PhRollout), _vp, _vp, _vp, _i],
     "ph_liar_selfplay_step_arch": [_vp, C.POINTER(PhLiarSelfPlay), C.POINTER(PhArch), C.POINTER(PhArch), _i, _ull, _i],
+    "ph_pool_forward_arch": [_vp, C.POINTER(PhSpec), C.POINTER(PhPoolMember), _i, _vp, _vp, _vp, _ull, _vp, _vp, _i,
+                             C.POINTER(C.POINTER(PhArch))],
+    "ph_liar_pool_step_arch": [_vp, C.POINTER(PhLiarPool), C.POINTER(PhArch), C.POINTER(C.POINTER(PhArch)), _i, _ull, _i],
+    "ph_liar_xplay_step_arch": [_vp, C.POINTER(PhLiarXplay), C.POINTER(C.POINTER(PhArch)), _ull, _i],
     "ph_block_selfplay_step_arch": [_vp, C.POINTER(PhBlockSelfPlay), C.POINTER(PhArch), C.POINTER(PhArch), _i, _ull],
     "ph_arch_scripted_rollout": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp,
                                  _vp, C.POINTER(PhRollout), _i, _i],

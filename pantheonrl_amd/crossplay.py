@@ -68,7 +68,7 @@ def run(argv=None):
     size = plan(args)
     from .envs.crossplay import MAX_STEPS_PER_GAME, VecLiarCrossPlay
     from .tester import load_member
-    members = [load_member(kind, {}, location, args.device) for kind, location in map(parse_agent, args.agents)]
+    members = [load_member(kind, {}, location, args.device, towers=True) for kind, location in map(parse_agent, args.agents)]
     # a game takes at most MAX_STEPS_PER_GAME steps of at most 3 moves
     record = 3 * MAX_STEPS_PER_GAME * size["episodes_per_table"] if args.record else 0
     xp = VecLiarCrossPlay(args.n_envs, members, episodes_per_table=size["episodes_per_table"], seed=args.seed,

@@ -184,6 +184,8 @@ struct ph_ctx {
   ph::PoolMemberDev* pool_dev = nullptr;
   ph::PoolMemberDev pool_host[PH_MAX_POOL];
   int pool_count = 0;                       // members pool_dev holds, 0 = nothing yet
+  bool pool_wide = false;                   // ... of which one is a 64-wide or a scripted member (pool_fwd16h_kernel has a tile to run)
+  size_t pool_tower_lds = 0;                // ... the largest forward carve of its tower members, 0 = no tower (found at the upload)
   int* pool_order = nullptr;                // (n)
   size_t pool_order_cap = 0;
   int* pool_tiles = nullptr;                // [pool_max_tiles + 1][3]; the last record's first word is the tile count
@@ -393,6 +395,8 @@ int fail_who(const char* who, const char* what) { return fail(std::string(who) +
 const char* const LIAR_ALIGN16 = ": hands/history must be 16-byte aligned";
 
 int arch_resolve(ph_ctx* ctx, const ph_spec* spec, const ph_arch* arch, ph::NetDims* nd, ph::ArchDims* ad);   // with the towers, below
+int arch_host_dims(const ph_spec* spec, const ph_arch* arch, ph::NetDims* nd, ph::ArchDims* ad);
+int arch_lds_refusal(const ph::NetDims& nd, const ph::ArchDims& ad);
 
 // a zeroed forward record with the spec resolved and the fields every forward entry point sets: for the 64-wide kernels (null
 // arch), or for the towers of `arch`, whose dimensions go to `ad` (arch_resolve: no Box actions, the LDS refusal, lay.P the arch's)
@@ -1857,20 +1861,41 @@ int ph_liar_selfplay_step_arch(ph_ctx* ctx, const ph_liar_selfplay* sp, const ph
 
 // ---- Liar's Dice against a pool of partners (ph_pool.h) ----
 namespace {
-// validate the members and bring the device-side table up to date (uploaded only when it changed; never inside graph capture)
-int pool_members(ph_ctx* ctx, const char* who, const ph_pool_member* members, int K, int n) {
+// validate the members and bring the device-side table up to date (uploaded only when it changed; never inside graph capture).
+// archs: null, or per member null (the member stays what its kind says on the 64-wide / scripted / clone kernels) or the arch of a
+// learner's or frozen member's towers, resolved into the table for pool_tower_kernel.
+int pool_members(ph_ctx* ctx, const char* who, const ph_spec* spec, const ph_pool_member* members, const ph_arch* const* archs, int K,
+                 int n) {
   const std::string w(who);
   if (!members) return fail(w + ": null member array");
   if (K < 1 || K > PH_MAX_POOL) return fail(w + ": the pool holds 1..PH_MAX_POOL members");
+  if (archs && !spec) return fail(w + ": null spec");
   ph::PoolMemberDev tab[PH_MAX_POOL];
-  std::memset(tab, 0, sizeof(tab));
+  // (the K rows in use are zeroed, compared and uploaded: this runs in front of every step)
+  const size_t used = sizeof(ph::PoolMemberDev) * (size_t)K;
+  std::memset(tab, 0, used);
+  bool wide = false;
+  size_t tower_lds = 0;
   for (int k = 0; k < K; ++k) {
     const ph_pool_member& m = members[k];
     ph::PoolMemberDev& d = tab[k];
     const std::string wk = w + ": member " + std::to_string(k);
     if (m.kind != PH_POOL_LEARNER && m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED && m.kind != PH_POOL_CLONE)
       return fail(wk + ": unknown kind");
-    d.kind = m.kind;
+    d.kind = d.fwd = m.kind;
+    if (archs && archs[k]) {
+      if (m.kind == PH_POOL_SCRIPTED || m.kind == PH_POOL_CLONE)
+        return fail(wk + ": an arch belongs to a learner or a frozen member, not to a scripted one or a clone");
+      ph::NetDims nd;
+      ph::ArchDims ad;
+      if (arch_host_dims(spec, archs[k], &nd, &ad) || arch_lds_refusal(nd, ad)) return 1;
+      d.ad = ad;
+      d.fwd = PH_POOL_CLONE;   // "not pool_fwd16h_kernel's tile"
+      d.tower = 1;
+      tower_lds = std::max(tower_lds, ph::arch_fwd_lds_bytes(nd, ad));   // (nd: the fields the carve depends on)
+    } else if (m.kind != PH_POOL_CLONE) {
+      wide = true;
+    }
     if (m.kind == PH_POOL_SCRIPTED) continue;
     if (!m.params) return fail(wk + ": null params");
     if ((uintptr_t)m.params % 16 != 0) return fail(wk + ": params must be 16-byte aligned");
@@ -1897,15 +1922,17 @@ int pool_members(ph_ctx* ctx, const char* who, const ph_pool_member* members, in
     d.term = m.term;
     d.open = m.open;
   }
-  if (ctx->pool_count != K || std::memcmp(ctx->pool_host, tab, sizeof(tab)) != 0) {
+  if (ctx->pool_count != K || std::memcmp(ctx->pool_host, tab, used) != 0) {
     if (ctx->capturing) return fail(w + ": the member table changed inside graph capture: run the same call once outside capture first");
     if (!ctx->pool_dev) PH_HIP(hipMalloc((void**)&ctx->pool_dev, sizeof(tab)));
     PH_HIP(hipStreamSynchronize(ctx->stream));   // launches in flight still read the table
-    std::memcpy(ctx->pool_host, tab, sizeof(tab));
+    std::memcpy(ctx->pool_host, tab, used);
     ctx->pool_count = 0;
-    PH_HIP(hipMemcpyAsync(ctx->pool_dev, ctx->pool_host, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+    PH_HIP(hipMemcpyAsync(ctx->pool_dev, ctx->pool_host, used, hipMemcpyHostToDevice, ctx->stream));
     PH_HIP(hipStreamSynchronize(ctx->stream));
     ctx->pool_count = K;
+    ctx->pool_wide = wide;
+    ctx->pool_tower_lds = tower_lds;
   }
   return 0;
 }
@@ -1950,9 +1977,9 @@ int pool_forward(ph_ctx* ctx, const char* who, const ph_spec* spec, int K, const
   p.b.tiles = ctx->pool_tiles;
   p.b.ntiles = ctx->pool_tiles + 3 * ntile;
   PH_HIP(ph::launch_pool_bucket(partnerid, active, n, K, p.b, ctx->stream));
-  bool clones_only = p.bc.P != 0;
-  for (int k = 0; k < ctx->pool_count; ++k) clones_only = clones_only && ctx->pool_host[k].kind == PH_POOL_CLONE;
-  PH_HIP(ph::launch_pool_fwd(p, K, ctx->stream, clones_only));
+  // which of the three kernels the table has tiles for (pool_members found out at the upload): 64-wide and scripted members,
+  // clones (p.bc.P), towers (their largest carve)
+  PH_HIP(ph::launch_pool_fwd(p, K, ctx->stream, !ctx->pool_wide, ctx->pool_tower_lds));
   return 0;
 }
 }  // namespace
@@ -1960,12 +1987,19 @@ int pool_forward(ph_ctx* ctx, const char* who, const ph_spec* spec, int K, const
 int ph_pool_forward(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* members, int n_members, const float* obs,
                     const int* partnerid, const unsigned char* active, unsigned long long counter, int* actions,
                     const float* episode_start_in, int n) {
+  return ph_pool_forward_arch(ctx, spec, members, n_members, obs, partnerid, active, counter, actions, episode_start_in, n, nullptr);
+}
+
+int ph_pool_forward_arch(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* members, int n_members, const float* obs,
+                         const int* partnerid, const unsigned char* active, unsigned long long counter, int* actions,
+                         const float* episode_start_in, int n, const ph_arch* const* member_archs) {
   DevGuard dev_guard(ctx);
   if (!ctx) return fail("null ctx");
   if (!spec || !obs || !partnerid || !active || !actions) return fail("ph_pool_forward: null argument");
   if (n <= 0) return fail("ph_pool_forward: n must be positive");
   if ((uintptr_t)actions % 8) return fail("ph_pool_forward: actions must be 8-byte aligned");
-  if (pool_members(ctx, "ph_pool_forward", members, n_members, n) || check_pool_clones("ph_pool_forward", ctx, spec)) return 1;
+  if (pool_members(ctx, "ph_pool_forward", spec, members, member_archs, n_members, n) || check_pool_clones("ph_pool_forward", ctx, spec))
+    return 1;
   for (int k = 0; k < n_members; ++k)
     if (members[k].kind == PH_POOL_LEARNER && !episode_start_in) return fail("ph_pool_forward: learners need episode_start_in");
   return pool_forward(ctx, "ph_pool_forward", spec, n_members, obs, partnerid, active, active, counter, actions, episode_start_in, n);
@@ -1981,7 +2015,12 @@ int ph_liar_default_actions(ph_ctx* ctx, const float* obs, const unsigned char* 
   return 0;
 }
 
-int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsigned long long counter, int deal_only) {
+// The pool step and the cross-play step, each written once for the entry point and its `_arch` form: C++ overloads of the entry
+// points' names that take the archs as well (null: every seat on today's kernels).
+extern "C++" {
+namespace {
+int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_arch, const ph_arch* const* member_archs, int ego_pos,
+                      unsigned long long counter, int deal_only) {
   DevGuard dev_guard(ctx);
   const char* who = "ph_liar_pool_step";
   if (!ctx || !pool) return fail_who(who, ": null argument");
@@ -1991,7 +2030,10 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsign
   if (!s.partnerid || !s.alt_acted || !s.can || !s.es_alt) return fail_who(who, ": incomplete description");
   if (s.resample != PH_POOL_ROBIN && s.resample != PH_POOL_RANDOM) return fail_who(who, ": unknown resample rule");
   if (check_liar_ego(who, s)) return 1;
-  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) || check_pool_clones(who, ctx, s.spec))
+  if (ego_arch && ph_arch_fits(s.spec, ego_arch)) return 1;   // before the first launch, as every member's arch
+  if (ego_arch && (uintptr_t)s.ego_params % 16 != 0) return fail_who(who, ": params must be 16-byte aligned");
+  if (pool_members(ctx, who, s.spec, s.members, member_archs, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) ||
+      check_pool_clones(who, ctx, s.spec))
     return 1;
   if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail_who(who, ": ego_pos out of range (buffer full?)");
   const ph::PoolBook book{s.n, s.n_members, s.resample, s.pool_seed, ctx->pool_dev, s.partnerid, s.alt_acted, s.can, s.es_alt};
@@ -1999,7 +2041,7 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsign
       ctx, g, book, liar_train_end(s, ego_pos, deal_only), counter, deal_only, {counter, 2 * counter, 2 * counter + 1},
       LiarSeats{nullptr, s.partnerid, nullptr},   // the log names the member at seat 1
       [&](unsigned long long c) {
-        return seat_forward(ctx, s.spec, nullptr, s.ego_params, s.obs_ego, s.n, s.ego_seed, c, s.ego_actions, s.ego_values,
+        return seat_forward(ctx, s.spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, c, s.ego_actions, s.ego_values,
                             s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start);
       },
       // every table's member -- behind a deal the freshly sampled one -- moves: one grouped launch
@@ -2009,7 +2051,8 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsign
 }
 
 // ---- cross-play evaluation of Liar's Dice (ph_xplay.h; tester.py:41-63 over n tables) ----
-int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long counter, int deal_only) {
+int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* const* member_archs, unsigned long long counter,
+                       int deal_only) {
   DevGuard dev_guard(ctx);
   const char* who = "ph_liar_xplay_step";
   if (!ctx || !xp) return fail_who(who, ": null argument");
@@ -2029,7 +2072,8 @@ int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long 
   for (int p = 0; p < 2 * s.n_pairs; ++p)
     if (s.pairs[p] < 0 || s.pairs[p] >= s.n_members)
       return fail("ph_liar_xplay_step: pair " + std::to_string(p / 2) + " names a member out of range");
-  if (pool_members(ctx, who, s.members, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) || check_pool_clones(who, ctx, s.spec))
+  if (pool_members(ctx, who, s.spec, s.members, member_archs, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) ||
+      check_pool_clones(who, ctx, s.spec))
     return 1;
   const ph::EvalEnd end{s.episodes_per_table, s.games, s.playing, s.tables_left, s.ep_return, s.ep_length, s.returns, s.lengths};
   // a seat's forward is one grouped launch over the member table, indexed by ego_id / alt_id; nothing is recorded
@@ -2040,6 +2084,24 @@ int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long 
       ctx, g, ph::NoBook{}, end, counter, deal_only, {3 * counter, 3 * counter + 1, 3 * counter + 2}, LiarSeats{s.ego_id, s.alt_id, s.playing},
       [&](unsigned long long c) { return seat(s.obs_ego, s.ego_id, s.playing, c, s.ego_actions); },
       [&](const float* obs, const unsigned char* active, unsigned long long c) { return seat(obs, s.alt_id, active, c, s.alt_actions); });
+}
+}  // namespace
+}  // extern "C++"
+
+int ph_liar_pool_step_arch(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_arch, const ph_arch* const* member_archs, int ego_pos,
+                           unsigned long long counter, int deal_only) {
+  return ph_liar_pool_step(ctx, pool, ego_arch, member_archs, ego_pos, counter, deal_only);
+}
+int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsigned long long counter, int deal_only) {
+  return ph_liar_pool_step_arch(ctx, pool, nullptr, nullptr, ego_pos, counter, deal_only);
+}
+
+int ph_liar_xplay_step_arch(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* const* member_archs, unsigned long long counter,
+                            int deal_only) {
+  return ph_liar_xplay_step(ctx, xp, member_archs, counter, deal_only);
+}
+int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long counter, int deal_only) {
+  return ph_liar_xplay_step_arch(ctx, xp, nullptr, counter, deal_only);
 }
 
 int ph_xplay_stats(ph_ctx* ctx, const float* returns, const int* lengths, const int* games, int n, int episodes_per_table, int n_pairs,

@@ -12,6 +12,7 @@
 #include "ph_rowtail.h"
 #include "ph_arch.h"
 #include "ph_ppo_loss.h"
+#include "ph_pool.h"
 
 namespace ph {
 
@@ -193,12 +194,16 @@ __device__ __forceinline__ void head_logits(float* smem, const ArchLds& S, const
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 // What a forward workgroup stages once: its tile's row indices (relative to a.obs), this net's biases and head vector, the
-// one-hot feature -> component table.  Caller barriers afterwards.
+// one-hot feature -> component table.  Caller barriers afterwards.  `map` (the pool's grouped forward): the tile's rows are the
+// tables map[0 .. rows) instead of row0 .. row0 + 31.
 __device__ __forceinline__ void tower_fwd_setup(float* smem, const ArchLds& S, const FwdArgs& a, const ArchDims& ad, int net, int row0,
-                                                int tid) {
+                                                int tid, const int* map = nullptr, int rows = 0) {
   constexpr int R = ARCH_FWD_ROWS;
   int* rowphys = (int*)(smem + S.rowphys);
-  if (tid < R) rowphys[tid] = (row0 + tid < a.n) ? row0 + tid : -1;
+  if (tid < R) {
+    if (map) rowphys[tid] = tid < rows ? map[tid] : -1;
+    else rowphys[tid] = (row0 + tid < a.n) ? row0 + tid : -1;
+  }
   stage_biases(smem, S, a.params, ad, a.nd, net, tid);
   if (a.nd.obs_kind != PH_SPACE_BOX) XStage<R, TNT>::build_fcomp((int*)(smem + S.fcomp), a.nd, tid);
 }
@@ -206,9 +211,11 @@ __device__ __forceinline__ void tower_fwd_setup(float* smem, const ArchLds& S, c
 // One forward of the workgroup's tile after tower_fwd_setup (and a barrier): every layer's products, then the value net's row
 // tail and observation copy, or the head product and the sampling tail.  Every global store goes through value_row_tail /
 // copy_obs_rows / general_row_tail, i.e. through rb_row: rectangular and ragged rollout-buffer rows alike.
-template <bool VALU>
+// MAP (the pool's grouped forward): the tile's rows are the tables rowphys[0 .. rows), in any order -- every tail and the
+// observation copy address table rowphys[t] instead of row0 + t.  The products are the same either way: they read rowphys only.
+template <bool VALU, bool MAP = false>
 __device__ __forceinline__ void tower_fwd_body(float* smem, const ArchLds& S, const FwdArgs& a, const ArchDims& ad, int net, int row0,
-                                               int tid) {
+                                               int tid, int rows = 0) {
   constexpr int R = ARCH_FWD_ROWS;
   const NetDims& nd = a.nd;
   const bool onehot = nd.obs_kind != PH_SPACE_BOX;
@@ -224,13 +231,23 @@ __device__ __forceinline__ void tower_fwd_body(float* smem, const ArchLds& S, co
     if (tid < R && rowphys[tid] >= 0) {
       float v = 0.f;
       for (int j = 0; j < wn; ++j) v = __builtin_fmaf(Hn[tid * ldh + j], smem[S.bos + j], v);
-      value_row_tail(a, row0 + tid, v + a.params[ad.lay.val_b]);
+      value_row_tail(a, MAP ? rowphys[tid] : row0 + tid, v + a.params[ad.lay.val_b]);
     }
-    copy_obs_rows(a, row0, (a.n - row0 < R) ? a.n - row0 : R, nd.D);
+    if constexpr (MAP) {
+      if (a.rb_obs)
+        for (int e = tid; e < rows * nd.D; e += TNT) {
+          const int r = e / nd.D, d = e - r * nd.D, gt = rowphys[r];
+          const long long ridx = rb_row(a, gt);
+          if (ridx >= 0) a.rb_obs[(size_t)ridx * nd.D + d] = a.obs[(size_t)gt * nd.D + d];
+        }
+    } else {
+      copy_obs_rows(a, row0, (a.n - row0 < R) ? a.n - row0 : R, nd.D);
+    }
     return;
   }
   head_logits<R, VALU>(smem, S, a.params, ad, nd, tid);
-  if (tid < R && rowphys[tid] >= 0) general_row_tail(a, nd, row0 + tid, smem + S.bufx + tid * (nd.Lp + 1), fwd_counter(a));
+  if (tid < R && rowphys[tid] >= 0)
+    general_row_tail(a, nd, MAP ? rowphys[tid] : row0 + tid, smem + S.bufx + tid * (nd.Lp + 1), fwd_counter(a));
 }
 
 template <bool VALU>
@@ -243,6 +260,54 @@ __global__ __launch_bounds__(TNT) void tower_fwd_kernel(FwdArgs a, ArchDims ad) 
   tower_fwd_setup(smem, S, a, ad, net, row0, tid);
   __syncthreads();
   tower_fwd_body<VALU>(smem, S, a, ad, net, row0, tid);
+}
+
+// ---- the tower tiles of the pool's grouped forward (ph_pool.h) ----------------------------------------------------------------------
+// One workgroup per (tile of the bucket pass, net), as pool_fwd16h_kernel: the tile names a member and <= 16 sorted positions.  A
+// tile whose member is no tower is another kernel's.  The member's part (weights, seed, caches, ragged buffer) is patched into the
+// workgroup's copy of the shared record exactly as pool_fwd16h_kernel does, and the member's ArchDims come from the member table in
+// DEVICE memory (uniform loads; a by-value array of them indexed by the member would send the argument block to scratch, ph_arch.h).
+// The forward is the 32-row body, half empty: rowphys[t] = order[first + t] for t < rows, else -1, so a table's products, tails and
+// draws -- (member seed, counter, table) -- are those of ph_arch_forward over all tables, bit for bit.  The launch's dynamic LDS is the
+// largest carve over the table's tower members; a workgroup carves with its own member's arch_lds.
+template <bool VALU>
+__global__ __launch_bounds__(TNT) void pool_tower_kernel(PoolFwd p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int R = ARCH_FWD_ROWS;
+  const int tile = blockIdx.x;
+  if (tile >= p.b.ntiles[0]) return;
+  const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1];
+  const int rows = p.b.tiles[3 * tile + 2] < POOL_TILE ? p.b.tiles[3 * tile + 2] : POOL_TILE;   // (device data: clamped once)
+  const PoolMemberDev& m = p.members[member];
+  if (!m.tower) return;   // pool_fwd16h_kernel's or pool_clone16_kernel's
+  const bool learner = m.kind == PH_POOL_LEARNER;
+  const int tid = threadIdx.x, net = blockIdx.y;
+  if (net == 1 && !learner && !m.values) return;
+  const ArchDims ad = m.ad;
+  FwdArgs a = p.a;
+  a.params = m.params;
+  a.seed = m.seed;
+  a.values = m.values;
+  a.logp = m.log_probs;
+  if (learner) {
+    a.rb_obs = m.rb_obs;
+    a.rb_act = m.rb_act;
+    a.rb_rew = m.rb_rew;
+    a.rb_es = m.rb_es;
+    a.rb_val = m.rb_val;
+    a.rb_logp = m.rb_logp;
+    a.pos_env = m.pos;
+    a.rb_T = m.rb_T;
+  } else {
+    a.pos_env = nullptr;
+    a.rec_mask = nullptr;
+    a.es_in = nullptr;
+  }
+  const bool onehot = a.nd.obs_kind != PH_SPACE_BOX;
+  const ArchLds S = arch_lds(ad, R, onehot ? a.nd.D : 0, a.nd.nchunk);
+  tower_fwd_setup(smem, S, a, ad, net, 0, tid, p.b.order + first, rows);
+  __syncthreads();
+  tower_fwd_body<VALU, true>(smem, S, a, ad, net, 0, tid, rows);
 }
 
 // ---- one-launch rollout against a scripted environment ---------------------------------------------------------------------------
@@ -595,6 +660,14 @@ hipError_t launch_arch_fwd(const FwdArgs& a, const ArchDims& ad, int gemm_mode, 
   const size_t lds = arch_fwd_lds_bytes(a.nd, ad);
   if (lds > ARCH_LDS_MAX) return hipErrorInvalidValue;
   return gemm_mode == 1 ? launch_fwd_inst<true>(a, ad, lds, s) : launch_fwd_inst<false>(a, ad, lds, s);
+}
+
+// only the MFMA instantiation is built: no entry point of the grouped forward takes a gemm_mode
+hipError_t launch_pool_tower(const PoolFwd& p, int K, size_t lds, hipStream_t s) {
+  if (p.a.nd.gauss || (p.a.nd.Lp != 32 && p.a.nd.Lp != 64) || p.a.n < 1 || lds == 0 || lds > ARCH_LDS_MAX) return hipErrorInvalidValue;
+  if (const hipError_t e = allow_dynamic_lds((const void*)pool_tower_kernel<false>, lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((pool_tower_kernel<false>), dim3(pool_max_tiles(p.a.n, K), 2), dim3(TNT), lds, s, p);
+  return hipGetLastError();
 }
 
 template <bool VALU>

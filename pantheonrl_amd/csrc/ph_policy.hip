@@ -1318,7 +1318,8 @@ static size_t fwd16h_lds_bytes() {
 // trunk, params in ph_bc_layout) is left to pool_clone16_kernel below, launched behind this kernel only when the member table holds
 // a clone: the tile needed 74 VGPRs on its own when this was tried, but inside this kernel -- inlined, or behind a call -- it moved the register
 // allocation of the 64-64 path (179 -> 189 VGPRs inlined; 191 and 112 bytes of scratch behind a call), which every population
-// without a clone would have paid for.
+// without a clone would have paid for.  A tower member's tile (policy_kwargs net_arch) is left, by the same argument, to
+// pool_tower_kernel in ph_arch.hip: the word this kernel reads (`fwd`) says PH_POOL_CLONE for it, so this kernel's text is what it was.
 template <bool VALU>
 __global__ __launch_bounds__(256) void pool_fwd16h_kernel(PoolFwd p) {
   const int tile = blockIdx.x;
@@ -1326,7 +1327,7 @@ __global__ __launch_bounds__(256) void pool_fwd16h_kernel(PoolFwd p) {
   const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1], rows = p.b.tiles[3 * tile + 2];
   const int* map = p.b.order + first;
   const PoolMemberDev& m = p.members[member];
-  const int kind = m.kind;
+  const int kind = m.fwd;
   if (kind == PH_POOL_SCRIPTED) {
     if (blockIdx.y == 0 && (int)threadIdx.x < rows) {
       const int g = map[threadIdx.x];
@@ -1334,7 +1335,7 @@ __global__ __launch_bounds__(256) void pool_fwd16h_kernel(PoolFwd p) {
     }
     return;
   }
-  if (kind == PH_POOL_CLONE) return;   // pool_clone16_kernel's
+  if (kind == PH_POOL_CLONE) return;   // pool_clone16_kernel's -- or a tower's, which `fwd` states as a clone: pool_tower_kernel's (ph_arch.hip)
   const bool learner = kind == PH_POOL_LEARNER;
   if (blockIdx.y == 1 && !learner && !m.values) return;
   FwdArgs a = p.a;
@@ -1984,17 +1985,19 @@ bool pool_clone_eligible(const NetDims& nd, const ph_bc_layout& lay) {
   return bc_clone_eligible(nd.obs_kind, nd.D, nd.L) && lay.P > lay.b1 && lay.P - lay.b1 <= BC_CLONE_SMALL_MAX && lay.b1 == lay.W1 + lay.F * BH &&
          sizeof(float) * (size_t)bc_clone_lds_floats(lay.P - lay.b1) <= fwd16h_lds_bytes();
 }
-hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool clones_only) {
+hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide, size_t tower_lds) {
   if (!pool_fwd_eligible(p.a.nd, p.a.n)) return hipErrorInvalidValue;
   if (p.bc.P != 0 && !pool_clone_eligible(p.a.nd, p.bc)) return hipErrorInvalidValue;
-  if (clones_only && p.bc.P == 0) return hipErrorInvalidValue;
-  if (!clones_only)   // (a table of clones alone has no tile for this kernel: every workgroup would return at its tile's kind)
+  if (no_wide && p.bc.P == 0 && tower_lds == 0) return hipErrorInvalidValue;
+  if (!no_wide)   // (a table of clones and towers alone has no tile for this kernel: every workgroup would return at its tile's kind)
     hipLaunchKernelGGL((pool_fwd16h_kernel<false>), dim3(pool_max_tiles(p.a.n, K), 2), dim3(256), fwd16h_lds_bytes(), s, p);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   if (p.bc.P != 0)   // the member table holds a clone: its tiles (the two kernels write disjoint rows of the actions)
     hipLaunchKernelGGL(pool_clone16_kernel, dim3(pool_max_tiles(p.a.n, K)), dim3(256), sizeof(float) * (size_t)bc_clone_lds_floats(p.bc.P - p.bc.b1),
                        s, p);
-  return hipGetLastError();
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (tower_lds != 0) return launch_pool_tower(p, K, tower_lds, s);   // the member table holds a tower: its tiles, rows disjoint again
+  return hipSuccess;
 }
 
 template <int R, int LP, bool VALU>

@@ -3,23 +3,32 @@
 // Kernels: ph_pool.hip (bucket pass, scripted rule), ph_envs.hip (the step's book-keeping) and ph_policy.hip (pool_fwd16h_kernel: the grouped forward is the
 // 16-row one-hot forward with its rows gathered through `order`, so it lives beside policy_fwd16h_body).  A PH_POOL_CLONE member
 // (the shared-trunk FeedForward32Policy, params in ph_bc_layout) is a non-learner like a frozen one -- PoolBook below asks for
-// `kind == PH_POOL_LEARNER` only -- and its tile of the grouped forward is ph_bc_row.h's bc_clone_tile.
+// `kind == PH_POOL_LEARNER` only -- and its tile of the grouped forward is ph_bc_row.h's bc_clone_tile.  A learner or frozen member
+// whose `tower` flag is set plays an MLP tower of that run-time shape (ph_arch.h): its tiles are pool_tower_kernel's (ph_arch.hip).
 #pragma once
 #include "ph_liar_step.h"
+#include "ph_arch.h"
 
 namespace ph {
 
 // a member as the kernels read it -- from DEVICE memory (the context keeps the table): a by-value array inside the kernel
 // arguments, indexed by the tile's member, would put the whole argument block into scratch memory (see ph_arch.h, ph_launch.h)
 struct PoolMemberDev {
-  int kind, rb_T;
+  int fwd;           // what pool_fwd16h_kernel asks, in ONE word: the member's kind, but PH_POOL_CLONE ("another kernel's tile") for a tower
+  int kind;          // PH_POOL_*: what the step's book asks (PoolBook), and the other tile kernels
+  int rb_T;
+  int tower;         // != 0: `ad` below describes the member's towers; its tiles are pool_tower_kernel's
   const float* params;
   float *rb_obs, *rb_act, *rb_rew, *rb_es, *rb_val, *rb_logp;   // array bases of the ragged buffer (learner), else null
   int* pos;
   unsigned char *boundary, *term, *open;
   float *values, *log_probs;
   unsigned long long seed;
+  ArchDims ad;   // a tower member's (learner or frozen); read from this table on the device, never from a kernel argument
 };
+// (pool_fwd16h_kernel is held to the text it had without towers: a tower flag that it reads beside `kind` is a second load behind the
+// branch on `kind`, a dependent round trip to L2 in front of every tile -- 1.1 us per cross-play step of a population without a tower,
+// measured -- and a flag folded into the kind's word with a compare of its own still measured 0.4 us per step)
 
 constexpr int POOL_TILE = 16;            // rows of one tile = rows of the 16-row forward
 constexpr int POOL_BUCKET_THREADS = 256;
@@ -130,8 +139,12 @@ struct PoolBook {
 };
 
 hipError_t launch_pool_bucket(const int* partnerid, const unsigned char* active, int n, int K, const PoolBuckets& b, hipStream_t s);
-// ph_policy.hip; p.bc.P != 0: the member table holds a clone (its tiles' kernel follows); clones_only: it holds nothing else (no 64-64 launch)
-hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool clones_only = false);
+// ph_policy.hip; p.bc.P != 0: the member table holds a clone (its tiles' kernel follows); tower_lds != 0: it holds a tower (the
+// largest arch_fwd_lds_bytes over its tower members; pool_tower_kernel follows); no_wide: it holds neither a 64-wide nor a scripted
+// member (no 64-64 launch)
+hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide = false, size_t tower_lds = 0);
+// ph_arch.hip: the tower tiles of the bucket pass (lds: the launch's dynamic LDS, at least every tower member's carve)
+hipError_t launch_pool_tower(const PoolFwd& p, int K, size_t lds, hipStream_t s);
 bool pool_fwd_eligible(const NetDims& nd, int n);                     // ph_policy.hip
 bool pool_clone_eligible(const NetDims& nd, const ph_bc_layout& lay); // ph_policy.hip: the clone tile's shapes and LDS inside the grouped launch
 hipError_t launch_liar_default_actions(const float* obs, const unsigned char* active, int* actions, int n, hipStream_t s);

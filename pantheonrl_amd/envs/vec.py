@@ -306,6 +306,39 @@ class FrozenVecPartner:
         return None
 
 
+class TowerFrozenVecPartner(FrozenVecPartner):
+    """FrozenVecPartner for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): a fixed tower policy as a pool / population
+    member.  In the native steps its rows run the tower tiles of the grouped forward (pool_tower_kernel); `get_action` is the walk's
+    form, one `ph_arch_forward` over all rows -- the same bits row by row."""
+
+    def __init__(self, policy):
+        who = type(self).__name__
+        if not is_tower(policy):
+            raise nat.NativeError(f"{who}: {type(policy).__name__} is not a net_arch tower policy; use FrozenVecPartner")
+        require_tower_lds(policy, who)
+        self.policy = policy
+        self._out = {}
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
+        pol = self.policy
+        n = int(obs.shape[0])
+        out = self._out.get(n)
+        if out is None:
+            out = self._out[n] = (th.zeros((n, pol.layout.A), dtype=th.int32, device=pol.device),
+                                  th.zeros(n, dtype=th.float32, device=pol.device), th.zeros(n, dtype=th.float32, device=pol.device))
+        pol._bind()
+        pol._counter += 1
+        nat.check(pol.ctx.lib.ph_arch_forward(
+            pol.ctx.handle, C.byref(pol.spec), C.byref(pol.arch), pol.params.data_ptr(), obs.data_ptr(), n, None, None, None, pol._seed,
+            pol._counter, 0, out[0].data_ptr(), None, out[1].data_ptr(), out[2].data_ptr(), None, None, None, 0, None, None, 0))
+        return out[0]
+
+
+def frozen_partner_for(policy) -> FrozenVecPartner:
+    """the frozen member class that plays `policy`"""
+    return (TowerFrozenVecPartner if is_tower(policy) else FrozenVecPartner)(policy)
+
+
 class ClonedVecPartner:
     """A pool / population member that plays a behavioural clone: a `FeedForward32Policy` (bc.py: one shared 32-32 tanh trunk,
     parameters in ph_bc_layout) on the Liar's Dice spaces -- the "human proxy" partner of the reference's workflow (train, record,
@@ -342,10 +375,13 @@ class ClonedVecPartner:
         return None
 
 
-def check_liar_member_policy(policy, who: str) -> None:
+def check_liar_member_policy(policy, who: str, towers: bool = False) -> None:
     """a pool / population member's policy runs on the grouped forward's kernels and plays on the Liar's Dice spaces: the 64-64
-    layout through `require_mlp_kernels`, a clone's through its BC layout (ClonedVecPartner has checked the one-hot observation)"""
-    if not isinstance(policy, FeedForward32Policy):
+    layout through `require_mlp_kernels`, a clone's through its BC layout (ClonedVecPartner has checked the one-hot observation);
+    `towers`: a net_arch tower whose forward carve fits the CU is taken too (the `_arch` steps)"""
+    if towers and is_tower(policy):
+        require_tower_lds(policy, who)
+    elif not isinstance(policy, FeedForward32Policy):
         require_mlp_kernels(policy, who)
     lay = policy.layout
     if (lay.D, lay.A, lay.L) != (30, 2, 19):
@@ -512,6 +548,17 @@ class VecLiarStep:
                 c.values, c.log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
         self._member_arr = arr
         return arr
+
+    def _member_archs(self, members):
+        """the `member_archs` array of the `_arch` steps beside `_member_array`'s: entry k points at member k's ph_arch where it
+        plays a tower, else NULL (the policies keep the archs alive)"""
+        archs = (C.POINTER(nat.PhArch) * len(members))()
+        for k, m in enumerate(members):
+            p = self._policy_of(m)
+            if p is not None and is_tower(p):
+                archs[k] = C.pointer(p.arch)
+        self._member_arch_arr = archs
+        return archs
 
     # -- the move log (csrc/ph_record.h): TurnBasedRecorder's rows of every table, filled inside the step ----------------------------
     def start_recording(self, max_moves_per_table: int) -> None:
@@ -898,7 +945,7 @@ class VecLiarPartnerPool(VecLiarTraining):
                 continue
             if isinstance(p, FeedForward32Policy) and not isinstance(who, ClonedVecPartner):
                 raise nat.NativeError("VecLiarPartnerPool: a FeedForward32Policy is seated as ClonedVecPartner(policy)")
-            check_liar_member_policy(p, type(self).__name__)
+            self._check_member(p)
         self.learners = [m for m in members if isinstance(m, RaggedVecOnPolicyAgent)]
         for m in self.learners:
             if m.E != n_envs:
@@ -913,6 +960,9 @@ class VecLiarPartnerPool(VecLiarTraining):
         if record:
             self.start_recording(record)
         self._first_deal()
+
+    def _check_member(self, policy) -> None:
+        check_liar_member_policy(policy, type(self).__name__)
 
     def _contexts(self):
         return [self.env.ctx] + [p.ctx for p in map(self._policy_of, [self.ego] + self.members) if p is not None]
@@ -965,6 +1015,37 @@ class VecLiarPartnerPool(VecLiarTraining):
         for m in self.learners:
             if m.full():
                 m.learn_from_buffer()
+
+
+class TowerVecLiarPartnerPool(VecLiarPartnerPool):
+    """VecLiarPartnerPool whose ego and members may play `policy_kwargs=dict(net_arch=...)` towers: the ego a TowerVecOnPolicyAgent,
+    learners TowerRaggedVecOnPolicyAgent, frozen members TowerFrozenVecPartner, beside every member the plain class takes.  It differs
+    from the plain class in its member check, in the archs kept beside the member array, and in its native call
+    (`ph_liar_pool_step_arch`: tower tiles of the grouped forward run in pool_tower_kernel).  The walk is the plain class's: the
+    member classes' own get_action / update."""
+
+    def _check_member(self, policy) -> None:
+        check_liar_member_policy(policy, type(self).__name__, towers=True)
+
+    def _member_array(self, members):
+        arr = super()._member_array(members)
+        self._ego_arch = seat_arch(self.ego)
+        self._member_archs(members)
+        return arr
+
+    def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
+        self._bind()
+        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
+        nat.check(ctx.lib.ph_liar_pool_step_arch(ctx.handle, C.byref(self._desc), self._ego_arch, self._member_arch_arr,
+                                                 int(rb.pos if ego_pos < 0 else ego_pos), int(counter), int(deal_only)))
+
+
+def liar_pool_for(n_envs: int, ego, members, **kwargs) -> VecLiarPartnerPool:
+    """the pool class that runs `ego` and `members`: the plain one when nobody plays a tower"""
+    members = list(members)
+    pols = [VecLiarStep._policy_of(m) for m in [ego] + members]
+    towers = any(p is not None and is_tower(p) for p in pols)
+    return (TowerVecLiarPartnerPool if towers else VecLiarPartnerPool)(n_envs, ego, members, **kwargs)
 
 
 class LiarIterationGraph:

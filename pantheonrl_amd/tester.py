@@ -83,11 +83,12 @@ def vectorised_check(args) -> None:
         raise EnvException(f"--n-envs: LiarsDice-v0 takes probegostart only, not {sorted(set(args.env_config) - {'probegostart'})}")
 
 
-def load_member(policy_type: str, config: dict, location, device):
+def load_member(policy_type: str, config: dict, location, device, towers: bool = False):
     """a seat of the device-resident evaluation: the scripted player, a behavioural clone saved by bctrainer ("BC": reached
     through `python -m pantheonrl_amd.crossplay ... --agents BC:<path>`; `tester ... BC ... --n-envs` stays refused on this command
-    line), or a frozen loaded PPO policy"""
-    from .envs.vec import ClonedVecPartner, FrozenVecPartner, VecLiarDefaultPartner
+    line), or a frozen loaded PPO policy.  `towers`: a checkpoint trained with policy_kwargs net_arch is seated as
+    TowerFrozenVecPartner (the crossplay command line passes it; `tester ... --n-envs` keeps FrozenVecPartner's refusal)"""
+    from .envs.vec import ClonedVecPartner, FrozenVecPartner, VecLiarDefaultPartner, frozen_partner_for
     if policy_type == "DEFAULT":
         return VecLiarDefaultPartner()
     if policy_type == "BC":
@@ -95,7 +96,7 @@ def load_member(policy_type: str, config: dict, location, device):
         return ClonedVecPartner(reconstruct_policy(location, device))
     cfg = {k: v for k, v in config.items() if k != "verbose"}
     cfg.setdefault("device", device)
-    return FrozenVecPartner(gen_load(cfg, "PPO", location).policy)
+    return (frozen_partner_for if towers else FrozenVecPartner)(gen_load(cfg, "PPO", location).policy)
 
 
 def run_vectorised(args) -> List[float]:

@@ -279,14 +279,15 @@ def record_capacity(iterations: int, n_steps: int) -> int:
 
 
 def run_pool(args, plan):
-    """the pool's object graph: the ego, one member per partner argument, `VecLiarPartnerPool.rollout_and_learn` per iteration"""
+    """the pool's object graph: the ego, one member per partner argument, `VecLiarPartnerPool.rollout_and_learn` per iteration
+    (`liar_pool_for`: the tower pool where the ego, a learner or a FIXED PPO checkpoint has policy_kwargs net_arch)"""
     import random as _random
 
     import torch as th
 
-    from .envs.vec import (ClonedVecPartner, FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner, VecLiarPartnerPool,
-                           VecLiarsDice)
-    from .vec import VecOnPolicyAgent
+    from .envs.vec import (ClonedVecPartner, VecLiarDefaultPartner, VecLiarsDice, frozen_partner_for, liar_pool_for,
+                           ragged_agent_for)
+    from .vec import vec_agent_for
     E = int(args.n_envs)
     spaces = type("Spaces", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
                                      _is_dummy_space_env=True))()
@@ -303,14 +304,14 @@ def run_pool(args, plan):
         return model
 
     ego_model = learner(args.ego_config, 0)
-    ego = VecOnPolicyAgent(ego_model)
+    ego = vec_agent_for(ego_model)
     members, models = [], []
     for i, (kind, config) in enumerate(plan["members"]):
         if kind == "PPO":
             models.append(learner(config, i + 1))
-            members.append(RaggedVecOnPolicyAgent(models[-1]))
+            members.append(ragged_agent_for(models[-1]))
         elif kind == "FIXED":
-            seat = ClonedVecPartner if config["type"] == "BC" else FrozenVecPartner
+            seat = ClonedVecPartner if config["type"] == "BC" else frozen_partner_for
             members.append(seat(gen_load(config, config["type"], config["location"]).policy))
         else:
             members.append(VecLiarDefaultPartner())
@@ -320,7 +321,7 @@ def run_pool(args, plan):
     n_steps = ego_model.n_steps
     iterations = max(1, -(-args.total_timesteps // (E * n_steps)))
     record = record_capacity(iterations, n_steps) if args.record is not None else 0
-    env = VecLiarPartnerPool(E, ego, members, seed=dice_seed, resample=plan["resample"], record=record, **plan["env_config"])
+    env = liar_pool_for(E, ego, members, seed=dice_seed, resample=plan["resample"], record=record, **plan["env_config"])
     for _ in range(iterations):
         env.rollout_and_learn(n_steps)
     th.cuda.synchronize()

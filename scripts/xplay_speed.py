@@ -8,7 +8,9 @@ Median of 5 runs per variant, the variants alternating within a round; the host 
 `--ms 1,4` / `--no-host` / `--out FILE` narrow the sweep or keep a copy of the lines.
 `--clones` times instead the native evaluation of three populations of M = 4 -- four frozen 64-64 members (the yardstick), four
 behavioural clones (ClonedVecPartner: the shared 32-32 trunk), two of each -- and reports games/s and microseconds per vectorised
-step for each, with the spread over the runs."""
+step for each, with the spread over the runs.
+`--towers` does the same for `policy_kwargs net_arch` towers (TowerFrozenVecPartner, pool_tower_kernel): four frozen 64-64 members
+(the yardstick), four (128, 128) towers, two and two, four (64, 64, 64) towers, and the walk of the two-and-two population."""
 import argparse
 import contextlib
 import io
@@ -25,7 +27,8 @@ from pantheonrl_amd.common import StaticPolicyAgent  # noqa: E402
 from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay  # noqa: E402
 from pantheonrl_amd.envs.liar import LiarEnv  # noqa: E402
 from pantheonrl_amd.bc import FeedForward32Policy  # noqa: E402
-from pantheonrl_amd.envs.vec import ClonedVecPartner, FrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice  # noqa: E402
+from pantheonrl_amd.envs.vec import (ClonedVecPartner, FrozenVecPartner, TowerFrozenVecPartner, VecLiarDefaultPartner,  # noqa: E402
+                                     VecLiarsDice)
 from pantheonrl_amd.tester import run_test  # noqa: E402
 
 E, G, ROUNDS = 256, 40, 5
@@ -35,6 +38,7 @@ _p.add_argument("--no-host", action="store_true")
 _p.add_argument("--host-games", type=int, default=E * G)
 _p.add_argument("--out")
 _p.add_argument("--clones", action="store_true")
+_p.add_argument("--towers", action="store_true")
 _args = _p.parse_args()
 MS = [int(m) for m in _args.ms.split(",")]
 spaces = type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
@@ -66,6 +70,30 @@ def device_run(M, native, seed, members=None):
     return E * G / dt, res.steps
 
 
+def sweep(title, pops):
+    """M = 4: the populations `pops` (name -> (members factory, native)) alternating, the first one the yardstick"""
+    say(f"{title}, E = {E} tables, M = 4, all 16 pairs, {G} games per table = "
+        f"{E * G} games per run; median of {ROUNDS} runs, populations alternating, after one warm-up round")
+    rate, us = {n: [] for n in pops}, {n: [] for n in pops}
+    for rnd in range(ROUNDS + 1):
+        for name, (make, native) in pops.items():
+            r, n = device_run(4, native, 100 + rnd, make())
+            if rnd:
+                rate[name].append(r)
+                us[name].append(1e6 * E * G / r / n)
+    for name in pops:
+        say(f"{name}: {statistics.median(rate[name]):,.0f} games/s (min {min(rate[name]):,.0f}, max {max(rate[name]):,.0f}); "
+            f"{statistics.median(us[name]):.1f} us per vectorised step (min {min(us[name]):.1f}, max {max(us[name]):.1f})")
+    yard = next(iter(pops))
+    base = statistics.median(us[yard])
+    for name in list(pops)[1:]:
+        say(f"{name}: {statistics.median(us[name]) / base:.3f}x the yardstick's time per step "
+            f"(the yardstick's own runs span {min(us[yard]) / base:.3f}..{max(us[yard]) / base:.3f})")
+    if _args.out:
+        with open(_args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def clone_sweep():
     """M = 4, native: frozen x 4 | clone x 4 | frozen x 2 + clone x 2"""
     import numpy as np
@@ -74,33 +102,31 @@ def clone_sweep():
         pol = FeedForward32Policy(spaces.observation_space, spaces.action_space, seed=50 + k)
         pol.set_flat_params(0.4 * np.random.default_rng(50 + k).standard_normal(pol.layout.P).astype(np.float32))
         clones.append(pol)
-    pops = {"frozen x4 (yardstick)": lambda: [FrozenVecPartner(policies[k]) for k in range(4)],
-            "clone x4": lambda: [ClonedVecPartner(clones[k]) for k in range(4)],
-            "frozen x2 + clone x2": lambda: [FrozenVecPartner(policies[0]), ClonedVecPartner(clones[0]), FrozenVecPartner(policies[1]),
-                                             ClonedVecPartner(clones[1])]}
-    say(f"cross-play of Liar's Dice with behavioural clones, native step, E = {E} tables, M = 4, all 16 pairs, {G} games per table = "
-        f"{E * G} games per run; median of {ROUNDS} runs, populations alternating, after one warm-up round")
-    rate, us = {n: [] for n in pops}, {n: [] for n in pops}
-    for rnd in range(ROUNDS + 1):
-        for name, make in pops.items():
-            r, n = device_run(4, True, 100 + rnd, make())
-            if rnd:
-                rate[name].append(r)
-                us[name].append(1e6 * E * G / r / n)
-    for name in pops:
-        say(f"{name}: {statistics.median(rate[name]):,.0f} games/s (min {min(rate[name]):,.0f}, max {max(rate[name]):,.0f}); "
-            f"{statistics.median(us[name]):.1f} us per vectorised step (min {min(us[name]):.1f}, max {max(us[name]):.1f})")
-    base = statistics.median(us["frozen x4 (yardstick)"])
-    for name in list(pops)[1:]:
-        say(f"{name}: {statistics.median(us[name]) / base:.3f}x the yardstick's time per step "
-            f"(the yardstick's own runs span {min(us['frozen x4 (yardstick)']) / base:.3f}..{max(us['frozen x4 (yardstick)']) / base:.3f})")
-    if _args.out:
-        with open(_args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    pops = {"frozen x4 (yardstick)": (lambda: [FrozenVecPartner(policies[k]) for k in range(4)], True),
+            "clone x4": (lambda: [ClonedVecPartner(clones[k]) for k in range(4)], True),
+            "frozen x2 + clone x2": (lambda: [FrozenVecPartner(policies[0]), ClonedVecPartner(clones[0]), FrozenVecPartner(policies[1]),
+                                              ClonedVecPartner(clones[1])], True)}
+    sweep("cross-play of Liar's Dice with behavioural clones, native step", pops)
 
 
-if _args.clones:
-    clone_sweep()
+def tower_sweep():
+    """M = 4: frozen x 4 | tower (128, 128) x 4 | frozen x 2 + tower x 2 | tower (64, 64, 64) x 4 | the walk of two and two"""
+    def towers(widths, seed):
+        kw = dict(policy_kwargs=dict(net_arch=[dict(pi=list(widths), vf=list(widths))]))
+        return [PPO("MlpPolicy", spaces, n_steps=2, n_envs=4, batch_size=8, n_epochs=1, seed=seed + k, **kw).policy for k in range(4)]
+    wide, deep = towers((128, 128), 60), towers((64, 64, 64), 70)
+    mixed = lambda: [FrozenVecPartner(policies[0]), TowerFrozenVecPartner(wide[0]), FrozenVecPartner(policies[1]),  # noqa: E731
+                     TowerFrozenVecPartner(wide[1])]
+    pops = {"frozen x4 (yardstick)": (lambda: [FrozenVecPartner(policies[k]) for k in range(4)], True),
+            "tower (128, 128) x4": (lambda: [TowerFrozenVecPartner(wide[k]) for k in range(4)], True),
+            "frozen x2 + tower (128, 128) x2": (mixed, True),
+            "tower (64, 64, 64) x4": (lambda: [TowerFrozenVecPartner(deep[k]) for k in range(4)], True),
+            "walk of frozen x2 + tower (128, 128) x2": (mixed, False)}
+    sweep("cross-play of Liar's Dice with net_arch towers, native step", pops)
+
+
+if _args.clones or _args.towers:
+    clone_sweep() if _args.clones else tower_sweep()
     sys.exit(0)
 
 
