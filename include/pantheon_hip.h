@@ -682,6 +682,38 @@ int ph_liar_xplay_step(ph_ctx *ctx, const ph_liar_xplay *xp, unsigned long long 
 int ph_xplay_stats(ph_ctx *ctx, const float *returns, const int *lengths, const int *games, int n, int episodes_per_table,
                    int n_pairs, double *stats);
 
+/* ---- episode returns and lengths of device-resident training, per pool member (csrc/ph_episode.h; additions, PH_ABI_VERSION
+ * unchanged).  Stands for what the reference reads out of SB3's Monitor records: OnPolicyAgent logs rollout/ep_rew_mean and
+ * rollout/ep_len_mean from model.ep_info_buffer (pantheonrl/common/agents.py:132-158; SB3 Monitor / ep_info_buffer) -- here over
+ * ALL episodes that ended, not a deque of the last 100.  Nothing is added to a step: the statistics are ONE launch behind the
+ * rollout, over what it left in the ego's rectangular buffer.  An episode of table e ends at row t iff episode_starts[t + 1][e] is
+ * set (t + 1 < T) or last_dones[e] is (t = T - 1); row 0's own start flag is never read.  Its return is the f32 sum of
+ * rewards[.][e] over its rows, added in ascending row order with the carry first (bitwise a sequential NumPy f32 loop); its
+ * length is its number of rows (one row = one ego move, ph_liar_xplay's meaning).  Games span rollouts: (carry_return,
+ * carry_length) hold the game in progress between calls, and carry_valid[e] == 0 drops the game in progress when it ends (it began
+ * before the statistics were attached) and is set from then on.  With n_members > 1 the member at seat 1 is replayed: an episode
+ * that ends at row t is credited to member[e], then member[e] <- the pool's resample rule (PH_POOL_ROBIN / PH_POOL_RANDOM) under
+ * (pool_seed, deal counter counter0 + t, table e) -- the context's RNG epoch word, when one is attached, is the counter's high half
+ * exactly as in ph_liar_pool_step -- so after a scan member[] equals the pool's partnerid[].  stats (n_members, PH_EPISODE_NSTAT)
+ * f64 = count, sum of returns, sum of squared returns, sum of lengths per member, ACCUMULATED INTO (zeroed: one rollout's figures;
+ * kept: running totals), summed in a fixed order without floating-point atomics: two runs on the same inputs give the same bits.
+ * No host synchronisation and no allocation once its workspace exists: capturable after one call outside capture. */
+#define PH_EPISODE_NSTAT 4
+typedef struct ph_episode_scan {
+  const ph_rollout *rb;                      /* host; rewards and episode_starts rows 0 .. T-1 are read, nothing is written */
+  int T;                                     /* rows filled, 1 .. rb->T */
+  const float *last_dones;                   /* (E) the end flags of row T-1 */
+  float *carry_return;                       /* (E) in/out */
+  int *carry_length;                         /* (E) in/out */
+  unsigned char *carry_valid;                /* (E) in/out: 0 = drop the game in progress */
+  int n_members;                             /* 1 .. PH_MAX_POOL; 1 = no attribution (member may be NULL) */
+  int *member;                               /* (E) in/out: the member at seat 1 of the game in progress */
+  int resample;                              /* PH_POOL_ROBIN / PH_POOL_RANDOM */
+  unsigned long long pool_seed, counter0;    /* row t was step counter0 + t */
+  double *stats;                             /* (n_members, PH_EPISODE_NSTAT) device, 8-byte aligned, accumulated into */
+} ph_episode_scan;
+int ph_episode_stats(ph_ctx *ctx, const ph_episode_scan *scan);
+
 /* ---- a move log of the vectorised Liar's Dice step on the device (csrc/ph_record.h; additions, PH_ABI_VERSION unchanged): the rows
  * TurnBasedRecorder (wrappers.py:82-160) produces for each table, [obs 30 | action 2 | flag] f32 with flag 0 ego moved, 1 partner
  * moved, + 2 where that move ended the game.  A step logs up to three moves per table, in the table's own order: the ego's move,

@@ -264,6 +264,16 @@ class PhLiarRecord(C.Structure):
 
 RECORD_ROW = 33          # 30 observation components, 2 action components, the move flag
 
+EPISODE_NSTAT = 4        # count, sum of returns, sum of squared returns, sum of lengths
+
+
+class PhEpisodeScan(C.Structure):
+    """ph_episode_scan: one scan of a filled rollout buffer for the ego's episode returns and lengths, per pool member"""
+    _fields_ = [("rb", C.POINTER(PhRollout)), ("T", C.c_int), ("last_dones", C.c_void_p), ("carry_return", C.c_void_p),
+                ("carry_length", C.c_void_p), ("carry_valid", C.c_void_p), ("n_members", C.c_int), ("member", C.c_void_p),
+                ("resample", C.c_int), ("pool_seed", C.c_ulonglong), ("counter0", C.c_ulonglong), ("stats", C.c_void_p)]
+
+
 SIGNATURES = {
     "ph_abi_version": [],
     "ph_roundrobin_env_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, _i],
@@ -322,6 +332,7 @@ SIGNATURES = {
     "ph_liar_pool_step": [_vp, C.POINTER(PhLiarPool), _i, _ull, _i],
     "ph_liar_xplay_step": [_vp, C.POINTER(PhLiarXplay), _ull, _i],
     "ph_xplay_stats": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "ph_episode_stats": [_vp, C.POINTER(PhEpisodeScan)],
     "ph_liar_record_attach": [_vp, C.POINTER(PhLiarRecord)],
     "ph_liar_record_export": [_vp, C.POINTER(PhLiarRecord), _i, _vp, _vp, _vp, C.c_longlong],
     "ph_block_reset": [_vp, _i, _vp, _vp, _ull, _ull, _i],

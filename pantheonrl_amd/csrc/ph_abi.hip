@@ -20,6 +20,7 @@
 #include "ph_pool.h"
 #include "ph_xplay.h"
 #include "ph_record.h"
+#include "ph_episode.h"
 
 namespace ph {
 
@@ -191,6 +192,9 @@ struct ph_ctx {
   int* pool_tiles = nullptr;                // [pool_max_tiles + 1][3]; the last record's first word is the tile count
   size_t pool_tiles_cap = 0;
   long long* prof = nullptr;                // caller-owned debug stamp buffer
+  double* ep_partial = nullptr;             // ph_episode_stats: [workgroups][PH_MAX_POOL][PH_EPISODE_NSTAT] partial sums of one scan
+  size_t ep_partial_cap = 0;
+  unsigned int* ep_ticket = nullptr;        // [1] workgroups of the scan in flight that have stored their partials (zero between launches)
   // ModularAlgorithm workspace (ph_modular_*): activations and head gradients in minibatch order, the towers' slab maps
   struct ModWs {
     float* act = nullptr;        // one allocation carved into the arrays below
@@ -759,7 +763,7 @@ int ph_ctx_destroy(ph_ctx* ctx) {
     if (s.act_off) (void)hipFree(s.act_off);
   }
   void* ptrs[] = {ctx->wimage, ctx->mw.act, ctx->mw.maps, ctx->mw.kl_sum, ctx->mw.scratch, ctx->advpart, ctx->p2p_dev, ctx->slabs, ctx->statpart, ctx->grad, ctx->blocksq, ctx->advstats, ctx->adam_bias, ctx->perm_idx, ctx->perm_phys, ctx->ximg, ctx->rec_pi, ctx->rec_vf, ctx->rowrec, ctx->step_words, ctx->step_gen, ctx->scalars, ctx->stop_flag,
-                  ctx->adap_extra, ctx->adap_loss, ctx->am_buf, ctx->pool_dev, ctx->pool_order, ctx->pool_tiles};
+                  ctx->adap_extra, ctx->adap_loss, ctx->am_buf, ctx->pool_dev, ctx->pool_order, ctx->pool_tiles, ctx->ep_partial, ctx->ep_ticket};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (ctx->act_stage_host) (void)hipHostFree(ctx->act_stage_host);
@@ -2113,6 +2117,51 @@ int ph_xplay_stats(ph_ctx* ctx, const float* returns, const int* lengths, const 
   if (n_pairs < 1 || n_pairs > n) return fail("ph_xplay_stats: 1..n pairs (every pair needs a table)");
   if ((uintptr_t)stats % 16) return fail("ph_xplay_stats: stats must be 16-byte aligned");
   PH_HIP(ph::launch_xplay_stats(returns, lengths, games, n, episodes_per_table, n_pairs, stats, ctx->stream));
+  return 0;
+}
+
+// ---- episode returns and lengths of a filled rollout buffer, per pool member (ph_episode.h) ----
+int ph_episode_stats(ph_ctx* ctx, const ph_episode_scan* scan) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_episode_stats";
+  static_assert(ph::EPISODE_NSTAT == PH_EPISODE_NSTAT, "episode statistics per member");
+  if (!ctx) return fail("null ctx");
+  if (!scan) return fail_who(who, ": null description");
+  const ph_episode_scan& s = *scan;
+  if (check_rb(s.rb)) return 1;
+  if (s.T < 1 || s.T > s.rb->T) return fail_who(who, ": T must be 1..rb->T rows");
+  if (s.n_members < 1 || s.n_members > PH_MAX_POOL) return fail_who(who, ": n_members must be 1..PH_MAX_POOL");
+  if (s.n_members > 1 && !s.member) return fail_who(who, ": n_members > 1 needs the member array");
+  if (s.resample != PH_POOL_ROBIN && s.resample != PH_POOL_RANDOM) return fail_who(who, ": unknown resample rule");
+  if (!s.last_dones || !s.carry_return || !s.carry_length || !s.carry_valid || !s.stats) return fail_who(who, ": incomplete description");
+  if ((uintptr_t)s.stats % 8 || ((uintptr_t)s.carry_return | (uintptr_t)s.carry_length | (uintptr_t)s.member) % 4)
+    return fail_who(who, ": stats must be 8-byte aligned, carry_return / carry_length / member 4-byte aligned");
+  const int E = s.rb->E;
+  if (ensure(ctx, ctx->ep_partial, ctx->ep_partial_cap, (size_t)ph::episode_workgroups(E) * PH_MAX_POOL * PH_EPISODE_NSTAT)) return 1;
+  if (!ctx->ep_ticket) {
+    if (ctx->capturing) return fail_who(who, ": first use inside graph capture: call it once outside capture first");
+    PH_HIP(hipMalloc((void**)&ctx->ep_ticket, sizeof(unsigned int)));
+    PH_HIP(hipMemsetAsync(ctx->ep_ticket, 0, sizeof(unsigned int), ctx->stream));   // ordered in front of the first scan's launch
+  }
+  ph::EpisodeScan a;
+  a.rewards = s.rb->rewards;
+  a.starts = s.rb->episode_starts;
+  a.last_dones = s.last_dones;
+  a.T = s.T;
+  a.E = E;
+  a.carry_return = s.carry_return;
+  a.carry_length = s.carry_length;
+  a.carry_valid = s.carry_valid;
+  a.K = s.n_members;
+  a.member = s.n_members > 1 ? s.member : nullptr;
+  a.resample = s.resample;
+  a.pool_seed = s.pool_seed;
+  a.counter0 = s.counter0;
+  a.epoch = ctx->rng_epoch;
+  a.stats = s.stats;
+  a.partial = ctx->ep_partial;
+  a.ticket = ctx->ep_ticket;
+  PH_HIP(ph::launch_episode_scan(a, ctx->stream));
   return 0;
 }
 

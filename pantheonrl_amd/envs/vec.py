@@ -759,6 +759,7 @@ class VecLiarTraining(VecLiarStep):
         self._init_game(n_envs, pol.ctx, pol.device, seed, probegostart, native)
         self.alt_acted = th.zeros(self.E, dtype=th.uint8, device=self.dev)
         self._episodes_dev = th.zeros(1, dtype=th.int64, device=self.dev)
+        self.row0_counter = 1      # the step counter of row 0 of the ego's buffer: what EpisodeStats replays the pool's resamples from
 
     @property
     def episodes(self) -> int:
@@ -802,11 +803,17 @@ class VecLiarTraining(VecLiarStep):
         ego = self.ego
         self.steps_done += 1
         c = self.steps_done
-        if not self.native:
-            return self._walk(c).to(th.uint8)
         model, rb = ego.model, ego.model.rollout_buffer
+        row0 = rb.pos == 0 or ego.n_steps >= model.n_steps       # this step fills row 0 (behind the roll-over, where one is due)
+        if not self.native:
+            done = self._walk(c).to(th.uint8)
+            if row0:
+                self.row0_counter = c
+            return done
         if ego.n_steps >= model.n_steps:
             ego.learn_from_buffer()
+        if row0:
+            self.row0_counter = c                                # behind the roll-over: its scan replayed the rollout before
         self._native_call(c)
         rb.pos += 1
         rb.full = rb.pos == rb.buffer_size

@@ -227,6 +227,43 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 POOL_KINDS = ("PPO", "FIXED", "DEFAULT")
+LOG_INTERVAL = 10      # iterations between two episode-statistics records of the device-resident trainers
+
+
+def pop_log_interval(env_config: dict) -> int:
+    """`--env-config '{"log_interval": N}'` of the device-resident trainers: taken out of (a copy of) the env-config before the rest
+    reaches the game, as `resample` is.  Every N iterations, and after the last one, the episode statistics are read and logged;
+    0 = never read (no host synchronisation at all)."""
+    value = env_config.pop("log_interval", LOG_INTERVAL)
+    if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+        raise EnvException(f"--env-config log_interval must be a non-negative integer, not {value!r}")
+    return value
+
+
+def vectorised_plan(args):
+    """the self-play pairings' share of --env-config: (log_interval, what remains for the game); the arguments are left alone"""
+    env_config = dict(args.env_config)
+    return pop_log_interval(env_config), env_config
+
+
+class EpisodeLog:
+    """The device-resident trainers' log: an EpisodeStats on the ego (always attached: one launch per iteration) and a logger in
+    the ego's verbosity; `after(iteration, last)` reads and records every `log_interval` iterations and after the last one --
+    the only host synchronisation this adds."""
+
+    def __init__(self, args, ego_model, ego, env, log_interval: int):
+        import time
+
+        from .episode_stats import EpisodeStats
+        from .logger import configure_logger
+        self.stats = EpisodeStats(ego, env)
+        self.logger = configure_logger(ego_model.verbose, args.tensorboard_log, args.tensorboard_name or "OnPolicyAlgorithm")
+        self.ego, self.interval, self._clock, self._t0 = ego, int(log_interval), time.time, time.time()
+
+    def after(self, iteration: int, last: bool = False) -> None:
+        if self.interval and (last or iteration % self.interval == 0):
+            from .episode_stats import record_episode_stats
+            record_episode_stats(self.logger, self.stats, iteration, self.ego.num_timesteps, self._clock() - self._t0)
 
 
 def pool_plan(args):
@@ -246,6 +283,7 @@ def pool_plan(args):
         raise EnvException(f"the partner pool holds at most {nat.PH_MAX_POOL} members")
     env_config = dict(args.env_config)
     resample = env_config.pop("resample", "robin")
+    log_interval = pop_log_interval(env_config)
     if resample not in nat.POOL_RESAMPLE:
         raise EnvException(f"--env-config resample must be one of {sorted(nat.POOL_RESAMPLE)}")
     members = []
@@ -260,7 +298,7 @@ def pool_plan(args):
         elif kind == "DEFAULT" and config:
             raise EnvException("No config possible for this default agent")
         members.append((kind, config))
-    return dict(members=members, resample=resample, env_config=env_config)
+    return dict(members=members, resample=resample, env_config=env_config, log_interval=log_interval)
 
 
 def vectorised_record_check(args) -> None:
@@ -322,8 +360,10 @@ def run_pool(args, plan):
     iterations = max(1, -(-args.total_timesteps // (E * n_steps)))
     record = record_capacity(iterations, n_steps) if args.record is not None else 0
     env = liar_pool_for(E, ego, members, seed=dice_seed, resample=plan["resample"], record=record, **plan["env_config"])
-    for _ in range(iterations):
+    log = EpisodeLog(args, ego_model, ego, env, plan["log_interval"])
+    for it in range(1, iterations + 1):
         env.rollout_and_learn(n_steps)
+        log.after(it, it == iterations)
     th.cuda.synchronize()
     if record:
         from .envs.vec import write_recording
@@ -352,6 +392,7 @@ def run_vectorised(args):
     plan = pool_plan(args)
     if plan is not None:
         return run_pool(args, plan)
+    log_interval, env_config = vectorised_plan(args)
     if args.ego != "PPO":
         raise EnvException("--n-envs supports the PPO-vs-PPO self-play pairing")
     block_variant = {"BlockEnv-v0": 0, "BlockEnv-v1": 1}.get(args.env)
@@ -383,16 +424,20 @@ def run_vectorised(args):
     if args.env == "RPS-v0":
         alt = vec_agent_for(models[1])
         env = VecRPS(E, models[0].policy.ctx, models[0].device)
-        for _ in range(iterations):
+        log = EpisodeLog(args, models[0], ego, env, log_interval)
+        for it in range(1, iterations + 1):
             selfplay_iteration(env, ego, alt, n_steps)
+            log.after(it, it == iterations)
     elif block_variant is not None:
         alt = ragged_agent_for(models[1])
         import random as _random
         base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
         world_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xB10CB10CB10C) & 0x7FFFFFFFFFFFFFFF      # a Philox key of the worlds' own
-        env = VecBlockSelfPlay(block_variant, E, ego, alt, seed=world_seed, **args.env_config)
-        for _ in range(iterations):
+        env = VecBlockSelfPlay(block_variant, E, ego, alt, seed=world_seed, **env_config)
+        log = EpisodeLog(args, models[0], ego, env, log_interval)
+        for it in range(1, iterations + 1):
             env.rollout_and_learn(n_steps)
+            log.after(it, it == iterations)
     else:
         alt = ragged_agent_for(models[1])
         # the dice get a Philox key of their own: keyed by the bare seed they would BE the ego's sampling uniforms (same key,
@@ -401,16 +446,20 @@ def run_vectorised(args):
         base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
         dice_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xD1CE0D1CE0D1CE) & 0x7FFFFFFFFFFFFFFF
         record = record_capacity(iterations, n_steps) if args.record is not None else 0     # recording runs launch by launch
-        env = VecLiarSelfPlay(E, ego, alt, seed=dice_seed, record=record, **args.env_config)
+        env = VecLiarSelfPlay(E, ego, alt, seed=dice_seed, record=record, **env_config)
+        log = EpisodeLog(args, models[0], ego, env, log_interval)       # in front of the graph: its scan is captured with the update
         if iterations >= 4 and env.native:
             # two launch-by-launch iterations size the workspaces, the rest replay one hipGraph per iteration
             from .envs.vec import LiarIterationGraph
             graph = LiarIterationGraph(env, n_steps, warmup=2)
-            for _ in range(iterations - 2):
+            log.after(2)                              # the two warm-up iterations ran inside the constructor: one record for both
+            for it in range(3, iterations + 1):
                 graph.launch()
+                log.after(it, it == iterations)       # a read lands between two replays
         else:
-            for _ in range(iterations):
+            for it in range(1, iterations + 1):
                 env.rollout_and_learn(n_steps)
+                log.after(it, it == iterations)
     th.cuda.synchronize()
     print(f"vectorised self-play: {iterations} iterations x {E} envs x {n_steps} steps; "
           f"ego updates {ego.iteration}, partner updates {alt.iteration}")

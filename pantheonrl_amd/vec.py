@@ -44,6 +44,7 @@ class VecOnPolicyAgent:
         self._spec, self._rb = C.byref(pol.spec), C.byref(rb.c_struct())
         self.sync_stats = False
         self._pending = None   # reward tensor of the previous update(), folded into the next step's launch
+        self.episode_stats = None   # an EpisodeStats (episode_stats.py): its scan runs behind every full rollout, in compute_returns
 
     # -- which kernels serve the policy (overridden by the tower agent) ------------------------------------------------------
     def _require_kernels(self, pol) -> None:
@@ -134,6 +135,8 @@ class VecOnPolicyAgent:
         """late rewards + GAE with the cached V(o_{T-1}) (quirk D-1) <- agents.py:127-130"""
         rb = self.model.rollout_buffer
         self.flush_rewards()
+        if self.episode_stats is not None:
+            self.episode_stats.scan()     # one launch over the reward and episode-start planes the rollout left behind
         nat.check(self._lib.ph_gae(self._h, self._rb, self.values.data_ptr(), self._last_episode_starts.data_ptr(),
                                    rb.gamma, rb.gae_lambda, int(rb.gae_mode)))
 
