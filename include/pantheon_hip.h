@@ -43,7 +43,8 @@ extern "C" {
                               7: ph_spec.act may be PH_SPACE_BOX on ph_layout_of / ph_policy_forward / ph_ppo_minibatch_grad / ph_ppo_train
                                   (an error before; no signature or struct changed)
                                  still 7: + ph_block_reset / _step / _obs, ph_block_selfplay_step, ph_block_replay_host (additions only)
-                                 still 7: + ph_bc_train_path (addition only) */
+                                 still 7: + ph_bc_train_path (addition only)
+                                 still 7: + ph_adap_rows, ph_adap_context_draw, ph_adap_vec_host, ph_liar_selfplay_step_adap (additions only) */
 #define PH_HIDDEN 64     /* SB3 MlpPolicy default net_arch pi=[64,64], vf=[64,64] (modular/policies.py:112-114) */
 #define PH_MAX_COMP 256  /* max MultiDiscrete components per space */
 #define PH_MAX_LOGITS 64 /* max total policy logits L */
@@ -1167,6 +1168,55 @@ int ph_arch_scripted_rollout(ph_ctx *ctx, const ph_spec *spec, const ph_arch *ar
                              const float *obs_seq, const float *rew_seq, const float *done_seq, int n, int n_steps,
                              const float *episode_start0, unsigned long long seed, unsigned long long counter0, int *actions_i32,
                              float *values, float *log_probs, const ph_rollout *rb, int pos0, int gemm_mode);
+
+/* ---- ADAP seats in the device-resident games (csrc/ph_adap_vec.h; additions, PH_ABI_VERSION unchanged) -------------------------
+ * An AdapPolicy (adap/policies.py:21-146) is, for the engine, the MLP over a Box row  features(observation) ++ context  of F + C
+ * floats.  On the device-resident paths the row is built on the device and every table owns a context that is redrawn there when
+ * the seat's episode ends (AdapAgent.update, adap/agent.py:147-151; ADAP.collect_rollouts, adap_learn.py:457-461).
+ *  ph_adap_rows: rows[e] = one_hot(obs[e]) ++ contexts[e]  (env_obs_space PH_SPACE_DISCRETE: SB3's one-hot in component order, a
+ *      component outside [0, nvec_i) clamped)  or  obs[e] ++ contexts[e]  (PH_SPACE_BOX: F = n).  One launch, float accesses only
+ *      (F + C may be odd); rows of tables with active[e] == 0 are left untouched.
+ *  ph_adap_context_draw: contexts[e] <- sampler's draw from philox_uniform(seed ^ salt, counter + (rng epoch word << 32), e,
+ *      component) for every table with redraw[e] != 0 (NULL: every table).  One launch.  context_size <= 64; PH_CTX_NATURAL_NUMBERS
+ *      needs context_size == 1.
+ *  ph_adap_vec_host: the same two functions on the CPU over HOST arrays; no context, no device.  do_draw != 0: contexts are drawn
+ *      first (at `counter`, no epoch word); rows != NULL: rows are built from obs and contexts.  Misuse is reported through
+ *      ph_last_error. */
+int ph_adap_rows(ph_ctx *ctx, const ph_space *env_obs_space /* host */, int context_size, const float *obs /* (n,D) */,
+                 const float *contexts /* (n,C) */, const unsigned char *active /* (n) or NULL */, float *rows /* (n,F+C) */, int n);
+int ph_adap_context_draw(ph_ctx *ctx, int sampler, int context_size, unsigned long long seed, unsigned long long counter,
+                         const unsigned char *redraw /* (n) or NULL */, float *contexts /* (n,C) */, int n);
+int ph_adap_vec_host(const ph_space *env_obs_space /* or NULL when rows is NULL */, int context_size, int sampler, int do_draw,
+                     unsigned long long seed, unsigned long long counter, const unsigned char *redraw /* (n) or NULL */,
+                     float *contexts /* (n,C) */, const float *obs /* (n,D) or NULL */, const unsigned char *active /* (n) or NULL */,
+                     float *rows /* (n,F+C) or NULL */, int n);
+/*  ph_liar_selfplay_step_adap: ph_liar_selfplay_step with an ADAP learner in either seat.  A NULL seat stays on the kernels it has
+ *      today (its parameters are s->ego_params / s->alt_params under s->spec); (NULL, NULL) is bit for bit ph_liar_selfplay_step.
+ *      The launch sequence is that step's with two additions:
+ *        - each forward of an ADAP seat is preceded by its row build (ph_adap_rows' launch) from the observation plane the forward
+ *          would have read (s->obs_ego; for seat 1 the reply's obs_next under `running`, the opening's obs_alt under `alt_opens`)
+ *          and the seat's contexts; the forward then runs on `rows` under the seat's Box spec and records `rows` into its buffer;
+ *        - behind the pass that ends games (after_reply) one redraw launch per drawing seat gives a new context, drawn at `counter`,
+ *          to every table in which that seat just received `done`.  For the ego that is every table whose game ended (s->done).
+ *          For the partner it is the tables where _update_players pays it with done, i.e. where it moved in that game -- which in
+ *          Liar's Dice is again every ended game: sanitize_action turns a call on the opening move into a bid (liar.py:58-67), so a
+ *          game never ends before both seats have moved.  A deal-only call redraws nothing: the first contexts of a run are the
+ *          caller's, drawn at counter 0.
+ *      shared != 0 (--share-latent, adap/agent.py:72-73): the seat reads the OTHER seat's `contexts` of the same table and never
+ *      draws; the other seat must then be an ADAP seat of the same context_size.  Both seats draw at the step's `counter`; their
+ *      keys differ because their seeds differ.  Refused with nothing launched: a seat whose spec is not a Box of F + C components
+ *      over the Liar's Dice observation, a rollout buffer of another row length, a context_size the sampler does not take, a
+ *      missing plane, misaligned parameters. */
+typedef struct ph_adap_seat {
+  const ph_spec *spec;      /* host: Box(F + C) observations, the seat's action space */
+  int context_size, sampler;
+  float *contexts;          /* (n, C) */
+  float *rows;              /* (n, F + C) scratch: the rows of the seat's latest forward */
+  unsigned long long seed;  /* the learner's policy seed: the draws' key is seed ^ salt */
+  int shared;
+} ph_adap_seat;
+int ph_liar_selfplay_step_adap(ph_ctx *ctx, const ph_liar_selfplay *s, const ph_adap_seat *ego /* host or NULL */,
+                               const ph_adap_seat *alt /* host or NULL */, int ego_pos, unsigned long long counter, int deal_only);
 
 /* ---- owning handle: one agent = its rollout buffer, weights and Adam state on the device ----------------------------------
  *   The pointer-level entry points above take device memory owned by the caller (the Python host uses torch

@@ -207,6 +207,16 @@ class PhBlockSelfPlay(C.Structure):
 
 PH_BLOCK_STATE_WORDS = 12
 
+
+class PhAdapSeat(C.Structure):
+    """ph_adap_seat: an ADAP learner at a seat of the vectorised Liar's Dice step (rows built and contexts redrawn on the device)"""
+    _fields_ = [("spec", C.POINTER(PhSpec)), ("context_size", C.c_int), ("sampler", C.c_int), ("contexts", C.c_void_p),
+                ("rows", C.c_void_p), ("seed", C.c_ulonglong), ("shared", C.c_int)]
+
+
+ADAP_VEC_SALT = 0xC0A7E87D5A17ADA9      # csrc/ph_adap_vec.h: the per-table contexts' Philox key is the policy seed ^ this constant
+ADAP_VEC_MAX_CONTEXT = 64
+
 PH_MAX_POOL = 8
 PH_POOL_LEARNER, PH_POOL_FROZEN, PH_POOL_SCRIPTED, PH_POOL_CLONE = 0, 1, 2, 3
 POOL_RESAMPLE = {"robin": 0, "random": 1}
@@ -403,6 +413,10 @@ SIGNATURES = {
     "ph_block_selfplay_step_arch": [_vp, C.POINTER(PhBlockSelfPlay), C.POINTER(PhArch), C.POINTER(PhArch), _i, _ull],
     "ph_arch_scripted_rollout": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp,
                                  _vp, C.POINTER(PhRollout), _i, _i],
+    "ph_adap_rows": [_vp, C.POINTER(PhSpace), _i, _vp, _vp, _vp, _vp, _i],
+    "ph_adap_context_draw": [_vp, _i, _i, _ull, _ull, _vp, _vp, _i],
+    "ph_adap_vec_host": [C.POINTER(PhSpace), _i, _i, _i, _ull, _ull, _vp, _vp, _vp, _vp, _vp, _i],
+    "ph_liar_selfplay_step_adap": [_vp, C.POINTER(PhLiarSelfPlay), C.POINTER(PhAdapSeat), C.POINTER(PhAdapSeat), _i, _ull, _i],
     "ph_bc_layout_of": [C.POINTER(PhSpec), C.POINTER(PhBcLayout)],
     "ph_bc_train_path": [C.POINTER(PhSpec), C.POINTER(_i)],
     "ph_bc_forward": [_vp, C.POINTER(PhSpec), _vp, _vp, _i, _vp, _vp, _vp, _ull, _ull, _i, _vp, _vp, _vp, _vp, _vp],
@@ -581,6 +595,47 @@ def feistel_indices(n: int, perm_seed: int, epoch: int, start: int = 0, count: O
     out = (C.c_int * count)()
     check(load().ph_feistel_indices(int(n), int(perm_seed), int(epoch), int(start), int(count), out))
     return np.frombuffer(out, dtype=np.int32).copy()
+
+
+def env_space_of(observation_space) -> PhSpace:
+    """the ph_space of an ENVIRONMENT's observation space as an ADAP seat's row build reads it (Box, Discrete, MultiDiscrete)"""
+    kind = type(observation_space).__name__
+    if kind == "Box":
+        import numpy as np
+        return make_space(PH_SPACE_BOX, int(np.prod(observation_space.shape)))
+    if kind == "Discrete":
+        return make_space(PH_SPACE_DISCRETE, 1, [int(observation_space.n)])
+    if kind == "MultiDiscrete":
+        nvec = [int(v) for v in observation_space.nvec]
+        return make_space(PH_SPACE_DISCRETE, len(nvec), nvec)
+    raise NativeError(f"ADAP rows: unsupported observation space {observation_space!r}")
+
+
+def adap_vec_host(context_size: int, n: int, sampler: Optional[str] = None, seed: int = 0, counter: int = 0, redraw=None,
+                  contexts=None, env_space: Optional[PhSpace] = None, obs=None, active=None, rows=None):
+    """the ADAP seat's two rules on the CPU (ph_adap_vec_host: the text the device kernels run).  sampler given: the contexts of the
+    tables in `redraw` (None: all) are drawn at (seed, counter) into `contexts` (n, C) (zeros when None).  env_space and obs (n, D)
+    given: rows (n, F + C) = features ++ contexts for the tables in `active` (None: all), written into `rows` (zeros when None).
+    -> (contexts, rows or None)"""
+    import numpy as np
+    n, cs = int(n), int(context_size)
+    contexts = np.zeros((n, max(cs, 0)), np.float32) if contexts is None else np.ascontiguousarray(contexts, np.float32).copy()
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rd = None if redraw is None else np.ascontiguousarray(redraw, np.uint8)
+    ac = None if active is None else np.ascontiguousarray(active, np.uint8)
+    ob = None if obs is None else np.ascontiguousarray(obs, np.float32)
+    if ob is not None:
+        D = env_space.n
+        F = D if env_space.kind == PH_SPACE_BOX else sum(env_space.nvec[i] for i in range(D))
+        rows = np.zeros((n, F + cs), np.float32) if rows is None else np.ascontiguousarray(rows, np.float32).copy()
+        if ob.size != n * D:
+            raise NativeError(f"adap_vec_host: obs holds {ob.size} values, not n * D = {n * D}")
+    else:
+        rows = None
+    check(load().ph_adap_vec_host(None if env_space is None else C.byref(env_space), cs,
+                                  CONTEXT_SAMPLERS.get(sampler, 0), int(sampler is not None), int(seed), int(counter), p(rd),
+                                  p(contexts), p(ob), p(ac), p(rows), n))
+    return contexts, rows
 
 
 def block_replay_host(variant: int, state=None, tokens=None, alt_actions=None, n: Optional[int] = None, seed: Optional[int] = None,

@@ -229,6 +229,9 @@ class ADAP(PPO):
         return SAMPLERS[self.context_sampler](self.context_size, num, self.context_rng)
 
     def _extra_state(self) -> dict:                 # saved under "extra" by PPO.save
+        source = getattr(self, "_context_source", None)
+        if source is not None:                      # device-resident play (vec.py: AdapSeat): the tables' contexts as they stand
+            self.policy.set_context(source.current_contexts())
         ctx = self.policy.get_context()
         return {"context_rng": self.context_rng.bit_generator.state,
                 "context": None if ctx is None else np.asarray(ctx, np.float32).tolist()}

@@ -21,6 +21,7 @@
 #include "ph_xplay.h"
 #include "ph_record.h"
 #include "ph_episode.h"
+#include "ph_adap_vec.h"
 
 namespace ph {
 
@@ -1804,9 +1805,12 @@ struct LiarSeats {
   const int *ego_id, *alt_id;        // (n) member at seat 0 / seat 1, or null: member 0
   const unsigned char* playing;      // (n) the tables that take part, or null: all
 };
-template <class Book, class End, class Seat0, class Seat1>
+struct NoRedraw {   // ended(): what follows the pass that ends games, before seat 1 opens the new ones (ADAP seats redraw there)
+  int operator()() const { return 0; }
+};
+template <class Book, class End, class Seat0, class Seat1, class Ended = NoRedraw>
 int liar_step_run(ph_ctx* ctx, const ph::LiarGame& g, const Book& book, const End& end, unsigned long long counter, int deal_only,
-                  const unsigned long long (&k)[3], const LiarSeats& seats, Seat0 seat0, Seat1 seat1) {
+                  const unsigned long long (&k)[3], const LiarSeats& seats, Seat0 seat0, Seat1 seat1, Ended ended = Ended{}) {
   hipStream_t st = ctx->stream;
   const bool rec = ctx->recording;
   if (rec && ctx->rec.n != g.n)
@@ -1822,6 +1826,7 @@ int liar_step_run(ph_ctx* ctx, const ph::LiarGame& g, const Book& book, const En
   }
   // reply played and credited; finished tables are re-dealt; where seat 1 opens the new game it moves once
   PH_HIP(ph::launch_liar_pass(1, g, book, end, counter, ctx->rng_epoch, deal_only, st));
+  if (!deal_only && ended()) return 1;
   if (seat1(g.obs_alt, g.alt_opens, k[2])) return 1;
   if (rec) PH_HIP(ph::launch_record_opening(ctx->rec, rs, st));
   PH_HIP(ph::launch_liar_pass(2, g, book, end, counter, ctx->rng_epoch, deal_only, st));
@@ -1830,24 +1835,110 @@ int liar_step_run(ph_ctx* ctx, const ph::LiarGame& g, const Book& book, const En
 
 }  // extern "C++"
 
-// self-play: either seat on the 64-wide kernels (null arch) or on towers; the partner's forwards are ragged
+// ---- ADAP seats (ph_adap_vec.h) ----
+// the row shape of an environment space under a context of C floats; host validation only
+int adap_row_shape(const char* who, const ph_space* env, int C, ph::AdapRowShape* out) {
+  if (!env) return fail_who(who, ": null observation space");
+  if (C < 1 || C > ph::ADAP_VEC_MAX_CONTEXT)
+    return fail(std::string(who) + ": context_size must be 1.." + std::to_string(ph::ADAP_VEC_MAX_CONTEXT));
+  std::memset(out, 0, sizeof(*out));
+  out->C = C;
+  if (env->kind == PH_SPACE_BOX) {
+    if (env->n < 1) return fail_who(who, ": an empty Box observation");
+    out->box = 1;
+    out->D = out->F = env->n;
+    return 0;
+  }
+  if (env->kind != PH_SPACE_DISCRETE) return fail_who(who, ": the observation space must be a Box or of the Discrete family");
+  if (env->n < 1 || env->n > PH_MAX_COMP) return fail_who(who, ": the observation space holds 1..PH_MAX_COMP components");
+  out->D = env->n;
+  for (int i = 0; i < env->n; ++i) {
+    if (env->nvec[i] < 1) return fail_who(who, ": a component of the observation space has no category");
+    out->off[i + 1] = out->off[i] + env->nvec[i];
+  }
+  out->F = out->off[env->n];
+  return 0;
+}
+int check_adap_sampler(const char* who, int sampler, int C) {
+  if (sampler < PH_CTX_L2 || sampler > PH_CTX_NATURAL_NUMBERS) return fail_who(who, ": unknown context sampler");
+  if (sampler == PH_CTX_NATURAL_NUMBERS && C != 1)
+    return fail_who(who, ": PH_CTX_NATURAL_NUMBERS draws one integer: it needs context_size == 1 (adap/util.py:80-89)");
+  return 0;
+}
+
+// the Liar's Dice observation an ADAP seat's rows are built from: MultiDiscrete([7] * 6 + [7, 12] * 12), 30 components, 270 features
+void liar_env_space(ph_space* env) {
+  std::memset(env, 0, sizeof(*env));
+  env->kind = PH_SPACE_DISCRETE;
+  env->n = 6 + 2 * ph::LD_MAXMOVES;
+  for (int i = 0; i < env->n; ++i) env->nvec[i] = (i < 6 || (i - 6) % 2 == 0) ? ph::LD_SIDES + 1 : 2 * ph::LD_DICE;
+}
+
+// an ADAP seat of a Liar's Dice step is well formed: a Box(F + C) spec, a sampler that takes C, its planes, aligned parameters
+int check_adap_seat(const char* who, const char* seat, const ph_adap_seat* a, const ph_adap_seat* other, const float* params,
+                    ph::AdapRowShape* shape) {
+  const std::string w = std::string(who) + ": " + seat + " seat";
+  if (!a->spec) return fail(w + ": null spec");
+  ph_space env;
+  liar_env_space(&env);
+  if (adap_row_shape(w.c_str(), &env, a->context_size, shape)) return 1;
+  if (check_adap_sampler(w.c_str(), a->sampler, a->context_size)) return 1;
+  if (a->spec->obs.kind != PH_SPACE_BOX || a->spec->obs.n != shape->F + shape->C)
+    return fail(w + ": the spec's observation must be a Box of F + C = " + std::to_string(shape->F + shape->C) + " components");
+  if (!a->rows) return fail(w + ": null rows");
+  if (a->shared) {
+    if (!other || other->shared || !other->contexts) return fail(w + ": shared != 0 needs an ADAP seat that draws on the other side");
+    if (other->context_size != a->context_size) return fail(w + ": shared != 0 needs the other seat's context_size");
+  } else if (!a->contexts) {
+    return fail(w + ": null contexts");
+  }
+  if (((uintptr_t)a->rows | (uintptr_t)a->contexts) % 4 || (uintptr_t)params % 16)
+    return fail(w + ": rows/contexts must be 4-byte aligned, params 16-byte aligned");
+  return 0;
+}
+
+// self-play: either seat on the 64-wide kernels (null arch) or on towers, or an ADAP learner (its rows built in front of its forward,
+// its contexts redrawn behind the pass that ends games); the partner's forwards are ragged
 int liar_selfplay_step_run(const char* who, ph_ctx* ctx, const ph_liar_selfplay* sp, const ph_arch* ego_arch, const ph_arch* alt_arch,
-                           int ego_pos, unsigned long long counter, int deal_only) {
+                           int ego_pos, unsigned long long counter, int deal_only, const ph_adap_seat* ego_adap = nullptr,
+                           const ph_adap_seat* alt_adap = nullptr) {
   if (check_liar_selfplay(who, ctx, sp)) return 1;
   const ph_liar_selfplay& s = *sp;
   if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail_who(who, ": ego_pos out of range (buffer full?)");
+  ph::AdapRowShape ego_shape, alt_shape;
+  if (ego_adap && check_adap_seat(who, "ego", ego_adap, alt_adap, s.ego_params, &ego_shape)) return 1;
+  if (alt_adap && check_adap_seat(who, "partner", alt_adap, ego_adap, s.alt_params, &alt_shape)) return 1;
+  const float* ego_ctx = ego_adap ? (ego_adap->shared ? alt_adap->contexts : ego_adap->contexts) : nullptr;
+  const float* alt_ctx = alt_adap ? (alt_adap->shared ? ego_adap->contexts : alt_adap->contexts) : nullptr;
+  hipStream_t st = ctx->stream;
   const ph::LearnerBook book{ph::SeatFields{s.n, s.alt_pos, s.alt_boundary, s.alt_term, s.alt_open, s.alt_acted, s.can, s.es_alt},
                              s.alt_rb->rewards, s.alt_rb->T};
   return liar_step_run(
       ctx, ph::liar_game_of(s), book, liar_train_end(s, ego_pos, deal_only), counter, deal_only, {counter, 2 * counter, 2 * counter + 1},
       LiarSeats{nullptr, nullptr, nullptr},
       [&](unsigned long long c) {
-        return seat_forward(ctx, s.spec, ego_arch, s.ego_params, s.obs_ego, s.n, s.ego_seed, c, s.ego_actions, s.ego_values,
-                            s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start);
+        const float* obs = s.obs_ego;
+        if (ego_adap) {
+          PH_HIP(ph::launch_adap_rows(ego_shape, s.obs_ego, ego_ctx, nullptr, ego_adap->rows, s.n, st));
+          obs = ego_adap->rows;
+        }
+        return seat_forward(ctx, ego_adap ? ego_adap->spec : s.spec, ego_arch, s.ego_params, obs, s.n, s.ego_seed, c, s.ego_actions,
+                            s.ego_values, s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start);
       },
-      [&](const float* obs, const unsigned char*, unsigned long long c) {
-        return seat_forward_ragged(ctx, s.spec, alt_arch, s.alt_params, obs, s.alt_seed, c, s.alt_actions, s.alt_values, s.alt_log_probs,
-                                   s.alt_rb, s.alt_pos, s.can, s.es_alt);
+      [&](const float* obs, const unsigned char* active, unsigned long long c) {
+        if (alt_adap) {
+          PH_HIP(ph::launch_adap_rows(alt_shape, obs, alt_ctx, active, alt_adap->rows, s.n, st));
+          obs = alt_adap->rows;
+        }
+        return seat_forward_ragged(ctx, alt_adap ? alt_adap->spec : s.spec, alt_arch, s.alt_params, obs, s.alt_seed, c, s.alt_actions,
+                                   s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt);
+      },
+      [&]() {   // both seats were paid `done` in the tables whose game just ended (pantheon_hip.h: a game never ends on its opening move)
+        for (const ph_adap_seat* a : {ego_adap, alt_adap})
+          if (a && !a->shared)
+            PH_HIP(ph::launch_adap_context_draw(a->sampler, a->context_size, a->seed, counter, ctx->rng_epoch, s.done, a->contexts, s.n,
+                                                st));
+        return 0;
       });
 }
 }  // namespace
@@ -1861,6 +1952,68 @@ int ph_liar_selfplay_step_arch(ph_ctx* ctx, const ph_liar_selfplay* sp, const ph
                                unsigned long long counter, int deal_only) {
   DevGuard dev_guard(ctx);
   return liar_selfplay_step_run("ph_liar_selfplay_step_arch", ctx, sp, ego_arch, alt_arch, ego_pos, counter, deal_only);
+}
+
+int ph_liar_selfplay_step_adap(ph_ctx* ctx, const ph_liar_selfplay* sp, const ph_adap_seat* ego, const ph_adap_seat* alt, int ego_pos,
+                               unsigned long long counter, int deal_only) {
+  DevGuard dev_guard(ctx);
+  return liar_selfplay_step_run("ph_liar_selfplay_step_adap", ctx, sp, nullptr, nullptr, ego_pos, counter, deal_only, ego, alt);
+}
+
+int ph_adap_rows(ph_ctx* ctx, const ph_space* env_obs_space, int context_size, const float* obs, const float* contexts,
+                 const unsigned char* active, float* rows, int n) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_adap_rows";
+  if (!ctx) return fail("null ctx");
+  ph::AdapRowShape shape;
+  if (adap_row_shape(who, env_obs_space, context_size, &shape)) return 1;
+  if (!obs || !contexts || !rows) return fail_who(who, ": null argument");
+  if (n <= 0 || (long long)n * (shape.F + shape.C) >= (1ll << 31)) return fail_who(who, ": n must be positive and n * (F + C) fit in int32");
+  if (((uintptr_t)obs | (uintptr_t)contexts | (uintptr_t)rows) % 4) return fail_who(who, ": obs/contexts/rows must be 4-byte aligned");
+  PH_HIP(ph::launch_adap_rows(shape, obs, contexts, active, rows, n, ctx->stream));
+  return 0;
+}
+
+int ph_adap_context_draw(ph_ctx* ctx, int sampler, int context_size, unsigned long long seed, unsigned long long counter,
+                         const unsigned char* redraw, float* contexts, int n) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_adap_context_draw";
+  if (!ctx) return fail("null ctx");
+  if (context_size < 1 || context_size > ph::ADAP_VEC_MAX_CONTEXT)
+    return fail(std::string(who) + ": context_size must be 1.." + std::to_string(ph::ADAP_VEC_MAX_CONTEXT));
+  if (check_adap_sampler(who, sampler, context_size)) return 1;
+  if (!contexts || (uintptr_t)contexts % 4) return fail_who(who, ": contexts must be a 4-byte aligned array");
+  if (n <= 0) return fail_who(who, ": n must be positive");
+  PH_HIP(ph::launch_adap_context_draw(sampler, context_size, seed, counter, ctx->rng_epoch, redraw, contexts, n, ctx->stream));
+  return 0;
+}
+
+int ph_adap_vec_host(const ph_space* env_obs_space, int context_size, int sampler, int do_draw, unsigned long long seed,
+                     unsigned long long counter, const unsigned char* redraw, float* contexts, const float* obs,
+                     const unsigned char* active, float* rows, int n) {
+  const char* who = "ph_adap_vec_host";
+  if (n <= 0 || !contexts) return fail_who(who, ": n must be positive and contexts given");
+  if (context_size < 1 || context_size > ph::ADAP_VEC_MAX_CONTEXT)
+    return fail(std::string(who) + ": context_size must be 1.." + std::to_string(ph::ADAP_VEC_MAX_CONTEXT));
+  if (do_draw) {
+    if (check_adap_sampler(who, sampler, context_size)) return 1;
+    for (int e = 0; e < n; ++e)
+      if (!redraw || redraw[e])
+        ph::adap_draw_context(sampler, context_size, seed, ph::adap_vec_counter(counter, nullptr), (uint32_t)e,
+                              contexts + (size_t)e * context_size);
+  }
+  if (!rows) return 0;
+  ph::AdapRowShape shape;
+  if (adap_row_shape(who, env_obs_space, context_size, &shape)) return 1;
+  if (!obs) return fail_who(who, ": rows need obs");
+  const int W = shape.F + shape.C;
+  for (int e = 0; e < n; ++e) {
+    if (active && !active[e]) continue;
+    for (int f = 0; f < W; ++f)
+      rows[(size_t)e * W + f] =
+          ph::adap_row_value(shape, shape.off, obs + (size_t)e * shape.D, contexts + (size_t)e * context_size, f);
+  }
+  return 0;
 }
 
 // ---- Liar's Dice against a pool of partners (ph_pool.h) ----

@@ -21,7 +21,7 @@ from .. import _native as nat
 from ..spaces import Discrete, MultiDiscrete
 from ..bc import FeedForward32Policy
 from ..ppo import require_mlp_kernels
-from ..vec import VecOnPolicyAgent, is_tower, require_tower_lds
+from ..vec import AdapSeat, VecOnPolicyAgent, is_adap, is_tower, require_tower_lds
 
 
 class VecRPS:
@@ -230,9 +230,33 @@ class TowerRaggedVecOnPolicyAgent(RaggedVecOnPolicyAgent):
         return self._lib.ph_arch_forward_ragged(self._h, self._spec, C.byref(pol.arch), *args, int(pol.gemm_mode))
 
 
-def ragged_agent_for(model) -> RaggedVecOnPolicyAgent:
+class AdapRaggedVecOnPolicyAgent(AdapSeat, RaggedVecOnPolicyAgent):
+    """RaggedVecOnPolicyAgent whose model is an ADAP learner over an AdapPolicy (vec.py: AdapSeat): get_action builds the rows of
+    the tables asked to move from the game's raw observations and records them; update gives a fresh context to the tables in
+    which the agent is paid `done` (the tables of `mask` whose game ended), unless a latent syncer's contexts are read."""
+
+    def __init__(self, model, latent_syncer=None):
+        super().__init__(model)
+        self._init_adap(latent_syncer)
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor) -> th.Tensor:
+        return super().get_action(self.build_rows(obs, rec_mask), rec_mask)
+
+    def update(self, reward: th.Tensor, done: th.Tensor, mask: th.Tensor) -> None:
+        super().update(reward, done, mask)
+        self._paid_done(mask.bool() & done.bool())
+
+
+def ragged_agent_for(model, latent_syncer=None) -> RaggedVecOnPolicyAgent:
     """the ragged vectorised agent class that runs `model`'s policy"""
+    if is_adap(model.policy):
+        return AdapRaggedVecOnPolicyAgent(model, latent_syncer)
     return (TowerRaggedVecOnPolicyAgent if is_tower(model.policy) else RaggedVecOnPolicyAgent)(model)
+
+
+def adap_seat(agent):
+    """the ph_adap_seat of a seat's agent for the `_adap` step entry point: a pointer, or None (the seat stays on its kernels)"""
+    return C.pointer(agent.seat_struct()) if isinstance(agent, AdapSeat) else None
 
 
 def seat_arch(agent):
@@ -846,6 +870,16 @@ class VecLiarSelfPlay(VecLiarTraining):
         self.towers = any(a is not None for a in self._archs)
         if self.towers:
             self.persistent = False                           # ph_liar_selfplay_rollout is built around the 64-wide blocks
+        # an ADAP learner in either seat: the `_adap` step, launch by launch (rows built and contexts redrawn inside it)
+        self._adap = (adap_seat(ego), adap_seat(alt))
+        self.adap = any(a is not None for a in self._adap)
+        if self.adap:
+            self.persistent = False
+            if self.towers:
+                raise nat.NativeError("VecLiarSelfPlay: an ADAP seat plays against PPO's 64-64 MlpPolicy or another ADAP learner, "
+                                      "not against a net_arch tower")
+            if record:
+                raise nat.NativeError("VecLiarSelfPlay: the move log is not kept with an ADAP seat (record=0)")
         if record:
             self.start_recording(record)                      # in front of the first deal: its openings are the logs' first rows
         self._first_deal()
@@ -870,12 +904,18 @@ class VecLiarSelfPlay(VecLiarTraining):
         s.alt_values, s.alt_log_probs, s.alt_pos = alt.values.data_ptr(), alt.log_probs.data_ptr(), alt.pos.data_ptr()
         s.alt_boundary, s.alt_term, s.alt_open = alt.boundary.data_ptr(), alt.term.data_ptr(), alt.open.data_ptr()
         s.zeros8, s.ones8 = self.zeros8.data_ptr(), self.ones8.data_ptr()
+        if self._adap[0] is not None and self._adap[1] is None:
+            s.spec = C.pointer(pa.spec)                       # the description's spec is the one of the seat(s) without a spec of their own
         self._desc = s
 
     def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
         self._bind()
         ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
         pos = int(rb.pos if ego_pos < 0 else ego_pos)
+        if self.adap:
+            nat.check(ctx.lib.ph_liar_selfplay_step_adap(ctx.handle, C.byref(self._desc), self._adap[0], self._adap[1], pos,
+                                                         int(counter), int(deal_only)))
+            return
         if self.towers:
             nat.check(ctx.lib.ph_liar_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
                                                          int(counter), int(deal_only)))
@@ -888,12 +928,21 @@ class VecLiarSelfPlay(VecLiarTraining):
         if self.towers:
             raise nat.NativeError("VecLiarSelfPlay.rollout_persistent: a net_arch tower policy does not run on the fused MLP kernels "
                                   "of the persistent rollout; use step()")
+        if self.adap:
+            raise nat.NativeError("VecLiarSelfPlay.rollout_persistent: an ADAP seat's rows and contexts are not part of the "
+                                  "persistent rollout; use step()")
         self._bind()
         ctx = self.env.ctx
         nat.check(ctx.lib.ph_liar_selfplay_rollout(ctx.handle, C.byref(self._desc), int(ego_pos), int(n_steps),
                                                    int(first_counter)))
 
     # -- the walk's hooks -------------------------------------------------------------------------------------------------------------
+    def _walk(self, c: int) -> th.Tensor:
+        for agent in (self.ego, self.alt):
+            if isinstance(agent, AdapSeat):
+                agent.draw_counter = c                        # an ADAP seat redraws at the step's counter, as the dice are dealt
+        return super()._walk(c)
+
     def _seat_act(self, seat: int, obs: th.Tensor, mask, counter: int) -> th.Tensor:
         if seat == 0:
             return self._ego_act(counter)
@@ -1069,6 +1118,9 @@ class LiarIterationGraph:
 
     def __init__(self, sp: VecLiarSelfPlay, n_steps: int, capture: bool = True, warmup: int = 2):
         assert sp.native, "the graph replays the engine-side step"
+        if getattr(sp, "adap", False):
+            raise nat.NativeError("LiarIterationGraph: an iteration with an ADAP seat is not captured (ADAP.train and the seat's "
+                                  "contexts under an RNG epoch word have no replay story yet); use rollout_and_learn")
         self.sp, self.T = sp, int(n_steps)
         ego, alt = sp.ego, sp.alt
         assert self.T == ego.model.n_steps and ego.model.rollout_buffer.pos == 0

@@ -301,6 +301,33 @@ def pool_plan(args):
     return dict(members=members, resample=resample, env_config=env_config, log_interval=log_interval)
 
 
+ADAP_VEC_ENVS = ("RPS-v0", "LiarsDice-v0")
+
+
+def adap_plan(args):
+    """`<env> {PPO,ADAP} {PPO,ADAP} --n-envs E` with at least one ADAP seat: who learns at which seat, whether the partner reads the
+    ego's contexts (--share-latent; latent_check has made sure both are ADAP), and --env-config's share -- checked before a device
+    is touched.  None when no seat is ADAP, or with a partner list (the pool's plan refuses an ADAP member in its own words)."""
+    kinds = [args.ego] + list(args.alt)
+    if not any(kind in ADAP_TYPES for kind in kinds):
+        return None
+    if "ADAP_MULT" in kinds:
+        raise EnvException("ADAP_MULT (AdapPolicyMult) has no device-resident form: with --n-envs an ADAP seat is ADAP")
+    if len(args.alt) != 1:
+        return None
+    if args.ego not in ("PPO", "ADAP") or args.alt[0] not in ("PPO", "ADAP"):
+        raise EnvException("--n-envs takes ego and partner each from PPO and ADAP when a seat is ADAP, not "
+                           f"{args.ego} against {args.alt[0]}")
+    if args.env not in ADAP_VEC_ENVS:
+        raise EnvException(f"ADAP with --n-envs exists for {' and '.join(ADAP_VEC_ENVS)}, not for the block worlds or {args.env}")
+    if args.record is not None:
+        raise EnvException("--n-envs cannot be combined with --record when a seat is ADAP: the device-resident recorder logs PPO "
+                           "seats")
+    log_interval, env_config = vectorised_plan(args)
+    return dict(ego=args.ego, alt=args.alt[0], share_latent=bool(args.share_latent), log_interval=log_interval,
+                env_config=env_config)
+
+
 def vectorised_record_check(args) -> None:
     """what `--n-envs` cannot combine with, by name, before a device is touched.  `--record` is the device-resident move log of
     the Liar's Dice step (envs/vec.py: VecLiarStep.start_recording); frame stacking changes every kernel's shape class"""
@@ -389,11 +416,12 @@ def run_vectorised(args):
     from .envs.vec import VecLiarsDice, VecLiarSelfPlay, VecRPS, ragged_agent_for, selfplay_iteration
     from .vec import vec_agent_for
     vectorised_record_check(args)
-    plan = pool_plan(args)
+    aplan = adap_plan(args)                    # an ADAP learner in either seat of the single-partner pairing
+    plan = pool_plan(args) if aplan is None else None
     if plan is not None:
         return run_pool(args, plan)
     log_interval, env_config = vectorised_plan(args)
-    if args.ego != "PPO":
+    if args.ego != "PPO" and aplan is None:
         raise EnvException("--n-envs supports the PPO-vs-PPO self-play pairing")
     block_variant = {"BlockEnv-v0": 0, "BlockEnv-v1": 1}.get(args.env)
     game = {"RPS-v0": VecRPS, "LiarsDice-v0": VecLiarsDice}.get(args.env)
@@ -408,6 +436,7 @@ def run_vectorised(args):
                                          _is_dummy_space_env=True))()
         seat_spaces = (spaces, spaces)
     models = []
+    kinds = (aplan["ego"], aplan["alt"]) if aplan is not None else ("PPO", "PPO")
     for offset, config in enumerate((dict(args.ego_config), dict(args.alt_config[0]))):
         spaces = seat_spaces[offset]
         config.setdefault("n_steps", 128)
@@ -415,14 +444,15 @@ def run_vectorised(args):
         config.update(env=spaces, device=args.device, n_envs=E)
         if args.seed is not None:
             config["seed"] = args.seed + offset
-        model = PPO(policy="MlpPolicy", **config)
+        model = ADAP(policy=AdapPolicy, **config) if kinds[offset] == "ADAP" else PPO(policy="MlpPolicy", **config)
         model.device_permutations = True
         models.append(model)
     ego = vec_agent_for(models[0])
+    syncer = ego if aplan is not None and aplan["share_latent"] else None     # --share-latent: the partner reads the ego's contexts
     n_steps = models[0].n_steps
     iterations = max(1, -(-args.total_timesteps // (E * n_steps)))
     if args.env == "RPS-v0":
-        alt = vec_agent_for(models[1])
+        alt = vec_agent_for(models[1], latent_syncer=syncer)
         env = VecRPS(E, models[0].policy.ctx, models[0].device)
         log = EpisodeLog(args, models[0], ego, env, log_interval)
         for it in range(1, iterations + 1):
@@ -439,7 +469,7 @@ def run_vectorised(args):
             env.rollout_and_learn(n_steps)
             log.after(it, it == iterations)
     else:
-        alt = ragged_agent_for(models[1])
+        alt = ragged_agent_for(models[1], latent_syncer=syncer)
         # the dice get a Philox key of their own: keyed by the bare seed they would BE the ego's sampling uniforms (same key,
         # same step counter, same row); without --seed every run deals a fresh sequence
         import random as _random
@@ -448,7 +478,7 @@ def run_vectorised(args):
         record = record_capacity(iterations, n_steps) if args.record is not None else 0     # recording runs launch by launch
         env = VecLiarSelfPlay(E, ego, alt, seed=dice_seed, record=record, **env_config)
         log = EpisodeLog(args, models[0], ego, env, log_interval)       # in front of the graph: its scan is captured with the update
-        if iterations >= 4 and env.native:
+        if iterations >= 4 and env.native and not env.adap:
             # two launch-by-launch iterations size the workspaces, the rest replay one hipGraph per iteration
             from .envs.vec import LiarIterationGraph
             graph = LiarIterationGraph(env, n_steps, warmup=2)

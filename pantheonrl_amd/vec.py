@@ -188,8 +188,94 @@ class TowerVecOnPolicyAgent(VecOnPolicyAgent):
         return self._lib.ph_arch_scripted_rollout(self._h, self._spec, self._arch, *args)
 
 
-def vec_agent_for(model: PPO) -> VecOnPolicyAgent:
+def is_adap(pol) -> bool:
+    """an AdapPolicy with the concatenated context (AdapPolicyMult is another network: it has no device-resident form)"""
+    from .adap import AdapPolicy, AdapPolicyMult
+    return isinstance(pol, AdapPolicy) and not isinstance(pol, AdapPolicyMult)
+
+
+class AdapSeat:
+    """What an ADAP learner adds to a vectorised agent (csrc/ph_adap_vec.h): one context per table on the device, the rows
+    features(observation) ++ context built there in front of every forward, and a fresh context for the tables in which the agent
+    is paid `done` (AdapAgent.update, adap/agent.py:147-151).  `latent_syncer` (another AdapSeat: --share-latent, agent.py:72-73)
+    makes the agent read that agent's contexts instead and never draw.  The draws are keyed by the policy's seed and counted by
+    `draw_counter`, which the game's driver sets to its step counter; left None, the counter of the policy's latest forward is used
+    (one forward per step: the rectangular agent of a simultaneous game).  The first contexts are drawn at counter 0."""
+
+    def _init_adap(self, latent_syncer=None) -> None:
+        model, pol = self.model, self.model.policy
+        if not is_adap(pol):
+            raise nat.NativeError(f"{type(self).__name__}: {type(pol).__name__} is not an AdapPolicy")
+        if latent_syncer is not None and latent_syncer.context_size != pol.context_size:
+            raise nat.NativeError(f"{type(self).__name__}: the latent syncer's contexts have another size")
+        dev = pol.device
+        self.context_size, self.sampler = int(pol.context_size), nat.CONTEXT_SAMPLERS[model.context_sampler]
+        self.env_space = nat.env_space_of(pol.observation_space)
+        self.contexts = th.zeros((self.E, self.context_size), dtype=th.float32, device=dev)
+        self.rows = th.zeros((self.E, pol.layout.D), dtype=th.float32, device=dev)
+        self.latent_syncer, self.draw_counter = latent_syncer, None
+        model._context_source = self                    # ADAP.save writes the contexts of the tables as they stand
+        if latent_syncer is None:
+            self.redraw(None, 0)
+
+    def current_contexts(self) -> th.Tensor:
+        return self.contexts if self.latent_syncer is None else self.latent_syncer.contexts
+
+    def seat_struct(self) -> "nat.PhAdapSeat":
+        """this seat for ph_liar_selfplay_step_adap (the policy keeps the spec alive)"""
+        pol, s = self.model.policy, nat.PhAdapSeat()
+        s.spec, s.context_size, s.sampler = C.pointer(pol.spec), self.context_size, self.sampler
+        s.contexts, s.rows, s.seed, s.shared = self.contexts.data_ptr(), self.rows.data_ptr(), pol._seed, int(self.latent_syncer is not None)
+        return s
+
+    def build_rows(self, obs: th.Tensor, active: Optional[th.Tensor] = None) -> th.Tensor:
+        pol = self.model.policy
+        pol._bind()
+        nat.check(self._lib.ph_adap_rows(self._h, C.byref(self.env_space), self.context_size, obs.data_ptr(),
+                                         self.current_contexts().data_ptr(), nat.ptr(active), self.rows.data_ptr(), self.E))
+        return self.rows
+
+    def redraw(self, flags: Optional[th.Tensor], counter: int) -> None:
+        """a fresh context, drawn at `counter`, for the tables flagged in `flags` (uint8; None: every table)"""
+        pol = self.model.policy
+        pol._bind()
+        nat.check(self._lib.ph_adap_context_draw(self._h, self.sampler, self.context_size, pol._seed, int(counter), nat.ptr(flags),
+                                                 self.contexts.data_ptr(), self.E))
+
+    def _paid_done(self, flags: th.Tensor) -> None:
+        if self.latent_syncer is None:
+            counter = self.model.policy._counter if self.draw_counter is None else self.draw_counter
+            self.redraw(flags.to(th.uint8).contiguous(), counter)
+
+
+class AdapVecOnPolicyAgent(AdapSeat, VecOnPolicyAgent):
+    """VecOnPolicyAgent whose model is an ADAP learner over an AdapPolicy: get_action takes the game's raw observations, builds
+    the rows on the device and runs the ordinary forward on them (the buffer stores the rows); update redraws the contexts of the
+    tables whose episode ended; learn_from_buffer ends in ADAP.train (ph_adap_train) on the device-built buffer."""
+
+    def __init__(self, model: PPO, latent_syncer: Optional[AdapSeat] = None):
+        super().__init__(model)
+        self._init_adap(latent_syncer)
+
+    def get_action(self, obs: th.Tensor, record: bool = True, action_mask: Optional[th.Tensor] = None,
+                   episode_start: Optional[th.Tensor] = None) -> th.Tensor:
+        if record and self.n_steps >= self.model.n_steps:
+            self.learn_from_buffer()          # in front of the row build: the update reads the buffer, not `rows`
+        return super().get_action(self.build_rows(obs), record, action_mask, episode_start)
+
+    def update(self, reward: th.Tensor, done: th.Tensor, env_mask: Optional[th.Tensor] = None) -> None:
+        super().update(reward, done, env_mask)
+        self._paid_done((done != 0) if env_mask is None else ((done != 0) & env_mask.bool()))
+
+    def rollout_scripted(self, data) -> None:
+        raise nat.NativeError("AdapVecOnPolicyAgent.rollout_scripted: the one-launch scripted rollout does not build ADAP rows or "
+                              "redraw contexts; step with get_action / update")
+
+
+def vec_agent_for(model: PPO, latent_syncer=None) -> VecOnPolicyAgent:
     """the vectorised agent class that runs `model`'s policy"""
+    if is_adap(model.policy):
+        return AdapVecOnPolicyAgent(model, latent_syncer)
     return (TowerVecOnPolicyAgent if is_tower(model.policy) else VecOnPolicyAgent)(model)
 
 
