@@ -126,6 +126,10 @@ int ph_ctx_sync(ph_ctx *ctx);
 int ph_graph_begin(ph_ctx *ctx);
 int ph_graph_end(ph_ctx *ctx, int *graph_id_out /* host */);
 int ph_graph_launch(ph_ctx *ctx, int graph_id);
+/* nodes of a captured graph = everything that was enqueued between begin/end: kernel launches, and memcpy / memset nodes where a
+ * call enqueues one (hipGraphGetNodes counts them all); a step that only launches kernels has one node per launch.  An addition for
+ * the launch-count tests; PH_ABI_VERSION unchanged */
+int ph_graph_nodes(ph_ctx *ctx, int graph_id, int *nodes_out /* host */);
 /* Device-resident RNG epoch.  Philox counters and permutation seeds are launch arguments, so a captured graph would
  * replay the same random numbers; when an epoch word (one device uint64, caller-owned) is attached, every random
  * stream is additionally keyed by *epoch, and ph_rng_epoch_advance enqueues *epoch += 1 (capturable). */
@@ -1217,6 +1221,45 @@ typedef struct ph_adap_seat {
 } ph_adap_seat;
 int ph_liar_selfplay_step_adap(ph_ctx *ctx, const ph_liar_selfplay *s, const ph_adap_seat *ego /* host or NULL */,
                                const ph_adap_seat *alt /* host or NULL */, int ego_pos, unsigned long long counter, int deal_only);
+/*  Frozen ADAP checkpoints as members of the Liar's Dice pool and of cross-play (additions; PH_ABI_VERSION unchanged; ph_pool_member,
+ *      ph_liar_pool and ph_liar_xplay keep their layouts: the descriptions travel beside them, as the archs do).  This is the
+ *      reference's FIXED '{"type":"ADAP","location":...,"latent_val":[...]}' partner (trainer.py:140-147: ADAP.load, then
+ *      policy.set_context(latent_val)) over n tables.  member_adaps: NULL, or a host array [n_members] whose entry k is NULL -- member k
+ *      stays what its kind and arch say -- or the description of the additive AdapPolicy a PH_POOL_FROZEN member plays: the member's
+ *      `params` are the 64-64 parameters under `spec` (Box(270 + C) observations, the step's action space), `seed` its Philox key, and
+ *      table e's row is one_hot(observation e) ++ contexts[e].
+ *        stated   draw == 0: the caller filled every row of `contexts` with the latent; nothing ever writes it.
+ *        sampled  draw != 0: every table owns a context of this member; one ph_adap_context_draw launch per sampling member and step,
+ *                 behind the pass that ends games, redraws it in every table that pass has dealt (alt_opens | ego_opens: in the pool
+ *                 exactly the tables of `done`; in an evaluation the ended games of tables that play on -- a retired table keeps its
+ *                 last context) -- key member seed ^ salt, counter the step's (+ the epoch word), block the table.  A deal-only call
+ *                 draws for the tables it deals (all of them at the first deal).  Two sampling members must be given different seeds,
+ *                 or their contexts are one stream.
+ *      A member's move for table e is bitwise ph_adap_rows over the observation and contexts[e], then ph_policy_forward under `spec`
+ *      with (member seed, counter); only actions[e] is written: a frozen member records nothing, values / log_probs are ignored.
+ *      Its tiles of the bucket pass run in ONE launch of their own behind the others (pool_adap_kernel: one workgroup per tile, the
+ *      general 32-row forward half empty, its X chunks built in LDS from the tile's 30 components and contexts: no row matrix in
+ *      global memory), made only when the member table holds an ADAP member, and the only launch when it holds nothing else.  With
+ *      every entry NULL each entry point is bit for bit and launch for launch its `_arch` counterpart (which is that call).
+ *      Refused with nothing launched: NULL contexts, context_size outside 1..64, a spec whose observation is not a Box of
+ *      270 + context_size or whose heads are not the step's (A, L) = (2, 19), a description on a member that is not PH_POOL_FROZEN
+ *      (a PH_POOL_LEARNER: ADAP learners do not sit in a pool), an arch beside it, PH_CTX_NATURAL_NUMBERS with context_size != 1. */
+typedef struct ph_pool_adap {
+  const ph_spec *spec;      /* host: Box(270 + C) observations, the step's action space */
+  int context_size, sampler;
+  float *contexts;          /* (n, C) device */
+  int draw;                 /* != 0: redrawn on the device with `sampler` where a game ends */
+} ph_pool_adap;
+int ph_pool_forward_adap(ph_ctx *ctx, const ph_spec *spec, const ph_pool_member *members, int n_members, const float *obs,
+                         const int *partnerid, const unsigned char *active, unsigned long long counter, int *actions,
+                         const float *episode_start_in, int n, const ph_arch *const *member_archs /* host or NULL */,
+                         const ph_pool_adap *const *member_adaps /* host or NULL */);
+int ph_liar_pool_step_adap(ph_ctx *ctx, const ph_liar_pool *pool, const ph_arch *ego_arch /* host or NULL */,
+                           const ph_arch *const *member_archs /* host or NULL */,
+                           const ph_pool_adap *const *member_adaps /* host or NULL */, int ego_pos, unsigned long long counter,
+                           int deal_only);
+int ph_liar_xplay_step_adap(ph_ctx *ctx, const ph_liar_xplay *xp, const ph_arch *const *member_archs /* host or NULL */,
+                            const ph_pool_adap *const *member_adaps /* host or NULL */, unsigned long long counter, int deal_only);
 
 /* ---- owning handle: one agent = its rollout buffer, weights and Adam state on the device ----------------------------------
  *   The pointer-level entry points above take device memory owned by the caller (the Python host uses torch

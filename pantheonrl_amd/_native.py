@@ -214,6 +214,12 @@ class PhAdapSeat(C.Structure):
                 ("rows", C.c_void_p), ("seed", C.c_ulonglong), ("shared", C.c_int)]
 
 
+class PhPoolAdap(C.Structure):
+    """ph_pool_adap: the frozen AdapPolicy checkpoint a PH_POOL_FROZEN member of the Liar's Dice pool / population plays"""
+    _fields_ = [("spec", C.POINTER(PhSpec)), ("context_size", C.c_int), ("sampler", C.c_int), ("contexts", C.c_void_p),
+                ("draw", C.c_int)]
+
+
 ADAP_VEC_SALT = 0xC0A7E87D5A17ADA9      # csrc/ph_adap_vec.h: the per-table contexts' Philox key is the policy seed ^ this constant
 ADAP_VEC_MAX_CONTEXT = 64
 
@@ -296,6 +302,7 @@ SIGNATURES = {
     "ph_graph_begin": [_vp],
     "ph_graph_end": [_vp, C.POINTER(_i)],
     "ph_graph_launch": [_vp, _i],
+    "ph_graph_nodes": [_vp, _i, C.POINTER(C.c_int)],
     "ph_ctx_set_rng_epoch": [_vp, _vp],
     "ph_rng_epoch_advance": [_vp],
     "ph_debug_set_profile_buffer": [_vp, _vp],
@@ -410,6 +417,11 @@ SIGNATURES = {
                              C.POINTER(C.POINTER(PhArch))],
     "ph_liar_pool_step_arch": [_vp, C.POINTER(PhLiarPool), C.POINTER(PhArch), C.POINTER(C.POINTER(PhArch)), _i, _ull, _i],
     "ph_liar_xplay_step_arch": [_vp, C.POINTER(PhLiarXplay), C.POINTER(C.POINTER(PhArch)), _ull, _i],
+    "ph_pool_forward_adap": [_vp, C.POINTER(PhSpec), C.POINTER(PhPoolMember), _i, _vp, _vp, _vp, _ull, _vp, _vp, _i,
+                             C.POINTER(C.POINTER(PhArch)), C.POINTER(C.POINTER(PhPoolAdap))],
+    "ph_liar_pool_step_adap": [_vp, C.POINTER(PhLiarPool), C.POINTER(PhArch), C.POINTER(C.POINTER(PhArch)),
+                               C.POINTER(C.POINTER(PhPoolAdap)), _i, _ull, _i],
+    "ph_liar_xplay_step_adap": [_vp, C.POINTER(PhLiarXplay), C.POINTER(C.POINTER(PhArch)), C.POINTER(C.POINTER(PhPoolAdap)), _ull, _i],
     "ph_block_selfplay_step_arch": [_vp, C.POINTER(PhBlockSelfPlay), C.POINTER(PhArch), C.POINTER(PhArch), _i, _ull],
     "ph_arch_scripted_rollout": [_vp, C.POINTER(PhSpec), C.POINTER(PhArch), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp,
                                  _vp, C.POINTER(PhRollout), _i, _i],

@@ -169,6 +169,7 @@ struct ph_ctx {
   int* stop_flag = nullptr;  // [1]
   std::vector<SpecCache> specs;
   std::vector<hipGraphExec_t> graphs;
+  std::vector<int> graph_nodes;             // nodes of each captured graph (kernel, memcpy and memset nodes alike), counted at ph_graph_end
   bool capturing = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   ph_p2p* p2p_dev = nullptr;      // device copy of the peer-to-peer descriptor used by the fused step launches
@@ -188,6 +189,7 @@ struct ph_ctx {
   int pool_count = 0;                       // members pool_dev holds, 0 = nothing yet
   bool pool_wide = false;                   // ... of which one is a 64-wide or a scripted member (pool_fwd16h_kernel has a tile to run)
   size_t pool_tower_lds = 0;                // ... the largest forward carve of its tower members, 0 = no tower (found at the upload)
+  bool pool_adap = false;                   // ... of which one is an ADAP member (pool_adap_kernel has a tile to run)
   int* pool_order = nullptr;                // (n)
   size_t pool_order_cap = 0;
   int* pool_tiles = nullptr;                // [pool_max_tiles + 1][3]; the last record's first word is the tile count
@@ -816,11 +818,21 @@ int ph_graph_end(ph_ctx* ctx, int* graph_id_out) {
   hipGraph_t g = nullptr;
   PH_HIP(hipStreamEndCapture(ctx->stream, &g));
   hipGraphExec_t ge = nullptr;
+  size_t nodes = 0;
+  (void)hipGraphGetNodes(g, nullptr, &nodes);
   hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (e != hipSuccess) return fail_hip("hipGraphInstantiate", e);
   ctx->graphs.push_back(ge);
+  ctx->graph_nodes.push_back((int)nodes);
   *graph_id_out = (int)ctx->graphs.size() - 1;
+  return 0;
+}
+
+int ph_graph_nodes(ph_ctx* ctx, int graph_id, int* nodes_out) {
+  if (!ctx || !nodes_out) return fail("null ctx/nodes_out");
+  if (graph_id < 0 || graph_id >= (int)ctx->graph_nodes.size()) return fail("bad graph id");
+  *nodes_out = ctx->graph_nodes[graph_id];
   return 0;
 }
 
@@ -1805,8 +1817,8 @@ struct LiarSeats {
   const int *ego_id, *alt_id;        // (n) member at seat 0 / seat 1, or null: member 0
   const unsigned char* playing;      // (n) the tables that take part, or null: all
 };
-struct NoRedraw {   // ended(): what follows the pass that ends games, before seat 1 opens the new ones (ADAP seats redraw there)
-  int operator()() const { return 0; }
+struct NoRedraw {   // ended(deal_only): what follows the pass that ends games, before seat 1 opens the new ones (ADAP redraws there)
+  int operator()(int) const { return 0; }
 };
 template <class Book, class End, class Seat0, class Seat1, class Ended = NoRedraw>
 int liar_step_run(ph_ctx* ctx, const ph::LiarGame& g, const Book& book, const End& end, unsigned long long counter, int deal_only,
@@ -1826,7 +1838,7 @@ int liar_step_run(ph_ctx* ctx, const ph::LiarGame& g, const Book& book, const En
   }
   // reply played and credited; finished tables are re-dealt; where seat 1 opens the new game it moves once
   PH_HIP(ph::launch_liar_pass(1, g, book, end, counter, ctx->rng_epoch, deal_only, st));
-  if (!deal_only && ended()) return 1;
+  if (ended(deal_only)) return 1;
   if (seat1(g.obs_alt, g.alt_opens, k[2])) return 1;
   if (rec) PH_HIP(ph::launch_record_opening(ctx->rec, rs, st));
   PH_HIP(ph::launch_liar_pass(2, g, book, end, counter, ctx->rng_epoch, deal_only, st));
@@ -1933,7 +1945,8 @@ int liar_selfplay_step_run(const char* who, ph_ctx* ctx, const ph_liar_selfplay*
         return seat_forward_ragged(ctx, alt_adap ? alt_adap->spec : s.spec, alt_arch, s.alt_params, obs, s.alt_seed, c, s.alt_actions,
                                    s.alt_values, s.alt_log_probs, s.alt_rb, s.alt_pos, s.can, s.es_alt);
       },
-      [&]() {   // both seats were paid `done` in the tables whose game just ended (pantheon_hip.h: a game never ends on its opening move)
+      [&](int deal) {   // both seats were paid `done` in the tables whose game just ended (pantheon_hip.h: a game never ends on its opening move)
+        if (deal) return 0;   // the first contexts of a run are the caller's
         for (const ph_adap_seat* a : {ego_adap, alt_adap})
           if (a && !a->shared)
             PH_HIP(ph::launch_adap_context_draw(a->sampler, a->context_size, a->seed, counter, ctx->rng_epoch, s.done, a->contexts, s.n,
@@ -2018,20 +2031,43 @@ int ph_adap_vec_host(const ph_space* env_obs_space, int context_size, int sample
 
 // ---- Liar's Dice against a pool of partners (ph_pool.h) ----
 namespace {
+// an ADAP member of the Liar's Dice pool is well formed: C in range, its contexts, a sampler that takes C, a Box(270 + C) spec with
+// the step's heads; its parameter layout goes to *lay
+int check_pool_adap(const char* who, const ph_spec* spec, const ph_pool_adap& ap, ph_layout* lay) {
+  const std::string w(who);
+  ph_space env;
+  liar_env_space(&env);
+  ph::AdapRowShape shape;
+  if (adap_row_shape(who, &env, ap.context_size, &shape)) return 1;
+  if (!ap.contexts) return fail(w + ": null contexts");
+  if ((uintptr_t)ap.contexts % 4) return fail(w + ": contexts must be 4-byte aligned");
+  if (check_adap_sampler(who, ap.sampler, ap.context_size)) return 1;
+  if (!ap.spec) return fail(w + ": null ADAP spec");
+  if (ap.spec->obs.kind != PH_SPACE_BOX || ap.spec->obs.n != shape.F + shape.C)
+    return fail(w + ": the ADAP spec's observation must be a Box of 270 + C = " + std::to_string(shape.F + shape.C) + " components");
+  if (ap.spec->act.kind != spec->act.kind || ap.spec->act.n != spec->act.n ||
+      std::memcmp(ap.spec->act.nvec, spec->act.nvec, sizeof(int) * (size_t)(spec->act.n > 0 ? spec->act.n : 0)) != 0)
+    return fail(w + ": the ADAP spec's action space must be the step's (Liar's Dice: (A, L) = (2, 19))");
+  if (layout_of(ap.spec, lay)) return 1;
+  if (lay->A != 2 || lay->L != 19) return fail(w + ": the ADAP spec's heads must be Liar's Dice's (A, L) = (2, 19)");
+  return 0;
+}
+
 // validate the members and bring the device-side table up to date (uploaded only when it changed; never inside graph capture).
 // archs: null, or per member null (the member stays what its kind says on the 64-wide / scripted / clone kernels) or the arch of a
-// learner's or frozen member's towers, resolved into the table for pool_tower_kernel.
-int pool_members(ph_ctx* ctx, const char* who, const ph_spec* spec, const ph_pool_member* members, const ph_arch* const* archs, int K,
-                 int n) {
+// learner's or frozen member's towers, resolved into the table for pool_tower_kernel.  adaps: null, or per member null or the
+// description of the AdapPolicy checkpoint a frozen member plays (pool_adap_kernel's tiles).
+int pool_members(ph_ctx* ctx, const char* who, const ph_spec* spec, const ph_pool_member* members, const ph_arch* const* archs,
+                 const ph_pool_adap* const* adaps, int K, int n) {
   const std::string w(who);
   if (!members) return fail(w + ": null member array");
   if (K < 1 || K > PH_MAX_POOL) return fail(w + ": the pool holds 1..PH_MAX_POOL members");
-  if (archs && !spec) return fail(w + ": null spec");
+  if ((archs || adaps) && !spec) return fail(w + ": null spec");
   ph::PoolMemberDev tab[PH_MAX_POOL];
   // (the K rows in use are zeroed, compared and uploaded: this runs in front of every step)
   const size_t used = sizeof(ph::PoolMemberDev) * (size_t)K;
   std::memset(tab, 0, used);
-  bool wide = false;
+  bool wide = false, adap = false;
   size_t tower_lds = 0;
   for (int k = 0; k < K; ++k) {
     const ph_pool_member& m = members[k];
@@ -2040,7 +2076,16 @@ int pool_members(ph_ctx* ctx, const char* who, const ph_spec* spec, const ph_poo
     if (m.kind != PH_POOL_LEARNER && m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED && m.kind != PH_POOL_CLONE)
       return fail(wk + ": unknown kind");
     d.kind = d.fwd = m.kind;
-    if (archs && archs[k]) {
+    if (adaps && adaps[k]) {
+      const ph_pool_adap& ap = *adaps[k];
+      if (m.kind != PH_POOL_FROZEN) return fail(wk + ": an ADAP checkpoint is a PH_POOL_FROZEN member (ADAP learners do not sit in a pool)");
+      if (archs && archs[k]) return fail(wk + ": an ADAP member takes no arch");
+      if (check_pool_adap(wk.c_str(), spec, ap, &d.adap_lay)) return 1;
+      d.adap_C = ap.context_size;
+      d.adap_ctx = ap.contexts;
+      d.fwd = PH_POOL_CLONE;   // "not pool_fwd16h_kernel's tile"
+      adap = true;
+    } else if (archs && archs[k]) {
       if (m.kind == PH_POOL_SCRIPTED || m.kind == PH_POOL_CLONE)
         return fail(wk + ": an arch belongs to a learner or a frozen member, not to a scripted one or a clone");
       ph::NetDims nd;
@@ -2090,7 +2135,22 @@ int pool_members(ph_ctx* ctx, const char* who, const ph_spec* spec, const ph_poo
     ctx->pool_count = K;
     ctx->pool_wide = wide;
     ctx->pool_tower_lds = tower_lds;
+    ctx->pool_adap = adap;
   }
+  return 0;
+}
+
+// one redraw launch per sampling ADAP member, behind the pass that ends games: the tables that pass has just dealt (alt_opens or
+// ego_opens: every table whose game ended and that plays on -- in the pool that is `done`; a retired table of an evaluation keeps a
+// stale `done` -- and, in a deal-only call, the tables the caller flagged) get a new context of that member, drawn at the step's
+// counter under the member's seed
+int pool_adap_redraw(ph_ctx* ctx, const ph_pool_member* members, const ph_pool_adap* const* adaps, int K, unsigned long long counter,
+                     const ph::LiarGame& g) {
+  if (!adaps) return 0;
+  for (int k = 0; k < K; ++k)
+    if (adaps[k] && adaps[k]->draw)
+      PH_HIP(ph::launch_adap_context_draw(adaps[k]->sampler, adaps[k]->context_size, members[k].seed, counter, ctx->rng_epoch, g.alt_opens,
+                                          adaps[k]->contexts, g.n, ctx->stream, g.ego_opens));
   return 0;
 }
 
@@ -2135,8 +2195,8 @@ int pool_forward(ph_ctx* ctx, const char* who, const ph_spec* spec, int K, const
   p.b.ntiles = ctx->pool_tiles + 3 * ntile;
   PH_HIP(ph::launch_pool_bucket(partnerid, active, n, K, p.b, ctx->stream));
   // which of the three kernels the table has tiles for (pool_members found out at the upload): 64-wide and scripted members,
-  // clones (p.bc.P), towers (their largest carve)
-  PH_HIP(ph::launch_pool_fwd(p, K, ctx->stream, !ctx->pool_wide, ctx->pool_tower_lds));
+  // clones (p.bc.P), towers (their largest carve), ADAP members
+  PH_HIP(ph::launch_pool_fwd(p, K, ctx->stream, !ctx->pool_wide, ctx->pool_tower_lds, ctx->pool_adap));
   return 0;
 }
 }  // namespace
@@ -2150,12 +2210,21 @@ int ph_pool_forward(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* memb
 int ph_pool_forward_arch(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* members, int n_members, const float* obs,
                          const int* partnerid, const unsigned char* active, unsigned long long counter, int* actions,
                          const float* episode_start_in, int n, const ph_arch* const* member_archs) {
+  return ph_pool_forward_adap(ctx, spec, members, n_members, obs, partnerid, active, counter, actions, episode_start_in, n, member_archs,
+                              nullptr);
+}
+
+int ph_pool_forward_adap(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* members, int n_members, const float* obs,
+                         const int* partnerid, const unsigned char* active, unsigned long long counter, int* actions,
+                         const float* episode_start_in, int n, const ph_arch* const* member_archs,
+                         const ph_pool_adap* const* member_adaps) {
   DevGuard dev_guard(ctx);
   if (!ctx) return fail("null ctx");
   if (!spec || !obs || !partnerid || !active || !actions) return fail("ph_pool_forward: null argument");
   if (n <= 0) return fail("ph_pool_forward: n must be positive");
   if ((uintptr_t)actions % 8) return fail("ph_pool_forward: actions must be 8-byte aligned");
-  if (pool_members(ctx, "ph_pool_forward", spec, members, member_archs, n_members, n) || check_pool_clones("ph_pool_forward", ctx, spec))
+  if (pool_members(ctx, "ph_pool_forward", spec, members, member_archs, member_adaps, n_members, n) ||
+      check_pool_clones("ph_pool_forward", ctx, spec))
     return 1;
   for (int k = 0; k < n_members; ++k)
     if (members[k].kind == PH_POOL_LEARNER && !episode_start_in) return fail("ph_pool_forward: learners need episode_start_in");
@@ -2173,11 +2242,11 @@ int ph_liar_default_actions(ph_ctx* ctx, const float* obs, const unsigned char* 
 }
 
 // The pool step and the cross-play step, each written once for the entry point and its `_arch` form: C++ overloads of the entry
-// points' names that take the archs as well (null: every seat on today's kernels).
+// points' names that take the archs and the ADAP descriptions as well (null: every seat on today's kernels).
 extern "C++" {
 namespace {
-int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_arch, const ph_arch* const* member_archs, int ego_pos,
-                      unsigned long long counter, int deal_only) {
+int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_arch, const ph_arch* const* member_archs,
+                      const ph_pool_adap* const* member_adaps, int ego_pos, unsigned long long counter, int deal_only) {
   DevGuard dev_guard(ctx);
   const char* who = "ph_liar_pool_step";
   if (!ctx || !pool) return fail_who(who, ": null argument");
@@ -2189,7 +2258,7 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_
   if (check_liar_ego(who, s)) return 1;
   if (ego_arch && ph_arch_fits(s.spec, ego_arch)) return 1;   // before the first launch, as every member's arch
   if (ego_arch && (uintptr_t)s.ego_params % 16 != 0) return fail_who(who, ": params must be 16-byte aligned");
-  if (pool_members(ctx, who, s.spec, s.members, member_archs, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) ||
+  if (pool_members(ctx, who, s.spec, s.members, member_archs, member_adaps, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) ||
       check_pool_clones(who, ctx, s.spec))
     return 1;
   if (!deal_only && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail_who(who, ": ego_pos out of range (buffer full?)");
@@ -2204,12 +2273,13 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_
       // every table's member -- behind a deal the freshly sampled one -- moves: one grouped launch
       [&](const float* obs, const unsigned char* active, unsigned long long c) {
         return pool_forward(ctx, who, s.spec, s.n_members, obs, s.partnerid, active, s.can, c, s.alt_actions, s.es_alt, s.n);
-      });
+      },
+      [&](int) { return pool_adap_redraw(ctx, s.members, member_adaps, s.n_members, counter, g); });
 }
 
 // ---- cross-play evaluation of Liar's Dice (ph_xplay.h; tester.py:41-63 over n tables) ----
-int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* const* member_archs, unsigned long long counter,
-                       int deal_only) {
+int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* const* member_archs,
+                       const ph_pool_adap* const* member_adaps, unsigned long long counter, int deal_only) {
   DevGuard dev_guard(ctx);
   const char* who = "ph_liar_xplay_step";
   if (!ctx || !xp) return fail_who(who, ": null argument");
@@ -2229,7 +2299,7 @@ int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* cons
   for (int p = 0; p < 2 * s.n_pairs; ++p)
     if (s.pairs[p] < 0 || s.pairs[p] >= s.n_members)
       return fail("ph_liar_xplay_step: pair " + std::to_string(p / 2) + " names a member out of range");
-  if (pool_members(ctx, who, s.spec, s.members, member_archs, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) ||
+  if (pool_members(ctx, who, s.spec, s.members, member_archs, member_adaps, s.n_members, s.n) || check_liar_one_hot(who, ctx, s.spec, s.n) ||
       check_pool_clones(who, ctx, s.spec))
     return 1;
   const ph::EvalEnd end{s.episodes_per_table, s.games, s.playing, s.tables_left, s.ep_return, s.ep_length, s.returns, s.lengths};
@@ -2240,14 +2310,19 @@ int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* cons
   return liar_step_run(
       ctx, g, ph::NoBook{}, end, counter, deal_only, {3 * counter, 3 * counter + 1, 3 * counter + 2}, LiarSeats{s.ego_id, s.alt_id, s.playing},
       [&](unsigned long long c) { return seat(s.obs_ego, s.ego_id, s.playing, c, s.ego_actions); },
-      [&](const float* obs, const unsigned char* active, unsigned long long c) { return seat(obs, s.alt_id, active, c, s.alt_actions); });
+      [&](const float* obs, const unsigned char* active, unsigned long long c) { return seat(obs, s.alt_id, active, c, s.alt_actions); },
+      [&](int) { return pool_adap_redraw(ctx, s.members, member_adaps, s.n_members, counter, g); });
 }
 }  // namespace
 }  // extern "C++"
 
 int ph_liar_pool_step_arch(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_arch, const ph_arch* const* member_archs, int ego_pos,
                            unsigned long long counter, int deal_only) {
-  return ph_liar_pool_step(ctx, pool, ego_arch, member_archs, ego_pos, counter, deal_only);
+  return ph_liar_pool_step(ctx, pool, ego_arch, member_archs, nullptr, ego_pos, counter, deal_only);
+}
+int ph_liar_pool_step_adap(ph_ctx* ctx, const ph_liar_pool* pool, const ph_arch* ego_arch, const ph_arch* const* member_archs,
+                           const ph_pool_adap* const* member_adaps, int ego_pos, unsigned long long counter, int deal_only) {
+  return ph_liar_pool_step(ctx, pool, ego_arch, member_archs, member_adaps, ego_pos, counter, deal_only);
 }
 int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsigned long long counter, int deal_only) {
   return ph_liar_pool_step_arch(ctx, pool, nullptr, nullptr, ego_pos, counter, deal_only);
@@ -2255,7 +2330,11 @@ int ph_liar_pool_step(ph_ctx* ctx, const ph_liar_pool* pool, int ego_pos, unsign
 
 int ph_liar_xplay_step_arch(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* const* member_archs, unsigned long long counter,
                             int deal_only) {
-  return ph_liar_xplay_step(ctx, xp, member_archs, counter, deal_only);
+  return ph_liar_xplay_step(ctx, xp, member_archs, nullptr, counter, deal_only);
+}
+int ph_liar_xplay_step_adap(ph_ctx* ctx, const ph_liar_xplay* xp, const ph_arch* const* member_archs,
+                            const ph_pool_adap* const* member_adaps, unsigned long long counter, int deal_only) {
+  return ph_liar_xplay_step(ctx, xp, member_archs, member_adaps, counter, deal_only);
 }
 int ph_liar_xplay_step(ph_ctx* ctx, const ph_liar_xplay* xp, unsigned long long counter, int deal_only) {
   return ph_liar_xplay_step_arch(ctx, xp, nullptr, counter, deal_only);

@@ -80,8 +80,10 @@ __host__ __device__ inline void adap_draw_context(int sampler, int cs, uint64_t 
 // rows (n, F + C) <- obs (n, D) ++ contexts (n, C) where active (null: everywhere); one lane per row element
 hipError_t launch_adap_rows(const AdapRowShape& shape, const float* obs, const float* contexts, const unsigned char* active, float* rows,
                             int n, hipStream_t st);
-// contexts (n, C) <- a draw at `counter` (+ the epoch word's high half) where redraw (null: everywhere); one lane per table
+// contexts (n, C) <- a draw at `counter` (+ the epoch word's high half) where redraw or redraw2 (both null: everywhere); one lane
+// per table
 hipError_t launch_adap_context_draw(int sampler, int cs, unsigned long long seed, unsigned long long counter,
-                                    const unsigned long long* epoch, const unsigned char* redraw, float* contexts, int n, hipStream_t st);
+                                    const unsigned long long* epoch, const unsigned char* redraw, float* contexts, int n, hipStream_t st,
+                                    const unsigned char* redraw2 = nullptr);
 
 }  // namespace ph

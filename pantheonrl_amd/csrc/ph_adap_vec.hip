@@ -29,10 +29,11 @@ __global__ __launch_bounds__(AV_THREADS) void adap_rows_kernel(const AdapRowShap
 __global__ __launch_bounds__(AV_THREADS) void adap_context_draw_kernel(int sampler, int cs, unsigned long long seed,
                                                                        unsigned long long counter, const unsigned long long* epoch,
                                                                        const unsigned char* __restrict__ redraw,
+                                                                       const unsigned char* __restrict__ redraw2,
                                                                        float* __restrict__ contexts, int n) {
   const int e = blockIdx.x * AV_THREADS + threadIdx.x;
   if (e >= n) return;
-  if (redraw && !redraw[e]) return;
+  if ((redraw || redraw2) && !(redraw && redraw[e]) && !(redraw2 && redraw2[e])) return;
   adap_draw_context(sampler, cs, seed, adap_vec_counter(counter, epoch), (uint32_t)e, contexts + (size_t)e * cs);
 }
 }  // namespace
@@ -46,9 +47,10 @@ hipError_t launch_adap_rows(const AdapRowShape& shape, const float* obs, const f
 }
 
 hipError_t launch_adap_context_draw(int sampler, int cs, unsigned long long seed, unsigned long long counter,
-                                    const unsigned long long* epoch, const unsigned char* redraw, float* contexts, int n, hipStream_t st) {
+                                    const unsigned long long* epoch, const unsigned char* redraw, float* contexts, int n, hipStream_t st,
+                                    const unsigned char* redraw2) {
   hipLaunchKernelGGL(adap_context_draw_kernel, dim3((n + AV_THREADS - 1) / AV_THREADS), dim3(AV_THREADS), 0, st, sampler, cs, seed,
-                     counter, epoch, redraw, contexts, n);
+                     counter, epoch, redraw, redraw2, contexts, n);
   return hipGetLastError();
 }
 

@@ -12,12 +12,79 @@
 #include "ph_liar_group.h"
 #include "ph_pool.h"
 #include "ph_bc_row.h"
+#include "ph_adap_vec.h"
 
 namespace ph {
 
 
-template <int R, int LP, bool VALU>
-__device__ __forceinline__ void policy_fwd_body(const FwdArgs& a) {
+// floats of policy_fwd_body's LDS carve (fwd_lds_bytes below)
+constexpr int fwd_lds_floats(int R, int Lp) { return 2 * R * LDH + 2 * HID * LDH + (HID + R) * (Lp + 1) + 3 * 64 + R; }
+
+// The X stage of an ADAP member's tile of the pool's grouped forward (pool_adap_kernel below): the rows of the first layer are
+// one_hot(observation) ++ context, built here from the tile's observation components and contexts -- staged in LDS once per tile
+// (stage) -- by adap_row_value, the one text of the row rule (ph_adap_vec.h).  No row matrix exists in global memory.  Rows beyond
+// the tile's tables (at most POOL_TILE of the body's R) are zero.
+template <int R, int NT>
+struct AdapXStage {
+  static constexpr int ITERS = R * HID / NT;
+  int D, F, C, rows;      // the environment's components and features, the member's context size, the tile's tables
+  const int* goff;        // device: prefix sums of the environment's nvec (D + 1)
+  const float* gobs;      // device: (n, D) observations
+  const float* gctx;      // device: (n, C) the member's contexts
+  int* off;               // LDS [D + 1]
+  float *obs, *ctx;       // LDS [POOL_TILE][D], [POOL_TILE][C]
+  // global -> LDS, every load in flight before the first store; rowphys must be visible, a barrier must follow
+  __device__ __forceinline__ void stage(const int* rowphys, int tid) {
+    // (D is the Liar's Dice observation's 30 components: the launcher checks it, so the row of an element is a constant divide;
+    //  a context element is slot (row, j) of a [POOL_TILE][64] grid with j < C: no divide by the run-time C)
+    constexpr int OD = 30, NO = (POOL_TILE * OD + NT - 1) / NT, NC = POOL_TILE * ADAP_VEC_MAX_CONTEXT / NT;
+    float vo[NO], vc[NC];
+    const int offv = tid <= OD ? goff[tid] : 0;
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+      const int e = tid + NT * i, r = e / OD;
+      vo[i] = (r < rows) ? gobs[(size_t)rowphys[r] * OD + (e - r * OD)] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int e = tid + NT * i, r = e / ADAP_VEC_MAX_CONTEXT, j = e % ADAP_VEC_MAX_CONTEXT;
+      vc[i] = (r < rows && j < C) ? gctx[(size_t)rowphys[r] * C + j] : 0.f;
+    }
+    if (tid <= OD) off[tid] = offv;
+#pragma unroll
+    for (int i = 0; i < NO; ++i)
+      if (tid + NT * i < POOL_TILE * OD) obs[tid + NT * i] = vo[i];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int e = tid + NT * i, r = e / ADAP_VEC_MAX_CONTEXT, j = e % ADAP_VEC_MAX_CONTEXT;
+      if (j < C) ctx[r * C + j] = vc[i];
+    }
+  }
+  __device__ __forceinline__ void issue(const int*, const float*, const NetDims&, int) {}
+  __device__ __forceinline__ void commit(float* dst, const int*, const float*, const NetDims&, int c) const {
+    const int tid = threadIdx.x, kk = tid & 63, f = c * HID + kk;
+    AdapRowShape s;
+    s.D = D;
+    s.F = F;
+    s.C = C;
+    s.box = 0;
+    float v[ITERS];
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i) {
+      const int r = (tid + NT * i) >> 6;
+      v[i] = (r < rows && f < F + C) ? adap_row_value(s, off, obs + r * D, ctx + r * C, f) : 0.f;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < ITERS; ++i) dst[((tid + NT * i) >> 6) * LDH + kk] = v[i];
+  }
+};
+
+// XS: where the first layer's rows come from (XStage: the observations in global memory).  MAP (the pool's grouped forward): the
+// tile's rows are the tables map[0 .. rows) instead of row0 .. row0 + R - 1, the policy net only; every output row of the 32x32 tile
+// walk depends on its own X row alone, so a table's bits do not depend on the tile or the slot it lands in.
+template <int R, int LP, bool VALU, class XS = XStage<R, R * 4>, bool MAP = false>
+__device__ __forceinline__ void policy_fwd_body(const FwdArgs& a, XS xr = XS(), const int* map = nullptr, int rows = 0) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NT = R * 4;
   const NetDims& nd = a.nd;
@@ -36,7 +103,7 @@ __device__ __forceinline__ void policy_fwd_body(const FwdArgs& a) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int mt = wave >> 1, nt = wave & 1;
-  const int net = blockIdx.y;
+  const int net = MAP ? 0 : blockIdx.y;
   const int row0 = blockIdx.x * R;
   const ph_layout& lay = nd.lay;
   const float* W1 = a.params + (net == 0 ? lay.pi_W1 : lay.vf_W1);
@@ -46,10 +113,13 @@ __device__ __forceinline__ void policy_fwd_body(const FwdArgs& a) {
 
   PH_STAMP(a.prof, 0);
   // ---- every staging load of the kernel is issued here, back to back: one memory latency in total ----
-  if (tid < R) rowphys[tid] = (row0 + tid < a.n) ? row0 + tid : -1;
+  if constexpr (MAP) {
+    if (tid < R) rowphys[tid] = tid < rows ? map[tid] : -1;
+  } else {
+    if (tid < R) rowphys[tid] = (row0 + tid < a.n) ? row0 + tid : -1;
+  }
   WStage<NT> w2r, w1r;
   WoStage<NT> wor;
-  XStage<R, NT> xr;
   w2r.issue(W2, 0, HID);
   w1r.issue(W1, 0, nd.F);
   if (net == 0) wor.issue(a.params + lay.act_W, nd.L, Lp);
@@ -62,6 +132,7 @@ __device__ __forceinline__ void policy_fwd_body(const FwdArgs& a) {
   PH_STAMP(a.prof, 8);
   __syncthreads();  // rowphys visible
   PH_STAMP(a.prof, 9);
+  if constexpr (MAP) xr.stage(rowphys, tid);
   xr.issue(rowphys, a.obs, nd, 0);
   w2r.commit(w2s);
   PH_STAMP(a.prof, 10);
@@ -73,6 +144,7 @@ __device__ __forceinline__ void policy_fwd_body(const FwdArgs& a) {
     bos[tid] = bias3;
   }
   PH_STAMP(a.prof, 11);
+  if constexpr (MAP) __syncthreads();   // the tile's components and contexts are staged
   xr.commit(bufA, rowphys, a.obs, nd, 0);
   __syncthreads();
   PH_STAMP(a.prof, 1);
@@ -141,7 +213,7 @@ __device__ __forceinline__ void policy_fwd_body(const FwdArgs& a) {
   PH_STAMP(a.prof, 6);
 
   // ---- distribution: one lane per row ----
-  if (tid < R && rowphys[tid] >= 0) general_row_tail(a, nd, row0 + tid, outs + tid * LDO, fwd_counter(a));
+  if (tid < R && rowphys[tid] >= 0) general_row_tail(a, nd, MAP ? rowphys[tid] : row0 + tid, outs + tid * LDO, fwd_counter(a));
   PH_STAMP(a.prof, 7);
 }
 
@@ -1373,6 +1445,51 @@ __global__ __launch_bounds__(256) void pool_clone16_kernel(PoolFwd p) {
   bc_clone_tile(bc_clone_args(p.a.nd, p.bc, m.params, p.a.obs, p.b.order + first, rows, m.seed, fwd_counter(p.a), p.a.act_i32), smem_dyn);
 }
 
+// ---- the ADAP tiles of the bucket pass: a frozen AdapPolicy checkpoint as a member (ph_pool.h) -------------------------------------
+// One workgroup per tile (the policy net: a frozen member records nothing and nothing caches its value).  A tile whose member is no
+// ADAP member is another kernel's.  The member's parameters, seed, context size, contexts and parameter layout are uniform loads
+// from the member table in DEVICE memory; the forward is policy_fwd_body<32, 32, false> -- the general forward that
+// ph_policy_forward launches for the member's Box(F + C) spec -- half empty, with the tile's tables as its rows and its X chunks
+// built in the kernel (AdapXStage), so table e's logits and its draw -- (member seed, counter, e) -- are those of
+// ph_adap_rows + ph_policy_forward over all tables, bit for bit.  Only actions[e] is written.
+constexpr int POOL_ADAP_ROWS = 32, POOL_ADAP_NT = POOL_ADAP_ROWS * 4;
+constexpr int POOL_ADAP_EXT = 32 + POOL_TILE * 30 + POOL_TILE * ADAP_VEC_MAX_CONTEXT;   // off, components, contexts: behind the body's carve
+__global__ __launch_bounds__(POOL_ADAP_NT) void pool_adap_kernel(PoolFwd p) {
+  extern __shared__ __attribute__((aligned(16))) float smem_dyn[];
+  constexpr int R = POOL_ADAP_ROWS;
+  const int tile = blockIdx.x;
+  if (tile >= p.b.ntiles[0]) return;
+  const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1];
+  const int rows = p.b.tiles[3 * tile + 2] < POOL_TILE ? p.b.tiles[3 * tile + 2] : POOL_TILE;   // (device data: clamped once)
+  const PoolMemberDev& m = p.members[member];
+  const int C = m.adap_C;
+  if (C == 0) return;   // pool_fwd16h_kernel's, pool_clone16_kernel's or pool_tower_kernel's
+  FwdArgs a = p.a;
+  AdapXStage<R, POOL_ADAP_NT> xs;
+  xs.D = a.nd.D;
+  xs.F = a.nd.F;
+  xs.C = C;
+  xs.rows = rows;
+  xs.goff = a.nd.obs_off;
+  xs.gobs = a.obs;
+  xs.gctx = m.adap_ctx;
+  xs.off = (int*)(smem_dyn + fwd_lds_floats(R, 32));
+  xs.obs = smem_dyn + fwd_lds_floats(R, 32) + 32;
+  xs.ctx = xs.obs + POOL_TILE * 30;
+  a.params = m.params;
+  a.seed = m.seed;
+  a.values = nullptr;
+  a.logp = nullptr;
+  a.pos_env = nullptr;
+  a.rec_mask = nullptr;
+  a.es_in = nullptr;
+  a.nd.lay = m.adap_lay;   // the member's Box(F + C) rows: what the body's first layer walks
+  a.nd.obs_kind = PH_SPACE_BOX;
+  a.nd.D = a.nd.F = a.nd.lay.F;
+  a.nd.nchunk = (a.nd.F + HID - 1) / HID;
+  policy_fwd_body<R, 32, false, AdapXStage<R, POOL_ADAP_NT>, true>(a, xs, p.b.order + first, rows);
+}
+
 // one net (policy: net 0, value: net 1) of `params` into a resident set, by the 256 lanes of the half that runs that net -- the very
 // loads and LDS positions the per-launch forward stages (policy_fwd16h_body), with the head's weights at leading dimension RES_LDO
 __device__ __forceinline__ void stage_resident_net(const ResidentNet& rn, const float* params, const NetDims& nd, int net, int tid) {
@@ -1985,10 +2102,10 @@ bool pool_clone_eligible(const NetDims& nd, const ph_bc_layout& lay) {
   return bc_clone_eligible(nd.obs_kind, nd.D, nd.L) && lay.P > lay.b1 && lay.P - lay.b1 <= BC_CLONE_SMALL_MAX && lay.b1 == lay.W1 + lay.F * BH &&
          sizeof(float) * (size_t)bc_clone_lds_floats(lay.P - lay.b1) <= fwd16h_lds_bytes();
 }
-hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide, size_t tower_lds) {
+hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide, size_t tower_lds, bool adap) {
   if (!pool_fwd_eligible(p.a.nd, p.a.n)) return hipErrorInvalidValue;
   if (p.bc.P != 0 && !pool_clone_eligible(p.a.nd, p.bc)) return hipErrorInvalidValue;
-  if (no_wide && p.bc.P == 0 && tower_lds == 0) return hipErrorInvalidValue;
+  if (no_wide && p.bc.P == 0 && tower_lds == 0 && !adap) return hipErrorInvalidValue;
   if (!no_wide)   // (a table of clones and towers alone has no tile for this kernel: every workgroup would return at its tile's kind)
     hipLaunchKernelGGL((pool_fwd16h_kernel<false>), dim3(pool_max_tiles(p.a.n, K), 2), dim3(256), fwd16h_lds_bytes(), s, p);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -1996,7 +2113,15 @@ hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide,
     hipLaunchKernelGGL(pool_clone16_kernel, dim3(pool_max_tiles(p.a.n, K)), dim3(256), sizeof(float) * (size_t)bc_clone_lds_floats(p.bc.P - p.bc.b1),
                        s, p);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (tower_lds != 0) return launch_pool_tower(p, K, tower_lds, s);   // the member table holds a tower: its tiles, rows disjoint again
+  if (tower_lds != 0)   // the member table holds a tower: its tiles, rows disjoint again
+    if (const hipError_t e = launch_pool_tower(p, K, tower_lds, s); e != hipSuccess) return e;
+  if (adap) {   // ... an ADAP member: its tiles
+    if (p.a.nd.Lp != 32 || p.a.nd.D != 30 || p.a.nd.gauss) return hipErrorInvalidValue;   // (the kernel's carve and instantiation)
+    const size_t lds = sizeof(float) * (size_t)(fwd_lds_floats(POOL_ADAP_ROWS, 32) + POOL_ADAP_EXT);
+    if (const hipError_t e = allow_dynamic_lds((const void*)pool_adap_kernel, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(pool_adap_kernel, dim3(pool_max_tiles(p.a.n, K)), dim3(POOL_ADAP_NT), lds, s, p);
+    return hipGetLastError();
+  }
   return hipSuccess;
 }
 
@@ -2015,8 +2140,7 @@ __global__ __launch_bounds__(R * 4) void policy_fwd_multi_kernel(FwdMulti m) {
 
 
 size_t fwd_lds_bytes(int R, int Lp) {
-  const int LDO = Lp + 1;
-  return sizeof(float) * (size_t)(2 * R * LDH + 2 * HID * LDH + (HID + R) * LDO + 3 * 64 + R);
+  return sizeof(float) * (size_t)fwd_lds_floats(R, Lp);
 }
 
 template <int R, int LP, bool VALU>

@@ -5,6 +5,9 @@
 // (the shared-trunk FeedForward32Policy, params in ph_bc_layout) is a non-learner like a frozen one -- PoolBook below asks for
 // `kind == PH_POOL_LEARNER` only -- and its tile of the grouped forward is ph_bc_row.h's bc_clone_tile.  A learner or frozen member
 // whose `tower` flag is set plays an MLP tower of that run-time shape (ph_arch.h): its tiles are pool_tower_kernel's (ph_arch.hip).
+// A frozen member whose `adap_C` is set plays an AdapPolicy checkpoint (adap/policies.py:21-146; seated by the reference as
+// FIXED '{"type":"ADAP",...,"latent_val":[...]}', trainer.py:140-147, set_context): the 64-64 MLP over one_hot(observation) ++ the
+// table's context, its tiles pool_adap_kernel's (ph_policy.hip).
 #pragma once
 #include "ph_liar_step.h"
 #include "ph_arch.h"
@@ -25,6 +28,11 @@ struct PoolMemberDev {
   float *values, *log_probs;
   unsigned long long seed;
   ArchDims ad;   // a tower member's (learner or frozen); read from this table on the device, never from a kernel argument
+  // an ADAP member's (frozen): context size (0: no ADAP member), its (n, C) contexts and the layout of its Box(F + C) parameters;
+  // read from this table on the device like `ad`.  `fwd` states it as PH_POOL_CLONE too.
+  int adap_C;
+  const float* adap_ctx;
+  ph_layout adap_lay;
 };
 // (pool_fwd16h_kernel is held to the text it had without towers: a tower flag that it reads beside `kind` is a second load behind the
 // branch on `kind`, a dependent round trip to L2 in front of every tile -- 1.1 us per cross-play step of a population without a tower,
@@ -141,8 +149,8 @@ struct PoolBook {
 hipError_t launch_pool_bucket(const int* partnerid, const unsigned char* active, int n, int K, const PoolBuckets& b, hipStream_t s);
 // ph_policy.hip; p.bc.P != 0: the member table holds a clone (its tiles' kernel follows); tower_lds != 0: it holds a tower (the
 // largest arch_fwd_lds_bytes over its tower members; pool_tower_kernel follows); no_wide: it holds neither a 64-wide nor a scripted
-// member (no 64-64 launch)
-hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide = false, size_t tower_lds = 0);
+// member (no 64-64 launch); adap: it holds an ADAP member (pool_adap_kernel follows, last)
+hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide = false, size_t tower_lds = 0, bool adap = false);
 // ph_arch.hip: the tower tiles of the bucket pass (lds: the launch's dynamic LDS, at least every tower member's carve)
 hipError_t launch_pool_tower(const PoolFwd& p, int K, size_t lds, hipStream_t s);
 bool pool_fwd_eligible(const NetDims& nd, int n);                     // ph_policy.hip

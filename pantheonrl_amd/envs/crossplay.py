@@ -17,8 +17,8 @@ import torch as th
 
 from .. import _native as nat
 from ..spaces import make_spec
-from .vec import (ClonedVecPartner, FrozenVecPartner, TowerFrozenVecPartner, VecLiarDefaultPartner, VecLiarsDice, VecLiarStep,
-                  check_liar_member_policy)
+from .vec import (AdapFrozenVecPartner, ClonedVecPartner, FrozenVecPartner, TowerFrozenVecPartner, VecLiarDefaultPartner,
+                  VecLiarsDice, VecLiarStep, check_liar_member_policy)
 
 MAX_STEPS_PER_GAME = 7       # 12 bids and a call: at most 7 moves of the ego, whoever opens
 
@@ -102,7 +102,8 @@ class CrossPlayResult:
 
 class VecLiarCrossPlay(VecLiarStep):
     """tester.py:41-63 for a population: n_envs Liar's Dice tables resident on the device, both seats held by members of ONE
-    population of M <= 8 frozen 64-64 policies (`FrozenVecPartner`), frozen net_arch towers (`TowerFrozenVecPartner`), behavioural clones (`ClonedVecPartner`: the shared 32-32 trunk of
+    population of M <= 8 frozen 64-64 policies (`FrozenVecPartner`), frozen net_arch towers (`TowerFrozenVecPartner`), frozen ADAP
+    checkpoints under a stated or a per-table sampled latent (`AdapFrozenVecPartner`), behavioural clones (`ClonedVecPartner`: the shared 32-32 trunk of
     bc.py) and scripted players (`VecLiarDefaultPartner`); the same object
     may sit in either seat, or in both.
 
@@ -140,7 +141,8 @@ class VecLiarCrossPlay(VecLiarStep):
             if not isinstance(m, (FrozenVecPartner, ClonedVecPartner)):
                 raise nat.NativeError("VecLiarCrossPlay: members are FrozenVecPartner / ClonedVecPartner / VecLiarDefaultPartner "
                                       f"(learners train in VecLiarPartnerPool), not {type(m).__name__}")
-            check_liar_member_policy(m.policy, type(self).__name__, towers=isinstance(m, TowerFrozenVecPartner))
+            check_liar_member_policy(m.policy, type(self).__name__, towers=isinstance(m, TowerFrozenVecPartner),
+                                     adap=isinstance(m, AdapFrozenVecPartner))
             dev = dev or m.policy.device
         dev = dev or th.device("cuda", th.cuda.current_device())
         self.ctx = nat.Context(dev.index or 0)
@@ -179,6 +181,8 @@ class VecLiarCrossPlay(VecLiarStep):
         s.members, s.n_members = self._member_array(self.members), self.M
         self.towers = any(isinstance(m, TowerFrozenVecPartner) for m in self.members)      # a tower member: the `_arch` step
         self._member_archs(self.members)
+        self.adaps = any(isinstance(m, AdapFrozenVecPartner) for m in self.members)       # a frozen ADAP member: the `_adap` step
+        self._member_adaps(self.members)
         s.pairs, s.n_pairs, s.episodes_per_table = self._pairs_arr, self.P, self.G
         for name in ("ego_id", "alt_id", "ego_actions", "alt_actions", "games", "playing", "tables_left", "ep_return", "ep_length",
                      "returns", "lengths"):
@@ -187,6 +191,10 @@ class VecLiarCrossPlay(VecLiarStep):
 
     def _native_call(self, counter: int, deal_only: bool = False) -> None:
         self._bind()
+        if self.adaps:
+            nat.check(self.ctx.lib.ph_liar_xplay_step_adap(self.ctx.handle, C.byref(self._desc), self._member_arch_arr,
+                                                           self._member_adap_arr, int(counter), int(deal_only)))
+            return
         if self.towers:
             nat.check(self.ctx.lib.ph_liar_xplay_step_arch(self.ctx.handle, C.byref(self._desc), self._member_arch_arr, int(counter),
                                                            int(deal_only)))

@@ -363,6 +363,127 @@ def frozen_partner_for(policy) -> FrozenVecPartner:
     return (TowerFrozenVecPartner if is_tower(policy) else FrozenVecPartner)(policy)
 
 
+def check_adap_member_policy(policy, who: str) -> None:
+    """a frozen ADAP member plays the additive AdapPolicy on its 64-64 towers: AdapPolicyMult and net_arch are refused by name"""
+    from ..adap import AdapPolicyMult
+    if isinstance(policy, AdapPolicyMult):
+        raise nat.NativeError(f"{who}: AdapPolicyMult (ADAP_MULT) has no device-resident form; an ADAP member is the additive AdapPolicy")
+    if not is_adap(policy):
+        raise nat.NativeError(f"{who}: {type(policy).__name__} is not an AdapPolicy")
+    if is_tower(policy) or getattr(policy, "net_arch", None) is not None:
+        raise nat.NativeError(f"{who}: an AdapPolicy with policy_kwargs net_arch is not a member: ADAP members play the 64-64 towers")
+    require_mlp_kernels(policy, who)
+    C_, lay = int(policy.context_size), policy.layout
+    if not 1 <= C_ <= nat.ADAP_VEC_MAX_CONTEXT:
+        raise nat.NativeError(f"{who}: context_size must be 1..{nat.ADAP_VEC_MAX_CONTEXT}, not {C_}")
+    if (lay.D, lay.A, lay.L) != (270 + C_, 2, 19) or policy.spec.obs.kind != nat.PH_SPACE_BOX:
+        raise nat.NativeError(f"{who}: the ADAP checkpoint must play on the Liar's Dice spaces (a Box of 270 + context_size = "
+                              f"{270 + C_} row components, 2 action components, 19 logits), not (D, A, L) = {(lay.D, lay.A, lay.L)}")
+
+
+class AdapFrozenVecPartner(FrozenVecPartner):
+    """A frozen ADAP checkpoint as a pool / population member: the reference's `FIXED '{"type":"ADAP","location":...,"latent_val":
+    [...]}'` partner (trainer.py:140-147: ADAP.load, then policy.set_context) for E tables.  `latent` is
+      * an array of context_size floats -- the stated form: one latent serves every table; or
+      * the string "sample" -- every table owns a context of this member, drawn on the device with `context_sampler` (the
+        checkpoint's own) at every deal of that table, the first included: one member is a whole population of partners.
+    The member owns the (E, C) context tensor (`contexts`, allocated by the pool / population it joins).  Its Philox key `seed` --
+    the policy's, unless the population had to tell two ADAP members apart -- keys its moves and, under the ADAP salt, its contexts.
+    In the native steps its rows run the ADAP tiles of the grouped forward (pool_adap_kernel); `get_action` is the walk's form, the
+    row build (`ph_adap_rows`) plus one `ph_policy_forward` over all rows -- the same bits row by row."""
+
+    def __init__(self, policy, latent, context_sampler: str = "l2"):
+        who = type(self).__name__
+        check_adap_member_policy(policy, who)
+        self.policy, self._out = policy, {}
+        self.context_size = int(policy.context_size)
+        self.sampled = isinstance(latent, str)
+        if self.sampled:
+            if latent != "sample":
+                raise nat.NativeError(f"{who}: latent is a list of context_size numbers or the string \"sample\", not {latent!r}")
+            if context_sampler not in nat.CONTEXT_SAMPLERS:
+                raise nat.NativeError(f"{who}: unknown context sampler {context_sampler!r}")
+            if context_sampler == "natural_numbers" and self.context_size != 1:
+                raise nat.NativeError(f"{who}: context_sampler 'natural_numbers' needs context_size 1")
+            self.latent = None
+        else:
+            self.latent = np.asarray(latent, np.float32).reshape(-1)
+            if self.latent.size != self.context_size:
+                raise nat.NativeError(f"{who}: the latent holds {self.latent.size} numbers, the checkpoint's context_size is "
+                                      f"{self.context_size}")
+        self.context_sampler, self.sampler = context_sampler, nat.CONTEXT_SAMPLERS[context_sampler]
+        self.seed = int(policy._seed)
+        self.env_space = nat.env_space_of(policy.observation_space)
+        self.contexts = self.rows = None
+
+    def attach(self, n_envs: int) -> None:
+        """the member's contexts of `n_envs` tables: every row the latent (stated), or zeros until the first deal draws (sampled).
+        One object, one population: the contexts (and the seed the population gives) are the member's state, so joining a second
+        population of the same size shares them with the first, and one of another size is refused."""
+        if self.contexts is not None:
+            if int(self.contexts.shape[0]) != int(n_envs):
+                raise nat.NativeError(f"{type(self).__name__}: this member holds the contexts of {int(self.contexts.shape[0])} tables of "
+                                      f"the population it joined; build another AdapFrozenVecPartner for one of {int(n_envs)} tables")
+            return
+        dev = self.policy.device
+        self.contexts = th.zeros((int(n_envs), self.context_size), dtype=th.float32, device=dev)
+        if not self.sampled:
+            self.contexts.copy_(th.as_tensor(self.latent).to(dev).expand(int(n_envs), -1))
+        self.rows = th.zeros((int(n_envs), self.policy.layout.D), dtype=th.float32, device=dev)
+
+    def adap_struct(self) -> "nat.PhPoolAdap":
+        """this member for the `_adap` entry points (the policy keeps the spec alive)"""
+        s = nat.PhPoolAdap()
+        s.spec, s.context_size, s.sampler = C.pointer(self.policy.spec), self.context_size, self.sampler
+        s.contexts, s.draw = self.contexts.data_ptr(), int(self.sampled)
+        return s
+
+    def redraw(self, flags, counter: int) -> None:
+        """the walk's redraw: a fresh context, drawn at `counter`, for the tables flagged in `flags` (uint8) -- the launch of the
+        native step under the same mask"""
+        if not self.sampled:
+            return
+        pol = self.policy
+        pol._bind()
+        nat.check(pol.ctx.lib.ph_adap_context_draw(pol.ctx.handle, self.sampler, self.context_size, self.seed, int(counter),
+                                                   nat.ptr(flags), self.contexts.data_ptr(), int(self.contexts.shape[0])))
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
+        pol = self.policy
+        n = int(obs.shape[0])
+        if self.contexts is None or int(self.contexts.shape[0]) != n:
+            raise nat.NativeError(f"{type(self).__name__}: attach({n}) first: the member owns one context per table")
+        out = self._out.get(n)
+        if out is None:
+            out = self._out[n] = (th.zeros((n, pol.layout.A), dtype=th.int32, device=pol.device),
+                                  th.zeros(n, dtype=th.float32, device=pol.device), th.zeros(n, dtype=th.float32, device=pol.device))
+        pol._bind()
+        pol._counter += 1
+        lib, h = pol.ctx.lib, pol.ctx.handle
+        nat.check(lib.ph_adap_rows(h, C.byref(self.env_space), self.context_size, obs.data_ptr(), self.contexts.data_ptr(), None,
+                                   self.rows.data_ptr(), n))
+        nat.check(lib.ph_policy_forward(
+            h, C.byref(pol.spec), pol.params.data_ptr(), self.rows.data_ptr(), n, None, None, None, self.seed, pol._counter,
+            0, out[0].data_ptr(), None, out[1].data_ptr(), out[2].data_ptr(), None, None, None, 0, None, None, 0))
+        return out[0]
+
+
+def attach_adap_members(members, n_envs: int) -> None:
+    """give every ADAP member of a pool / population its contexts of n_envs tables, and a Philox key of its own: two ADAP members
+    with one seed -- the same file loaded twice -- would draw one stream of contexts (and of moves), so a later one is moved to
+    seed + k * the golden-ratio word until it is free"""
+    taken = set()
+    for k, m in enumerate(members):
+        if not isinstance(m, AdapFrozenVecPartner):
+            continue
+        seed = int(m.policy._seed)
+        while seed in taken:
+            seed = (seed + (k + 1) * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+        taken.add(seed)
+        m.seed = seed
+        m.attach(n_envs)
+
+
 class ClonedVecPartner:
     """A pool / population member that plays a behavioural clone: a `FeedForward32Policy` (bc.py: one shared 32-32 tanh trunk,
     parameters in ph_bc_layout) on the Liar's Dice spaces -- the "human proxy" partner of the reference's workflow (train, record,
@@ -399,10 +520,19 @@ class ClonedVecPartner:
         return None
 
 
-def check_liar_member_policy(policy, who: str, towers: bool = False) -> None:
+def check_liar_member_policy(policy, who: str, towers: bool = False, adap: bool = False) -> None:
     """a pool / population member's policy runs on the grouped forward's kernels and plays on the Liar's Dice spaces: the 64-64
     layout through `require_mlp_kernels`, a clone's through its BC layout (ClonedVecPartner has checked the one-hot observation);
-    `towers`: a net_arch tower whose forward carve fits the CU is taken too (the `_arch` steps)"""
+    `towers`: a net_arch tower whose forward carve fits the CU is taken too (the `_arch` steps); `adap`: the policy is held by an
+    AdapFrozenVecPartner -- the additive AdapPolicy over Box(270 + C) rows (the `_adap` steps)"""
+    from ..adap import AdapPolicy
+    if adap:
+        check_adap_member_policy(policy, who)
+        return
+    if isinstance(policy, AdapPolicy):
+        raise nat.NativeError(f"{who}: an AdapPolicy sits in a pool or population only as AdapFrozenVecPartner(policy, latent) -- a "
+                              "frozen checkpoint under a latent, in liar_pool_for's pool or a VecLiarCrossPlay; an ADAP learner or "
+                              "an ADAP ego does not")
     if towers and is_tower(policy):
         require_tower_lds(policy, who)
     elif not isinstance(policy, FeedForward32Policy):
@@ -511,6 +641,7 @@ class VecLiarStep:
         self.steps_done = 0
         self.recording = False
         self._ctxs = tuple(dict.fromkeys(self._contexts()))     # each engine context once: `_bind` runs in front of every step
+        attach_adap_members(getattr(self, "members", ()), self.E)
 
     def _first_deal(self) -> None:
         """the constructor's deal: step 0's re-deal half for every table"""
@@ -564,6 +695,8 @@ class VecLiarStep:
             if p is None:
                 continue
             c.params, c.seed = p.params.data_ptr(), p._seed       # (a clone: its ph_bc_layout vector and key, nothing else)
+            if isinstance(m, AdapFrozenVecPartner):
+                c.seed = m.seed                                   # (its own key where two ADAP members loaded one file)
             if learner:
                 rbc = m.model.rollout_buffer.c_struct()
                 self._member_rbc.append(rbc)
@@ -583,6 +716,18 @@ class VecLiarStep:
                 archs[k] = C.pointer(p.arch)
         self._member_arch_arr = archs
         return archs
+
+    def _member_adaps(self, members):
+        """the `member_adaps` array of the `_adap` steps: entry k points at member k's ph_pool_adap where it is an
+        AdapFrozenVecPartner, else NULL (`_member_adap_keep` keeps the structs alive)"""
+        adaps = (C.POINTER(nat.PhPoolAdap) * len(members))()
+        self._member_adap_keep = []
+        for k, m in enumerate(members):
+            if isinstance(m, AdapFrozenVecPartner):
+                self._member_adap_keep.append(m.adap_struct())
+                adaps[k] = C.pointer(self._member_adap_keep[-1])
+        self._member_adap_arr = adaps
+        return adaps
 
     # -- the move log (csrc/ph_record.h): TurnBasedRecorder's rows of every table, filled inside the step ----------------------------
     def start_recording(self, max_moves_per_table: int) -> None:
@@ -729,6 +874,9 @@ class VecLiarStep:
                                     self.E))
         rm = reset_mask.bool()
         self._on_deal(rm, c)
+        for m in getattr(self, "members", ()):                      # a sampling ADAP member: a fresh context in every table dealt
+            if isinstance(m, AdapFrozenVecPartner):
+                m.redraw(reset_mask, c)
         alt_opens = (rm & ~self.ego_first.bool()).to(th.uint8)
         nat.check(lib.ph_liar_obs(h, *game, self.zeros8.data_ptr(), alt_opens.data_ptr(), self.obs_alt.data_ptr(), self.E))
         a_alt = self._seat_act(1, self.obs_alt, alt_opens, self._counters(c)[2])
@@ -1001,7 +1149,7 @@ class VecLiarPartnerPool(VecLiarTraining):
                 continue
             if isinstance(p, FeedForward32Policy) and not isinstance(who, ClonedVecPartner):
                 raise nat.NativeError("VecLiarPartnerPool: a FeedForward32Policy is seated as ClonedVecPartner(policy)")
-            self._check_member(p)
+            self._check_member(p, who)
         self.learners = [m for m in members if isinstance(m, RaggedVecOnPolicyAgent)]
         for m in self.learners:
             if m.E != n_envs:
@@ -1017,7 +1165,7 @@ class VecLiarPartnerPool(VecLiarTraining):
             self.start_recording(record)
         self._first_deal()
 
-    def _check_member(self, policy) -> None:
+    def _check_member(self, policy, seat=None) -> None:
         check_liar_member_policy(policy, type(self).__name__)
 
     def _contexts(self):
@@ -1080,7 +1228,7 @@ class TowerVecLiarPartnerPool(VecLiarPartnerPool):
     (`ph_liar_pool_step_arch`: tower tiles of the grouped forward run in pool_tower_kernel).  The walk is the plain class's: the
     member classes' own get_action / update."""
 
-    def _check_member(self, policy) -> None:
+    def _check_member(self, policy, seat=None) -> None:
         check_liar_member_policy(policy, type(self).__name__, towers=True)
 
     def _member_array(self, members):
@@ -1096,9 +1244,33 @@ class TowerVecLiarPartnerPool(VecLiarPartnerPool):
                                                  int(rb.pos if ego_pos < 0 else ego_pos), int(counter), int(deal_only)))
 
 
+class AdapVecLiarPartnerPool(TowerVecLiarPartnerPool):
+    """TowerVecLiarPartnerPool whose members may also be frozen ADAP checkpoints (AdapFrozenVecPartner, stated or sampled latent).
+    It differs in its member check, in the ADAP descriptions kept beside the member array, and in its native call
+    (`ph_liar_pool_step_adap`: ADAP tiles of the grouped forward run in pool_adap_kernel, a sampling member's contexts are redrawn
+    behind the pass that ends games).  The walk is the plain class's, with the members' own redraw at every deal."""
+
+    def _check_member(self, policy, seat=None) -> None:
+        check_liar_member_policy(policy, type(self).__name__, towers=True, adap=isinstance(seat, AdapFrozenVecPartner))
+
+    def _member_array(self, members):
+        arr = super()._member_array(members)
+        self._member_adaps(members)
+        return arr
+
+    def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
+        self._bind()
+        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
+        nat.check(ctx.lib.ph_liar_pool_step_adap(ctx.handle, C.byref(self._desc), self._ego_arch, self._member_arch_arr,
+                                                 self._member_adap_arr, int(rb.pos if ego_pos < 0 else ego_pos), int(counter),
+                                                 int(deal_only)))
+
+
 def liar_pool_for(n_envs: int, ego, members, **kwargs) -> VecLiarPartnerPool:
-    """the pool class that runs `ego` and `members`: the plain one when nobody plays a tower"""
+    """the pool class that runs `ego` and `members`: the plain one when nobody plays a tower or a frozen ADAP checkpoint"""
     members = list(members)
+    if any(isinstance(m, AdapFrozenVecPartner) for m in members):
+        return AdapVecLiarPartnerPool(n_envs, ego, members, **kwargs)
     pols = [VecLiarStep._policy_of(m) for m in [ego] + members]
     towers = any(p is not None and is_tower(p) for p in pols)
     return (TowerVecLiarPartnerPool if towers else VecLiarPartnerPool)(n_envs, ego, members, **kwargs)

@@ -292,13 +292,42 @@ def pool_plan(args):
         if kind == "FIXED":
             if "type" not in config or "location" not in config:
                 raise EnvException("a FIXED partner needs 'type' and 'location' in its --alt-config")
-            if config["type"] not in ("PPO", "BC"):
+            if config["type"] == "ADAP" and "latent_val" in config:
+                config["latent_val"] = check_adap_latent(config["latent_val"], "a FIXED ADAP member's latent_val")
+            elif config["type"] not in ("PPO", "BC"):
                 raise EnvException("a FIXED member must be a PPO checkpoint (the 64-64 MlpPolicy) or a BC policy (bctrainer's "
-                                   f"shared 32-32 trunk), not {config['type']}")
+                                   "shared 32-32 trunk) or an ADAP checkpoint with 'latent_val' (a list of context_size numbers, or "
+                                   f"\"sample\": a context per table, redrawn at every deal), not {config['type']}")
         elif kind == "DEFAULT" and config:
             raise EnvException("No config possible for this default agent")
         members.append((kind, config))
     return dict(members=members, resample=resample, env_config=env_config, log_interval=log_interval)
+
+
+def check_adap_latent(latent, what: str):
+    """the latent of a frozen ADAP member of the device-resident pool / population: the string "sample" (a context per table, drawn
+    with the checkpoint's sampler at every deal) or a list of numbers (the reference's latent_val, trainer.py:140-147; its length is
+    held against the checkpoint's context_size when the file is loaded) -> "sample" or a list of floats"""
+    if isinstance(latent, str):
+        if latent != "sample":
+            raise EnvException(f"{what} is a list of context_size numbers or \"sample\", not {latent!r}")
+        return latent
+    ok = isinstance(latent, (list, tuple)) and 1 <= len(latent) <= 64 and all(
+        isinstance(v, (int, float)) and not isinstance(v, bool) and v == v for v in latent)
+    if not ok:
+        raise EnvException(f"{what} is a list of context_size (1..64) numbers or \"sample\", not {latent!r}")
+    return [float(v) for v in latent]
+
+
+def load_adap_member(location, latent, device):
+    """a frozen ADAP checkpoint as a member of the device-resident pool / population (envs/vec.py: AdapFrozenVecPartner) under
+    `latent`: the reference's FIXED ADAP partner (trainer.py:140-147: ADAP.load, then set_context) for every table"""
+    from .envs.vec import AdapFrozenVecPartner
+    model = ADAP.load(location, device=device)
+    try:
+        return AdapFrozenVecPartner(model.policy, latent, model.context_sampler)
+    except Exception as e:     # the member's own words (AdapPolicyMult, a latent of another length, ...)
+        raise EnvException(str(e)) from e
 
 
 ADAP_VEC_ENVS = ("RPS-v0", "LiarsDice-v0")
@@ -345,7 +374,8 @@ def record_capacity(iterations: int, n_steps: int) -> int:
 
 def run_pool(args, plan):
     """the pool's object graph: the ego, one member per partner argument, `VecLiarPartnerPool.rollout_and_learn` per iteration
-    (`liar_pool_for`: the tower pool where the ego, a learner or a FIXED PPO checkpoint has policy_kwargs net_arch)"""
+    (`liar_pool_for`: the tower pool where the ego, a learner or a FIXED PPO checkpoint has policy_kwargs net_arch, the ADAP pool
+    where a FIXED member is an ADAP checkpoint under a latent_val)"""
     import random as _random
 
     import torch as th
@@ -376,8 +406,11 @@ def run_pool(args, plan):
             models.append(learner(config, i + 1))
             members.append(ragged_agent_for(models[-1]))
         elif kind == "FIXED":
-            seat = ClonedVecPartner if config["type"] == "BC" else frozen_partner_for
-            members.append(seat(gen_load(config, config["type"], config["location"]).policy))
+            if config["type"] == "ADAP":
+                members.append(load_adap_member(config["location"], config["latent_val"], config.get("device", args.device)))
+            else:
+                seat = ClonedVecPartner if config["type"] == "BC" else frozen_partner_for
+                members.append(seat(gen_load(config, config["type"], config["location"]).policy))
         else:
             members.append(VecLiarDefaultPartner())
         print(f"Partner {i}: {members[-1]}")

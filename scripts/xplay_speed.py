@@ -10,7 +10,11 @@ Median of 5 runs per variant, the variants alternating within a round; the host 
 behavioural clones (ClonedVecPartner: the shared 32-32 trunk), two of each -- and reports games/s and microseconds per vectorised
 step for each, with the spread over the runs.
 `--towers` does the same for `policy_kwargs net_arch` towers (TowerFrozenVecPartner, pool_tower_kernel): four frozen 64-64 members
-(the yardstick), four (128, 128) towers, two and two, four (64, 64, 64) towers, and the walk of the two-and-two population."""
+(the yardstick), four (128, 128) towers, two and two, four (64, 64, 64) towers, and the walk of the two-and-two population.
+`--adap` does the same for frozen ADAP checkpoints (AdapFrozenVecPartner, pool_adap_kernel; context_size 3): four frozen 64-64
+members (the yardstick), four under a stated latent, four under sampled latents, two frozen and two ADAP (one of each form), and the
+walk of that last population.  `--yardstick` times the yardstick population alone (for a comparison of two builds of the library,
+one process each)."""
 import argparse
 import contextlib
 import io
@@ -27,8 +31,8 @@ from pantheonrl_amd.common import StaticPolicyAgent  # noqa: E402
 from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay  # noqa: E402
 from pantheonrl_amd.envs.liar import LiarEnv  # noqa: E402
 from pantheonrl_amd.bc import FeedForward32Policy  # noqa: E402
-from pantheonrl_amd.envs.vec import (ClonedVecPartner, FrozenVecPartner, TowerFrozenVecPartner, VecLiarDefaultPartner,  # noqa: E402
-                                     VecLiarsDice)
+from pantheonrl_amd.envs.vec import (AdapFrozenVecPartner, ClonedVecPartner, FrozenVecPartner, TowerFrozenVecPartner,  # noqa: E402
+                                     VecLiarDefaultPartner, VecLiarsDice)
 from pantheonrl_amd.tester import run_test  # noqa: E402
 
 E, G, ROUNDS = 256, 40, 5
@@ -39,6 +43,8 @@ _p.add_argument("--host-games", type=int, default=E * G)
 _p.add_argument("--out")
 _p.add_argument("--clones", action="store_true")
 _p.add_argument("--towers", action="store_true")
+_p.add_argument("--adap", action="store_true")
+_p.add_argument("--yardstick", action="store_true")
 _args = _p.parse_args()
 MS = [int(m) for m in _args.ms.split(",")]
 spaces = type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
@@ -125,8 +131,28 @@ def tower_sweep():
     sweep("cross-play of Liar's Dice with net_arch towers, native step", pops)
 
 
-if _args.clones or _args.towers:
-    clone_sweep() if _args.clones else tower_sweep()
+def adap_sweep():
+    """M = 4: frozen x 4 | ADAP stated x 4 | ADAP sampled x 4 | frozen x 2 + ADAP x 2 | the walk of the last"""
+    import numpy as np
+    from pantheonrl_amd.adap import ADAP, AdapPolicy
+    adaps = [ADAP(AdapPolicy, spaces, context_size=3, n_steps=2, n_envs=4, batch_size=4, n_epochs=1, seed=80 + k).policy for k in range(4)]
+    latent = lambda k: np.random.default_rng(80 + k).standard_normal(3).astype(np.float32)  # noqa: E731
+    mixed = lambda: [FrozenVecPartner(policies[0]), AdapFrozenVecPartner(adaps[0], latent(0)), FrozenVecPartner(policies[1]),  # noqa: E731
+                     AdapFrozenVecPartner(adaps[1], "sample")]
+    pops = {"frozen x4 (yardstick)": (lambda: [FrozenVecPartner(policies[k]) for k in range(4)], True),
+            "ADAP stated x4": (lambda: [AdapFrozenVecPartner(adaps[k], latent(k)) for k in range(4)], True),
+            "ADAP sampled x4": (lambda: [AdapFrozenVecPartner(adaps[k], "sample") for k in range(4)], True),
+            "frozen x2 + ADAP x2 (stated, sampled)": (mixed, True),
+            "walk of frozen x2 + ADAP x2": (mixed, False)}
+    sweep("cross-play of Liar's Dice with frozen ADAP checkpoints (context_size 3), native step", pops)
+
+
+if _args.yardstick:
+    sweep("cross-play of Liar's Dice, native step, the yardstick population alone",
+          {"frozen x4 (yardstick)": (lambda: [FrozenVecPartner(policies[k]) for k in range(4)], True)})
+    sys.exit(0)
+if _args.clones or _args.towers or _args.adap:
+    clone_sweep() if _args.clones else tower_sweep() if _args.towers else adap_sweep()
     sys.exit(0)
 
 
