@@ -104,8 +104,9 @@ def native_spec(case: Case):
     return sp.make_spec(H.to_space(case.obs), H.to_space(case.act))
 
 
-def checker(case: Case, N: int, seed: int = 3):
-    """-> (FeedForward32Oracle perturbed as tests/test_gpu_bc._pair does, obs (N, D), acts (N, A)), all seeded"""
+def checker(case: Case, N: int, seed: int = 3, prepare=None):
+    """-> (FeedForward32Oracle perturbed as tests/test_gpu_bc._pair does, obs (N, D), acts (N, A)), all seeded.
+    prepare(checker): called on the checker right after it is built (tests/sharp_cases.py sharpens its last layer there)"""
     rng = np.random.default_rng(seed)
     obs = H.sample_obs(case.obs, N, rng)
     acts = np.stack([rng.integers(0, k, size=N) for k in case.act.nvec], axis=1).astype(np.float32)
@@ -115,6 +116,8 @@ def checker(case: Case, N: int, seed: int = 3):
         g = th.Generator().manual_seed(seed + 1)
         for p in orac.parameters():
             p.add_(0.2 * th.randn(p.shape, generator=g) * (1.0 if p.ndim == 1 else 0.3))
+    if prepare is not None:
+        prepare(orac)
     return orac, obs, acts
 
 

@@ -48,14 +48,17 @@ def _context_samples(cs, nb, n_ctx, n_states, seed):
     return sidx, orc.adap_sample_contexts("l2", cs, n_ctx, rng.random((n_ctx, cs)))
 
 
-def _grad_pair(name, T, E, idx, hp, n_ctx, n_states, coef, seed=5, sampler=None, gemm_mode=0, fill=None):
+def _grad_pair(name, T, E, idx, hp, n_ctx, n_states, coef, seed=5, sampler=None, gemm_mode=0, fill=None, prepare=None):
     """device and oracle gradient of one minibatch with the context term; samples teacher-forced unless `sampler`.  fill: another
     buffer builder than helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py); idx may be a function (checker,
-    buffer) -> rows"""
+    buffer) -> rows.  prepare(checker): called on the checker right after it is built, before the buffer and the
+    device policy are made (tests/sharp_cases.py sharpens its action head there)"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
     cs = CTX[name]
     orac = H.oracle_policy(name, seed=seed)
+    if prepare is not None:
+        prepare(orac)
     ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
     if callable(idx):
         idx = idx(orac, ob)

@@ -104,13 +104,16 @@ def _hyper(nat, hp):
     return PPO.hyper(model)
 
 
-def _grad_pair(name, T, E, nb, hp, coef=None, n_ctx=5, n_states=32, seed=5, fill=None, idx=None):
+def _grad_pair(name, T, E, nb, hp, coef=None, n_ctx=5, n_states=32, seed=5, fill=None, idx=None, prepare=None):
     """fill: another buffer builder than helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py); idx: the minibatch
-    rows, or a function (checker, buffer) -> rows, instead of the first nb of a seeded permutation"""
+    rows, or a function (checker, buffer) -> rows, instead of the first nb of a seeded permutation.  prepare(checker): called on the checker right after it is built, before the buffer and the
+    device policy are made (tests/sharp_cases.py sharpens its action head there)"""
     from pantheonrl_amd import _native as nat
     from tests.test_gpu_adap import _adap_struct, _context_samples
     cs = CTX[name]
     orac = _oracle(name, seed=seed)
+    if prepare is not None:
+        prepare(orac)
     ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
     pol = _device(name, orac)
     buf = H.make_device_buffer(name, pol, T, E)

@@ -135,12 +135,15 @@ def test_forward_and_store_writes_the_row_forward_plus_add_writes(name, arch):
 
 
 # ---- minibatch gradient --------------------------------------------------------------------------------------------------------
-def _grad_pair(name, arch, T, E, idx, hp, seed=11, gemm_mode=0, fill=None):
+def _grad_pair(name, arch, T, E, idx, hp, seed=11, gemm_mode=0, fill=None, prepare=None):
     """fill: another buffer builder than helpers.filled_oracle_buffer (a stale buffer: tests/offpolicy_cases.py); idx may be a
-    function (checker, buffer) -> rows"""
+    function (checker, buffer) -> rows.  prepare(checker): called on the checker right after it is built, before the buffer and the
+    device policy are made (tests/sharp_cases.py sharpens its action head there)"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
     orac = A.oracle_policy(name, arch, seed=seed)
+    if prepare is not None:
+        prepare(orac)
     ob = (fill or H.filled_oracle_buffer)(name, orac, T, E, seed=seed)
     if callable(idx):
         idx = idx(orac, ob)

@@ -182,13 +182,16 @@ def test_forward_and_store_writes_the_partner_rollout_row():
 # ----------------------------------------------------------------------------------------------------------------
 # one minibatch: the gradient of the whole loss (learn.py:244-318) w.r.t. every parameter
 # ----------------------------------------------------------------------------------------------------------------
-def _grad_pair(name, K, partner, T, E, nb, coef, hp, kw=None, seed=5, gemm_mode=0, fill=None, idx=None):
+def _grad_pair(name, K, partner, T, E, nb, coef, hp, kw=None, seed=5, gemm_mode=0, fill=None, idx=None, prepare=None):
     """fill: another buffer builder (name, checker, T, E, seed=) than _filled (a stale buffer: tests/offpolicy_cases.py); idx: the
-    minibatch rows, or a function (checker, buffer) -> rows, instead of the first nb of a seeded permutation"""
+    minibatch rows, or a function (checker, buffer) -> rows, instead of the first nb of a seeded permutation.  prepare(checker): called on the checker right after it is built, before the buffer and the
+    device policy are made (tests/sharp_cases.py sharpens its action head there)"""
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.modular import ModularAlgorithm  # noqa: F401  (import check)
     kw = kw or {}
     orac = _oracle(name, K, seed=seed, **kw)
+    if prepare is not None:
+        prepare(orac)
     ob = fill(name, orac, T, E, seed=seed) if fill is not None else _filled(orac, name, partner, T, E, seed=seed)
     pol = _device(name, orac, K, **kw)
     pol.gemm_mode = gemm_mode

@@ -290,16 +290,20 @@ def test_buffer_add_reward_reset_and_fused_step():
 # ----------------------------------------------------------------------------------------------------------------
 # K3/K5/K6 PPO update
 # ----------------------------------------------------------------------------------------------------------------
-def _grad_pair(name, T, E, idx, hp: orc.PPOHyper, seed=11, gemm_mode=0, f64=False, obs_fn=None, w1_scale=1.0, fill=None):
+def _grad_pair(name, T, E, idx, hp: orc.PPOHyper, seed=11, gemm_mode=0, f64=False, obs_fn=None, w1_scale=1.0, fill=None,
+               prepare=None):
     """device minibatch gradient, the oracle's autograd gradient (float32 as the reference computes it; f64: the same graph in
     float64 -- the yardstick for "which float32 path is closer to the true gradient").  obs_fn: other observation
     distributions than N(0, 1); w1_scale multiplies both first-layer weight matrices (keeps pre-activations in tanh's live range
     when the observations are rescaled).  fill: another buffer builder than helpers.filled_oracle_buffer (a stale buffer:
-    tests/offpolicy_cases.py); idx may be a function (checker, buffer) -> rows"""
+    tests/offpolicy_cases.py); idx may be a function (checker, buffer) -> rows.  prepare(checker): called on the checker right after it is built, before the buffer and the
+    device policy are made (tests/sharp_cases.py sharpens its action head there)"""
     import ctypes as C
     from pantheonrl_amd import _native as nat
     from pantheonrl_amd.ppo import PPO
     orac = H.oracle_policy(name, seed=seed)
+    if prepare is not None:
+        prepare(orac)
     if w1_scale != 1.0:
         with th.no_grad():
             orac.policy_net[0].weight.mul_(w1_scale)

@@ -49,8 +49,9 @@ def _np(t, shape=None):
 
 
 # ---- a. categorical heads, own draws; b. the negative control ---------------------------------------------------------------------------
-def _device(case):
-    orac = S.checker(case.id)
+def _device(case, orac=None):
+    """the case's device object holding the parameters of `orac` (default: the case's cached checker)"""
+    orac = S.checker(case.id) if orac is None else orac
     if case.family == "mlp":
         return H.device_policy(case.name, orac)
     if case.family == "arch":
