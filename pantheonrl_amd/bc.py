@@ -96,11 +96,14 @@ class FeedForward32Policy:
         m = None if mask is None else th.as_tensor(mask).to(device=dev, dtype=th.uint8).reshape(n, lay.L).contiguous()
         self.ctx.set_stream(th.cuda.current_stream(dev).cuda_stream)
         self._counter += 1
-        nat.check(self.ctx.lib.ph_bc_forward(self.ctx.handle, C.byref(self.spec), self.params.data_ptr(), obs_t.data_ptr(), n,
-                                             nat.ptr(m), nat.ptr(u), nat.ptr(g), self._seed, self._counter,
-                                             int(bool(deterministic)), acts.data_ptr(), values.data_ptr(), logp.data_ptr(),
-                                             ent.data_ptr(), nat.ptr(logits)))
+        nat.check(self._native_forward(self.params.data_ptr(), obs_t.data_ptr(), n, nat.ptr(m), nat.ptr(u), nat.ptr(g), self._seed,
+                                       self._counter, int(bool(deterministic)), acts.data_ptr(), values.data_ptr(), logp.data_ptr(),
+                                       ent.data_ptr(), nat.ptr(logits)))
         return acts, values.reshape(n, 1), logp, ent, logits
+
+    def _native_forward(self, *args) -> int:
+        """the forward entry point of this policy's network: ph_bc_forward's arguments after the spec"""
+        return self.ctx.lib.ph_bc_forward(self.ctx.handle, C.byref(self.spec), *args)
 
     def forward(self, obs, deterministic: bool = False, action_mask=None, uniforms=None):
         """-> (actions, values (n,1), log_prob (n,)) like ActorCriticPolicy.forward (util.py:79): usable by StaticPolicyAgent"""

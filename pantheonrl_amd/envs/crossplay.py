@@ -178,11 +178,9 @@ class VecLiarCrossPlay(VecLiarStep):
         self._pairs_arr = (C.c_int * (2 * self.P))(*[int(v) for v in self.pairs.reshape(-1)])
         s = self._fill_game(nat.PhLiarXplay(), book=False)
         s.spec = C.pointer(self.spec)
-        s.members, s.n_members = self._member_array(self.members), self.M
-        self.towers = any(isinstance(m, TowerFrozenVecPartner) for m in self.members)      # a tower member: the `_arch` step
-        self._member_archs(self.members)
-        self.adaps = any(isinstance(m, AdapFrozenVecPartner) for m in self.members)       # a frozen ADAP member: the `_adap` step
-        self._member_adaps(self.members)
+        self.towers = any(isinstance(m, TowerFrozenVecPartner) for m in self.members)      # a tower member: the step needs the archs
+        self.adaps = any(isinstance(m, AdapFrozenVecPartner) for m in self.members)       # a frozen ADAP member: archs and descriptions
+        s.members, s.n_members = self._member_arrays(self.members, self.towers or self.adaps, self.adaps), self.M
         s.pairs, s.n_pairs, s.episodes_per_table = self._pairs_arr, self.P, self.G
         for name in ("ego_id", "alt_id", "ego_actions", "alt_actions", "games", "playing", "tables_left", "ep_return", "ep_length",
                      "returns", "lengths"):
@@ -191,15 +189,9 @@ class VecLiarCrossPlay(VecLiarStep):
 
     def _native_call(self, counter: int, deal_only: bool = False) -> None:
         self._bind()
-        if self.adaps:
-            nat.check(self.ctx.lib.ph_liar_xplay_step_adap(self.ctx.handle, C.byref(self._desc), self._member_arch_arr,
-                                                           self._member_adap_arr, int(counter), int(deal_only)))
-            return
-        if self.towers:
-            nat.check(self.ctx.lib.ph_liar_xplay_step_arch(self.ctx.handle, C.byref(self._desc), self._member_arch_arr, int(counter),
-                                                           int(deal_only)))
-            return
-        nat.check(self.ctx.lib.ph_liar_xplay_step(self.ctx.handle, C.byref(self._desc), int(counter), int(deal_only)))
+        # the widest entry point; an array no member needs is None (`_member_arrays`): the narrow entry points' own forward
+        nat.check(self.ctx.lib.ph_liar_xplay_step_adap(self.ctx.handle, C.byref(self._desc), self._member_arch_arr,
+                                                       self._member_adap_arr, int(counter), int(deal_only)))
 
     # -- the walk's hooks ----------------------------------------------------------------------------------------------------------
     def _seat_act(self, seat: int, obs: th.Tensor, mask: th.Tensor, counter: int) -> th.Tensor:

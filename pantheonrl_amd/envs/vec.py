@@ -128,10 +128,6 @@ class RaggedVecOnPolicyAgent:
     def _require_kernels(self, pol) -> None:
         require_mlp_kernels(pol, type(self).__name__)     # ph_policy_forward_ragged and the self-play steps read a ph_layout vector
 
-    def _forward_ragged(self, pol, *args) -> int:
-        """ph_policy_forward_ragged's arguments from `params` on"""
-        return self._lib.ph_policy_forward_ragged(self._h, self._spec, *args)
-
     def get_action(self, obs: th.Tensor, rec_mask: th.Tensor) -> th.Tensor:
         """forward in every env; record the transition where rec_mask is set and the column still has room"""
         pol = self.model.policy
@@ -141,8 +137,8 @@ class RaggedVecOnPolicyAgent:
         blocked = rec_mask.bool() & ~room
         es = self.boundary.to(th.float32)
         pol._counter += 1
-        nat.check(self._forward_ragged(
-            pol, pol.params.data_ptr(), obs.data_ptr(), None, pol._seed, pol._counter, 0,
+        nat.check(pol._native_forward_ragged(       # the entry point of the policy's network (ppo.py)
+            pol.params.data_ptr(), obs.data_ptr(), None, pol._seed, pol._counter, 0,
             self.actions.data_ptr(), self.values.data_ptr(), self.log_probs.data_ptr(), self._rb, self.pos.data_ptr(),
             can.data_ptr(), es.data_ptr()))
         nat.check(self._lib.ph_ragged_advance(self._h, self._rb, self.pos.data_ptr(), can.data_ptr()))
@@ -217,17 +213,15 @@ class RaggedVecOnPolicyAgent:
 
 
 class TowerRaggedVecOnPolicyAgent(RaggedVecOnPolicyAgent):
-    """RaggedVecOnPolicyAgent for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): get_action is ph_arch_forward_ragged;
-    everything else is inherited (the updates end in model.train(), which dispatches to ph_arch_train)."""
+    """RaggedVecOnPolicyAgent for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): the class is what it accepts, a tower
+    whose forward carve fits the CU.  get_action runs the ragged forward the policy names (the tower kernels), and the updates end
+    in model.train(), which dispatches to ph_arch_train."""
 
     def _require_kernels(self, pol) -> None:
         if not is_tower(pol):
             raise nat.NativeError(f"{type(self).__name__}: {type(pol).__name__} is not a net_arch tower policy; use "
                                   "RaggedVecOnPolicyAgent")
         require_tower_lds(pol, type(self).__name__)
-
-    def _forward_ragged(self, pol, *args) -> int:
-        return self._lib.ph_arch_forward_ragged(self._h, self._spec, C.byref(pol.arch), *args, int(pol.gemm_mode))
 
 
 class AdapRaggedVecOnPolicyAgent(AdapSeat, RaggedVecOnPolicyAgent):
@@ -304,15 +298,27 @@ class FrozenVecPartner:
     kind = nat.PH_POOL_FROZEN
 
     def __init__(self, policy):
+        self._require_kernels(policy)
+        self.policy = policy
+        self._out = {}
+
+    def _require_kernels(self, policy) -> None:
+        """what this member class accepts (the subclasses override it)"""
         if isinstance(policy, FeedForward32Policy):
             # its ph_bc_layout vector (one shared 32-32 trunk) is a sixth of the 64-64 ph_layout vector the frozen forward reads
             raise nat.NativeError(f"{type(self).__name__}: a FeedForward32Policy (the shared 32-32 trunk of behavioural cloning) is "
                                   "not a 64-64 policy; seat it as ClonedVecPartner(policy)")
         require_mlp_kernels(policy, type(self).__name__)
-        self.policy = policy
-        self._out = {}
 
-    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
+    def _rows(self, obs: th.Tensor) -> th.Tensor:
+        """what the forward reads: the game's observations (the ADAP member builds its rows from them)"""
+        return obs
+
+    def _forward(self, obs: th.Tensor, seed: int) -> th.Tensor:
+        """every frozen member's move, written once: the output buffers of n rows (allocated at the first call with that n), the
+        policy's engine context on the current stream, the next Philox counter, and ONE forward of the member's rows through the
+        entry point the policy names for its network (ppo.py: `_native_forward`) under the key `seed` -- no buffer, no mask,
+        nothing recorded"""
         pol = self.policy
         n = int(obs.shape[0])
         out = self._out.get(n)
@@ -321,10 +327,13 @@ class FrozenVecPartner:
                                   th.zeros(n, dtype=th.float32, device=pol.device), th.zeros(n, dtype=th.float32, device=pol.device))
         pol._bind()
         pol._counter += 1
-        nat.check(pol.ctx.lib.ph_policy_forward(
-            pol.ctx.handle, C.byref(pol.spec), pol.params.data_ptr(), obs.data_ptr(), n, None, None, None, pol._seed, pol._counter,
+        nat.check(pol._native_forward(
+            pol.params.data_ptr(), self._rows(obs).data_ptr(), n, None, None, None, seed, pol._counter,
             0, out[0].data_ptr(), None, out[1].data_ptr(), out[2].data_ptr(), None, None, None, 0, None, None, 0))
         return out[0]
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
+        return self._forward(obs, self.policy._seed)
 
     def update(self, reward, done, mask=None) -> None:
         return None
@@ -333,29 +342,13 @@ class FrozenVecPartner:
 class TowerFrozenVecPartner(FrozenVecPartner):
     """FrozenVecPartner for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): a fixed tower policy as a pool / population
     member.  In the native steps its rows run the tower tiles of the grouped forward (pool_tower_kernel); `get_action` is the walk's
-    form, one `ph_arch_forward` over all rows -- the same bits row by row."""
+    form, one tower forward over all rows (the base class's, through the policy's entry point) -- the same bits row by row."""
 
-    def __init__(self, policy):
+    def _require_kernels(self, policy) -> None:
         who = type(self).__name__
         if not is_tower(policy):
             raise nat.NativeError(f"{who}: {type(policy).__name__} is not a net_arch tower policy; use FrozenVecPartner")
         require_tower_lds(policy, who)
-        self.policy = policy
-        self._out = {}
-
-    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
-        pol = self.policy
-        n = int(obs.shape[0])
-        out = self._out.get(n)
-        if out is None:
-            out = self._out[n] = (th.zeros((n, pol.layout.A), dtype=th.int32, device=pol.device),
-                                  th.zeros(n, dtype=th.float32, device=pol.device), th.zeros(n, dtype=th.float32, device=pol.device))
-        pol._bind()
-        pol._counter += 1
-        nat.check(pol.ctx.lib.ph_arch_forward(
-            pol.ctx.handle, C.byref(pol.spec), C.byref(pol.arch), pol.params.data_ptr(), obs.data_ptr(), n, None, None, None, pol._seed,
-            pol._counter, 0, out[0].data_ptr(), None, out[1].data_ptr(), out[2].data_ptr(), None, None, None, 0, None, None, 0))
-        return out[0]
 
 
 def frozen_partner_for(policy) -> FrozenVecPartner:
@@ -390,12 +383,14 @@ class AdapFrozenVecPartner(FrozenVecPartner):
     The member owns the (E, C) context tensor (`contexts`, allocated by the pool / population it joins).  Its Philox key `seed` --
     the policy's, unless the population had to tell two ADAP members apart -- keys its moves and, under the ADAP salt, its contexts.
     In the native steps its rows run the ADAP tiles of the grouped forward (pool_adap_kernel); `get_action` is the walk's form, the
-    row build (`ph_adap_rows`) plus one `ph_policy_forward` over all rows -- the same bits row by row."""
+    row build (`ph_adap_rows`) plus the base class's one forward over all rows -- the same bits row by row."""
+
+    def _require_kernels(self, policy) -> None:
+        check_adap_member_policy(policy, type(self).__name__)
 
     def __init__(self, policy, latent, context_sampler: str = "l2"):
         who = type(self).__name__
-        check_adap_member_policy(policy, who)
-        self.policy, self._out = policy, {}
+        super().__init__(policy)
         self.context_size = int(policy.context_size)
         self.sampled = isinstance(latent, str)
         if self.sampled:
@@ -448,24 +443,18 @@ class AdapFrozenVecPartner(FrozenVecPartner):
         nat.check(pol.ctx.lib.ph_adap_context_draw(pol.ctx.handle, self.sampler, self.context_size, self.seed, int(counter),
                                                    nat.ptr(flags), self.contexts.data_ptr(), int(self.contexts.shape[0])))
 
-    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
+    def _rows(self, obs: th.Tensor) -> th.Tensor:
+        """features(observation) ++ the table's context, built on the device (the shared body has bound the stream)"""
         pol = self.policy
+        nat.check(pol.ctx.lib.ph_adap_rows(pol.ctx.handle, C.byref(self.env_space), self.context_size, obs.data_ptr(),
+                                           self.contexts.data_ptr(), None, self.rows.data_ptr(), int(obs.shape[0])))
+        return self.rows
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor = None) -> th.Tensor:
         n = int(obs.shape[0])
         if self.contexts is None or int(self.contexts.shape[0]) != n:
             raise nat.NativeError(f"{type(self).__name__}: attach({n}) first: the member owns one context per table")
-        out = self._out.get(n)
-        if out is None:
-            out = self._out[n] = (th.zeros((n, pol.layout.A), dtype=th.int32, device=pol.device),
-                                  th.zeros(n, dtype=th.float32, device=pol.device), th.zeros(n, dtype=th.float32, device=pol.device))
-        pol._bind()
-        pol._counter += 1
-        lib, h = pol.ctx.lib, pol.ctx.handle
-        nat.check(lib.ph_adap_rows(h, C.byref(self.env_space), self.context_size, obs.data_ptr(), self.contexts.data_ptr(), None,
-                                   self.rows.data_ptr(), n))
-        nat.check(lib.ph_policy_forward(
-            h, C.byref(pol.spec), pol.params.data_ptr(), self.rows.data_ptr(), n, None, None, None, self.seed, pol._counter,
-            0, out[0].data_ptr(), None, out[1].data_ptr(), out[2].data_ptr(), None, None, None, 0, None, None, 0))
-        return out[0]
+        return self._forward(obs, self.seed)
 
 
 def attach_adap_members(members, n_envs: int) -> None:
@@ -489,7 +478,9 @@ class ClonedVecPartner:
     parameters in ph_bc_layout) on the Liar's Dice spaces -- the "human proxy" partner of the reference's workflow (train, record,
     bctrainer, play the clone).  Like FrozenVecPartner it samples under its own Philox key and counter, records nothing, and `update`
     is a no-op.  In the native steps its rows run the clone tile of the grouped forward; `get_action` is the walk's form, one
-    `ph_bc_forward` over all rows -- the same bits row by row."""
+    `ph_bc_forward` over all rows -- the same bits row by row.  It does not share FrozenVecPartner's body: the clone's forward
+    returns actions only (one output buffer, no value or log-probability planes) and its policy has no `_bind`, so a shared helper
+    would branch per caller."""
     kind = nat.PH_POOL_CLONE
 
     def __init__(self, policy):
@@ -512,8 +503,8 @@ class ClonedVecPartner:
             out = self._out[n] = th.zeros((n, pol.layout.A), dtype=th.int32, device=pol.device)
         pol.ctx.set_stream(th.cuda.current_stream(pol.device).cuda_stream)
         pol._counter += 1
-        nat.check(pol.ctx.lib.ph_bc_forward(pol.ctx.handle, C.byref(pol.spec), pol.params.data_ptr(), obs.data_ptr(), n, None, None, None,
-                                            pol._seed, pol._counter, 0, out.data_ptr(), None, None, None, None))
+        nat.check(pol._native_forward(pol.params.data_ptr(), obs.data_ptr(), n, None, None, None, pol._seed, pol._counter, 0,
+                                      out.data_ptr(), None, None, None, None))
         return out
 
     def update(self, reward, done, mask=None) -> None:
@@ -523,8 +514,10 @@ class ClonedVecPartner:
 def check_liar_member_policy(policy, who: str, towers: bool = False, adap: bool = False) -> None:
     """a pool / population member's policy runs on the grouped forward's kernels and plays on the Liar's Dice spaces: the 64-64
     layout through `require_mlp_kernels`, a clone's through its BC layout (ClonedVecPartner has checked the one-hot observation);
-    `towers`: a net_arch tower whose forward carve fits the CU is taken too (the `_arch` steps); `adap`: the policy is held by an
-    AdapFrozenVecPartner -- the additive AdapPolicy over Box(270 + C) rows (the `_adap` steps)"""
+    `towers`: a net_arch tower whose forward carve fits the CU is taken too (tower tiles of the grouped forward); `adap`: the policy
+    is held by an AdapFrozenVecPartner -- the additive AdapPolicy over Box(270 + C) rows (ADAP tiles).  The pool classes state both
+    as class attributes (`accepts_towers` / `accepts_adaps`, read in VecLiarPartnerPool._check_member); cross-play, which seats
+    every member kind, states them per member."""
     from ..adap import AdapPolicy
     if adap:
         check_adap_member_policy(policy, who)
@@ -704,6 +697,20 @@ class VecLiarStep:
                 c.pos, c.boundary, c.term, c.open = (t.data_ptr() for t in (m.pos, m.boundary, m.term, m.open))
                 c.values, c.log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
         self._member_arr = arr
+        return arr
+
+    def _member_arrays(self, members, towers: bool, adaps: bool, ego=None):
+        """everything the one native call of a pool / population hands over beside its description: the member array (returned,
+        and kept in `_member_arr`), `_member_arch_arr` where `towers`, `_member_adap_arr` where `adaps`, and `_ego_arch`, the
+        ph_arch of a tower ego (the pool's `ego`; cross-play has none).  What is not asked for is None: the step is handed NULL
+        there and keeps every member on the 64-wide kernels, which is what the narrow entry points forward (csrc/ph_abi.hip)."""
+        arr = self._member_array(members)
+        self._ego_arch = seat_arch(ego) if towers and ego is not None else None
+        self._member_arch_arr = self._member_adap_arr = None
+        if towers:
+            self._member_archs(members)          # (stores `_member_arch_arr`)
+        if adaps:
+            self._member_adaps(members)          # (stores `_member_adap_arr` and `_member_adap_keep`)
         return arr
 
     def _member_archs(self, members):
@@ -1064,11 +1071,9 @@ class VecLiarSelfPlay(VecLiarTraining):
             nat.check(ctx.lib.ph_liar_selfplay_step_adap(ctx.handle, C.byref(self._desc), self._adap[0], self._adap[1], pos,
                                                          int(counter), int(deal_only)))
             return
-        if self.towers:
-            nat.check(ctx.lib.ph_liar_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
-                                                         int(counter), int(deal_only)))
-            return
-        nat.check(ctx.lib.ph_liar_selfplay_step(ctx.handle, C.byref(self._desc), pos, int(counter), int(deal_only)))
+        # two forms because the signatures differ (seats / archs); no tower in either seat: (None, None), the plain step
+        nat.check(ctx.lib.ph_liar_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
+                                                     int(counter), int(deal_only)))
 
     def rollout_persistent(self, n_steps: int, first_counter: int, ego_pos: int = 0) -> None:
         """n_steps vectorised steps as ONE persistent launch (`ph_liar_selfplay_rollout`: one workgroup owns 16 tables for the
@@ -1134,6 +1139,9 @@ class VecLiarPartnerPool(VecLiarTraining):
     native=True: one `ph_liar_pool_step` per vectorised step -- a bucket pass and ONE grouped forward per partner move whatever
     K is, no host synchronisation.  native=False: the readable walk (VecLiarStep) -- per-member get_action / update calls with
     torch masks (K full forwards per partner move), the per-call entry points only, the same counters; bitwise the native step."""
+    # what the member check takes beside the plain kinds -- and so which arrays the native call is handed beside the member array
+    accepts_towers = False      # net_arch towers as ego / members (TowerVecLiarPartnerPool)
+    accepts_adaps = False       # AdapFrozenVecPartner members (AdapVecLiarPartnerPool)
 
     def __init__(self, n_envs: int, ego: VecOnPolicyAgent, members, seed: int = 0, probegostart: float = 0.5,
                  resample: str = "robin", native: bool = True, record: int = 0):
@@ -1166,14 +1174,16 @@ class VecLiarPartnerPool(VecLiarTraining):
         self._first_deal()
 
     def _check_member(self, policy, seat=None) -> None:
-        check_liar_member_policy(policy, type(self).__name__)
+        check_liar_member_policy(policy, type(self).__name__, towers=self.accepts_towers,
+                                 adap=self.accepts_adaps and isinstance(seat, AdapFrozenVecPartner))
 
     def _contexts(self):
         return [self.env.ctx] + [p.ctx for p in map(self._policy_of, [self.ego] + self.members) if p is not None]
 
     def _build_native(self) -> None:
         s = self._fill_training(nat.PhLiarPool())
-        s.members, s.n_members, s.partnerid = self._member_array(self.members), self.K, self.partnerid.data_ptr()
+        s.members = self._member_arrays(self.members, self.accepts_towers, self.accepts_adaps, ego=self.ego)
+        s.n_members, s.partnerid = self.K, self.partnerid.data_ptr()
         s.resample, s.pool_seed = nat.POOL_RESAMPLE[self.resample], self.pool_seed
         s.alt_actions = self.alt_actions.data_ptr()
         self._desc = s
@@ -1181,8 +1191,10 @@ class VecLiarPartnerPool(VecLiarTraining):
     def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
         self._bind()
         ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
-        nat.check(ctx.lib.ph_liar_pool_step(ctx.handle, C.byref(self._desc), int(rb.pos if ego_pos < 0 else ego_pos), int(counter),
-                                            int(deal_only)))
+        # the widest entry point; what the class does not accept is None (`_member_arrays`): the narrow entry points' own forward
+        nat.check(ctx.lib.ph_liar_pool_step_adap(ctx.handle, C.byref(self._desc), self._ego_arch, self._member_arch_arr,
+                                                 self._member_adap_arr, int(rb.pos if ego_pos < 0 else ego_pos), int(counter),
+                                                 int(deal_only)))
 
     # -- the walk's hooks -------------------------------------------------------------------------------------------------------------
     def _seat_act(self, seat: int, obs: th.Tensor, mask, counter: int) -> th.Tensor:
@@ -1224,46 +1236,18 @@ class VecLiarPartnerPool(VecLiarTraining):
 class TowerVecLiarPartnerPool(VecLiarPartnerPool):
     """VecLiarPartnerPool whose ego and members may play `policy_kwargs=dict(net_arch=...)` towers: the ego a TowerVecOnPolicyAgent,
     learners TowerRaggedVecOnPolicyAgent, frozen members TowerFrozenVecPartner, beside every member the plain class takes.  It differs
-    from the plain class in its member check, in the archs kept beside the member array, and in its native call
-    (`ph_liar_pool_step_arch`: tower tiles of the grouped forward run in pool_tower_kernel).  The walk is the plain class's: the
-    member classes' own get_action / update."""
-
-    def _check_member(self, policy, seat=None) -> None:
-        check_liar_member_policy(policy, type(self).__name__, towers=True)
-
-    def _member_array(self, members):
-        arr = super()._member_array(members)
-        self._ego_arch = seat_arch(self.ego)
-        self._member_archs(members)
-        return arr
-
-    def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
-        self._bind()
-        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
-        nat.check(ctx.lib.ph_liar_pool_step_arch(ctx.handle, C.byref(self._desc), self._ego_arch, self._member_arch_arr,
-                                                 int(rb.pos if ego_pos < 0 else ego_pos), int(counter), int(deal_only)))
+    from the plain class in what its member check accepts, and so in the archs the step is handed beside the member array (tower
+    tiles of the grouped forward run in pool_tower_kernel).  The walk is the plain class's: the member classes' own get_action /
+    update."""
+    accepts_towers = True
 
 
 class AdapVecLiarPartnerPool(TowerVecLiarPartnerPool):
     """TowerVecLiarPartnerPool whose members may also be frozen ADAP checkpoints (AdapFrozenVecPartner, stated or sampled latent).
-    It differs in its member check, in the ADAP descriptions kept beside the member array, and in its native call
-    (`ph_liar_pool_step_adap`: ADAP tiles of the grouped forward run in pool_adap_kernel, a sampling member's contexts are redrawn
-    behind the pass that ends games).  The walk is the plain class's, with the members' own redraw at every deal."""
-
-    def _check_member(self, policy, seat=None) -> None:
-        check_liar_member_policy(policy, type(self).__name__, towers=True, adap=isinstance(seat, AdapFrozenVecPartner))
-
-    def _member_array(self, members):
-        arr = super()._member_array(members)
-        self._member_adaps(members)
-        return arr
-
-    def _native_call(self, counter: int, deal_only: bool = False, ego_pos: int = -1) -> None:
-        self._bind()
-        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
-        nat.check(ctx.lib.ph_liar_pool_step_adap(ctx.handle, C.byref(self._desc), self._ego_arch, self._member_arch_arr,
-                                                 self._member_adap_arr, int(rb.pos if ego_pos < 0 else ego_pos), int(counter),
-                                                 int(deal_only)))
+    It differs in what its member check accepts, and so in the ADAP descriptions the step is handed beside the member array (ADAP
+    tiles of the grouped forward run in pool_adap_kernel, a sampling member's contexts are redrawn behind the pass that ends
+    games).  The walk is the plain class's, with the members' own redraw at every deal."""
+    accepts_adaps = True
 
 
 def liar_pool_for(n_envs: int, ego, members, **kwargs) -> VecLiarPartnerPool:
@@ -1516,11 +1500,9 @@ class VecBlockSelfPlay:
         self._bind()
         ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
         pos = int(rb.pos if ego_pos < 0 else ego_pos)
-        if self.towers:
-            nat.check(ctx.lib.ph_block_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
-                                                          int(counter)))
-            return
-        nat.check(ctx.lib.ph_block_selfplay_step(ctx.handle, C.byref(self._desc), pos, int(counter)))
+        # no tower in either seat: (None, None), the plain step
+        nat.check(ctx.lib.ph_block_selfplay_step_arch(ctx.handle, C.byref(self._desc), self._archs[0], self._archs[1], pos,
+                                                      int(counter)))
 
     def step(self):
         """-> (E,) uint8 device tensor: tables whose game ended in this step"""

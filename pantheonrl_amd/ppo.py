@@ -320,9 +320,18 @@ class ActorCriticPolicy:
             int(pos), nat.ptr(es), None, int(self.gemm_mode)))
         return acts, values, logp, ent, logits
 
+    # -- the entry points that serve this policy's network: every caller passes ONE argument list, the 64-wide one's after the spec --
     def _native_forward(self, *args) -> int:
-        """the forward entry point of this policy's network: ph_policy_forward's arguments after the spec"""
+        """the forward: ph_policy_forward's arguments after the spec"""
         return self.ctx.lib.ph_policy_forward(self.ctx.handle, C.byref(self.spec), *args)
+
+    def _native_forward_ragged(self, *args) -> int:
+        """the forward with per-environment write rows: ph_policy_forward_ragged's arguments after the spec"""
+        return self.ctx.lib.ph_policy_forward_ragged(self.ctx.handle, C.byref(self.spec), *args)
+
+    def _native_scripted(self, *args) -> int:
+        """the one-launch scripted rollout: ph_scripted_rollout's arguments after the spec"""
+        return self.ctx.lib.ph_scripted_rollout(self.ctx.handle, C.byref(self.spec), *args)
 
     def _shape_actions(self, acts: th.Tensor) -> th.Tensor:
         # SB3: actions.reshape((-1,) + action_space.shape); Discrete has shape ()
@@ -537,6 +546,14 @@ class ArchActorCriticPolicy(ActorCriticPolicy):
 
     def _native_forward(self, *args) -> int:
         return self.ctx.lib.ph_arch_forward(self.ctx.handle, C.byref(self.spec), C.byref(self.arch), *args)
+
+    def _native_forward_ragged(self, *args) -> int:
+        """ph_arch_forward_ragged: the tower form takes a trailing gemm_mode the 64-wide one does not"""
+        return self.ctx.lib.ph_arch_forward_ragged(self.ctx.handle, C.byref(self.spec), C.byref(self.arch), *args, int(self.gemm_mode))
+
+    def _native_scripted(self, *args) -> int:
+        """ph_arch_scripted_rollout (any spec / arch pair the forward takes)"""
+        return self.ctx.lib.ph_arch_scripted_rollout(self.ctx.handle, C.byref(self.spec), C.byref(self.arch), *args)
 
     def forward_and_store_host(self, *a, **k):
         raise nat.NativeError("ArchActorCriticPolicy: the one-call host step belongs to the 64-wide kernels; use forward_and_store")

@@ -41,22 +41,14 @@ class VecOnPolicyAgent:
         self.values = th.zeros((E,), dtype=th.float32, device=dev)
         self.log_probs = th.zeros((E,), dtype=th.float32, device=dev)
         self._lib, self._h = pol.ctx.lib, pol.ctx.handle
-        self._spec, self._rb = C.byref(pol.spec), C.byref(rb.c_struct())
+        self._rb = C.byref(rb.c_struct())
         self.sync_stats = False
         self._pending = None   # reward tensor of the previous update(), folded into the next step's launch
         self.episode_stats = None   # an EpisodeStats (episode_stats.py): its scan runs behind every full rollout, in compute_returns
 
-    # -- which kernels serve the policy (overridden by the tower agent) ------------------------------------------------------
+    # -- which policies this agent runs (overridden by the tower agent); the policy names its own entry points (ppo.py) ---------
     def _require_kernels(self, pol) -> None:
         require_mlp_kernels(pol, type(self).__name__)
-
-    def _forward(self, *args) -> int:
-        """ph_policy_forward's arguments from `params` on"""
-        return self._lib.ph_policy_forward(self._h, self._spec, *args)
-
-    def _scripted(self, *args) -> int:
-        """ph_scripted_rollout's arguments from `params` on"""
-        return self._lib.ph_scripted_rollout(self._h, self._spec, *args)
 
     # -- callbacks --------------------------------------------------------------------------------------------------
     def get_action(self, obs: th.Tensor, record: bool = True, action_mask: Optional[th.Tensor] = None,
@@ -68,7 +60,7 @@ class VecOnPolicyAgent:
         es = self._last_episode_starts if episode_start is None else episode_start
         pending = self._pending if (record and rb.pos >= 1) else None
         pol._counter += 1
-        nat.check(self._forward(
+        nat.check(pol._native_forward(
             pol.params.data_ptr(), obs.data_ptr(), self.E, nat.ptr(action_mask), None, None,
             pol._seed, pol._counter, 0, self.actions.data_ptr(), None, self.values.data_ptr(),
             self.log_probs.data_ptr(), None, None, self._rb if record else None, rb.pos if record else 0,
@@ -92,7 +84,7 @@ class VecOnPolicyAgent:
         if rb.pos != 0 or data.T != rb.buffer_size or data.E != self.E:
             raise nat.NativeError("rollout_scripted: needs an empty rollout buffer of data.T rows and data.E environments")
         self.flush_rewards()
-        nat.check(self._scripted(
+        nat.check(pol._native_scripted(
             pol.params.data_ptr(), data.obs.data_ptr(), data.rewards.data_ptr(), data.dones.data_ptr(),
             self.E, data.T, self._last_episode_starts.data_ptr(), pol._seed, pol._counter + 1, self.actions.data_ptr(),
             self.values.data_ptr(), self.log_probs.data_ptr(), self._rb, 0, int(pol.gemm_mode)))
@@ -171,21 +163,14 @@ def is_tower(pol) -> bool:
 
 
 class TowerVecOnPolicyAgent(VecOnPolicyAgent):
-    """VecOnPolicyAgent for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): the same callbacks on the tower kernels --
-    get_action is ph_arch_forward (row write and pending-reward fold included), rollout_scripted is ph_arch_scripted_rollout (any
-    spec / arch pair the forward takes), and model.train() already dispatches to ph_arch_train."""
+    """VecOnPolicyAgent for `policy_kwargs=dict(net_arch=...)` (ArchActorCriticPolicy): the same callbacks on the tower kernels the
+    policy names -- its forward (row write and pending-reward fold included), its one-launch scripted rollout, and model.train(),
+    which already dispatches to ph_arch_train.  The class is what it accepts: a tower whose forward carve fits the CU."""
 
     def _require_kernels(self, pol) -> None:
         if not is_tower(pol):
             raise nat.NativeError(f"{type(self).__name__}: {type(pol).__name__} is not a net_arch tower policy; use VecOnPolicyAgent")
         require_tower_lds(pol, type(self).__name__)
-        self._arch = C.byref(pol.arch)
-
-    def _forward(self, *args) -> int:
-        return self._lib.ph_arch_forward(self._h, self._spec, self._arch, *args)
-
-    def _scripted(self, *args) -> int:
-        return self._lib.ph_arch_scripted_rollout(self._h, self._spec, self._arch, *args)
 
 
 def is_adap(pol) -> bool:

@@ -219,7 +219,7 @@ def make_device_buffer(name: str, pol, T: int, E: int):
 # --------------------------------------------------------------------------------------
 def _flat_layout(oracle, flat_fn=None):
     """(parameters in optimizer order, idx): flat vector entry i is entry idx[i] of the concatenated parameters.  Read off the
-    class's own flat_params() (or `flat_fn(oracle)`, e.g. test_gpu_modular._flat) by filling every parameter with its running
+    class's own flat_params() (or `flat_fn(oracle)`, e.g. modular_cases._flat) by filling every parameter with its running
     index -- float32 holds integers below 2**24 exactly -- so the order and the transpositions can never differ from it."""
     params = list(oracle.parameters())
     total = sum(p.numel() for p in params)

@@ -36,8 +36,8 @@ import torch as th
 from oracle import sb3_oracle as orc
 from tests import arch_oracle as A
 from tests import helpers as H
-from tests import test_gpu_adapmult as AM
-from tests import test_gpu_modular as M
+from tests import adapmult_cases as AM
+from tests import modular_cases as M
 
 SEED = 11
 
@@ -191,7 +191,7 @@ def context_samples(c: Case, nb: int, seed: int = SEED):
     """ADAP's teacher-forced samples (state positions, contexts) for a minibatch of nb rows, or None"""
     if c.coef is None or c.family not in ("adap", "adapmult"):
         return None
-    from tests.test_gpu_adap import CTX, _context_samples
+    from tests.adap_cases import CTX, _context_samples
     return _context_samples(CTX[c.config], nb, 5, 32, seed)
 
 
@@ -202,7 +202,7 @@ def checker_loss(c: Case, orac, mb, samples=None):
         return orc.modular_minibatch_loss(orac, mb, hp, c.partner, c.coef)
     loss, stats = orc.ppo_minibatch_loss(orac, mb, hp)
     if samples is not None:
-        from tests.test_gpu_adap import CTX
+        from tests.adap_cases import CTX
         sidx, ctxs = samples
         cl = orc.adap_context_loss(orac, mb["observations"], CTX[c.config], sidx[sidx >= 0], ctxs)
         loss = loss + c.coef * cl
@@ -302,7 +302,7 @@ def train_samples(t: TrainCase, n_mb: int, nb: int):
     """ADAP's teacher-forced samples per minibatch -> (state_idx (n_mb, N_STATES) int32, contexts (n_mb, N_CTX, cs), AdapTerm) or None"""
     if t.family not in ("adap", "adapmult"):
         return None
-    from tests.test_gpu_adap import CTX
+    from tests.adap_cases import CTX
     cs = CTX[t.config]
     rng = np.random.default_rng(t.seed)
     sidx = np.stack([rng.permutation(nb)[:N_STATES] for _ in range(n_mb)]).astype(np.int32)

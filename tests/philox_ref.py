@@ -83,6 +83,7 @@ def box_muller(u1, u2, dtype=np.float64) -> np.ndarray:
 
 LIAR_DICE, LIAR_SIDES = 6, 6                 # dice per player, sides (LiarEnv)
 FIRST_MOVER_BLOCK = 100
+ADAP_SALT = 0xADA9C0DE                         # csrc/ph_adap.hip, ph_adapmult.hip: key = epoch_key((seed ^ salt) + epoch, minibatch)
 
 
 def liar_deal(key64, counter64, tables) -> np.ndarray:

@@ -33,7 +33,7 @@ FORWARD_TOL = 2e-5
 class Case:
     id: str
     family: str                # mlp | arch | adapmult | modular | bc
-    name: str                  # helpers.CONFIGS name, test_gpu_modular.SHAPES name or a bc_cases id
+    name: str                  # helpers.CONFIGS name, modular_cases.SHAPES name or a bc_cases id
     rows: tuple
     kernel: str
     gemm_modes: tuple = (None,)
@@ -79,10 +79,10 @@ def checker(case_id: str):
         from tests import arch_oracle as A
         return A.oracle_policy(case.name, case.extra["arch"], seed=3)
     if case.family == "adapmult":
-        from tests.test_gpu_adapmult import _oracle
+        from tests.adapmult_cases import _oracle
         return _oracle(case.name, seed=3)
     if case.family == "modular":
-        from tests.test_gpu_modular import _oracle
+        from tests.modular_cases import _oracle
         return _oracle(case.name, case.extra["K"], **case.extra["kw"])
     from tests import bc_cases as B
     return B.checker(B.BY_ID[case.name], 1)[0]
@@ -91,7 +91,7 @@ def checker(case_id: str):
 def spaces(case: Case):
     """(observation SpaceSpec, action SpaceSpec)"""
     if case.family == "modular":
-        from tests.test_gpu_modular import SHAPES
+        from tests.modular_cases import SHAPES
         return SHAPES[case.name]
     if case.family == "bc":
         from tests import bc_cases as B
@@ -254,3 +254,25 @@ def pool_prediction(obs, pid, counter: int):
             moved = (predict(probs, shifted_uniforms(n, 2, POOL_KEYS[k], counter, name))[0] != a).any(axis=1)
             ctl[name] += float(moved[mine].sum()) / n
     return acts, near, ctl
+
+
+def device(case, orac=None):
+    """the case's device object holding the parameters of `orac` (default: the case's cached checker) -- the one function here
+    that needs a GPU"""
+    orac = checker(case.id) if orac is None else orac
+    if case.family == "mlp":
+        return H.device_policy(case.name, orac)
+    if case.family == "arch":
+        from tests import arch_oracle as A
+        return A.device_policy(case.name, orac)
+    if case.family == "adapmult":
+        from tests.adapmult_cases import _device as dev
+        return dev(case.name, orac)
+    if case.family == "modular":
+        from tests.modular_cases import _device as dev
+        return dev(case.name, orac, case.extra["K"], **case.extra["kw"])
+    from pantheonrl_amd.bc import FeedForward32Policy
+    obs_s, act_s = spaces(case)
+    pol = FeedForward32Policy(H.to_space(obs_s), H.to_space(act_s), device="cuda:0", seed=7)
+    pol.set_flat_params(orac.flat_params())
+    return pol

@@ -54,7 +54,7 @@ def heads(checker) -> list:
     """the categorical action heads: action_net of the MLP, net_arch, ADAP and ADAP-MULT checkers, every DISTINCT partner head of the
     Modular checker, the last layer of the BC checker"""
     if isinstance(checker, orc.ModularPolicyOracle):
-        from tests.test_gpu_modular import _unique
+        from tests.modular_cases import _unique
         return [pm["act"] for pm in _unique(checker)]
     return [checker.action_net]
 
@@ -303,7 +303,7 @@ BC_WEIGHTS = ((1e-3, 0.0), (0.5, 0.0))        # bc_cases.WEIGHTS without the L2 
 @dataclass(frozen=True)
 class GradCase:
     family: str                 # ppo | arch | modular | adap | adapmult | bc
-    config: str                 # helpers.CONFIGS / test_gpu_modular.SHAPES name, or a bc_cases id
+    config: str                 # helpers.CONFIGS / modular_cases.SHAPES name, or a bc_cases id
     gemm_mode: int
     kernel: str
     arch: Optional[Tuple[int, ...]] = None
@@ -382,7 +382,7 @@ def fill(g: GradCase):
         with th.random.fork_rng(devices=[]):
             th.manual_seed(seed)
             if g.family == "modular":
-                from tests.test_gpu_modular import _filled
+                from tests.modular_cases import _filled
                 ob = _filled(orac, name, g.partner, T_, E_, seed=seed)
             else:
                 ob = H.filled_oracle_buffer(name, orac, T_, E_, seed=seed)

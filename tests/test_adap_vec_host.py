@@ -13,7 +13,7 @@ from pantheonrl_amd import spaces as sp
 from pantheonrl_amd import trainer
 from pantheonrl_amd.envs import vec as V
 from tests import adap_vec_ref as A
-from tests.test_philox_host import ADAP_SALT
+from tests.philox_ref import ADAP_SALT
 
 N = 300
 COUNTERS = (0, 9, 2 ** 33 + 1)

@@ -9,7 +9,7 @@ import pytest
 from oracle import sb3_oracle as orc
 from tests import bc_cases as B
 from tests import helpers as H
-from tests.test_optimizer_checks import bc_flat_grads
+from tests.optimizer_cases import bc_flat_grads
 
 N = 33
 IDS = [c.id for c in B.CASES]
@@ -46,7 +46,7 @@ def test_the_table_names_every_path_and_its_dispatch_column_is_the_librarys():
 
 def test_flat_gradient_has_the_layout_of_bc_flat_grads():
     """B.gradient reads the gradient through helpers.flat_grads_exact; where every parameter has one (l2_weight > 0) that is
-    test_optimizer_checks.bc_flat_grads entry for entry"""
+    optimizer_cases.bc_flat_grads entry for entry"""
     import copy
     import torch as th
     case = B.BY_ID["box33-3x30x7"]

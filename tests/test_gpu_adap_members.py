@@ -12,32 +12,18 @@ import pytest
 import torch as th
 
 from pantheonrl_amd import _native as nat
-from tests.test_gpu_tower_members import (_interleave, _member, _pool_state, _ppo, _same_pool_state, _sharpen, _spaces, _xstate)
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
 
-# ADAP member kinds of this file: name -> (context_size, latent form, sampler)
-ADAPS = dict(adapS3=(3, "stated", "l2"), adapR3=(3, "sample", "l2"), adapS1=(1, "stated", "l2"), adapR52=(52, "sample", "l2"),
-             adapC4=(4, "sample", "categorical"))
-
-
-def _adap_model(cs, seed, sampler="l2"):
-    from pantheonrl_amd.adap import ADAP, AdapPolicy
-    m = ADAP(AdapPolicy, _spaces(), context_sampler=sampler, context_size=cs, n_steps=2, n_envs=4, batch_size=4, n_epochs=1, seed=seed)
-    _sharpen(m.policy, seed)
-    return m
-
-
-def _latent(cs, seed):
-    return np.random.default_rng(900 + seed).standard_normal(cs).astype(np.float32)
-
 
 def _any_member(kind, E, T_alt, seed):
-    from pantheonrl_amd.envs.vec import AdapFrozenVecPartner
-    if kind not in ADAPS:
-        return _member(kind, E, T_alt, seed, sharpen=kind != "learner")
-    cs, form, sampler = ADAPS[kind]
-    return AdapFrozenVecPartner(_adap_model(cs, seed, sampler).policy, "sample" if form == "sample" else _latent(cs, seed), sampler)
+    """a member of any kind; every policy that does not learn is sharpened"""
+    return LC.member(kind, E, T_alt, seed, sharp=lambda k: k != "learner")
+
+
+def _apool(E, kinds, resample="robin", native=True, seed=11, record=0, T_ego=8, T_alt=4):
+    return LC.pool(E, T_ego, T_alt, kinds, seed=seed, native=native, resample=resample, record=record, sharp=lambda k: k != "learner")
 
 
 def _arrays(members):
@@ -50,10 +36,8 @@ def _arrays(members):
 
 def _host_ctx(n):
     from pantheonrl_amd.vec import VecOnPolicyAgent
-    host = VecOnPolicyAgent(_ppo(n, 2, 0))
-    ctx = host.model.policy.ctx
-    ctx.set_stream(th.cuda.current_stream(host.model.policy.device).cuda_stream)
-    return host, ctx
+    host = VecOnPolicyAgent(LC.ppo(n, 2, 0))
+    return host, LC.ctx_of(host)
 
 
 # ---- 1. the grouped forward on its own -------------------------------------------------------------------------------------------
@@ -74,7 +58,7 @@ CASES = {
 def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     from pantheonrl_amd.envs.vec import AdapFrozenVecPartner, attach_adap_members
     kinds, counts, holes = CASES[case]
-    pid_l = _interleave(counts).tolist()
+    pid_l = LC.interleave(counts).tolist()
     active_l = [1] * len(pid_l)
     for at, k in holes:
         pid_l.insert(at, k)
@@ -84,8 +68,8 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     act = active_h.astype(bool)
     assert np.bincount(pid_h[act], minlength=K).tolist() == counts
     rng = np.random.default_rng(5)
-    obs_h = (rng.random((n, 30)) * np.asarray(_spaces().observation_space.nvec)).astype(np.int64).astype(np.float32)
-    adap_rows = np.nonzero(act & np.isin(pid_h, [k for k, kind in enumerate(kinds) if kind in ADAPS]))[0]
+    obs_h = (rng.random((n, 30)) * np.asarray(LC.spaces().observation_space.nvec)).astype(np.int64).astype(np.float32)
+    adap_rows = np.nonzero(act & np.isin(pid_h, [k for k, kind in enumerate(kinds) if kind in LC.ADAPS]))[0]
     if len(adap_rows):                                      # out-of-range components in rows an ADAP member moves in: clamped
         obs_h[adap_rows[0], 7], obs_h[adap_rows[-1], 0], obs_h[adap_rows[len(adap_rows) // 2], 29] = 99.0, -3.0, 12.0
     obs, pid, active = th.as_tensor(obs_h).cuda(), th.as_tensor(pid_h).cuda(), th.as_tensor(active_h).cuda()
@@ -101,7 +85,7 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
         sets.append(members)
     grouped, plain = sets
     arr, archs, adaps, keep = _arrays(grouped)
-    assert sum(bool(a) for a in adaps) == sum(kind in ADAPS for kind in kinds) >= 1
+    assert sum(bool(a) for a in adaps) == sum(kind in LC.ADAPS for kind in kinds) >= 1
     actions = th.full((n, 2), -7, dtype=th.int32, device="cuda")
     nat.check(lib.ph_pool_forward_adap(h, spec, arr, K, obs.data_ptr(), pid.data_ptr(), active.data_ptr(), counter, actions.data_ptr(),
                                        None, n, archs, adaps))
@@ -116,20 +100,20 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
             nat.check(lib.ph_liar_default_actions(h, obs.data_ptr(), rows.data_ptr(), want.data_ptr(), n))
             assert np.array_equal(got[mine], want.cpu().numpy()[mine])
             continue
-        if kinds[k] in ADAPS:
+        if kinds[k] in LC.ADAPS:
             assert np.array_equal(g.contexts.cpu().numpy().view(np.uint32), p.contexts.cpu().numpy().view(np.uint32))
-            if ADAPS[kinds[k]][1] == "sample":
-                cs, _, sampler = ADAPS[kinds[k]]
+            if LC.ADAPS[kinds[k]][1] == "sample":
+                cs, _, sampler = LC.ADAPS[kinds[k]]
                 host_ctx, _ = nat.adap_vec_host(cs, n, sampler=sampler, seed=g.seed, counter=5)
                 assert np.array_equal(g.contexts.cpu().numpy().view(np.uint32), host_ctx.view(np.uint32))
-                assert len(np.unique(host_ctx, axis=0)) > min(n, ADAPS[kinds[k]][0]) // 2      # a context per table
+                assert len(np.unique(host_ctx, axis=0)) > min(n, LC.ADAPS[kinds[k]][0]) // 2      # a context per table
         p.policy._counter = counter - 1
         want = p.get_action(obs).cpu().numpy()              # ONE per-member forward over all n rows (row index = table)
         assert (want >= 0).all() and np.array_equal(got[mine], want[mine]), (k, kinds[k])
         if mine.sum() >= 10:
             assert len(np.unique(want[mine], axis=0)) > 3   # a spread of moves: nothing vacuous
-        if kinds[k] in ADAPS and mine.any():                # the rows the member saw: one_hot(clamped observation) ++ its context
-            cs = ADAPS[kinds[k]][0]
+        if kinds[k] in LC.ADAPS and mine.any():                # the rows the member saw: one_hot(clamped observation) ++ its context
+            cs = LC.ADAPS[kinds[k]][0]
             _, rows = nat.adap_vec_host(cs, n, contexts=p.contexts.cpu().numpy(), env_space=p.env_space, obs=obs_h)
             assert np.array_equal(p.rows.cpu().numpy().view(np.uint32), rows.view(np.uint32))
             assert (rows[:, :270].sum(axis=1) == 30).all()
@@ -141,13 +125,13 @@ def test_stated_member_is_bitwise_the_loaded_host_policy_under_set_context(cs, t
     from pantheonrl_amd.adap import ADAP
     from pantheonrl_amd.envs.vec import AdapFrozenVecPartner, attach_adap_members
     n, counter = 37, 13
-    model = _adap_model(cs, 31)
+    model = LC.adap_model(cs, 31)
     model.save(str(tmp_path / "m"))
-    latent = _latent(cs, 31)
+    latent = LC.latent(cs, 31)
     member = AdapFrozenVecPartner(model.policy, latent)
     attach_adap_members([member], n)
     rng = np.random.default_rng(8)
-    obs_h = (rng.random((n, 30)) * np.asarray(_spaces().observation_space.nvec)).astype(np.int64).astype(np.float32)
+    obs_h = (rng.random((n, 30)) * np.asarray(LC.spaces().observation_space.nvec)).astype(np.int64).astype(np.float32)
     obs = th.as_tensor(obs_h).cuda()
     host, ctx = _host_ctx(n)
     arr, archs, adaps, keep = _arrays([member])
@@ -166,14 +150,6 @@ def test_stated_member_is_bitwise_the_loaded_host_policy_under_set_context(cs, t
 
 
 # ---- 3. / 4. / 5. the native steps against the walk, and the sampled contexts --------------------------------------------------------
-def _apool(E, kinds, resample="robin", native=True, seed=11, record=0, T_ego=8, T_alt=4):
-    from pantheonrl_amd.envs.vec import liar_pool_for
-    from pantheonrl_amd.vec import vec_agent_for
-    ego = vec_agent_for(_ppo(E, T_ego, seed))
-    members = [_any_member(kind, E, T_alt, seed + 1 + k) for k, kind in enumerate(kinds)]
-    return liar_pool_for(E, ego, members, seed=seed + 7, resample=resample, native=native, record=record), ego, members
-
-
 def _contexts(members):
     from pantheonrl_amd.envs.vec import AdapFrozenVecPartner
     th.cuda.synchronize()
@@ -205,12 +181,12 @@ def test_native_pool_step_with_adap_members_is_bitwise_the_walk(resample):
         assert np.array_equal(da.cpu().numpy(), db.cpu().numpy()), step
         _same_contexts(_contexts(ma), _contexts(mb), step)
         pids.append(a.partnerid.cpu().numpy().copy())
-    sa, sb = _pool_state(a, ego_a), _pool_state(b, ego_b)
-    _same_pool_state(sa, sb)
+    sa, sb = LC.train_state(a, ego_a), LC.train_state(b, ego_b)
+    LC.same_state(sa, sb)
     assert trained >= 1 and sa["ego_it"] >= 2 and sa["episodes"] > 50 and len(np.unique(np.stack(pids))) == 4
     assert np.array_equal(a.alt_actions.cpu().numpy(), b.alt_actions.cpu().numpy())
     lat = _contexts(ma)[1]
-    assert (lat == _latent(3, 11 + 2)[None, :]).all()       # the stated member's contexts never move
+    assert (lat == LC.latent(3, 11 + 2)[None, :]).all()       # the stated member's contexts never move
 
 
 def test_native_crossplay_step_with_adap_members_is_bitwise_the_walk_after_every_step():
@@ -224,7 +200,7 @@ def test_native_crossplay_step_with_adap_members_is_bitwise_the_walk_after_every
     assert a.P == 16 and a.adaps and not a.towers
     steps = 0
     while True:
-        sa, sb = _xstate(a), _xstate(b)
+        sa, sb = LC.xstate(a), LC.xstate(b)
         for key in sa:
             assert np.array_equal(sa[key], sb[key]), (steps, key)
         _same_contexts(_contexts(ma), _contexts(mb), steps)
@@ -247,10 +223,10 @@ def test_sampled_contexts_change_only_where_games_end_and_are_the_host_draw():
     from pantheonrl_amd.envs.vec import AdapFrozenVecPartner, liar_pool_for
     from pantheonrl_amd.vec import vec_agent_for
     E = 40
-    pol = _adap_model(3, 77).policy
+    pol = LC.adap_model(3, 77).policy
     members = [AdapFrozenVecPartner(pol, "sample"), AdapFrozenVecPartner(pol, "sample"),
-               AdapFrozenVecPartner(_adap_model(4, 78, "categorical").policy, "sample", "categorical")]
-    sp = liar_pool_for(E, vec_agent_for(_ppo(E, 64, 1)), members, seed=4)
+               AdapFrozenVecPartner(LC.adap_model(4, 78, "categorical").policy, "sample", "categorical")]
+    sp = liar_pool_for(E, vec_agent_for(LC.ppo(E, 64, 1)), members, seed=4)
     assert members[0].seed == pol._seed and members[1].seed != members[0].seed
     samplers = ["l2", "l2", "categorical"]
     prev = _contexts(members)
@@ -279,7 +255,6 @@ def test_sampled_contexts_change_only_where_games_end_and_are_the_host_draw():
 def test_recorded_games_replay_through_the_host_game_and_the_host_policy():
     from pantheonrl_amd.common import StaticPolicyAgent
     from pantheonrl_amd.common.observation import Observation
-    from tests.test_gpu_record import _replay_through_the_reference_recorder
     E, steps = 12, 10
     kinds = ["adapR3", "adapS3", "scripted"]
     sp, ego, members = _apool(E, kinds, seed=2, record=3 * steps + 1, T_ego=16)
@@ -312,7 +287,7 @@ def test_recorded_games_replay_through_the_host_game_and_the_host_policy():
                     ended = ended or flag >= 2
                     continue
                 k = int(who[i])
-                if kinds[k] in ADAPS:                       # a reply reads the context before the step's redraw, an opening the new one
+                if kinds[k] in LC.ADAPS:                       # a reply reads the context before the step's redraw, an opening the new one
                     moves.append((e, k, rows[i, :30].copy(), rows[i, 30:32].copy(), 2 * c + 1 if ended else 2 * c,
                                   (after if ended else before)[k][e].copy()))
                 ended = ended or flag >= 2
@@ -325,7 +300,7 @@ def test_recorded_games_replay_through_the_host_game_and_the_host_policy():
         mine = rows[off[e]:off[e + 1]]
         for row in mine:
             events[e].append(("move", row[None, 30:32].astype(np.int64), np.array([int(row[32]) % 2 == 0]), np.ones(1, bool)))
-        tr, games = _replay_through_the_reference_recorder(events[e], 0)
+        tr, games = LC.replay_through_the_reference_recorder(events[e], 0)
         assert np.array_equal(np.asarray(tr.obs), mine[:, :30]) and np.array_equal(np.asarray(tr.acts), mine[:, 30:32]), e
         assert np.array_equal(np.asarray(tr.flags), mine[:, 32]), e
         total += games
@@ -405,7 +380,7 @@ def test_launch_counts_and_capture():
         stream.synchronize()
     th.cuda.synchronize()
     assert sp.episodes > episodes
-    _same_pool_state(_pool_state(sp, ego), _pool_state(eager, ego_e), ego_rows=6)
+    LC.same_state(LC.train_state(sp, ego), LC.train_state(eager, ego_e), ego_rows=6)
     _same_contexts(_contexts(mg), _contexts(me), "graph")
 
 
@@ -495,22 +470,22 @@ def test_adap_misuse_is_an_error_string_and_nothing_is_launched():
         AdapFrozenVecPartner(mult, [1.0, 0.0, 0.0])
     with pytest.raises(nat.NativeError, match="not an AdapPolicy"):
         AdapFrozenVecPartner(members[3].policy, [1.0, 0.0, 0.0])
-    arched = _adap_model(3, 9).policy                      # an AdapPolicy that was given net_arch: refused by name
+    arched = LC.adap_model(3, 9).policy                      # an AdapPolicy that was given net_arch: refused by name
     arched.net_arch = (128, 128)
     with pytest.raises(nat.NativeError, match="net_arch"):
         AdapFrozenVecPartner(arched, [1.0, 0.0, 0.0])
     with pytest.raises(nat.NativeError, match="16 tables"):               # one object, one population: its contexts are 16 tables'
         members[0].attach(8)
-    plain_ego = vec_agent_for(_ppo(16, 4, 3))
+    plain_ego = vec_agent_for(LC.ppo(16, 4, 3))
     for cls in (VecLiarPartnerPool, TowerVecLiarPartnerPool):
         with pytest.raises(nat.NativeError, match="AdapFrozenVecPartner"):
             cls(16, plain_ego, [members[0]])
     with pytest.raises(nat.NativeError, match="AdapFrozenVecPartner"):    # an ADAP policy without a latent is no member
         liar_pool_for(16, plain_ego, [FrozenVecPartner(pol), members[0]])
     with pytest.raises(nat.NativeError, match="ADAP learner"):            # ... nor an ADAP learner, nor an ADAP ego
-        liar_pool_for(16, plain_ego, [ragged_agent_for(_adap_model(3, 5)), members[0]])
+        liar_pool_for(16, plain_ego, [ragged_agent_for(LC.adap_model(3, 5)), members[0]])
     with pytest.raises(nat.NativeError, match="ADAP learner"):
-        liar_pool_for(16, vec_agent_for(_adap_model(3, 6)), [members[0]])
+        liar_pool_for(16, vec_agent_for(LC.adap_model(3, 6)), [members[0]])
     assert type(liar_pool_for(16, plain_ego, [members[3], members[2]])) is VecLiarPartnerPool
     # ... and the contexts still step
     sp.step()
@@ -531,9 +506,9 @@ def test_all_null_member_adaps_is_bitwise_the_entry_point_it_extends():
                 nat.check(ctx.lib.ph_liar_pool_step_adap(ctx.handle, C.byref(sp._desc), None, None, adaps if c % 2 else None, c - 1, c, 0))
             else:
                 nat.check(ctx.lib.ph_liar_pool_step_arch(ctx.handle, C.byref(sp._desc), None, None, c - 1, c, 0))
-    a, b = _pool_state(old, ego_o), _pool_state(new, ego_n)
+    a, b = LC.train_state(old, ego_o), LC.train_state(new, ego_n)
     assert a["episodes"] > 0
-    _same_pool_state(a, b, ego_rows=3)
+    LC.same_state(a, b, ego_rows=3)
 
 
 # ---- 9. end to end -------------------------------------------------------------------------------------------------------------------

@@ -11,8 +11,8 @@ import torch as th
 from oracle import sb3_oracle as orc
 from tests import adap_vec_ref as A
 from tests import helpers as H
-from tests import test_gpu_adap as TA
-from tests.test_gpu_arch_vec import _assert_same_run, _liar_state, _walk_steps
+from tests import adap_cases as TA
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
 
@@ -108,20 +108,9 @@ def test_draw_kernel_is_bitwise_the_host_statement(sampler, cs, n):
 # ---- 2. the engine-side step is the walk ----------------------------------------------------------------------------------------------
 def _adap_selfplay(E, T_ego, T_alt, kinds, share=False, seed=0, native=True, sampler="l2", calls=None):
     """calls: a list that collects the partner's forwards of the walk -- (moves, mask, the contexts it read) -- the first deal's too"""
-    from pantheonrl_amd.envs.vec import VecLiarSelfPlay, ragged_agent_for
-    from pantheonrl_amd.vec import vec_agent_for
     spaces = _game_spaces("liar")
-    ego = vec_agent_for(_model(kinds[0], spaces, T_ego, E, seed, sampler))
-    alt = ragged_agent_for(_model(kinds[1], spaces, T_alt, E, seed + 1, sampler), latent_syncer=ego if share else None)
-    if calls is not None:
-        inner = alt.get_action
-
-        def logged(obs, rec_mask):
-            acts = inner(obs, rec_mask)
-            calls.append((acts.cpu().numpy().copy(), rec_mask.cpu().numpy().astype(bool), alt.current_contexts().cpu().numpy().copy()))
-            return acts
-        alt.get_action = logged
-    return VecLiarSelfPlay(E, ego, alt, seed=seed + 7, native=native), ego, alt
+    return LC.selfplay(E, _model(kinds[0], spaces, T_ego, E, seed, sampler), _model(kinds[1], spaces, T_alt, E, seed + 1, sampler),
+                       seed=seed, native=native, calls=calls, latent_syncer=share)
 
 
 def _contexts_of(sp, ego, alt):
@@ -145,14 +134,14 @@ def test_liar_native_adap_step_is_bitwise_the_per_call_walk(kinds, share):
         assert isinstance(alt, AdapRaggedVecOnPolicyAgent) == (kinds[1] == "ADAP")
         assert sp.adap and sp.persistent is False
         alt.model.rollout_buffer.gae_mode = ego.model.rollout_buffer.gae_mode = 1
-        trained = _walk_steps(sp, alt, 3 * T_ego)
-        runs.append(_liar_state(sp, ego, alt, trained=trained, **_contexts_of(sp, ego, alt)))
+        trained = LC.train_steps(sp, 3 * T_ego)[0]
+        runs.append(dict(LC.train_state(sp, ego), trained=trained, **_contexts_of(sp, ego, alt)))
     a, b = runs
     assert a["trained"] >= 1 and a["ego_it"] >= 2 and a["episodes"] > E
     assert ("ctx_ego" in a) == (kinds[0] == "ADAP") and ("ctx_alt" in a) == (kinds[1] == "ADAP")
     if kinds[0] == "ADAP":
         assert a["e_observations"].shape[-1] == 273
-    _assert_same_run(a, b)
+    LC.same_state(a, b)
 
 
 def test_liar_adap_step_with_two_null_seats_is_the_plain_step():
@@ -163,11 +152,13 @@ def test_liar_adap_step_with_two_null_seats_is_the_plain_step():
         assert not sp.adap
         if through_adap:
             sp.adap = True                        # _native_call then goes through ph_liar_selfplay_step_adap(NULL, NULL)
+        else:
+            LC.step_through_the_plain_entry_point(sp)         # ph_liar_selfplay_step itself, not the driver's _arch(NULL, NULL)
         sp.persistent = False
         alt.model.rollout_buffer.gae_mode = ego.model.rollout_buffer.gae_mode = 1
-        trained = _walk_steps(sp, alt, 2 * T_ego)
-        runs.append(_liar_state(sp, ego, alt, trained=trained))
-    _assert_same_run(*runs)
+        trained = LC.train_steps(sp, 2 * T_ego)[0]
+        runs.append(dict(LC.train_state(sp, ego), trained=trained))
+    LC.same_state(*runs)
 
 
 def test_a_bad_seat_is_an_error_string_not_a_launch():

@@ -15,6 +15,7 @@ import torch as th
 from pantheonrl_amd import _native as nat
 from tests import arch_oracle as A
 from tests import helpers as H
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -116,52 +117,15 @@ def test_ragged_tower_forward_writes_exactly_the_recorded_rows(name, arch):
 
 # ---- 2. / 3. Liar's Dice ---------------------------------------------------------------------------------------------------------
 def _liar_selfplay(E, T_ego, T_alt, ego_arch, alt_arch, seed=0, native=True):
-    from pantheonrl_amd.envs.vec import VecLiarsDice, VecLiarSelfPlay, ragged_agent_for
-    from pantheonrl_amd.vec import vec_agent_for
-    spaces = type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
-                                _is_dummy_space_env=True))()
-    ego = vec_agent_for(_model(spaces, ego_arch, T_ego, E, seed))
-    alt = ragged_agent_for(_model(spaces, alt_arch, T_alt, E, seed + 1))
-    calls = []
-    inner = alt.get_action
-
-    def logged(obs, rec_mask):
-        acts = inner(obs, rec_mask)
-        calls.append((acts.cpu().numpy().copy(), rec_mask.cpu().numpy().astype(bool)))
-        return acts
-    alt.get_action = logged
-    return VecLiarSelfPlay(E, ego, alt, seed=seed + 7, native=native), ego, alt, calls
+    """-> (self-play, ego, alt, the partner's forwards of the walk); a seat's arch None: the default 64-wide policy"""
+    calls, spaces = [], LC.spaces()
+    sp, ego, alt = LC.selfplay(E, _model(spaces, ego_arch, T_ego, E, seed), _model(spaces, alt_arch, T_alt, E, seed + 1), seed=seed,
+                               native=native, calls=calls)
+    return sp, ego, alt, calls
 
 
 def _liar_state(sp, ego, alt, **more):
-    th.cuda.synchronize()
-    be, ba = ego.model.rollout_buffer.host(), alt.model.rollout_buffer.host()
-    return dict(hands=sp.env.hands.cpu().numpy(), hist=sp.env.history.cpu().numpy(), obs=sp.obs_ego.cpu().numpy(),
-                pos=alt.pos.cpu().numpy(), flags=np.stack([t.cpu().numpy() for t in (alt.boundary, alt.term, alt.open)]),
-                acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes, ego_it=ego.iteration,
-                pe=ego.model.policy.get_flat_params(), pa=alt.model.policy.get_flat_params(),
-                **{"e_" + k: v for k, v in be.items() if k in ("observations", "actions", "rewards", "episode_starts")},
-                **{"a_" + k: v for k, v in ba.items()}, **more)
-
-
-def _assert_same_run(a, b):
-    pos = a["pos"]
-    for key in a:
-        x, y = a[key], b[key]
-        if key.startswith("a_") and getattr(x, "ndim", 0) >= 2:      # only the recorded rows of the ragged buffer are defined
-            rows = np.arange(x.shape[0])[:, None] < pos[None, :]
-            x, y = x[rows], y[rows]
-        assert np.array_equal(x, y), key
-
-
-def _walk_steps(sp, alt, steps):
-    trained = 0
-    for _ in range(steps):
-        sp.step()
-        if alt.full():
-            alt.learn_from_buffer()
-            trained += 1
-    return trained
+    return dict(LC.train_state(sp, ego), **more)
 
 
 @pytest.mark.parametrize("ego_arch,alt_arch", [((128, 128), (32,)), ((96, 160, 32), None), (None, (256, 128))],
@@ -177,26 +141,27 @@ def test_liar_native_arch_step_is_bitwise_the_per_call_walk(ego_arch, alt_arch):
         assert isinstance(alt, TowerRaggedVecOnPolicyAgent) == (alt_arch is not None)
         assert sp.persistent is False
         alt.model.rollout_buffer.gae_mode = ego.model.rollout_buffer.gae_mode = 1
-        trained = _walk_steps(sp, alt, 3 * T_ego)
+        trained = LC.train_steps(sp, 3 * T_ego)[0]
         runs.append(_liar_state(sp, ego, alt, trained=trained))
     a, b = runs
     assert a["trained"] >= 1 and a["ego_it"] >= 2 and a["episodes"] > E
-    _assert_same_run(a, b)
+    LC.same_state(a, b)
 
 
 def test_liar_arch_step_with_two_null_arches_is_the_plain_step():
+    """the driver's own call -- always ph_liar_selfplay_step_arch, (NULL, NULL) without a tower -- against a run that steps
+    through ph_liar_selfplay_step itself"""
     E, T_ego, T_alt = 48, 8, 6
     runs = []
     for through_arch in (False, True):
         sp, ego, alt, _ = _liar_selfplay(E, T_ego, T_alt, None, None, seed=3)
-        assert not sp.towers
-        if through_arch:
-            sp.towers = True                      # _native_call then goes through ph_liar_selfplay_step_arch(NULL, NULL)
-            sp.persistent = False
+        assert not sp.towers and sp._archs == (None, None)
+        if not through_arch:
+            LC.step_through_the_plain_entry_point(sp)
         alt.model.rollout_buffer.gae_mode = ego.model.rollout_buffer.gae_mode = 1
-        trained = _walk_steps(sp, alt, 2 * T_ego)
+        trained = LC.train_steps(sp, 2 * T_ego)[0]
         runs.append(_liar_state(sp, ego, alt, trained=trained))
-    _assert_same_run(*runs)
+    LC.same_state(*runs)
 
 
 def test_liar_walk_with_towers_matches_the_python_step_loop():
@@ -301,18 +266,17 @@ def test_block_native_arch_step_is_bitwise_the_per_call_walk(variant, tower_seat
         sp = VecBlockSelfPlay(variant, E, ego, alt, seed=18, native=native)
         assert sp.towers
         alt.model.rollout_buffer.gae_mode = ego.model.rollout_buffer.gae_mode = 1
-        trained = _walk_steps(sp, alt, 3 * T_ego)
-        th.cuda.synchronize()
-        be, ba = ego.model.rollout_buffer.host(), alt.model.rollout_buffer.host()
+        trained = LC.train_steps(sp, 3 * T_ego, [alt])[0]
+        be, ba, pos = ego.model.rollout_buffer.host(), alt.model.rollout_buffer.host(), alt.pos.cpu().numpy()
         runs.append(dict(state=sp.env.state.cpu().numpy(), obs=sp.obs_ego.cpu().numpy(), obs_alt=sp.obs_alt.cpu().numpy(),
-                         pos=alt.pos.cpu().numpy(), flags=np.stack([t.cpu().numpy() for t in (alt.boundary, alt.term, alt.open)]),
+                         pos=pos, flags=np.stack([t.cpu().numpy() for t in (alt.boundary, alt.term, alt.open)]),
                          acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes, trained=trained, ego_it=ego.iteration,
                          pe=ego.model.policy.get_flat_params(), pa=alt.model.policy.get_flat_params(),
                          **{"e_" + k: v for k, v in be.items() if k in ("observations", "actions", "rewards", "episode_starts")},
-                         **{"a_" + k: v for k, v in ba.items()}))
+                         **{"a_" + k: LC.recorded_rows(v, pos) for k, v in ba.items()}))
     a, b = runs
     assert a["trained"] >= 1 and a["ego_it"] >= 2
-    _assert_same_run(a, b)
+    LC.same_state(a, b)
 
 
 # ---- 5. LiarIterationGraph ---------------------------------------------------------------------------------------------------------

@@ -17,32 +17,12 @@ import torch as th
 
 from tests import bc_cases as B
 from tests import helpers as H
+from tests.bc_shape_cases import _assert_path, _clone, _reset
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TRAIN_IDS = [c.id for c in B.TRAINABLE]
 ALL_IDS = [c.id for c in B.CASES]
-VALU_ONLY = os.environ.get("PH_BC_MFMA", "1").startswith("0")
-
-
-def _clone(case, obs, acts, batch_size=128, **opt):
-    from pantheonrl_amd.bc import BC
-    from pantheonrl_amd.common import TransitionsMinimal
-    return BC(H.to_space(case.obs), H.to_space(case.act), expert_data=TransitionsMinimal(obs, acts),
-              optimizer_kwargs=dict(betas=(0.0, 0.999), **opt), batch_size=batch_size)
-
-
-def _reset(clone, p0, ent_weight, l2_weight):
-    clone.policy.set_flat_params(p0)
-    H.load_device_adam_state(clone, np.zeros_like(p0), np.zeros_like(p0), 0)
-    clone.ent_weight, clone.l2_weight = float(ent_weight), float(l2_weight)
-
-
-def _assert_path(case, clone):
-    from pantheonrl_amd import _native as nat
-    want = min(case.path, 1) if VALU_ONLY else case.path
-    assert nat.bc_train_path(clone.policy.spec) == want, (case.id, nat.bc_train_path(clone.policy.spec), want)
-    return want
 
 
 def _assert_value_head(m, p0, case, l2_weight, where):

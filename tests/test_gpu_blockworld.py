@@ -198,11 +198,19 @@ def test_vec_block_selfplay_matches_the_python_step_loop(variant):
 def test_vec_block_native_step_is_bitwise_the_per_call_step(variant):
     """ph_block_selfplay_step (one engine call per vectorised step, masks on the device) against the per-call / torch-mask walk
     with the same RNG counters: identical game state, observations, both rollout buffers, partner book-keeping and -- after
-    both learners have trained -- identical parameters."""
+    both learners have trained -- identical parameters.  The native run steps through ph_block_selfplay_step itself; a third run
+    makes the driver's own call, ph_block_selfplay_step_arch(NULL, NULL), and holds the same bits."""
     E, T_ego, T_alt = 48, 8, 6
     runs = []
-    for native in (True, False):
+    for native, plain in ((True, True), (False, False), (True, False)):
         sp, ego, alt, _ = _selfplay(variant, E, T_ego, T_alt, seed=11, native=native)
+        if plain:
+            def plain_step(counter, ego_pos=-1, sp=sp, rb=ego.model.rollout_buffer):
+                sp._bind()
+                nat.check(sp.env.ctx.lib.ph_block_selfplay_step(sp.env.ctx.handle, C.byref(sp._desc),
+                                                                int(rb.pos if ego_pos < 0 else ego_pos), int(counter)))
+            assert sp._archs == (None, None)
+            sp._native_call = plain_step
         alt.model.rollout_buffer.gae_mode = ego.model.rollout_buffer.gae_mode = 1
         trained = 0
         for _ in range(3 * T_ego):
@@ -218,15 +226,16 @@ def test_vec_block_native_step_is_bitwise_the_per_call_step(variant):
                          pe=ego.model.policy.get_flat_params(), pa=alt.model.policy.get_flat_params(),
                          **{"e_" + k: v for k, v in be.items() if k in ("observations", "actions", "rewards", "episode_starts")},
                          **{"a_" + k: v for k, v in ba.items()}))
-    a, b = runs
+    a = runs[0]
     assert a["trained"] >= 1 and a["ego_it"] >= 2
     pos = a["pos"]
-    for key in a:
-        x, y = a[key], b[key]
-        if key.startswith("a_") and getattr(x, "ndim", 0) >= 2:      # only the recorded rows of the ragged buffer are defined
-            rows = np.arange(x.shape[0])[:, None] < pos[None, :]
-            x, y = x[rows], y[rows]
-        assert np.array_equal(x, y), key
+    for b in runs[1:]:
+        for key in a:
+            x, y = a[key], b[key]
+            if key.startswith("a_") and getattr(x, "ndim", 0) >= 2:      # only the recorded rows of the ragged buffer are defined
+                rows = np.arange(x.shape[0])[:, None] < pos[None, :]
+                x, y = x[rows], y[rows]
+            assert np.array_equal(x, y), key
 
 
 def test_native_step_does_no_host_work_and_captures():

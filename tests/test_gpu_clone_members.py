@@ -9,82 +9,12 @@ import pytest
 import torch as th
 
 from pantheonrl_amd import _native as nat
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
 
-RB_KEYS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs")
-XSTATE = ("hands", "history", "nmoves", "obs_ego", "obs_alt", "games", "playing", "tables_left", "returns", "lengths", "ep_return",
-          "ep_length")
-KIND = dict(learner=nat.PH_POOL_LEARNER, frozen=nat.PH_POOL_FROZEN, scripted=nat.PH_POOL_SCRIPTED, clone=nat.PH_POOL_CLONE)
-
-
-def _spaces():
-    from pantheonrl_amd.envs.vec import VecLiarsDice
-    return type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
-                              _is_dummy_space_env=True))()
-
-
-def _ppo(E, T, seed):
-    from pantheonrl_amd import PPO
-    model = PPO("MlpPolicy", _spaces(), n_steps=T, n_envs=E, batch_size=max(8, E * T // 2), n_epochs=2, seed=seed)
-    model.device_permutations = True
-    model.rollout_buffer.gae_mode = 1
-    return model
-
-
-def _clone_policy(seed):
-    """a FeedForward32Policy on the Liar's Dice spaces with parameters of order one (sharp enough that a wrong bit moves a sample);
-    the same seed gives the same parameters and the same Philox key"""
-    from pantheonrl_amd.bc import FeedForward32Policy
-    s = _spaces()
-    pol = FeedForward32Policy(s.observation_space, s.action_space, seed=1000 + seed)
-    pol.set_flat_params(0.4 * np.random.default_rng(seed).standard_normal(pol.layout.P).astype(np.float32))
-    return pol
-
-
-def _member(kind, E, T_alt, seed):
-    from pantheonrl_amd.envs.vec import ClonedVecPartner, FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner
-    if kind == "learner":
-        return RaggedVecOnPolicyAgent(_ppo(E, T_alt, seed))
-    if kind == "frozen":
-        return FrozenVecPartner(_ppo(E, 2, seed).policy)
-    if kind == "clone":
-        return ClonedVecPartner(_clone_policy(seed))
-    return VecLiarDefaultPartner()
-
-
-def _pool(E, T_ego, T_alt, kinds, seed=0, native=True, resample="robin", record=0):
-    from pantheonrl_amd.envs.vec import VecLiarPartnerPool
-    from pantheonrl_amd.vec import VecOnPolicyAgent
-    ego = VecOnPolicyAgent(_ppo(E, T_ego, seed))
-    members = [_member(kind, E, T_alt, seed + 1 + k) for k, kind in enumerate(kinds)]
-    return VecLiarPartnerPool(E, ego, members, seed=seed + 7, resample=resample, native=native, record=record), ego, members
-
-
-def _xplay(E, kinds, G, pairs=None, seed=5, native=True, record=0):
-    from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
-    members = [_member(kind, 4, 2, 20 + k) for k, kind in enumerate(kinds)]
-    return VecLiarCrossPlay(E, members, pairs=pairs, episodes_per_table=G, seed=seed, native=native, record=record)
-
-
-def _ctx_of(agent):
-    ctx = agent.model.policy.ctx
-    ctx.set_stream(th.cuda.current_stream(agent.model.policy.device).cuda_stream)
-    return ctx
-
 
 # ---- 1. the grouped forward on its own -------------------------------------------------------------------------------------------
-def _interleave(counts):
-    """member ids with the given counts, interleaved by table index (round robin over the members that still have rows left)"""
-    left, out = list(counts), []
-    while any(left):
-        for k in range(len(left)):
-            if left[k]:
-                out.append(k)
-                left[k] -= 1
-    return np.asarray(out, np.int32)
-
-
 def _forward_case(name):
     """-> (kinds, partnerid, active).  The mixed case has active-row counts [17, 16, 1, 0, 16] per member, interleaved by table
     index: a full tile plus one row, a one-row tile, a member with no rows, clone tiles beside tiles of every other kind, two clones
@@ -92,10 +22,10 @@ def _forward_case(name):
     active rows with four inactive ones in between (one of them naming the member that has no row)."""
     mixed = ["clone", "frozen", "clone", "scripted", "learner"]
     if name == "mixed50":
-        pid = _interleave([17, 16, 1, 0, 16])
+        pid = LC.interleave([17, 16, 1, 0, 16])
         return mixed, pid, np.ones(50, np.uint8)
     if name == "mixed54":
-        pid, active = _interleave([17, 16, 1, 0, 16]).tolist(), [1] * 50
+        pid, active = LC.interleave([17, 16, 1, 0, 16]).tolist(), [1] * 50
         for at, k in ((3, 0), (17, 3), (30, 2), (41, 4)):
             pid.insert(at, k)
             active.insert(at, 0)
@@ -116,21 +46,21 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     kinds, pid_h, active_h = _forward_case(case)
     n, K, T, counter = len(pid_h), len(kinds), 4, 9
     rng = np.random.default_rng(5)
-    obs_space = _spaces().observation_space
+    obs_space = LC.spaces().observation_space
     obs = th.as_tensor((rng.random((n, 30)) * np.asarray(obs_space.nvec)).astype(np.int64).astype(np.float32)).cuda()
     pid, active = th.as_tensor(pid_h).cuda(), th.as_tensor(active_h).cuda()
-    host = VecOnPolicyAgent(_ppo(n, 2, 0))
-    ctx = _ctx_of(host)
+    host = VecOnPolicyAgent(LC.ppo(n, 2, 0))
+    ctx = LC.ctx_of(host)
     lib, h, spec = ctx.lib, ctx.handle, C.byref(host.model.policy.spec)
     sets = []
     for _ in range(2):                                    # two identical sets: one for the grouped launch, one for the yardstick
-        members = [_member(kind, n, T, 20 + k) for k, kind in enumerate(kinds)]
+        members = [LC.member(kind, n, T, 20 + k) for k, kind in enumerate(kinds)]
         fill = np.random.default_rng(6)
         for k, m in enumerate(members):
             if kinds[k] != "learner":
                 continue
             rb = m.model.rollout_buffer
-            for key in RB_KEYS:
+            for key in LC.RB_KEYS:
                 t = getattr(rb, key)
                 t.copy_(th.as_tensor(fill.standard_normal(tuple(t.shape)).astype(np.float32)))
             m.pos.copy_(th.as_tensor(((2 * np.arange(n) + k) % (T + 1)).astype(np.int32)))   # every fill level, full columns included
@@ -151,7 +81,7 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     arr = (nat.PhPoolMember * K)()
     keep = []
     for k, m in enumerate(grouped):
-        arr[k].kind = KIND[kinds[k]]
+        arr[k].kind = LC.KINDS[kinds[k]][0]
         if kinds[k] == "scripted":
             continue
         pol = m.model.policy if kinds[k] == "learner" else m.policy
@@ -218,68 +148,23 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
 
 
 # ---- 2. the native step is bitwise the walk --------------------------------------------------------------------------------------
-def _pool_state(sp, ego):
-    th.cuda.synchronize()
-    out = dict(hands=sp.env.hands.cpu().numpy(), hist=sp.env.history.cpu().numpy(), nmoves=sp.env.nmoves.cpu().numpy(),
-               obs=sp.obs_ego.cpu().numpy(), pid_now=sp.partnerid.cpu().numpy(), acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes,
-               ego_it=ego.iteration, pe=ego.model.policy.get_flat_params())
-    be = ego.model.rollout_buffer.host()
-    out.update({"e_" + k: v for k, v in be.items() if k in ("observations", "actions", "rewards", "episode_starts")})
-    for i, m in enumerate(sp.learners):
-        out[f"pos{i}"] = m.pos.cpu().numpy()
-        out[f"flags{i}"] = np.stack([t.cpu().numpy() for t in (m.boundary, m.term, m.open)])
-        out[f"values{i}"] = m.values.cpu().numpy()
-        out[f"p{i}"] = m.model.policy.get_flat_params()
-        out.update({f"a{i}_" + k: v for k, v in m.model.rollout_buffer.host().items() if k in RB_KEYS})
-    return out
-
-
-def _run_pool(native, resample, kinds, E, T_ego, T_alt, steps, seed=11):
-    sp, ego, members = _pool(E, T_ego, T_alt, kinds, seed=seed, native=native, resample=resample)
-    trained = [0] * len(sp.learners)
-    pids = []
-    for _ in range(steps):
-        sp.step()
-        pids.append(sp.partnerid.cpu().numpy().copy())
-        for i, m in enumerate(sp.learners):
-            if m.full():
-                m.learn_from_buffer()
-                trained[i] += 1
-    out = _pool_state(sp, ego)
-    out.update(pid=np.stack(pids), trained=trained)
-    return out
-
-
 @pytest.mark.parametrize("resample", ["robin", "random"])
 def test_native_pool_step_with_clones_is_bitwise_the_walk(resample):
     kinds = ["learner", "clone", "scripted", "clone"]
-    a, b = (_run_pool(native, resample, kinds, E=50, T_ego=8, T_alt=4, steps=24) for native in (True, False))
+    a, b = (LC.run_pool(native, resample, kinds, E=50, T_ego=8, T_alt=4, steps=24) for native in (True, False))
     assert min(a["trained"]) >= 1 and a["trained"] == b["trained"], a["trained"]
     assert a["ego_it"] >= 2 and a["episodes"] > 50
     assert len(np.unique(a["pid"])) == 4                   # every member sat somewhere, both clones included
-    for key in a:
-        x, y = a[key], b[key]
-        if key[0] == "a" and key[1].isdigit() and getattr(x, "ndim", 0) >= 2:       # only the recorded rows of a ragged buffer are defined
-            pos = a["pos" + key[1]]
-            rows = np.arange(x.shape[0])[:, None] < pos[None, :]
-            x, y = x[rows], y[rows]
-        assert np.array_equal(x, y), key
-
-
-def _xstate(xp):
-    th.cuda.synchronize()
-    out = {k: getattr(xp.env if k in ("hands", "history", "nmoves") else xp, k).cpu().numpy().copy() for k in XSTATE}
-    out["ego_first"] = xp.ego_first.cpu().numpy().copy()
-    return out
+    LC.same_state(a, b)
 
 
 def test_native_crossplay_step_with_clones_is_bitwise_the_walk_after_every_step():
     E, G, kinds = 50, 3, ["clone", "frozen", "scripted", "clone"]          # all 16 pairs on 50 tables
-    a, b = (_xplay(E, kinds, G, native=native) for native in (True, False))
+    a, b = (LC.xplay(E, kinds, G, native=native) for native in (True, False))
     assert a.P == 16
     steps = 0
     while True:
-        sa, sb = _xstate(a), _xstate(b)
+        sa, sb = LC.xstate(a), LC.xstate(b)
         for key in sa:
             assert np.array_equal(sa[key], sb[key]), (steps, key)
         if sb["tables_left"][0] == 0:
@@ -303,7 +188,7 @@ def test_recorded_clone_games_replay_through_the_host_game():
     from pantheonrl_amd.envs.liar import LiarEnv
     E, G = 12, 2
     pairs = [(0, 0), (0, 1), (1, 0)]                        # (clone, clone), (clone, scripted), (scripted, clone)
-    xp = _xplay(E, ["clone", "scripted"], G, pairs=pairs, record=3 * MAX_STEPS_PER_GAME * G)
+    xp = LC.xplay(E, ["clone", "scripted"], G, pairs=pairs, record=3 * MAX_STEPS_PER_GAME * G)
     # the deals: hands and who opens, game by game, read from the device between steps
     deals = [[None] * G for _ in range(E)]
 
@@ -353,7 +238,7 @@ def test_recorded_clone_games_replay_through_the_host_game():
 # ---- 4. no host work ---------------------------------------------------------------------------------------------------------------
 def test_native_pool_step_with_clones_does_no_host_work_and_captures():
     kinds = ["learner", "clone", "scripted", "clone"]
-    (eager, ego_e, _), (sp, ego, _) = (_pool(32, 8, 8, kinds, seed=3) for _ in range(2))
+    (eager, ego_e, _), (sp, ego, _) = (LC.pool(32, 8, 8, kinds, seed=3) for _ in range(2))
     for c in range(1, 7):
         eager._native_call(c, ego_pos=c - 1)
     stream = th.cuda.Stream(device=sp.dev)
@@ -377,15 +262,8 @@ def test_native_pool_step_with_clones_does_no_host_work_and_captures():
         stream.synchronize()
     th.cuda.synchronize()
     assert sp.episodes > episodes
-    a, b = _pool_state(sp, ego), _pool_state(eager, ego_e)
-    for key in a:
-        x, y = a[key], b[key]
-        if key[0] == "a" and key[1].isdigit() and getattr(x, "ndim", 0) >= 2:
-            rows = np.arange(x.shape[0])[:, None] < a["pos" + key[1]][None, :]
-            x, y = x[rows], y[rows]
-        if key.startswith("e_"):
-            x, y = x[:6], y[:6]
-        assert np.array_equal(x, y), key
+    a, b = LC.train_state(sp, ego), LC.train_state(eager, ego_e)
+    LC.same_state(a, b, ego_rows=6)
 
 
 # ---- 5. misuse ---------------------------------------------------------------------------------------------------------------------
@@ -394,7 +272,7 @@ def test_clone_misuse_is_an_error_string_and_nothing_is_launched():
     from pantheonrl_amd.bc import FeedForward32Policy
     from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
     from pantheonrl_amd.envs.vec import ClonedVecPartner, FrozenVecPartner, RaggedVecOnPolicyAgent
-    sp, ego, members = _pool(16, 4, 4, ["clone", "frozen", "scripted"], seed=1)
+    sp, ego, members = LC.pool(16, 4, 4, ["clone", "frozen", "scripted"], seed=1)
     ctx = sp.env.ctx
     sp._bind()
     lib, h, d = ctx.lib, ctx.handle, sp._desc
@@ -414,15 +292,15 @@ def test_clone_misuse_is_an_error_string_and_nothing_is_launched():
     th.cuda.synchronize()
     for k, v in before.items():                              # refused in front of the first launch: the game did not move
         assert np.array_equal(getattr(sp.env, k).cpu().numpy(), v), k
-    s = _spaces()
+    s = LC.spaces()
     with pytest.raises(nat.NativeError, match="ClonedVecPartner"):
         FrozenVecPartner(FeedForward32Policy(s.observation_space, s.action_space, seed=1))
     with pytest.raises(nat.NativeError, match="Liar's Dice spaces"):
         ClonedVecPartner(FeedForward32Policy(sps.Discrete(1), sps.Discrete(3), seed=1))          # RPS
     with pytest.raises(nat.NativeError, match="FeedForward32Policy"):
-        ClonedVecPartner(_ppo(4, 2, 3).policy)                                                   # a 64-64 ActorCriticPolicy
+        ClonedVecPartner(LC.ppo(4, 2, 3).policy)                                                   # a 64-64 ActorCriticPolicy
     with pytest.raises(nat.NativeError, match="learners train in VecLiarPartnerPool"):
-        VecLiarCrossPlay(8, [RaggedVecOnPolicyAgent(_ppo(8, 2, 3))])
+        VecLiarCrossPlay(8, [RaggedVecOnPolicyAgent(LC.ppo(8, 2, 3))])
     # ... and the context still steps
     sp.step()
     th.cuda.synchronize()

@@ -10,45 +10,20 @@ import pytest
 import torch as th
 
 from pantheonrl_amd import _native as nat
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
-
-STATE = ("hands", "history", "nmoves", "obs_ego", "obs_alt", "games", "playing", "tables_left", "returns", "lengths", "ep_return",
-         "ep_length")
-
-
-def _spaces():
-    from pantheonrl_amd.envs.vec import VecLiarsDice
-    return type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
-                              _is_dummy_space_env=True))()
 
 
 def _ppo(seed, **kw):
     from pantheonrl_amd import PPO
-    return PPO("MlpPolicy", _spaces(), n_steps=2, n_envs=4, batch_size=8, n_epochs=1, seed=seed, **kw)
-
-
-def _members(kinds, seed=20):
-    from pantheonrl_amd.envs.vec import FrozenVecPartner, VecLiarDefaultPartner
-    return [FrozenVecPartner(_ppo(seed + k).policy) if kind == "frozen" else VecLiarDefaultPartner() for k, kind in enumerate(kinds)]
-
-
-def _xplay(E, kinds, G, pairs=None, seed=5, native=True, cls=None, member_seed=20):
-    from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
-    return (cls or VecLiarCrossPlay)(E, _members(kinds, member_seed), pairs=pairs, episodes_per_table=G, seed=seed, native=native)
-
-
-def _state(xp):
-    th.cuda.synchronize()
-    out = {k: getattr(xp.env if k in ("hands", "history", "nmoves") else xp, k).cpu().numpy().copy() for k in STATE}
-    out["ego_first"] = xp.ego_first.cpu().numpy().copy()
-    return out
+    return PPO("MlpPolicy", LC.spaces(), n_steps=2, n_envs=4, batch_size=8, n_epochs=1, seed=seed, **kw)
 
 
 # ---- 1. the native step is bitwise the walk --------------------------------------------------------------------------------------
 def test_native_crossplay_step_is_bitwise_the_walk_after_every_step():
     E, G, kinds = 50, 3, ["frozen", "frozen", "scripted", "frozen"]        # 16 pairs on 50 tables: 3 or 4 tables each
-    a, b = (_xplay(E, kinds, G, native=native) for native in (True, False))
+    a, b = (LC.xplay(E, kinds, G, native=native) for native in (True, False))
     assert a.P == 16 and np.bincount(a.pair_of_table).tolist() == [4, 4] + [3] * 14
     assert np.array_equal(a.ego_id.cpu().numpy(), a.pairs[np.arange(E) % 16, 0])
     assert np.array_equal(a.alt_id.cpu().numpy(), a.pairs[np.arange(E) % 16, 1])
@@ -56,7 +31,7 @@ def test_native_crossplay_step_is_bitwise_the_walk_after_every_step():
     partner_opened = False
     steps = 0
     while True:
-        sa, sb = _state(a), _state(b)
+        sa, sb = LC.xstate(a), LC.xstate(b)
         for key in sa:
             assert np.array_equal(sa[key], sb[key]), (steps, key)
         assert np.array_equal(sb["playing"], (sb["games"] < G).astype(np.uint8))
@@ -80,15 +55,15 @@ def test_native_crossplay_step_is_bitwise_the_walk_after_every_step():
 
 # ---- 2. idle means idle ------------------------------------------------------------------------------------------------------------
 def test_a_table_that_spent_its_budget_never_changes_again():
-    xp = _xplay(20, ["frozen", "scripted"], 2)
+    xp = LC.xplay(20, ["frozen", "scripted"], 2)
     res = xp.run(chunk=3)
     assert xp.left() == 0 and res.steps <= 14 and (res.count == 2 * 5).all()
     scratch = ("ego_actions", "alt_actions", "_running", "_alt_opens", "_ego_opens", "_done")
-    before = _state(xp)
+    before = LC.xstate(xp)
     before.update({k: getattr(xp, k).cpu().numpy().copy() for k in scratch})
     for _ in range(4):
         xp.step()
-    after = _state(xp)
+    after = LC.xstate(xp)
     after.update({k: getattr(xp, k).cpu().numpy().copy() for k in scratch})
     for key in before:
         assert np.array_equal(before[key], after[key]), key
@@ -131,7 +106,7 @@ def test_crossplay_walk_matches_the_host_multiagentenv_table_by_table():
 
     E, G, kinds = 24, 3, ["frozen", "scripted", "frozen"]
     pairs = [(0, 0), (1, 0), (0, 1), (2, 0), (1, 1)]          # a diagonal pair, the scripted member in seat 0, in seat 1, in both
-    xp = _xplay(E, kinds, G, pairs=pairs, seed=2, native=False, cls=Logged)
+    xp = LC.xplay(E, kinds, G, pairs=pairs, seed=2, native=False, cls=Logged)
     ego_kind = [kinds[pairs[e % 5][0]] for e in range(E)]
     alt_kind = [kinds[pairs[e % 5][1]] for e in range(E)]
     shadows = [Shadow() for _ in range(E)]
@@ -197,7 +172,7 @@ def test_statistics_kernel_is_the_host_statement_and_runs_are_bitwise_repeatable
     E, G, kinds = 40, 5, ["frozen", "scripted", "frozen"]           # 9 pairs on 40 tables: 5 or 4 tables each
     runs = []
     for seed in (5, 5, 6):
-        xp = _xplay(E, kinds, G, seed=seed)
+        xp = LC.xplay(E, kinds, G, seed=seed)
         res = xp.run()
         runs.append((res, xp.stats.cpu().numpy().copy()))
     res, raw = runs[0]
@@ -215,7 +190,7 @@ def test_statistics_kernel_is_the_host_statement_and_runs_are_bitwise_repeatable
     m = res.matrix("mean")
     assert m.shape == (3, 3) and np.array_equal(m.reshape(-1), res.mean) and not np.isnan(m).any()
     # a partial pair list leaves nan where nothing was played
-    part = _xplay(8, kinds, 1, pairs=[(0, 1), (2, 2)]).run().matrix("count")
+    part = LC.xplay(8, kinds, 1, pairs=[(0, 1), (2, 2)]).run().matrix("count")
     assert part[0, 1] == 4 and part[2, 2] == 4 and np.isnan(part).sum() == 7
     # the same seeds: the same bits; another dice seed: other games
     again, raw_again = runs[1]
@@ -227,7 +202,7 @@ def test_statistics_kernel_is_the_host_statement_and_runs_are_bitwise_repeatable
 # ---- 5. graph capture --------------------------------------------------------------------------------------------------------------
 def test_a_captured_chunk_of_crossplay_steps_replays_with_no_host_work():
     kinds = ["frozen", "scripted", "frozen"]
-    xp, eager = _xplay(32, kinds, 6), _xplay(32, kinds, 6)
+    xp, eager = LC.xplay(32, kinds, 6), LC.xplay(32, kinds, 6)
     for c in range(1, 7):
         eager.step()
     stream = th.cuda.Stream(device=xp.dev)
@@ -250,7 +225,7 @@ def test_a_captured_chunk_of_crossplay_steps_replays_with_no_host_work():
         stream.synchronize()
     th.cuda.synchronize()
     assert int(xp.games.sum().item()) > games                       # games advance across the replay
-    sa, sb = _state(xp), _state(eager)
+    sa, sb = LC.xstate(xp), LC.xstate(eager)
     for key in sa:                                                   # and the replay is the four eager steps
         assert np.array_equal(sa[key], sb[key]), key
 
@@ -260,7 +235,7 @@ def test_crossplay_abi_misuse_is_reported_not_fatal():
     from pantheonrl_amd import spaces as sps
     from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
     from pantheonrl_amd.envs.vec import VecLiarDefaultPartner
-    xp = _xplay(16, ["frozen", "scripted", "frozen"], 2)
+    xp = LC.xplay(16, ["frozen", "scripted", "frozen"], 2)
     xp._bind()
     lib, h, d = xp.ctx.lib, xp.ctx.handle, xp._desc
     err = lambda: lib.ph_last_error()  # noqa: E731

@@ -8,6 +8,7 @@ import pytest
 import torch as th
 
 from pantheonrl_amd import _native as nat
+from tests import liar_cases as LC
 from tests.episode_stats_oracle import EpisodeOracle
 
 pytestmark = pytest.mark.gpu
@@ -165,12 +166,6 @@ def test_misuse_is_refused_by_name():
 
 
 # ---- the real environments -----------------------------------------------------------------------------------------------------
-def _spaces():
-    from pantheonrl_amd.envs.vec import VecLiarsDice
-    return type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
-                              _is_dummy_space_env=True))()
-
-
 def _ppo(spaces, E, T, seed):
     from pantheonrl_amd import PPO
     model = PPO("MlpPolicy", spaces, n_steps=T, n_envs=E, batch_size=max(8, E * T // 2), n_epochs=2, seed=seed)
@@ -179,10 +174,7 @@ def _ppo(spaces, E, T, seed):
 
 
 def _selfplay(E, T, seed=5, persistent=None):
-    from pantheonrl_amd.envs.vec import RaggedVecOnPolicyAgent, VecLiarSelfPlay
-    from pantheonrl_amd.vec import VecOnPolicyAgent
-    ego, alt = VecOnPolicyAgent(_ppo(_spaces(), E, T, seed)), RaggedVecOnPolicyAgent(_ppo(_spaces(), E, 6, seed + 1))
-    sp = VecLiarSelfPlay(E, ego, alt, seed=seed + 7)
+    sp, ego, alt = LC.selfplay(E, _ppo(LC.spaces(), E, T, seed), _ppo(LC.spaces(), E, 6, seed + 1), seed=seed)
     if persistent is not None:
         sp.persistent = persistent
     return sp, ego, alt
@@ -197,8 +189,8 @@ def test_pool_episodes_are_credited_to_the_member_that_sat(resample):
     from pantheonrl_amd.episode_stats import EpisodeStats
     from pantheonrl_amd.vec import VecOnPolicyAgent
     E, T, K = 48, 8, 3
-    ego = VecOnPolicyAgent(_ppo(_spaces(), E, T, 2))
-    members = [VecLiarDefaultPartner(), VecLiarDefaultPartner(), RaggedVecOnPolicyAgent(_ppo(_spaces(), E, 6, 3))]
+    ego = VecOnPolicyAgent(_ppo(LC.spaces(), E, T, 2))
+    members = [VecLiarDefaultPartner(), VecLiarDefaultPartner(), RaggedVecOnPolicyAgent(_ppo(LC.spaces(), E, 6, 3))]
     env = VecLiarPartnerPool(E, ego, members, seed=9, resample=resample)
     stats = EpisodeStats(ego, env)
     assert env.episode_stats is stats and ego.episode_stats is stats and stats.K == K

@@ -13,7 +13,7 @@ import torch as th
 
 from oracle import sb3_oracle as orc
 from tests import helpers as H
-from tests.test_gpu_parity import _assert_grads, _assert_train_stats, _grad_pair, _train_pair
+from tests.parity_cases import _assert_grads, _assert_train_stats, _grad_pair, _train_pair
 
 pytestmark = pytest.mark.gpu
 

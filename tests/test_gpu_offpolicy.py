@@ -34,21 +34,21 @@ def _device_pair(c, mode):
     """-> (g, g_ref, st, st_ref) through the family's own _grad_pair, with the case's stale buffer and edge-free rows passed in"""
     hp, fill, idx = OC.hyper(c), OC.fill(c), OC.pick_idx(c)
     if c.family == "ppo":
-        from tests.test_gpu_parity import _grad_pair
+        from tests.parity_cases import _grad_pair
         g, g_ref, st, st_ref, _ = _grad_pair(c.config, c.T, c.E, idx, hp, seed=OC.SEED, gemm_mode=mode, fill=fill)
     elif c.family == "arch":
-        from tests.test_gpu_arch import _grad_pair
+        from tests.arch_cases import _grad_pair
         out, g_ref, st_ref = _grad_pair(c.config, c.arch, c.T, c.E, idx, hp, seed=OC.SEED, gemm_mode=mode, fill=fill)
         g, st = out[0]
     elif c.family == "modular":
-        from tests.test_gpu_modular import _grad_pair
+        from tests.modular_cases import _grad_pair
         g, g_ref, st, st_ref, _ = _grad_pair(c.config, c.K, c.partner, c.T, c.E, c.nb, c.coef, hp, seed=OC.SEED, gemm_mode=mode,
                                              fill=fill, idx=idx)
     elif c.family == "adap":
-        from tests.test_gpu_adap import _grad_pair
+        from tests.adap_cases import _grad_pair
         g, g_ref, st, st_ref = _grad_pair(c.config, c.T, c.E, idx, hp, 5, 32, c.coef, seed=OC.SEED, gemm_mode=mode, fill=fill)[:4]
     else:
-        from tests.test_gpu_adapmult import _grad_pair
+        from tests.adapmult_cases import _grad_pair
         assert mode == 0
         g, g_ref, st, st_ref = _grad_pair(c.config, c.T, c.E, c.nb, hp, coef=c.coef, seed=OC.SEED, fill=fill, idx=idx)[:4]
     return g, g_ref, st, st_ref
@@ -97,15 +97,15 @@ def _device_train(t, T, E, hp, bufs, perms, samples, orac0):
     which builds the same checker and, through `fill`, gets the same buffer)"""
     given = lambda *a, **k: bufs[0]     # noqa: E731
     if t.family == "ppo":
-        from tests.test_gpu_parity import _train_pair
+        from tests.parity_cases import _train_pair
         assert np.array_equal(perms, OC.train_perms(t, hp.n_epochs, N=T * E))
         return _train_pair(t.config, T, E, hp, seed=t.seed, fill=given, exclusive=t.exclusive)[0]
     if t.family == "arch":
-        from tests.test_gpu_arch import _train_pair
+        from tests.arch_cases import _train_pair
         assert np.array_equal(perms, OC.train_perms(t, hp.n_epochs, N=T * E))
         return _train_pair(t.config, t.arch, T, E, hp, seed=t.seed, fill=given)[0]
     if t.family == "modular":
-        from tests import test_gpu_modular as M
+        from tests import modular_cases as M
         model = M._algo(t.config, len(bufs), T, E, hp, t.coef)
         model.policy.set_flat_params(M._flat(orac0))
         for rb, ob in zip(model.rollout_buffer, bufs):
@@ -113,10 +113,10 @@ def _device_train(t, T, E, hp, bufs, perms, samples, orac0):
         model.train(perms=np.asarray([list(perms)] * len(bufs)))
         return model
     if t.family == "adap":
-        from tests.test_gpu_adap import _adap_model
+        from tests.adap_cases import _adap_model
         model = _adap_model(t.config, T, E, hp, coef=t.coef, n_ctx=OC.N_CTX, n_states=OC.N_STATES)
     else:
-        from tests.test_gpu_adapmult import _model
+        from tests.adapmult_cases import _model
         model = _model(t.config, T, E, hp, t.coef, n_ctx=OC.N_CTX, n_states=OC.N_STATES)
     model.policy.set_flat_params(orac0.flat_params())
     H.upload_buffer(model.rollout_buffer, bufs[0])
@@ -125,9 +125,9 @@ def _device_train(t, T, E, hp, bufs, perms, samples, orac0):
 
 
 def _assert_rows(t, st, ref, where):
-    """last_train_stats rows against the checker's: the project's train rule (tests/test_gpu_parity._assert_train_stats), with
+    """last_train_stats rows against the checker's: the project's train rule (tests/parity_cases._assert_train_stats), with
     clip_fraction EXACT (no edge row in any minibatch: tests/test_offpolicy_checks.py)"""
-    from tests.test_gpu_parity import _assert_train_stats
+    from tests.parity_cases import _assert_train_stats
     st = np.asarray(st).reshape(-1, st.shape[-1])
     st = st[np.abs(st).sum(-1) > 0]
     assert len(st) == len(ref["stats"]), (where, len(st), len(ref["stats"]))

@@ -26,9 +26,9 @@ from oracle import sb3_oracle as orc
 from tests import arch_oracle as A
 from tests import helpers as H
 from tests import optimizer_bound as OB
-from tests import test_gpu_adapmult as AM
-from tests import test_gpu_modular as M
-from tests import test_optimizer_checks as OC
+from tests import adapmult_cases as AM
+from tests import modular_cases as M
+from tests import optimizer_cases as OC
 
 pytestmark = pytest.mark.gpu
 

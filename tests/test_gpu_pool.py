@@ -11,50 +11,11 @@ import pytest
 import torch as th
 
 from pantheonrl_amd import _native as nat
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-RB_KEYS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs")
-
-
-def _spaces():
-    from pantheonrl_amd.envs.vec import VecLiarsDice
-    return type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
-                              _is_dummy_space_env=True))()
-
-
-def _ppo(E, T, seed):
-    from pantheonrl_amd import PPO
-    model = PPO("MlpPolicy", _spaces(), n_steps=T, n_envs=E, batch_size=max(8, E * T // 2), n_epochs=2, seed=seed)
-    model.device_permutations = True
-    model.rollout_buffer.gae_mode = 1
-    return model
-
-
-def _member(kind, E, T_alt, seed):
-    from pantheonrl_amd.envs.vec import FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner
-    if kind == "learner":
-        return RaggedVecOnPolicyAgent(_ppo(E, T_alt, seed))
-    if kind == "frozen":
-        return FrozenVecPartner(_ppo(E, 2, seed).policy)
-    return VecLiarDefaultPartner()
-
-
-def _pool(E, T_ego, T_alt, kinds, seed=0, native=True, resample="robin", before=None):
-    from pantheonrl_amd.envs.vec import VecLiarPartnerPool
-    from pantheonrl_amd.vec import VecOnPolicyAgent
-    ego = VecOnPolicyAgent(_ppo(E, T_ego, seed))
-    members = [_member(kind, E, T_alt, seed + 1 + k) for k, kind in enumerate(kinds)]
-    if before is not None:
-        before(members)             # e.g. loggers that must see the constructor's deal
-    return VecLiarPartnerPool(E, ego, members, seed=seed + 7, resample=resample, native=native), ego, members
-
-
-def _ctx_of(ego):
-    ctx = ego.model.policy.ctx
-    ctx.set_stream(th.cuda.current_stream(ego.model.policy.device).cuda_stream)
-    return ctx
 
 
 # ---- 1. the scripted rule ------------------------------------------------------------------------------------------------------
@@ -64,7 +25,7 @@ def test_scripted_rule_is_the_reference_default_agent_on_active_rows_only():
     want = np.asarray(ref["liar_actions"], np.int32)
     n = obs.shape[0]
     assert n == 400
-    ctx = _ctx_of(_pool(4, 2, 2, ["scripted"])[1])
+    ctx = LC.ctx_of(LC.pool(4, 2, 2, ["scripted"])[1])
     active = th.as_tensor((np.arange(n) % 3 != 1).astype(np.uint8)).cuda()
     out = th.full((n, 2), -7, dtype=th.int32, device="cuda")
     nat.check(ctx.lib.ph_liar_default_actions(ctx.handle, obs.data_ptr(), active.data_ptr(), out.data_ptr(), n))
@@ -95,21 +56,21 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     kinds, pid_h, active_h = _forward_case(case)
     n, K, T, counter = len(pid_h), len(kinds), 4, 9
     rng = np.random.default_rng(5)
-    obs_space = _spaces().observation_space
+    obs_space = LC.spaces().observation_space
     obs = th.as_tensor((rng.random((n, 30)) * np.asarray(obs_space.nvec)).astype(np.int64).astype(np.float32)).cuda()
     pid, active = th.as_tensor(pid_h).cuda(), th.as_tensor(active_h).cuda()
-    host = VecOnPolicyAgent(_ppo(n, 2, 0))
-    ctx = _ctx_of(host)
+    host = VecOnPolicyAgent(LC.ppo(n, 2, 0))
+    ctx = LC.ctx_of(host)
     lib, h, spec = ctx.lib, ctx.handle, C.byref(host.model.policy.spec)
     sets = []
     for _ in range(2):                                    # two identical sets: one for the grouped launch, one for the yardstick
-        members = [_member(kind, n, T, 20 + k) for k, kind in enumerate(kinds)]
+        members = [LC.member(kind, n, T, 20 + k) for k, kind in enumerate(kinds)]
         fill = np.random.default_rng(6)
         for k, m in enumerate(members):
             if kinds[k] != "learner":
                 continue
             rb = m.model.rollout_buffer
-            for key in RB_KEYS:
+            for key in LC.RB_KEYS:
                 t = getattr(rb, key)
                 t.copy_(th.as_tensor(fill.standard_normal(tuple(t.shape)).astype(np.float32)))
             m.pos.copy_(th.as_tensor(((2 * np.arange(n) + k) % (T + 1)).astype(np.int32)))   # every fill level, full columns included
@@ -179,46 +140,14 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
 
 
 # ---- 3. the native step is bitwise the walk ------------------------------------------------------------------------------------
-def _run_pool(native, resample, kinds, E, T_ego, T_alt, steps, seed=11):
-    sp, ego, members = _pool(E, T_ego, T_alt, kinds, seed=seed, native=native, resample=resample)
-    trained = [0] * len(sp.learners)
-    pids = []
-    for _ in range(steps):
-        sp.step()
-        pids.append(sp.partnerid.cpu().numpy().copy())
-        for i, m in enumerate(sp.learners):
-            if m.full():
-                m.learn_from_buffer()
-                trained[i] += 1
-    th.cuda.synchronize()
-    out = dict(hands=sp.env.hands.cpu().numpy(), hist=sp.env.history.cpu().numpy(), nmoves=sp.env.nmoves.cpu().numpy(),
-               obs=sp.obs_ego.cpu().numpy(), pid=np.stack(pids), acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes,
-               trained=trained, ego_it=ego.iteration, pe=ego.model.policy.get_flat_params())
-    be = ego.model.rollout_buffer.host()
-    out.update({"e_" + k: v for k, v in be.items() if k in ("observations", "actions", "rewards", "episode_starts")})
-    for i, m in enumerate(sp.learners):
-        out[f"pos{i}"] = m.pos.cpu().numpy()
-        out[f"flags{i}"] = np.stack([t.cpu().numpy() for t in (m.boundary, m.term, m.open)])
-        out[f"values{i}"] = m.values.cpu().numpy()
-        out[f"p{i}"] = m.model.policy.get_flat_params()
-        out.update({f"a{i}_" + k: v for k, v in m.model.rollout_buffer.host().items() if k in RB_KEYS})
-    return out
-
-
 @pytest.mark.parametrize("resample", ["robin", "random"])
 def test_native_pool_step_is_bitwise_the_walk(resample):
     kinds = ["learner", "frozen", "scripted", "learner"]
-    a, b = (_run_pool(native, resample, kinds, E=48, T_ego=8, T_alt=4, steps=32) for native in (True, False))
+    a, b = (LC.run_pool(native, resample, kinds, E=48, T_ego=8, T_alt=4, steps=32) for native in (True, False))
     assert min(a["trained"]) >= 1 and a["trained"] == b["trained"], a["trained"]      # each learner trained: nothing vacuous
     assert a["ego_it"] >= 3 and a["episodes"] > 48
     assert a["pid"].min() >= 0 and a["pid"].max() == 3 and len(np.unique(a["pid"])) == 4
-    for key in a:
-        x, y = a[key], b[key]
-        if key[0] == "a" and key[1].isdigit() and getattr(x, "ndim", 0) >= 2:       # only the recorded rows of a ragged buffer are defined
-            pos = a["pos" + key[1]]
-            rows = np.arange(x.shape[0])[:, None] < pos[None, :]
-            x, y = x[rows], y[rows]
-        assert np.array_equal(x, y), key
+    LC.same_state(a, b)             # (only the recorded rows of a ragged buffer are defined: the snapshot holds no others)
 
 
 # ---- 4. per-table replay through the host MultiAgentEnv ------------------------------------------------------------------------
@@ -265,7 +194,7 @@ def test_pool_walk_matches_the_host_multiagentenv_table_by_table(resample):
                 _log.append((acts.cpu().numpy().copy(), rec_mask.cpu().numpy().astype(bool)))
                 return acts
             members[k].get_action = logged
-    sp, ego, members = _pool(E, T, 64, kinds, seed=2, native=False, resample=resample, before=log_moves)
+    sp, ego, members = LC.pool(E, T, 64, kinds, seed=2, native=False, resample=resample, before=log_moves)
     shadows = [Shadow() for _ in range(E)]
     partners = [[LiarDefaultAgent() if kinds[k] == "scripted" else Replay() for k in range(K)] for _ in range(E)]
     for s, ps in zip(shadows, partners):
@@ -347,11 +276,11 @@ def test_pool_of_one_learner_is_bitwise_the_single_partner_selfplay(monkeypatch)
     runs = []
     for pool in (True, False):
         if pool:
-            sp, ego, members = _pool(E, T_ego, T_alt, ["learner"], seed=4)
+            sp, ego, members = LC.pool(E, T_ego, T_alt, ["learner"], seed=4)
             alt = members[0]
             assert alt.min_full == E
         else:
-            ego, alt = VecOnPolicyAgent(_ppo(E, T_ego, 4)), RaggedVecOnPolicyAgent(_ppo(E, T_alt, 5))
+            ego, alt = VecOnPolicyAgent(LC.ppo(E, T_ego, 4)), RaggedVecOnPolicyAgent(LC.ppo(E, T_alt, 5))
             sp = VecLiarSelfPlay(E, ego, alt, seed=4 + 7, native=True)
             assert not sp.persistent
         for _ in range(steps // T_ego):
@@ -361,22 +290,21 @@ def test_pool_of_one_learner_is_bitwise_the_single_partner_selfplay(monkeypatch)
                    pos=alt.pos.cpu().numpy(), flags=np.stack([t.cpu().numpy() for t in (alt.boundary, alt.term, alt.open)]),
                    acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes, it=(ego.iteration, alt.iteration),
                    values=alt.values.cpu().numpy(), pe=ego.model.policy.get_flat_params(), pa=alt.model.policy.get_flat_params())
-        out.update({"e_" + k: v for k, v in ego.model.rollout_buffer.host().items() if k in RB_KEYS})
-        out.update({"a_" + k: v for k, v in alt.model.rollout_buffer.host().items() if k in RB_KEYS})
+        out.update({"e_" + k: v for k, v in ego.model.rollout_buffer.host().items() if k in LC.RB_KEYS})
+        out.update({"a_" + k: v for k, v in alt.model.rollout_buffer.host().items() if k in LC.RB_KEYS})
         runs.append(out)
     a, b = runs
     assert a["it"][0] == 3 and a["it"][1] >= 1
     for key in a:
         x, y = a[key], b[key]
         if key.startswith("a_"):
-            rows = np.arange(x.shape[0])[:, None] < a["pos"][None, :]
-            x, y = x[rows], y[rows]
+            x, y = LC.recorded_rows(x, a["pos"]), LC.recorded_rows(y, a["pos"])
         assert np.array_equal(x, y), key
 
 
 # ---- 6. graph capture ------------------------------------------------------------------------------------------------------------
 def test_native_pool_step_does_no_host_work_and_captures():
-    sp, ego, members = _pool(32, 8, 8, ["learner", "frozen", "scripted", "learner"], seed=3)
+    sp, ego, members = LC.pool(32, 8, 8, ["learner", "frozen", "scripted", "learner"], seed=3)
     stream = th.cuda.Stream(device=sp.dev)
     th.cuda.synchronize()
     with th.cuda.stream(stream):
@@ -405,7 +333,7 @@ def test_native_pool_step_does_no_host_work_and_captures():
 # ---- 7. ABI misuse ---------------------------------------------------------------------------------------------------------------
 def test_pool_abi_misuse_is_reported_not_fatal():
     from pantheonrl_amd import spaces as sps
-    sp, ego, members = _pool(16, 4, 4, ["learner", "frozen", "scripted"], seed=1)
+    sp, ego, members = LC.pool(16, 4, 4, ["learner", "frozen", "scripted"], seed=1)
     ctx = sp.env.ctx
     sp._bind()
     lib, h, d = ctx.lib, ctx.handle, sp._desc
@@ -467,7 +395,7 @@ def test_trainer_runs_a_pool_of_ppo_fixed_and_default_partners(tmp_path):
     from pantheonrl_amd import PPO
     from pantheonrl_amd.envs.vec import FrozenVecPartner, VecLiarDefaultPartner, VecLiarPartnerPool
     from pantheonrl_amd.trainer import run
-    old = _ppo(32, 8, 9)
+    old = LC.ppo(32, 8, 9)
     old.save(str(tmp_path / "old"))
     fixed = json.dumps({"type": "PPO", "location": str(tmp_path / "old")})
     ego, partners, env = run(["LiarsDice-v0", "PPO", "PPO", "FIXED", "DEFAULT", "--n-envs", "32", "-t", "8192", "--seed", "1",

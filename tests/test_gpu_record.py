@@ -3,64 +3,35 @@ self-play, the pool and cross-play; the log against the reference recorder (Turn
 table; capacity; the export's seat filters; graph capture; the persistent rollout's refusal; the command lines end to end.
 Every comparison is exact."""
 import ctypes as C
-from collections import deque
 
 import numpy as np
 import pytest
 import torch as th
 
 from pantheonrl_amd import _native as nat
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
 
-RB_KEYS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs")
 POOL_KINDS = ["learner", "frozen", "scripted", "learner"]
 
 
-def _spaces():
-    from pantheonrl_amd.envs.vec import VecLiarsDice
-    return type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
-                              _is_dummy_space_env=True))()
-
-
-def _ppo(E, T, seed, arch=None):
-    from pantheonrl_amd import PPO
-    kw = dict(policy_kwargs={"net_arch": [{"pi": list(arch), "vf": list(arch)}]}) if arch else {}
-    model = PPO("MlpPolicy", _spaces(), n_steps=T, n_envs=E, batch_size=max(8, E * T // 2), n_epochs=2, seed=seed, **kw)
-    model.device_permutations = True
-    model.rollout_buffer.gae_mode = 1
-    return model
-
-
 def _selfplay(E, T_ego, T_alt, native, record, towers=False, seed=4):
-    from pantheonrl_amd.envs.vec import VecLiarSelfPlay, ragged_agent_for
-    from pantheonrl_amd.vec import vec_agent_for
-    ego = vec_agent_for(_ppo(E, T_ego, seed, (128, 128) if towers else None))
-    alt = ragged_agent_for(_ppo(E, T_alt, seed + 1, (32,) if towers else None))
-    return VecLiarSelfPlay(E, ego, alt, seed=seed + 7, native=native, record=record)
+    ego, alt = LC.ppo(E, T_ego, seed, (128, 128) if towers else None), LC.ppo(E, T_alt, seed + 1, (32,) if towers else None)
+    return LC.selfplay(E, ego, alt, seed=seed, native=native, record=record)[0]
 
 
 def _pool(E, T_ego, T_alt, native, record, resample="robin", seed=11, kinds=POOL_KINDS):
-    from pantheonrl_amd.envs.vec import FrozenVecPartner, RaggedVecOnPolicyAgent, VecLiarDefaultPartner, VecLiarPartnerPool
-    from pantheonrl_amd.vec import VecOnPolicyAgent
-    ego = VecOnPolicyAgent(_ppo(E, T_ego, seed))
-    members = []
-    for k, kind in enumerate(kinds):
-        if kind == "learner":
-            members.append(RaggedVecOnPolicyAgent(_ppo(E, T_alt, seed + 1 + k)))
-        elif kind == "frozen":
-            members.append(FrozenVecPartner(_ppo(E, 2, seed + 1 + k).policy))
-        else:
-            members.append(VecLiarDefaultPartner())
-    return VecLiarPartnerPool(E, ego, members, seed=seed + 7, resample=resample, native=native, record=record)
+    return LC.pool(E, T_ego, T_alt, kinds, seed=seed, native=native, resample=resample, record=record)[0]
 
 
 def _xplay(E, G, native, record, kinds=("frozen", "frozen", "scripted"), seed=5):
-    from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
-    from pantheonrl_amd.envs.vec import FrozenVecPartner, VecLiarDefaultPartner
-    members = [FrozenVecPartner(_ppo(4, 2, 20 + k).policy) if kind == "frozen" else VecLiarDefaultPartner()
-               for k, kind in enumerate(kinds)]
-    return VecLiarCrossPlay(E, members, episodes_per_table=G, seed=seed, native=native, record=record)
+    return LC.xplay(E, kinds, G, seed=seed, native=native, record=record)
+
+
+def _train_state(sp):
+    """the end state of a training run: the game, both seats' recorded rows, the parameters after the updates"""
+    return LC.train_state(sp, sp.ego)
 
 
 def _train_steps(sp, steps):
@@ -73,40 +44,9 @@ def _train_steps(sp, steps):
     th.cuda.synchronize()
 
 
-def _train_state(sp):
-    """the end state of a training run: the game, both seats' recorded rows, the parameters after the updates"""
-    th.cuda.synchronize()
-    ego = sp.ego
-    out = dict(hands=sp.env.hands.cpu().numpy(), hist=sp.env.history.cpu().numpy(), nmoves=sp.env.nmoves.cpu().numpy(),
-               obs=sp.obs_ego.cpu().numpy(), acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes, ego_it=ego.iteration,
-               pe=ego.model.policy.get_flat_params())
-    out.update({"e_" + k: v for k, v in ego.model.rollout_buffer.host().items() if k in RB_KEYS})
-    for i, m in enumerate(sp.learners):
-        pos = m.pos.cpu().numpy()
-        out[f"pos{i}"], out[f"it{i}"], out[f"p{i}"] = pos, m.iteration, m.model.policy.get_flat_params()
-        for k, v in m.model.rollout_buffer.host().items():
-            if k in RB_KEYS:         # only the recorded rows of a ragged buffer are defined
-                out[f"a{i}_{k}"] = v[np.arange(v.shape[0])[:, None] < pos[None, :]] if v.ndim >= 2 else v
-    return out
-
-
-def _xplay_state(xp):
-    th.cuda.synchronize()
-    keys = ("obs_ego", "games", "playing", "tables_left", "returns", "lengths", "ep_return", "ep_length")
-    out = {k: getattr(xp, k).cpu().numpy().copy() for k in keys}
-    out.update(hands=xp.env.hands.cpu().numpy(), hist=xp.env.history.cpu().numpy(), nmoves=xp.env.nmoves.cpu().numpy())
-    return out
-
-
 def _log(sp, seat=None):
     rec = sp.recorded(seat)
     return dict(rows=rec.rows.cpu().numpy(), member=rec.member.cpu().numpy(), offsets=rec.table_offsets, dropped=rec.dropped)
-
-
-def _same(a, b, what):
-    assert a.keys() == b.keys()
-    for key in a:
-        assert np.array_equal(a[key], b[key]), (what, key)
 
 
 def _check_log_shape(log, E):
@@ -128,8 +68,8 @@ def test_selfplay_native_log_is_the_walks_and_the_recorder_only_reads(towers):
         assert sp.towers == towers
         _train_steps(sp, steps)
         runs[name] = (_train_state(sp), _log(sp) if record else None)
-    _same(runs["native"][1], runs["walk"][1], "log")
-    _same(runs["native"][0], runs["plain"][0], "state, recorder attached vs none")
+    LC.same_state(runs["native"][1], runs["walk"][1], "log")
+    LC.same_state(runs["native"][0], runs["plain"][0], "state, recorder attached vs none")
     log, state = runs["native"][1], runs["native"][0]
     _check_log_shape(log, E)
     assert not log["dropped"].any() and not log["member"].any()
@@ -146,8 +86,8 @@ def test_pool_native_log_is_the_walks_and_the_recorder_only_reads(resample):
         sp = _pool(E, 8, 4, native, record, resample=resample)
         _train_steps(sp, steps)
         runs[name] = (_train_state(sp), _log(sp) if record else None)
-    _same(runs["native"][1], runs["walk"][1], "log")
-    _same(runs["native"][0], runs["plain"][0], "state, recorder attached vs none")
+    LC.same_state(runs["native"][1], runs["walk"][1], "log")
+    LC.same_state(runs["native"][0], runs["plain"][0], "state, recorder attached vs none")
     log, state = runs["native"][1], runs["native"][0]
     _check_log_shape(log, E)
     assert not log["dropped"].any()
@@ -166,9 +106,9 @@ def test_crossplay_native_log_is_the_walks_and_the_recorder_only_reads():
         assert xp.P == 9
         res = xp.run(chunk=3)
         assert (res.count >= 2 * G).all()
-        runs[name] = (_xplay_state(xp), _log(xp) if record else None, xp)
-    _same(runs["native"][1], runs["walk"][1], "log")
-    _same(runs["native"][0], runs["plain"][0], "state, recorder attached vs none")
+        runs[name] = (LC.xstate(xp), _log(xp) if record else None, xp)
+    LC.same_state(runs["native"][1], runs["walk"][1], "log")
+    LC.same_state(runs["native"][0], runs["plain"][0], "state, recorder attached vs none")
     state, log, xp = runs["native"]
     _check_log_shape(log, E)
     assert not log["dropped"].any() and state["games"].sum() == E * G == (log["rows"][:, 32] >= 2).sum()
@@ -180,7 +120,7 @@ def test_crossplay_native_log_is_the_walks_and_the_recorder_only_reads():
     # idle tables log nothing: further steps leave the log as it is
     for _ in range(3):
         xp.step()
-    _same(_log(xp), log, "idle")
+    LC.same_state(_log(xp), log, "idle")
 
 
 # ---- 2. the log is the reference recorder's ------------------------------------------------------------------------------------------
@@ -203,60 +143,6 @@ def _spy(monkeypatch):
     monkeypatch.setattr(VecLiarsDice, "player_step", player_step)
     monkeypatch.setattr(VecLiarStep, "_deal", deal)
     return events
-
-
-def _replay_through_the_reference_recorder(events, e):
-    """table e's deals and moves played through TurnBasedRecorder(LiarEnv) -> its get_transitions()"""
-    from pantheonrl_amd.common import Agent, Observation
-    from pantheonrl_amd.common.wrappers import TurnBasedRecorder
-    from pantheonrl_amd.envs.liar import LiarEnv
-
-    class Shadow(LiarEnv):
-        def __init__(self):
-            super().__init__()
-            self.deals = deque()
-
-        def multi_reset(self, egofirst):
-            first, hands = self.deals.popleft()
-            assert bool(first) == bool(egofirst)
-            self.history, self.egohand, self.althand = [], [int(x) for x in hands[:6]], [int(x) for x in hands[6:]]
-            return self.getObs(egofirst)
-
-    class Recorder(TurnBasedRecorder):
-        def n_reset(self):                   # who opens is the device's draw
-            self.ego_next = bool(self.env.deals[0][0])
-            first = self.multi_reset(self.ego_next)
-            return (0 if self.ego_next else 1,), (Observation(first),)
-
-    class Replay(Agent):
-        def __init__(self):
-            self.moves = deque()
-
-        def get_action(self, obs, record=True):
-            return self.moves.popleft()
-
-        def update(self, reward, done):
-            return None
-
-    shadow, partner, ego_moves = Shadow(), Replay(), []
-    for ev in events:
-        if ev[0] == "deal":
-            if ev[1][e]:
-                shadow.deals.append((ev[3][e], ev[2][e].copy()))
-        elif ev[3][e]:
-            (ego_moves if ev[2][e] else partner.moves).append(ev[1][e].copy())
-    rec = Recorder(shadow)
-    rec.add_partner_agent(partner)
-    rec.reset()
-    games = 0
-    for a in ego_moves:
-        _, _, done, _ = rec.step(a)
-        if done:
-            games += 1
-            if shadow.deals:
-                rec.reset()
-    assert not shadow.deals and not partner.moves
-    return rec.get_transitions(), games
 
 
 @pytest.mark.parametrize("mode", ["pool-robin", "pool-random", "crossplay"])
@@ -282,7 +168,7 @@ def test_walk_log_is_the_reference_recorders_table_by_table(mode, monkeypatch):
     assert not rec.dropped.any() and len(rows) == off[-1]
     total = 0
     for e in range(E):
-        tr, games = _replay_through_the_reference_recorder(events, e)
+        tr, games = LC.replay_through_the_reference_recorder(events, e)
         mine = rows[off[e]:off[e + 1]]
         assert games >= 2, (e, games)
         assert len(tr.flags) == len(mine), e
@@ -316,7 +202,7 @@ def test_a_full_table_drops_and_counts_and_nothing_is_written_past_it(monkeypatc
         for _ in range(steps):
             sp.step()
     a, b = _log(small), _log(ample)
-    _same(a, _log(walk), "the walk drops and counts the same moves")
+    LC.same_state(a, _log(walk), "the walk drops and counts the same moves")
     nb = np.diff(b["offsets"])
     assert (nb > cap).all() and not b["dropped"].any()
     assert np.array_equal(a["offsets"], cap * np.arange(E + 1))
@@ -328,7 +214,7 @@ def test_a_full_table_drops_and_counts_and_nothing_is_written_past_it(monkeypatc
     assert np.array_equal(small._rec_count.cpu().numpy(), np.full(E, cap))
     for c, (rows, member) in guards.items():
         assert (rows[E * c * 33:] == sentinel).all().item() and (member[E * c:] == sentinel).all().item(), c
-    _same(_train_state(small), _train_state(ample), "a full log does not perturb the run")
+    LC.same_state(_train_state(small), _train_state(ample), "a full log does not perturb the run")
 
 
 # ---- 4. the export -----------------------------------------------------------------------------------------------------------------------
@@ -391,7 +277,7 @@ def test_a_recording_pool_step_captures_and_attaching_inside_capture_is_refused(
     graph.replay()
     th.cuda.synchronize()
     assert int(sp._rec_count.sum().item()) >= before + 4 * E
-    _same(_log(sp), _log(eager), "replayed log vs eager log")
+    LC.same_state(_log(sp), _log(eager), "replayed log vs eager log")
     assert sp.recording and sp.episodes == eager.episodes
 
 

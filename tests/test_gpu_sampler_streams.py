@@ -49,27 +49,6 @@ def _np(t, shape=None):
 
 
 # ---- a. categorical heads, own draws; b. the negative control ---------------------------------------------------------------------------
-def _device(case, orac=None):
-    """the case's device object holding the parameters of `orac` (default: the case's cached checker)"""
-    orac = S.checker(case.id) if orac is None else orac
-    if case.family == "mlp":
-        return H.device_policy(case.name, orac)
-    if case.family == "arch":
-        from tests import arch_oracle as A
-        return A.device_policy(case.name, orac)
-    if case.family == "adapmult":
-        from tests.test_gpu_adapmult import _device as dev
-        return dev(case.name, orac)
-    if case.family == "modular":
-        from tests.test_gpu_modular import _device as dev
-        return dev(case.name, orac, case.extra["K"], **case.extra["kw"])
-    from pantheonrl_amd.bc import FeedForward32Policy
-    obs_s, act_s = S.spaces(case)
-    pol = FeedForward32Policy(H.to_space(obs_s), H.to_space(act_s), device=DEV, seed=7)
-    pol.set_flat_params(orac.flat_params())
-    return pol
-
-
 def _forward(case, pol, obs, mask, c, uniforms=None):
     """one forward at (S.KEY, c): the launch advances the counter before it passes it on"""
     pol._seed, pol._counter = S.KEY, c - 1
@@ -86,7 +65,7 @@ def test_categorical_heads_draw_the_host_stream(cid):
     actions and the checker's log-prob at 2e-5.  Inside: the negative control on the host prediction.  What each case reaches:
     sampler_cases.CASES[].kernel."""
     case = S.BY_ID[cid]
-    pol = _device(case)
+    pol = S.device(case)
     A = len(S.spaces(case)[1].nvec)
     for mode in case.gemm_modes:
         if mode is not None:
@@ -404,8 +383,8 @@ def test_adap_samples_are_the_host_statement(kind, T, E, nb, sampler, epoch):
     from pantheonrl_amd.adap import AdapPolicyMult
     from pantheonrl_amd.ppo import ActorCriticPolicy, RolloutBuffer
     from oracle import sb3_oracle as orc
-    from tests.test_gpu_adap import _adap_struct
-    from tests.test_gpu_adapmult import _hyper
+    from tests.adap_cases import _adap_struct
+    from tests.adapmult_cases import _hyper
     obs_s, act_s = H.CONFIGS["adap_small"]
     cs = 1 if sampler == "natural_numbers" else 3
     n_ctx, n_states, seed = 5, 32, 2 ** 40 + 11

@@ -85,7 +85,7 @@ def test_forward_heads_on_sharp_policies(cid, scale):
     drawn action's log-prob within A_lp, values within 2e-5 s); deterministic=True (logits within A_z, the argmax on rows whose top
     two logits differ by more than 2 max A_z); evaluate_actions on the most likely, least likely and one random action set (log-prob
     within A_lp, entropy within A_H and >= -A_H, value within 2e-5 s, everything finite); gemm_mode 1 the bits of mode 0"""
-    from tests.test_gpu_sampler_streams import _device
+    from tests.sampler_cases import device as _device
     fc = SC.FORWARD_BY_ID[cid]
     case = fc.case
     print(cid, "x%d" % scale, "->", case.kernel)
@@ -141,29 +141,29 @@ def _device_pair(g, scale, nb, mode):
     hp, fill, idx, prep = SC.hyper(), SC.fill(g), SC.minibatch_rows(nb), SC.preparer(scale)
     cl = None
     if g.family == "ppo":
-        from tests.test_gpu_parity import _grad_pair
+        from tests.parity_cases import _grad_pair
         grad, g_ref, st, _, _ = _grad_pair(g.config, SC.T, SC.E, idx, hp, seed=OC.SEED, gemm_mode=mode, fill=fill, prepare=prep)
     elif g.family == "arch":
-        from tests.test_gpu_arch import _grad_pair
+        from tests.arch_cases import _grad_pair
         out, g_ref, _ = _grad_pair(g.config, g.arch, SC.T, SC.E, idx, hp, seed=OC.SEED, gemm_mode=mode, fill=fill, prepare=prep)
         grad, st = out[0]
     elif g.family == "modular":
-        from tests.test_gpu_modular import _grad_pair
+        from tests.modular_cases import _grad_pair
         grad, g_ref, st, _, _ = _grad_pair(g.config, g.K, g.partner, SC.T, SC.E, nb, g.coef, hp, seed=OC.SEED, gemm_mode=mode, fill=fill,
                                            idx=idx, prepare=prep)
     elif g.family == "adap":
-        from tests.test_gpu_adap import _grad_pair
+        from tests.adap_cases import _grad_pair
         grad, g_ref, st, _, cl = _grad_pair(g.config, SC.T, SC.E, idx, hp, 5, 32, g.coef, seed=OC.SEED, gemm_mode=mode, fill=fill,
                                             prepare=prep)[:5]
     else:
-        from tests.test_gpu_adapmult import _grad_pair
+        from tests.adapmult_cases import _grad_pair
         assert mode == 0
         grad, g_ref, st, _, cl = _grad_pair(g.config, SC.T, SC.E, nb, hp, coef=g.coef, seed=OC.SEED, fill=fill, idx=idx, prepare=prep)
     return grad, g_ref, st, cl
 
 
 def _bc_gradient_case(g, scale, R):
-    from tests.test_gpu_bc_shapes import _assert_path, _clone, _reset
+    from tests.bc_shape_cases import _assert_path, _clone, _reset
     for nb in SC.NBS:
         b = SC.bc_build(g, scale, nb)
         case, orac, obs, acts = b["case"], b["orac"], b["obs"], b["acts"]

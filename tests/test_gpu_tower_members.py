@@ -11,78 +11,14 @@ import pytest
 import torch as th
 
 from pantheonrl_amd import _native as nat
+from tests import liar_cases as LC
 
 pytestmark = pytest.mark.gpu
 
-RB_KEYS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs")
-XSTATE = ("hands", "history", "nmoves", "obs_ego", "obs_alt", "games", "playing", "tables_left", "returns", "lengths", "ep_return",
-          "ep_length")
-# member kinds of this file: (PH_POOL_* kind, tower widths or None)
-KINDS = dict(learner=(nat.PH_POOL_LEARNER, None), frozen=(nat.PH_POOL_FROZEN, None), scripted=(nat.PH_POOL_SCRIPTED, None),
-             clone=(nat.PH_POOL_CLONE, None), ltower32=(nat.PH_POOL_LEARNER, (32,)), ftower32=(nat.PH_POOL_FROZEN, (32,)),
-             ftower128=(nat.PH_POOL_FROZEN, (128, 128)), ftower256=(nat.PH_POOL_FROZEN, (256, 128)),
-             ftower64x3=(nat.PH_POOL_FROZEN, (64, 64, 64)))
 
-
-def _spaces():
-    from pantheonrl_amd.envs.vec import VecLiarsDice
-    return type("S", (), dict(observation_space=VecLiarsDice.observation_space, action_space=VecLiarsDice.action_space,
-                              _is_dummy_space_env=True))()
-
-
-def _ppo(E, T, seed, arch=None):
-    from pantheonrl_amd import PPO
-    kwargs = dict(policy_kwargs=dict(net_arch=[dict(pi=list(arch), vf=list(arch))])) if arch else {}
-    model = PPO("MlpPolicy", _spaces(), n_steps=T, n_envs=E, batch_size=max(8, E * T // 2), n_epochs=2, seed=seed, **kwargs)
-    model.device_permutations = True
-    model.rollout_buffer.gae_mode = 1
-    return model
-
-
-def _sharpen(policy, seed):
-    """parameters of order one, so that the moves spread and a wrong bit moves a sample; the same seed gives the same parameters"""
-    policy.set_flat_params(0.4 * np.random.default_rng(seed).standard_normal(policy.layout.P).astype(np.float32))
-    return policy
-
-
-def _member(kind, E, T_alt, seed, sharpen=False):
-    from pantheonrl_amd.bc import FeedForward32Policy
-    from pantheonrl_amd.envs.vec import ClonedVecPartner, VecLiarDefaultPartner, frozen_partner_for, ragged_agent_for
-    pool_kind, arch = KINDS[kind]
-    if pool_kind == nat.PH_POOL_SCRIPTED:
-        return VecLiarDefaultPartner()
-    if pool_kind == nat.PH_POOL_CLONE:
-        s = _spaces()
-        return ClonedVecPartner(_sharpen(FeedForward32Policy(s.observation_space, s.action_space, seed=1000 + seed), seed))
-    if pool_kind == nat.PH_POOL_LEARNER:
-        m = ragged_agent_for(_ppo(E, T_alt, seed, arch))
-        pol = m.model.policy
-    else:
-        m = frozen_partner_for(_ppo(E, 2, seed, arch).policy)
-        pol = m.policy
-    if sharpen:
-        _sharpen(pol, seed)
-    return m
-
-
-def _pool(E, T_ego, T_alt, kinds, ego_arch=(128, 128), seed=0, native=True, resample="robin", record=0):
-    from pantheonrl_amd.envs.vec import liar_pool_for
-    from pantheonrl_amd.vec import vec_agent_for
-    ego = vec_agent_for(_ppo(E, T_ego, seed, ego_arch))
-    members = [_member(kind, E, T_alt, seed + 1 + k) for k, kind in enumerate(kinds)]
-    return liar_pool_for(E, ego, members, seed=seed + 7, resample=resample, native=native, record=record), ego, members
-
-
-def _xplay(E, kinds, G, pairs=None, seed=5, native=True, record=0):
-    from pantheonrl_amd.envs.crossplay import VecLiarCrossPlay
-    members = [_member(kind, 4, 2, 20 + k) for k, kind in enumerate(kinds)]
-    return VecLiarCrossPlay(E, members, pairs=pairs, episodes_per_table=G, seed=seed, native=native, record=record)
-
-
-def _ctx_of(agent):
-    ctx = agent.model.policy.ctx
-    ctx.set_stream(th.cuda.current_stream(agent.model.policy.device).cuda_stream)
-    return ctx
+def _pool(E, T_ego, T_alt, kinds, ego_arch=(128, 128), **kw):
+    """this file's pools have a tower ego unless told otherwise"""
+    return LC.pool(E, T_ego, T_alt, kinds, ego_arch=ego_arch, **kw)
 
 
 def _arch_array(members):
@@ -98,26 +34,15 @@ def _arch_array(members):
 
 
 # ---- 1. the grouped forward on its own -------------------------------------------------------------------------------------------
-def _interleave(counts):
-    """member ids with the given counts, interleaved by table index (round robin over the members that still have rows left)"""
-    left, out = list(counts), []
-    while any(left):
-        for k in range(len(left)):
-            if left[k]:
-                out.append(k)
-                left[k] -= 1
-    return np.asarray(out, np.int32)
-
-
 def _forward_case(name):
     """-> (kinds, partnerid, active).  The mixed case has active-row counts [17, 16, 1, 0, 16] per member, interleaved by table
     index: a full tower tile plus one row, a one-row tower tile (a learner), a member without a tile, tower tiles beside tiles of
     every other kind.  `mixed54`: the same active rows with four inactive ones in between."""
     mixed = ["ftower128", "frozen", "ltower32", "scripted", "learner"]
     if name == "mixed50":
-        return mixed, _interleave([17, 16, 1, 0, 16]), np.ones(50, np.uint8)
+        return mixed, LC.interleave([17, 16, 1, 0, 16]), np.ones(50, np.uint8)
     if name == "mixed54":
-        pid, active = _interleave([17, 16, 1, 0, 16]).tolist(), [1] * 50
+        pid, active = LC.interleave([17, 16, 1, 0, 16]).tolist(), [1] * 50
         for at, k in ((3, 0), (17, 3), (30, 2), (41, 4)):
             pid.insert(at, k)
             active.insert(at, 0)
@@ -125,7 +50,7 @@ def _forward_case(name):
         assert np.bincount(pid[active != 0], minlength=5).tolist() == [17, 16, 1, 0, 16] and len(pid) == 54
         return mixed, pid, active
     if name == "tower3clone":  # a three-layer tower beside a clone: the tower and the clone kernels, no 64-wide launch
-        return ["ftower64x3", "clone"], _interleave([12, 11]), np.ones(23, np.uint8)
+        return ["ftower64x3", "clone"], LC.interleave([12, 11]), np.ones(23, np.uint8)
     if name == "learner19":    # a learner tower alone: a full tile plus three rows, every recorded field
         return ["ltower32"], np.zeros(19, np.int32), np.ones(19, np.uint8)
     assert name == "tile16"    # exactly one full tile of the widest arch
@@ -138,24 +63,24 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     kinds, pid_h, active_h = _forward_case(case)
     n, K, T, counter = len(pid_h), len(kinds), 4, 9
     rng = np.random.default_rng(5)
-    obs_space = _spaces().observation_space
+    obs_space = LC.spaces().observation_space
     obs = th.as_tensor((rng.random((n, 30)) * np.asarray(obs_space.nvec)).astype(np.int64).astype(np.float32)).cuda()
     pid, active = th.as_tensor(pid_h).cuda(), th.as_tensor(active_h).cuda()
-    host = VecOnPolicyAgent(_ppo(n, 2, 0))
-    ctx = _ctx_of(host)
+    host = VecOnPolicyAgent(LC.ppo(n, 2, 0))
+    ctx = LC.ctx_of(host)
     lib, h, spec = ctx.lib, ctx.handle, C.byref(host.model.policy.spec)
     sets = []
     for _ in range(2):                                    # two identical sets: one for the grouped launch, one for the yardstick
-        members = [_member(kind, n, T, 20 + k, sharpen=True) for k, kind in enumerate(kinds)]
+        members = [LC.member(kind, n, T, 20 + k, sharp=True) for k, kind in enumerate(kinds)]
         fill = np.random.default_rng(6)
         for k, m in enumerate(members):
-            if KINDS[kinds[k]][0] == nat.PH_POOL_FROZEN:  # caches, so that floats are compared and not only sampled integers
+            if LC.KINDS[kinds[k]][0] == nat.PH_POOL_FROZEN:  # caches, so that floats are compared and not only sampled integers
                 m.values = th.full((n,), -3.0, dtype=th.float32, device="cuda")
                 m.log_probs = th.full((n,), -5.0, dtype=th.float32, device="cuda")
-            if KINDS[kinds[k]][0] != nat.PH_POOL_LEARNER:
+            if LC.KINDS[kinds[k]][0] != nat.PH_POOL_LEARNER:
                 continue
             rb = m.model.rollout_buffer
-            for key in RB_KEYS:
+            for key in LC.RB_KEYS:
                 t = getattr(rb, key)
                 t.copy_(th.as_tensor(fill.standard_normal(tuple(t.shape)).astype(np.float32)))
             m.pos.copy_(th.as_tensor(((2 * np.arange(n) + k) % (T + 1)).astype(np.int32)))   # every fill level, full columns included
@@ -166,13 +91,13 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     grouped, plain = sets
     es = th.zeros(n, dtype=th.float32, device="cuda")
     for k, m in enumerate(grouped):
-        if KINDS[kinds[k]][0] == nat.PH_POOL_LEARNER:
+        if LC.KINDS[kinds[k]][0] == nat.PH_POOL_LEARNER:
             es = th.where(pid == k, m.boundary.to(th.float32), es)
     es = es.contiguous()
     arr = (nat.PhPoolMember * K)()
     keep = []
     for k, m in enumerate(grouped):
-        kind = KINDS[kinds[k]][0]
+        kind = LC.KINDS[kinds[k]][0]
         arr[k].kind = kind
         if kind == nat.PH_POOL_SCRIPTED:
             continue
@@ -186,7 +111,7 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
             arr[k].pos, arr[k].boundary, arr[k].term, arr[k].open = (t.data_ptr() for t in (m.pos, m.boundary, m.term, m.open))
             arr[k].values, arr[k].log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
     archs = _arch_array(grouped)
-    assert sum(bool(a) for a in archs) == sum(KINDS[kind][1] is not None for kind in kinds) >= 1
+    assert sum(bool(a) for a in archs) == sum(LC.KINDS[kind][1] is not None for kind in kinds) >= 1
     actions = th.full((n, 2), -7, dtype=th.int32, device="cuda")
     nat.check(lib.ph_pool_forward_arch(h, spec, arr, K, obs.data_ptr(), pid.data_ptr(), active.data_ptr(), counter, actions.data_ptr(),
                                        es.data_ptr(), n, archs))
@@ -196,7 +121,7 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
     assert (got[~act] == -7).all()                          # inactive rows keep their sentinel
     for k, (g, p) in enumerate(zip(grouped, plain)):
         mine = act & (pid_h == k)
-        kind, arch = KINDS[kinds[k]]
+        kind, arch = LC.KINDS[kinds[k]]
         if kind == nat.PH_POOL_SCRIPTED:
             want = th.full((n, 2), -7, dtype=th.int32, device="cuda")
             rows = th.as_tensor(mine.astype(np.uint8)).cuda()
@@ -249,75 +174,26 @@ def test_grouped_forward_is_bitwise_the_per_member_entry_points(case):
 
 
 # ---- 2. the native step is bitwise the walk --------------------------------------------------------------------------------------
-def _pool_state(sp, ego):
-    th.cuda.synchronize()
-    out = dict(hands=sp.env.hands.cpu().numpy(), hist=sp.env.history.cpu().numpy(), nmoves=sp.env.nmoves.cpu().numpy(),
-               obs=sp.obs_ego.cpu().numpy(), pid_now=sp.partnerid.cpu().numpy(), acted=sp.alt_acted.cpu().numpy(), episodes=sp.episodes,
-               ego_it=ego.iteration, pe=ego.model.policy.get_flat_params())
-    be = ego.model.rollout_buffer.host()
-    out.update({"e_" + k: v for k, v in be.items() if k in RB_KEYS})          # values and log-probs too: the ego's forward is a tower's
-    for i, m in enumerate(sp.learners):
-        out[f"pos{i}"] = m.pos.cpu().numpy()
-        out[f"flags{i}"] = np.stack([t.cpu().numpy() for t in (m.boundary, m.term, m.open)])
-        out[f"values{i}"] = m.values.cpu().numpy()
-        out[f"p{i}"] = m.model.policy.get_flat_params()
-        out.update({f"a{i}_" + k: v for k, v in m.model.rollout_buffer.host().items() if k in RB_KEYS})
-    return out
-
-
-def _same_pool_state(a, b, ego_rows=None):
-    for key in a:
-        x, y = a[key], b[key]
-        if key[0] == "a" and key[1].isdigit() and getattr(x, "ndim", 0) >= 2:       # only the recorded rows of a ragged buffer are defined
-            rows = np.arange(x.shape[0])[:, None] < a["pos" + key[1]][None, :]
-            x, y = x[rows], y[rows]
-        if key.startswith("e_") and ego_rows is not None:
-            x, y = x[:ego_rows], y[:ego_rows]
-        assert np.array_equal(x, y), key
-
-
-def _run_pool(native, resample, kinds, E, T_ego, T_alt, steps, seed=11):
-    sp, ego, members = _pool(E, T_ego, T_alt, kinds, seed=seed, native=native, resample=resample)
-    trained = [0] * len(sp.learners)
-    pids = []
-    for _ in range(steps):
-        sp.step()
-        pids.append(sp.partnerid.cpu().numpy().copy())
-        for i, m in enumerate(sp.learners):
-            if m.full():
-                m.learn_from_buffer()
-                trained[i] += 1
-    out = _pool_state(sp, ego)
-    out.update(pid=np.stack(pids), trained=trained)
-    return out
-
-
 @pytest.mark.parametrize("resample", ["robin", "random"])
 def test_native_pool_step_with_towers_is_bitwise_the_walk(resample):
     from pantheonrl_amd.envs.vec import TowerVecLiarPartnerPool
     kinds = ["ltower32", "ftower64x3", "scripted", "learner"]
-    a, b = (_run_pool(native, resample, kinds, E=50, T_ego=8, T_alt=4, steps=24) for native in (True, False))
+    a, b = (LC.run_pool(native, resample, kinds, E=50, T_ego=8, T_alt=4, steps=24, ego_arch=(128, 128))
+            for native in (True, False))
     assert len(a["trained"]) == 2 and min(a["trained"]) >= 1 and a["trained"] == b["trained"], a["trained"]
     assert a["ego_it"] >= 2 and a["episodes"] > 50
     assert len(np.unique(a["pid"])) == 4                   # every member sat somewhere
-    _same_pool_state(a, b)
+    LC.same_state(a, b)
     assert isinstance(_pool(8, 2, 2, kinds)[0], TowerVecLiarPartnerPool)
-
-
-def _xstate(xp):
-    th.cuda.synchronize()
-    out = {k: getattr(xp.env if k in ("hands", "history", "nmoves") else xp, k).cpu().numpy().copy() for k in XSTATE}
-    out["ego_first"] = xp.ego_first.cpu().numpy().copy()
-    return out
 
 
 def test_native_crossplay_step_with_towers_is_bitwise_the_walk_after_every_step():
     E, G, kinds = 32, 2, ["ftower128", "ftower32", "frozen", "scripted"]          # all 16 pairs on 32 tables
-    a, b = (_xplay(E, kinds, G, native=native) for native in (True, False))
+    a, b = (LC.xplay(E, kinds, G, native=native) for native in (True, False))
     assert a.P == 16 and a.towers
     steps = 0
     while True:
-        sa, sb = _xstate(a), _xstate(b)
+        sa, sb = LC.xstate(a), LC.xstate(b)
         for key in sa:
             assert np.array_equal(sa[key], sb[key]), (steps, key)
         if sb["tables_left"][0] == 0:
@@ -337,8 +213,7 @@ def test_native_crossplay_step_with_towers_is_bitwise_the_walk_after_every_step(
 # ---- 3. the games are real games: recording needs no change ------------------------------------------------------------------------
 def test_recorded_tower_pool_games_replay_through_the_reference_recorder():
     """the native pool step with tower members logs moves like any member's: every table's log is what TurnBasedRecorder(LiarEnv)
-    produces when it is dealt the device's hands and fed the logged moves (tests/test_gpu_record.py's replay)"""
-    from tests.test_gpu_record import _replay_through_the_reference_recorder
+    produces when it is dealt the device's hands and fed the logged moves (tests/liar_cases.py's replay)"""
     E, steps = 12, 10
     kinds = ["ftower128", "ltower32", "scripted"]
     sp, ego, members = _pool(E, 16, 16, kinds, seed=2, record=3 * steps + 1)
@@ -360,7 +235,7 @@ def test_recorded_tower_pool_games_replay_through_the_reference_recorder():
         mine, who = rows[off[e]:off[e + 1]], member[off[e]:off[e + 1]]
         for row in mine:
             events[e].append(("move", row[None, 30:32].astype(np.int64), np.array([int(row[32]) % 2 == 0]), np.ones(1, bool)))
-        tr, games = _replay_through_the_reference_recorder(events[e], 0)
+        tr, games = LC.replay_through_the_reference_recorder(events[e], 0)
         assert len(tr.flags) == len(mine), e
         assert np.array_equal(np.asarray(tr.obs), mine[:, :30]), e
         assert np.array_equal(np.asarray(tr.acts), mine[:, 30:32]), e
@@ -401,7 +276,7 @@ def test_native_pool_step_with_towers_does_no_host_work_and_captures():
         stream.synchronize()
     th.cuda.synchronize()
     assert sp.episodes > episodes
-    _same_pool_state(_pool_state(sp, ego), _pool_state(eager, ego_e), ego_rows=6)
+    LC.same_state(LC.train_state(sp, ego), LC.train_state(eager, ego_e), ego_rows=6)
 
 
 # ---- 5. misuse ---------------------------------------------------------------------------------------------------------------------
@@ -445,7 +320,7 @@ def test_tower_misuse_is_an_error_string_and_nothing_is_launched():
     assert lib.ph_pool_forward_arch(h, spec, arr, 4, obs.data_ptr(), pid.data_ptr(), act8.data_ptr(), 1, out.data_ptr(), None, n,
                                     archs) != 0 and b"not to a scripted one or a clone" in err()
     archs[2] = None
-    xp = _xplay(16, ["ftower32", "scripted"], 1)
+    xp = LC.xplay(16, ["ftower32", "scripted"], 1)
     xp._bind()
     xp._member_arch_arr[1] = xp._member_arch_arr[0]
     assert xp.ctx.lib.ph_liar_xplay_step_arch(xp.ctx.handle, C.byref(xp._desc), xp._member_arch_arr, 1, 0) != 0
@@ -455,7 +330,7 @@ def test_tower_misuse_is_an_error_string_and_nothing_is_launched():
     for k, v in before.items():                              # refused in front of the first launch: the game did not move
         assert np.array_equal(getattr(sp.env, k).cpu().numpy(), v), k
     # the plain classes keep refusing towers; the factories pick the classes
-    plain_ego = vec_agent_for(_ppo(16, 4, 3))
+    plain_ego = vec_agent_for(LC.ppo(16, 4, 3))
     with pytest.raises(nat.NativeError, match="fused MLP kernels"):
         VecLiarPartnerPool(16, plain_ego, [members[0]])
     with pytest.raises(nat.NativeError, match="fused MLP kernels"):
@@ -469,7 +344,7 @@ def test_tower_misuse_is_an_error_string_and_nothing_is_launched():
     assert type(liar_pool_for(16, plain_ego, [members[3], members[2]])) is VecLiarPartnerPool
     assert type(liar_pool_for(16, plain_ego, [members[0]])) is TowerVecLiarPartnerPool
     with pytest.raises(nat.NativeError, match="learners train in VecLiarPartnerPool"):
-        VecLiarCrossPlay(8, [_member("ltower32", 8, 2, 3)])
+        VecLiarCrossPlay(8, [LC.member("ltower32", 8, 2, 3)])
     # ... and the contexts still step
     sp.step()
     xp.step()
@@ -490,18 +365,18 @@ def test_all_null_member_archs_is_bitwise_the_entry_point_it_extends():
                 nat.check(ctx.lib.ph_liar_pool_step_arch(ctx.handle, C.byref(sp._desc), None, archs if c % 2 else None, c - 1, c, 0))
             else:
                 nat.check(ctx.lib.ph_liar_pool_step(ctx.handle, C.byref(sp._desc), c - 1, c, 0))
-    a, b = _pool_state(old, ego_o), _pool_state(new, ego_n)
+    a, b = LC.train_state(old, ego_o), LC.train_state(new, ego_n)
     assert a["episodes"] > 0
-    _same_pool_state(a, b, ego_rows=3)
+    LC.same_state(a, b, ego_rows=3)
     for i, m in enumerate(old.learners):
         assert (a[f"pos{i}"] > 0).any()
     # cross-play: the same for ph_liar_xplay_step
-    xa, xb = (_xplay(16, ["frozen", "scripted"], 2) for _ in range(2))
+    xa, xb = (LC.xplay(16, ["frozen", "scripted"], 2) for _ in range(2))
     for xp in (xa, xb):
         xp._bind()
     nat.check(xa.ctx.lib.ph_liar_xplay_step(xa.ctx.handle, C.byref(xa._desc), 1, 0))
     nat.check(xb.ctx.lib.ph_liar_xplay_step_arch(xb.ctx.handle, C.byref(xb._desc), (C.POINTER(nat.PhArch) * 2)(), 1, 0))
-    sa, sb = _xstate(xa), _xstate(xb)
+    sa, sb = LC.xstate(xa), LC.xstate(xb)
     for key in sa:
         assert np.array_equal(sa[key], sb[key]), key
 

@@ -77,7 +77,7 @@ def test_epoch_key_is_the_splitmix_finaliser():
 # who draws what: (stream, key, the blocks / components it can reach, the counters it uses).  Rows of one key must never reach the same
 # (block or component, counter); streams under different keys are separated by the key.  The row slot is the table (dice, first mover,
 # pool), the global row of the launch (actions) or the context index (ADAP).
-ADAP_SALT = 0xADA9C0DE                         # csrc/ph_adap.hip, ph_adapmult.hip: key = epoch_key((seed ^ salt) + epoch, minibatch)
+ADAP_SALT = R.ADAP_SALT
 GAUSS_SECOND = 128                             # csrc/ph_rowtail.h: the Gaussian head's second uniform sits at component c + 128
 ADAP_MAX_CTX = 64                              # a context is part of a Box observation row; far below any other user of its key
 
