@@ -12,7 +12,7 @@
 // occupy one wave for 2 K cycles at the VALU's own f32 rate (guide section 3); the same tile as plain FMAs is spread over all
 // four SIMDs of the CU, so the products here are VALU loops on LDS operands.
 #include "ph_launch.h"
-#include "ph_bc_row.h"
+#include "ph_bc_loss.h"   // the row loss, the minibatch schedule, the statistics row and the Adam step of both training kernels
 
 namespace ph {
 
@@ -76,23 +76,19 @@ __global__ __launch_bounds__(256) void bc_train_kernel(BcArgs a) {
   int step0 = *a.step;
   __syncthreads();
 
-  const int per_epoch = (a.N + a.batch - 1) / a.batch;
-  int total = a.n_epochs * per_epoch;
-  if (a.max_batches > 0 && a.max_batches < total) total = a.max_batches;
-  // beta^t of Adam's bias corrections as running products in fp64 (thread 0; one pow at the start instead of two per step)
-  double b1t = pow((double)a.beta1, (double)step0), b2t = pow((double)a.beta2, (double)step0);
+  const BcSchedule sch = bc_schedule(a.N, a.batch, a.n_epochs, a.max_batches);
+  const int total = sch.total;
+  double b1t = pow((double)a.beta1, (double)step0), b2t = pow((double)a.beta2, (double)step0);   // bc_bias_corrections (thread 0)
 
   BC_PROF_DECL;
   for (int mb = 0; mb < total; ++mb) {
-    const int ep = mb / per_epoch, b = mb - ep * per_epoch;
-    const int start = b * a.batch;
-    const int nb = (a.N - start < a.batch) ? a.N - start : a.batch;
+    const int nb = sch.tile(mb, 0).nb;
     const float inv_nb = 1.0f / (float)nb;
     float s_lp = 0.f, s_h = 0.f, s_pt = 0.f;   // batch sums of log-prob, entropy, prob of the true action (threads < BR)
 
     for (int t0 = 0; t0 < nb; t0 += BR) {
       // ---- tile rows and features ----
-      if (tid < BR) rowidx[tid] = (t0 + tid < nb) ? a.order[(size_t)ep * a.N + start + t0 + tid] : -1;
+      if (tid < BR) rowidx[tid] = sch.row(a.order, sch.tile(mb, t0), tid);
       __syncthreads();
       for (int e = tid; e < BR * nd.A; e += 256) {
         const int row = rowidx[e / nd.A];
@@ -109,10 +105,8 @@ __global__ __launch_bounds__(256) void bc_train_kernel(BcArgs a) {
         for (int e = tid; e < BR * nd.D; e += 256) {
           const int r = e / nd.D, comp = e - r * nd.D, row = rowidx[r];
           if (row < 0) continue;
-          const int lo = nd.obs_off[comp], n = nd.obs_off[comp + 1] - lo;
-          int x = (int)a.obs[(size_t)row * nd.D + comp];
-          x = x < 0 ? 0 : (x >= n ? n - 1 : x);
-          xs[r * FP + lo + x] = 1.f;
+          const int lo = nd.obs_off[comp];   // the hot column of the row in xs: the component's first column + the clamped value
+          xs[bc_hot_feature(r * FP + lo, nd.obs_off[comp + 1] - lo, a.obs[(size_t)row * nd.D + comp])] = 1.f;
         }
       }
       __syncthreads();
@@ -158,41 +152,9 @@ __global__ __launch_bounds__(256) void bc_train_kernel(BcArgs a) {
       }
       __syncthreads();
       BC_STAMP(3);
-      // ---- per row: log-prob of the expert action, entropy, dL/dlogits (one lane per row; sums over action components) ----
-      if (tid < BR) {
-        float* z = zs + tid * (L + 1);
-        const int row = rowidx[tid];
-        if (row >= 0) {
-          float lp = 0.f, ent = 0.f;
-          for (int comp = 0; comp < nd.A; ++comp) {
-            const int lo = nd.act_off[comp], n = nd.act_off[comp + 1] - lo;
-            float mx = -3.0e38f;
-            for (int c = 0; c < n; ++c) mx = fmaxf(mx, z[lo + c]);
-            float se = 0.f;
-            for (int c = 0; c < n; ++c) se += __expf(z[lo + c] - mx);
-            const float lse = mx + __logf(se);
-            int act = rowact[tid * nd.A + comp];
-            act = act < 0 ? 0 : (act >= n ? n - 1 : act);
-            float h = 0.f;
-            for (int c = 0; c < n; ++c) {
-              const float lq = z[lo + c] - lse;
-              h -= __expf(lq) * lq;
-            }
-            lp += z[lo + act] - lse;
-            ent += h;
-            // d/dz_c [ -(1/nb) log p_a - (w/nb) H ] = -(1/nb)([c = a] - p_c) + (w/nb) p_c ((z_c - lse) + H)
-            for (int c = 0; c < n; ++c) {
-              const float lq = z[lo + c] - lse, pc = __expf(lq);
-              z[lo + c] = -inv_nb * (((c == act) ? 1.f : 0.f) - pc) + a.ent_weight * inv_nb * pc * (lq + h);
-            }
-          }
-          s_lp += lp;
-          s_h += ent;
-          s_pt += __expf(lp);
-        } else {
-          for (int c = 0; c < L; ++c) z[c] = 0.f;
-        }
-      }
+      // ---- per row: log-prob of the expert action, entropy, dL/dlogits (one lane per row) ----
+      if (tid < BR)
+        bc_loss_row(zs + tid * (L + 1), rowact + tid * nd.A, rowidx[tid] >= 0, nd.act_off, nd.A, L, inv_nb, a.ent_weight, s_lp, s_h, s_pt);
       __syncthreads();
       BC_STAMP(4);
       // ---- dZ2 = (dlogits act_W^T) * (1 - H2^2) ----
@@ -288,10 +250,10 @@ __global__ __launch_bounds__(256) void bc_train_kernel(BcArgs a) {
     const float mean_h = block_sum(tid < BR ? s_h : 0.f, red, tid) * inv_nb;
     const float mean_pt = block_sum(tid < BR ? s_pt : 0.f, red, tid) * inv_nb;
     if (tid == 0) {
-      b1t *= (double)a.beta1;
-      b2t *= (double)a.beta2;
-      bcorr[0] = (float)((double)a.lr / (1.0 - b1t));
-      bcorr[1] = (float)sqrt(1.0 - b2t);
+      bc_bias_corrections(b1t, b2t, a.beta1, a.beta2, a.lr, bcorr);
+      // bc_write_stats (ph_bc_loss.h), written out: this kernel scales its block sums in every thread, in front of this branch; with
+      // the helper called here the scaling is emitted behind the branch and the kernel spills one more SGPR (49 -> 50), wherever
+      // the call stands, and the conversion's rule is that no kernel's registers move.  Another statistic is this site and the header.
       if (a.stats) {
         float* st = a.stats + (size_t)mb * PH_BC_NSTAT;
         const float neglogp = -mean_lp, ent_loss = -a.ent_weight * mean_h, l2_loss = a.l2_weight * l2_norm;
@@ -311,13 +273,10 @@ __global__ __launch_bounds__(256) void bc_train_kernel(BcArgs a) {
 #pragma unroll 4
     for (int p = tid; p < P; p += 256) {
       const float w = ps[p];
-      const float gr = gs[p] + a.l2_weight * w;
-      const float m0 = a.adam_m[p], v0 = a.adam_v[p];
-      const float m = m0 + (gr - m0) * (1.0f - a.beta1);           // exp_avg.lerp_(grad, 1 - beta1)
-      const float v = v0 * a.beta2 + (1.0f - a.beta2) * gr * gr;   // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
-      a.adam_m[p] = m;
-      a.adam_v[p] = v;
-      ps[p] = w - step_size * (m / (sqrtf(v) / bc2s + a.eps));     // param.addcdiv_(exp_avg, denom, -step_size)
+      const BcMoments mo = bc_adam_moments(gs[p], w, a.adam_m[p], a.adam_v[p], a.l2_weight, a.beta1, a.beta2);
+      a.adam_m[p] = mo.m;
+      a.adam_v[p] = mo.v;
+      ps[p] = bc_adam_param_ieee(w, mo.m, mo.v, step_size, bc2s, a.eps);   // torch's update as written (ph_bc_loss.h: why there are two)
     }
     __syncthreads();
   }
@@ -343,10 +302,6 @@ __global__ __launch_bounds__(256) void bc_train_kernel(BcArgs a) {
 //   * Adam's moments live in LDS beside the parameters when they fit (else they stream through L2).
 // Box or one-hot observations with D <= 128 stored components, heads up to 64 logits; other shapes take the kernel above.
 constexpr int BC_XR = 16;   // raw observation values prefetched per thread: 32 rows * D / 256
-
-struct BcTile {   // which rows of the visiting order a tile covers
-  int ep, start, t0, nb;
-};
 
 // the four split-K partial tiles of element o, all reads issued together (4 unrolled elements: 16 reads in flight)
 #define BC_PART4(dst, base)                                                                                        \
@@ -402,31 +357,19 @@ __global__ __launch_bounds__(256) void bc_train_mfma_kernel(BcArgs a) {
   for (int e = tid; e < BR * XP; e += 256) xs[e] = 0.f;
   for (int e = tid; e < BR * ZP; e += 256) zs[e] = 0.f;
   const int step0 = *a.step;
-  const int per_epoch = (a.N + a.batch - 1) / a.batch;
-  int total = a.n_epochs * per_epoch;
-  if (a.max_batches > 0 && a.max_batches < total) total = a.max_batches;
+  const BcSchedule sch = bc_schedule(a.N, a.batch, a.n_epochs, a.max_batches);
+  const int total = sch.total;
   double b1t = pow((double)a.beta1, (double)step0), b2t = pow((double)a.beta2, (double)step0);
   BC_PROF_DECL;
 
   // flat tile sequence over (minibatch, 32-row tile)
-  auto tile_of = [&](int mb, int t0) -> BcTile {
-    BcTile t;
-    t.ep = mb / per_epoch;
-    const int b = mb - t.ep * per_epoch;
-    t.start = b * a.batch;
-    t.nb = (a.N - t.start < a.batch) ? a.N - t.start : a.batch;
-    t.t0 = t0;
-    return t;
-  };
   auto advance = [&](int& mb, int& t0) {   // -> the tile after (mb, t0); mb == total when the run is over
-    const BcTile t = tile_of(mb, t0);
-    if (t0 + BR < t.nb) t0 += BR;
+    if (t0 + BR < sch.tile(mb, t0).nb) t0 += BR;
     else { mb += 1; t0 = 0; }
   };
   auto index_of = [&](int mb, int t0) -> int {   // dataset row this thread (tid < BR) serves in that tile, -1 = none
     if (tid >= BR || mb >= total) return -1;
-    const BcTile t = tile_of(mb, t0);
-    return (t0 + tid < t.nb) ? a.order[(size_t)t.ep * a.N + t.start + t0 + tid] : -1;
+    return sch.row(a.order, sch.tile(mb, t0), tid);
   };
   const int n_raw = BR * D;               // raw observation values of a tile, n_raw <= 256 * BC_XR
   float xr[BC_XR];
@@ -457,16 +400,11 @@ __global__ __launch_bounds__(256) void bc_train_mfma_kernel(BcArgs a) {
   int idx_ahead = index_of(mb_i, t0_i);
 
   for (int mb = 0; mb < total; ++mb) {
-    const BcTile cur = tile_of(mb, 0);
-    const int nb = cur.nb;
+    const int nb = sch.tile(mb, 0).nb;
     const float inv_nb = 1.0f / (float)nb;
     float s_lp = 0.f, s_h = 0.f, s_pt = 0.f;
-    if (tid == 255) {   // this step's bias corrections (fp64, off the critical path: consumed after the statistics barrier)
-      b1t *= (double)a.beta1;
-      b2t *= (double)a.beta2;
-      bcorr[0] = (float)((double)a.lr / (1.0 - b1t));
-      bcorr[1] = (float)sqrt(1.0 - b2t);
-    }
+    // this step's bias corrections (fp64, off the critical path: consumed after the statistics barrier)
+    if (tid == 255) bc_bias_corrections(b1t, b2t, a.beta1, a.beta2, a.lr, bcorr);
 
     for (int t0 = 0; t0 < nb; t0 += BR) {
       // ---- P0: the prefetched rows land in LDS; the next tile's rows and the index after that are requested ----
@@ -487,6 +425,10 @@ __global__ __launch_bounds__(256) void bc_train_mfma_kernel(BcArgs a) {
           if (e < n_raw) {
             const int r = e / D, comp = e - r * D;
             if (rownext[r] >= 0) {
+              // bc_hot_feature (ph_bc_row.h), written out: called here -- with this very expression tree -- the compiler merges the
+              // two obs_off loads and drops the branch, and bc_train_mfma_kernel<false> changes its AGPR count (104 -> 102); the
+              // conversion's rule is that no kernel's registers move (ph_ppo_split_oh.hip's policy tail is the precedent).  A change
+              // to the clamp is this site and the header.
               const int lo = nd.obs_off[comp], n = nd.obs_off[comp + 1] - lo;
               int x = (int)xr[i];
               x = x < 0 ? 0 : (x >= n ? n - 1 : x);
@@ -562,35 +504,7 @@ __global__ __launch_bounds__(256) void bc_train_mfma_kernel(BcArgs a) {
       // ---- P4: per row: log-prob of the expert action, entropy, dL/dlogits ----
       if (tid < BR) {
         float* z = zs + tid * ZP;
-        if (rowidx[tid] >= 0) {
-          float lp = 0.f, ent = 0.f;
-          for (int comp = 0; comp < nd.A; ++comp) {
-            const int lo = nd.act_off[comp], n = nd.act_off[comp + 1] - lo;
-            float mx = -3.0e38f;
-            for (int c = 0; c < n; ++c) mx = fmaxf(mx, z[lo + c]);
-            float se = 0.f;
-            for (int c = 0; c < n; ++c) se += __expf(z[lo + c] - mx);
-            const float lse = mx + __logf(se);
-            int act = rowact[tid * nd.A + comp];
-            act = act < 0 ? 0 : (act >= n ? n - 1 : act);
-            float h = 0.f;
-            for (int c = 0; c < n; ++c) {
-              const float lq = z[lo + c] - lse;
-              h -= __expf(lq) * lq;
-            }
-            lp += z[lo + act] - lse;
-            ent += h;
-            for (int c = 0; c < n; ++c) {
-              const float lq = z[lo + c] - lse, pc = __expf(lq);
-              z[lo + c] = -inv_nb * (((c == act) ? 1.f : 0.f) - pc) + a.ent_weight * inv_nb * pc * (lq + h);
-            }
-          }
-          s_lp += lp;
-          s_h += ent;
-          s_pt += __expf(lp);
-        } else {
-          for (int c = 0; c < L; ++c) z[c] = 0.f;
-        }
+        bc_loss_row(z, rowact + tid * nd.A, rowidx[tid] >= 0, nd.act_off, nd.A, L, inv_nb, a.ent_weight, s_lp, s_h, s_pt);
         for (int c = L; c < Lk; ++c) z[c] = 0.f;      // K padding of the next product
       }
       __syncthreads();
@@ -701,48 +615,20 @@ __global__ __launch_bounds__(256) void bc_train_mfma_kernel(BcArgs a) {
       float t4[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) t4[k] = (red[k] + red[4 + k]) + (red[8 + k] + red[12 + k]);
-      if (a.stats) {
-        float* st = a.stats + (size_t)mb * PH_BC_NSTAT;
-        const float l2_norm = 0.5f * t4[0], mean_lp = t4[1] * inv_nb, mean_h = t4[2] * inv_nb;
-        const float neglogp = -mean_lp, ent_loss = -a.ent_weight * mean_h, l2_loss = a.l2_weight * l2_norm;
-        st[0] = neglogp;
-        st[1] = mean_h;
-        st[2] = ent_loss;
-        st[3] = t4[3] * inv_nb;
-        st[4] = l2_norm;
-        st[5] = l2_loss;
-        st[6] = neglogp + ent_loss + l2_loss;
-        st[7] = (float)nb;
-      }
+      if (a.stats) bc_write_stats(a.stats + (size_t)mb * PH_BC_NSTAT, t4[0], t4[1], t4[2], t4[3], inv_nb, nb, a.ent_weight, a.l2_weight);
     }
     __syncthreads();
     BC_STAMP(8);
-    // torch's update with the two divisions and the square root on the hardware's 1-ulp v_rcp_f32 / v_sqrt_f32 (the IEEE
-    // sequences cost ~60 instructions per parameter here -- the Adam loop was the longest phase of a step); the resulting
-    // last-bit differences are far inside what 1e-3-sized Adam steps do to a near-zero gradient entry anyway
     const float step_size = bcorr[0], inv_bc2s = __builtin_amdgcn_rcpf(bcorr[1]);
 #pragma unroll 4
     for (int p = tid; p < P; p += 256) {
+      float* mp = moments_in_lds ? ms + p : a.adam_m + p;   // a template constant chooses: LDS or global, never a generic pointer
+      float* vp = moments_in_lds ? vs + p : a.adam_v + p;
       const float w = ps[p];
-      const float gr = gs[p] + a.l2_weight * w;
-      float m0, v0;
-      if constexpr (moments_in_lds) {
-        m0 = ms[p];
-        v0 = vs[p];
-      } else {
-        m0 = a.adam_m[p];
-        v0 = a.adam_v[p];
-      }
-      const float m = m0 + (gr - m0) * (1.0f - a.beta1);
-      const float v = v0 * a.beta2 + (1.0f - a.beta2) * gr * gr;
-      if constexpr (moments_in_lds) {
-        ms[p] = m;
-        vs[p] = v;
-      } else {
-        a.adam_m[p] = m;
-        a.adam_v[p] = v;
-      }
-      ps[p] = w - step_size * m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * inv_bc2s + a.eps);
+      const BcMoments mo = bc_adam_moments(gs[p], w, *mp, *vp, a.l2_weight, a.beta1, a.beta2);
+      *mp = mo.m;
+      *vp = mo.v;
+      ps[p] = bc_adam_param_fast(w, mo.m, mo.v, step_size, inv_bc2s, a.eps);   // v_rcp_f32 / v_sqrt_f32 (ph_bc_loss.h: why there are two)
     }
     __syncthreads();
     BC_STAMP(9);
@@ -791,27 +677,8 @@ int bc_train_path(int D, int F, int A, int L, int P) {
 hipError_t launch_bc_train(const NetDims& nd, const ph_bc_layout& lay, float* params, float* adam_m, float* adam_v, int* step,
                            const float* obs, const float* acts, const int* order, int N, int batch, int n_epochs,
                            int max_batches, const ph_bc_hyper& hp, float* stats, hipStream_t s) {
-  BcArgs a;
-  a.nd = nd;
-  a.lay = lay;
-  a.params = params;
-  a.adam_m = adam_m;
-  a.adam_v = adam_v;
-  a.step = step;
-  a.obs = obs;
-  a.acts = acts;
-  a.order = order;
-  a.N = N;
-  a.batch = batch;
-  a.n_epochs = n_epochs;
-  a.max_batches = max_batches;
-  a.lr = hp.learning_rate;
-  a.beta1 = hp.adam_beta1;
-  a.beta2 = hp.adam_beta2;
-  a.eps = hp.adam_eps;
-  a.ent_weight = hp.ent_weight;
-  a.l2_weight = hp.l2_weight;
-  a.stats = stats;
+  const BcArgs a{nd, lay, params, adam_m, adam_v, step, obs, acts, order, N, batch, n_epochs, max_batches, hp.learning_rate,
+                 hp.adam_beta1, hp.adam_beta2, hp.adam_eps, hp.ent_weight, hp.l2_weight, stats};
   const int path = bc_train_path(nd.D, nd.F, nd.A, nd.L, lay.P);
   if (path >= 2) {
     const bool moments = path == 3;
@@ -905,11 +772,7 @@ __global__ __launch_bounds__(64) void bc_forward_kernel(BcFwdArgs a) {
       const float u = a.uniforms ? a.uniforms[(size_t)row * nd.A + comp] : philox_uniform(a.seed, a.counter, (uint32_t)row, (uint32_t)comp);
       act = bc_sample_cdf(z, n, lse, u);
     }
-    float h = 0.f;
-    for (int c = 0; c < n; ++c) {
-      const float lq = z(c) - lse;
-      h -= __expf(lq) * lq;
-    }
+    const float h = bc_entropy(z, n, lse);
     lp_sum += z(act) - lse;
     ent_sum += h;
     if (a.act_i32) a.act_i32[(size_t)row * nd.A + comp] = act;
@@ -924,23 +787,7 @@ hipError_t launch_bc_forward(const NetDims& nd, const ph_bc_layout& lay, const f
                              const unsigned char* mask, const float* uniforms, const float* given, uint64_t seed,
                              uint64_t counter, int deterministic, int* act_i32, float* values, float* logp, float* entropy,
                              float* logits, hipStream_t s) {
-  BcFwdArgs a;
-  a.nd = nd;
-  a.lay = lay;
-  a.params = params;
-  a.obs = obs;
-  a.n = n;
-  a.mask = mask;
-  a.uniforms = uniforms;
-  a.given = given;
-  a.seed = seed;
-  a.counter = counter;
-  a.deterministic = deterministic;
-  a.act_i32 = act_i32;
-  a.values = values;
-  a.logp = logp;
-  a.entropy = entropy;
-  a.logits = logits;
+  const BcFwdArgs a{nd, lay, params, obs, n, mask, uniforms, given, seed, counter, deterministic, act_i32, values, logp, entropy, logits};
   const size_t lds = bc_forward_lds_bytes(lay.P);
   if (const hipError_t e = allow_dynamic_lds((const void*)bc_forward_kernel, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(bc_forward_kernel, dim3((n + 63) / 64), dim3(64), lds, s, a);

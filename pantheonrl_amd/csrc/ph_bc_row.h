@@ -58,6 +58,17 @@ __device__ __forceinline__ float bc_lse(Z z, int n, float mx) {
   return mx + __logf(se);
 }
 
+// entropy of the component: -sum_c p_c log p_c, log p_c = z(c) - lse
+template <class Z>
+__device__ __forceinline__ float bc_entropy(Z z, int n, float lse) {
+  float h = 0.f;
+  for (int c = 0; c < n; ++c) {
+    const float lq = z(c) - lse;
+    h -= __expf(lq) * lq;
+  }
+  return h;
+}
+
 // the class a uniform u selects: the first c with u < cdf(c), cdf the running sum of exp(z - lse); the last class otherwise
 template <class Z>
 __device__ __forceinline__ int bc_sample_cdf(Z z, int n, float lse, float u) {
