@@ -44,7 +44,8 @@ extern "C" {
                                   (an error before; no signature or struct changed)
                                  still 7: + ph_block_reset / _step / _obs, ph_block_selfplay_step, ph_block_replay_host (additions only)
                                  still 7: + ph_bc_train_path (addition only)
-                                 still 7: + ph_adap_rows, ph_adap_context_draw, ph_adap_vec_host, ph_liar_selfplay_step_adap (additions only) */
+                                 still 7: + ph_adap_rows, ph_adap_context_draw, ph_adap_vec_host, ph_liar_selfplay_step_adap (additions only)
+                                 still 7: + ph_block_scripted_actions / _host, ph_block_group_forward, ph_block_xplay_step (additions only) */
 #define PH_HIDDEN 64     /* SB3 MlpPolicy default net_arch pi=[64,64], vf=[64,64] (modular/policies.py:112-114) */
 #define PH_MAX_COMP 256  /* max MultiDiscrete components per space */
 #define PH_MAX_LOGITS 64 /* max total policy logits L */
@@ -811,6 +812,75 @@ int ph_block_selfplay_step(ph_ctx *ctx, const ph_block_selfplay *s, int ego_pos,
 int ph_block_replay_host(int variant, int n, int rounds, int *state, const int *tokens, const int *alt_actions, float *alt_obs_out,
                          float *rewards_out, unsigned char *done_out, float *ego_obs_out, int do_reset, unsigned long long seed,
                          unsigned long long counter, int max_draws);
+
+/* ---- cross-play evaluation of the block worlds (csrc/ph_block.h, ph_block.hip; additions, PH_ABI_VERSION unchanged): every
+ * planner of a population with every constructor, frozen or scripted, n tables at once.
+ *
+ * The scripted constructors (envs/blockworld.py) as one integer rule of a constructor observation row: variant 1 with
+ * PH_BLOCK_RULE_DEFAULT is DefaultConstructorAgent; variant 0 with PH_BLOCK_RULE_DEFAULT is SBWDefaultAgent and with
+ * PH_BLOCK_RULE_EASY SBWEasyPartner (EASY exists for variant 0 only).  The reference's quirks are kept: a red-range token whose
+ * row is done looks at row token - 8, counted from the bottom; the pass move is (0, colour of block 0); SBWEasyPartner halves tokens
+ * above 10.  One stated deviation: where SBWEasyPartner answers the negative block index token - 8 (tokens 6, 7, 12-15), which the
+ * host game reads from the end of its list, the rule gives the index modulo 5 (-2 -> 3, -1 -> 4): the move the host game makes,
+ * inside the action space.  obs (n,50) | (n,21) f32, actions (n,3) | (n,2) int32; rows with active[e] == 0 (NULL = all) are not
+ * touched.  The _host form runs the same text on the CPU: no context, host pointers. */
+#define PH_BLOCK_RULE_DEFAULT 0
+#define PH_BLOCK_RULE_EASY 1
+int ph_block_scripted_actions(ph_ctx *ctx, int variant, int rule, const float *obs, const unsigned char *active, int *actions, int n);
+int ph_block_scripted_actions_host(int variant, int rule, const float *obs, int *actions, int n);
+/* The grouped forward for any categorical spec whose padded logit count is 32 (n < 16384; not the 16-row dense class of one
+ * Discrete head of <= 8 logits over one feature chunk): ONE bucket pass (ph_pool_forward's: a stable counting sort of the rows with
+ * active[e] != 0 by member_of[e], 16-row tiles per member) and ONE launch in which a workgroup runs one tile's policy net with its
+ * member's parameters and seed, read from a member table in device memory.  Members are PH_POOL_FROZEN (params: a ph_layout vector of
+ * `spec`, 16-byte aligned; seed: its Philox key; the other fields are ignored) or PH_POOL_SCRIPTED (a block-world constructor spec
+ * only; `seed` holds the PH_BLOCK_RULE_*).  A PH_POOL_LEARNER or PH_POOL_CLONE member, a spec with Box actions and a rule the
+ * variant does not have are refused before anything is launched.  Row e of a frozen member draws with (member seed, counter, e) and
+ * its action is bitwise what ph_policy_forward(spec, member params, obs, n, seed, counter) with gemm_mode 0 samples for row e in the
+ * same process: a tile runs the body ph_policy_forward picks for the spec -- the 16-row one-hot body or the general 32-row body, half
+ * empty.  Scripted members' rows follow ph_block_scripted_actions, in a launch of their own, made only when the table holds a
+ * scripted member.  Only actions[e] of active rows is written.  The context keeps two member tables besides the Liar's Dice one:
+ * one for specs that are a block-world constructor's, one for every other spec (the planners'); each is uploaded, with a stream
+ * synchronisation, when the members passed in differ from it. */
+int ph_block_group_forward(ph_ctx *ctx, const ph_spec *spec, const ph_pool_member *members, int n_members, const float *obs,
+                           const int *member_of, const unsigned char *active, unsigned long long counter, int *actions, int n);
+/* n tables, 1..PH_MAX_POOL planners and 1..PH_MAX_POOL constructors: table e plays pairs[e % n_pairs] = (planner, constructor) for
+ * exactly episodes_per_table games and then goes idle -- masked out of every launch, its state and logs frozen.  A game's return is
+ * the f32 sum of the ego rewards, its length the number of planner tokens.  Only the planner's last token ends a game, so nothing
+ * bounds one: the caller runs steps in chunks, reads tables_left between them and stops at a cap of its own; ph_xplay_stats covers
+ * the logged games (games[e] of table e). */
+typedef struct ph_block_xplay {
+  int n, variant;
+  const ph_spec *ego_spec, *alt_spec;        /* planner / constructor spaces of the variant */
+  int *state;                                /* (n, PH_BLOCK_STATE_WORDS) */
+  unsigned long long world_seed;
+  const ph_pool_member *planners;            /* host array [n_planners]: PH_POOL_FROZEN */
+  int n_planners;
+  const ph_pool_member *constructors;        /* host array [n_constructors]: PH_POOL_FROZEN / PH_POOL_SCRIPTED (seed = rule) */
+  int n_constructors;
+  const int *pairs;                          /* host array [n_pairs][2]: (planner, constructor) */
+  int n_pairs;                               /* 1..n */
+  int episodes_per_table;                    /* G >= 1 */
+  const int *ego_id, *alt_id;                /* (n) device: pairs[e % n_pairs][0] / [1] */
+  int *ego_actions;                          /* (n) */
+  int *alt_actions;                          /* (n,3) | (n,2) */
+  float *obs_ego, *obs_alt;                  /* planner / constructor observation of every table */
+  int *games;                                /* (n) games finished */
+  unsigned char *playing;                    /* (n) 1 while games[e] < G */
+  int *tables_left;                          /* [1] tables with budget left */
+  float *ep_return;                          /* (n) return of the game in progress */
+  int *ep_length;                            /* (n) planner tokens of the game in progress */
+  float *returns;                            /* (n,G) log */
+  int *lengths;                              /* (n,G) log */
+  unsigned char *running;                    /* scratch (n): tables whose game goes on behind the planner's token */
+} ph_block_xplay;
+/* One step: grouped planner forward over the playing tables -> after_ego (the token played; on the end token the game logged at
+ * [e, games[e]], games += 1, then the next world and its planner observation, or tables_left -= 1 when the budget is spent;
+ * otherwise the constructor's observation) -> grouped constructor forward over the running tables -> after_alt (the move played,
+ * the planner's observation).  Six launches, seven when a constructor is scripted, whatever the number of members; no host
+ * synchronisation.  RNG counters of step c >= 1: planner forward 2c, constructor forward 2c + 1, worlds c.  first != 0: nothing is
+ * played -- every table gets its first world (world counter 0) and its planner observation; the caller has set games = 0,
+ * playing = 1, tables_left = n and cleared ep_return / ep_length. */
+int ph_block_xplay_step(ph_ctx *ctx, const ph_block_xplay *xp, unsigned long long counter, int first);
 
 /* n_steps vectorised agent steps against a SCRIPTED environment -- observations, rewards and dones of every step already
  * resident on the device (the synthetic rollout driver of SURVEY.md 8d; a recorded trajectory being replayed) -- in ONE launch:

@@ -272,6 +272,25 @@ class PhLiarXplay(C.Structure):
                 ("alt_opens", C.c_void_p), ("ego_opens", C.c_void_p), ("done", C.c_void_p)]
 
 
+PH_BLOCK_RULE_DEFAULT, PH_BLOCK_RULE_EASY = 0, 1
+BLOCK_RULES = {"DEFAULT": PH_BLOCK_RULE_DEFAULT, "EASY": PH_BLOCK_RULE_EASY}
+
+
+class PhBlockXplay(C.Structure):
+    """ph_block_xplay: cross-play evaluation of a block world -- a member table per seat, a pair per table, a game budget per table"""
+    _fields_ = [("n", C.c_int), ("variant", C.c_int), ("ego_spec", C.POINTER(PhSpec)), ("alt_spec", C.POINTER(PhSpec)),
+                ("state", C.c_void_p), ("world_seed", C.c_ulonglong),
+                ("planners", C.POINTER(PhPoolMember)), ("n_planners", C.c_int),
+                ("constructors", C.POINTER(PhPoolMember)), ("n_constructors", C.c_int),
+                ("pairs", C.POINTER(C.c_int)), ("n_pairs", C.c_int), ("episodes_per_table", C.c_int),
+                ("ego_id", C.c_void_p), ("alt_id", C.c_void_p),
+                ("ego_actions", C.c_void_p), ("alt_actions", C.c_void_p),
+                ("obs_ego", C.c_void_p), ("obs_alt", C.c_void_p),
+                ("games", C.c_void_p), ("playing", C.c_void_p), ("tables_left", C.c_void_p),
+                ("ep_return", C.c_void_p), ("ep_length", C.c_void_p), ("returns", C.c_void_p), ("lengths", C.c_void_p),
+                ("running", C.c_void_p)]
+
+
 class PhLiarRecord(C.Structure):
     """ph_liar_record: the device-resident move log of the vectorised Liar's Dice step (rows [obs 30 | action 2 | flag])"""
     _fields_ = [("n", C.c_int), ("cap", C.c_int), ("rows", C.c_void_p), ("member", C.c_void_p),
@@ -357,6 +376,10 @@ SIGNATURES = {
     "ph_block_obs": [_vp, _i, _vp, _i, _vp, _vp, _i],
     "ph_block_selfplay_step": [_vp, C.POINTER(PhBlockSelfPlay), _i, _ull],
     "ph_block_replay_host": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ull, _ull, _i],
+    "ph_block_scripted_actions": [_vp, _i, _i, _vp, _vp, _vp, _i],
+    "ph_block_scripted_actions_host": [_i, _i, _vp, _vp, _i],
+    "ph_block_group_forward": [_vp, C.POINTER(PhSpec), C.POINTER(PhPoolMember), _i, _vp, _vp, _vp, _ull, _vp, _i],
+    "ph_block_xplay_step": [_vp, C.POINTER(PhBlockXplay), _ull, _i],
     "ph_framestack_push": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "ph_scripted_rollout": [_vp, C.POINTER(PhSpec), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp, _vp,
                             C.POINTER(PhRollout), _i, _i],
@@ -672,3 +695,15 @@ def block_replay_host(variant: int, state=None, tokens=None, alt_actions=None, n
     check(load().ph_block_replay_host(int(variant), n, R, p(state), p(tok), p(act), p(alt_obs), p(rew), p(done), p(ego_obs),
                                       int(reset), int(seed or 0), int(counter), int(max_draws)))
     return dict(state=state, alt_obs=alt_obs, rewards=rew, done=done, ego_obs=ego_obs)
+
+
+def block_scripted_actions_host(variant: int, rule: int, obs):
+    """the scripted constructors on the CPU (ph_block_scripted_actions_host: the rule text the device kernels run).  obs (n, 50 | 21)
+    constructor observation rows -> (n, 3 | 2) int32 moves"""
+    import numpy as np
+    Da, A = (50, 3) if variant == 1 else (21, 2)
+    rows = np.ascontiguousarray(obs, np.float32).reshape(-1, Da)
+    out = np.zeros((rows.shape[0], A), np.int32)
+    check(load().ph_block_scripted_actions_host(int(variant), int(rule), rows.ctypes.data_as(C.c_void_p),
+                                                out.ctypes.data_as(C.c_void_p), rows.shape[0]))
+    return out

@@ -194,7 +194,14 @@ struct ph_ctx {
   size_t pool_order_cap = 0;
   int* pool_tiles = nullptr;                // [pool_max_tiles + 1][3]; the last record's first word is the tile count
   size_t pool_tiles_cap = 0;
-  long long* prof = nullptr;                // caller-owned debug stamp buffer
+  // the block worlds' grouped forward (ph_block_group_forward): a member table per seat -- [1] a constructor spec's, [0] every other
+  // spec's (the planners') -- beside the Liar's Dice table above, with what each holds
+  ph::PoolMemberDev* group_dev[2] = {nullptr, nullptr};
+  ph::PoolMemberDev group_host[2][PH_MAX_POOL];
+  int group_count[2] = {0, 0};
+  bool group_scripted[2] = {false, false};  // ... of which one is scripted (launch_block_group_scripted has rows to write)
+  bool group_frozen[2] = {false, false};    // ... of which one is frozen (launch_group_fwd has a tile to run)
+  long long* prof = nullptr;               // caller-owned debug stamp buffer
   double* ep_partial = nullptr;             // ph_episode_stats: [workgroups][PH_MAX_POOL][PH_EPISODE_NSTAT] partial sums of one scan
   size_t ep_partial_cap = 0;
   unsigned int* ep_ticket = nullptr;        // [1] workgroups of the scan in flight that have stored their partials (zero between launches)
@@ -766,7 +773,8 @@ int ph_ctx_destroy(ph_ctx* ctx) {
     if (s.act_off) (void)hipFree(s.act_off);
   }
   void* ptrs[] = {ctx->wimage, ctx->mw.act, ctx->mw.maps, ctx->mw.kl_sum, ctx->mw.scratch, ctx->advpart, ctx->p2p_dev, ctx->slabs, ctx->statpart, ctx->grad, ctx->blocksq, ctx->advstats, ctx->adam_bias, ctx->perm_idx, ctx->perm_phys, ctx->ximg, ctx->rec_pi, ctx->rec_vf, ctx->rowrec, ctx->step_words, ctx->step_gen, ctx->scalars, ctx->stop_flag,
-                  ctx->adap_extra, ctx->adap_loss, ctx->am_buf, ctx->pool_dev, ctx->pool_order, ctx->pool_tiles, ctx->ep_partial, ctx->ep_ticket};
+                  ctx->adap_extra, ctx->adap_loss, ctx->am_buf, ctx->pool_dev, ctx->pool_order, ctx->pool_tiles, ctx->ep_partial, ctx->ep_ticket,
+                  ctx->group_dev[0], ctx->group_dev[1]};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (ctx->act_stage_host) (void)hipHostFree(ctx->act_stage_host);
@@ -2557,6 +2565,176 @@ int ph_block_replay_host(int variant, int n, int rounds, int* state, const int* 
     }
     ph::bw_pack(t, variant, w);
   }
+  return 0;
+}
+
+// ---- cross-play evaluation of the block worlds: scripted constructors, the grouped forward, the step ----
+namespace {
+int check_block_rule(const char* who, int variant, int rule) {
+  if (variant != 0 && variant != 1) return fail_who(who, ": variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (rule != PH_BLOCK_RULE_DEFAULT && rule != PH_BLOCK_RULE_EASY) return fail_who(who, ": unknown rule (PH_BLOCK_RULE_DEFAULT / PH_BLOCK_RULE_EASY)");
+  if (rule == PH_BLOCK_RULE_EASY && variant != 0) return fail_who(who, ": PH_BLOCK_RULE_EASY (SBWEasyPartner) exists for BlockEnv-v0 only");
+  return 0;
+}
+// the variant whose constructor spaces the layout describes, -1 when it describes neither's
+int block_constructor_variant(const ph_layout& l) {
+  for (int v = 0; v < 2; ++v)
+    if (l.D == ph::bw_alt_obs_len(v) && l.A == ph::bw_alt_act_len(v) && l.L == (v ? 11 : 8) && l.F == (v ? 30 + 3 * ph::BW_CELLS : 16 + 19 * ph::BW_BLOCKS))
+      return v;
+  return -1;
+}
+// validate the members of one seat and bring that seat's device-side table up to date (pool_members' manner: uploaded only when it
+// changed, never inside graph capture).  ctor_variant: the variant whose constructor the spec is, -1: scripted members are refused.
+int group_members(ph_ctx* ctx, const char* who, int table, int ctor_variant, const ph_pool_member* members, int K) {
+  const std::string w(who);
+  if (!members) return fail(w + ": null member array");
+  if (K < 1 || K > PH_MAX_POOL) return fail(w + ": a seat holds 1..PH_MAX_POOL members");
+  ph::PoolMemberDev tab[PH_MAX_POOL];
+  const size_t used = sizeof(ph::PoolMemberDev) * (size_t)K;
+  std::memset(tab, 0, used);
+  bool scripted = false, frozen = false;
+  for (int k = 0; k < K; ++k) {
+    const ph_pool_member& m = members[k];
+    ph::PoolMemberDev& d = tab[k];
+    const std::string wk = w + ": member " + std::to_string(k);
+    if (m.kind == PH_POOL_LEARNER) return fail(wk + " is a PH_POOL_LEARNER: an evaluation seats frozen and scripted members only");
+    if (m.kind == PH_POOL_CLONE) return fail(wk + " is a PH_POOL_CLONE: a BC clone does not sit in the block worlds' grouped forward");
+    if (m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED) return fail(wk + ": unknown kind");
+    d.kind = d.fwd = m.kind;
+    if (m.kind == PH_POOL_SCRIPTED) {
+      if (ctor_variant < 0) return fail(wk + ": a scripted member needs a block-world constructor spec");
+      if (check_block_rule(wk.c_str(), ctor_variant, m.seed > 1ull ? -1 : (int)m.seed)) return 1;   // (`seed` holds the rule)
+      d.rb_T = (int)m.seed;
+      scripted = true;
+      continue;
+    }
+    if (!m.params) return fail(wk + ": null params");
+    if ((uintptr_t)m.params % 16 != 0) return fail(wk + ": params must be 16-byte aligned");
+    d.params = m.params;
+    d.seed = m.seed;
+    frozen = true;
+  }
+  if (ctx->group_count[table] != K || std::memcmp(ctx->group_host[table], tab, used) != 0) {
+    if (ctx->capturing) return fail(w + ": the member table changed inside graph capture: run the same call once outside capture first");
+    if (!ctx->group_dev[table]) PH_HIP(hipMalloc((void**)&ctx->group_dev[table], sizeof(tab)));
+    PH_HIP(hipStreamSynchronize(ctx->stream));   // launches in flight still read the table
+    std::memcpy(ctx->group_host[table], tab, used);
+    ctx->group_count[table] = 0;
+    PH_HIP(hipMemcpyAsync(ctx->group_dev[table], ctx->group_host[table], used, hipMemcpyHostToDevice, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->group_count[table] = K;
+    ctx->group_scripted[table] = scripted;
+    ctx->group_frozen[table] = frozen;
+  }
+  return 0;
+}
+// the spec's member table (block_constructor_variant into *ctor_variant) -- before anything is launched
+int group_table_of(const ph_spec* spec, int* ctor_variant) {
+  ph_layout lay;
+  if (layout_of(spec, &lay)) return -1;
+  *ctor_variant = block_constructor_variant(lay);
+  return *ctor_variant >= 0 ? 1 : 0;
+}
+// bucket pass + the frozen members' tiles + the scripted members' rows over the tables with active[e] != 0
+int group_forward(ph_ctx* ctx, const char* who, int table, int ctor_variant, const ph_spec* spec, int K, const float* obs,
+                  const int* member_of, const unsigned char* active, unsigned long long counter, int* actions, int n) {
+  ph::PoolFwd p;
+  std::memset(&p, 0, sizeof(p));
+  if (fwd_args(p.a, ctx, spec, false, nullptr, obs, n, 0, counter, actions, nullptr, nullptr)) return 1;
+  if (!ph::group_fwd_eligible(p.a.nd, n))
+    return fail_who(who, ": the spec is not in the grouped forward's class (categorical heads of at most 32 logits, n < 16384, not the "
+                         "16-row dense class of one Discrete head of <= 8 logits over one feature chunk)");
+  if (ctx->group_frozen[table]) {
+    if (ensure(ctx, ctx->pool_order, ctx->pool_order_cap, (size_t)n)) return 1;
+    const size_t ntile = (size_t)ph::pool_max_tiles(n, PH_MAX_POOL);
+    if (ensure(ctx, ctx->pool_tiles, ctx->pool_tiles_cap, 3 * (ntile + 1))) return 1;
+    p.members = ctx->group_dev[table];
+    p.b.order = ctx->pool_order;
+    p.b.tiles = ctx->pool_tiles;
+    p.b.ntiles = ctx->pool_tiles + 3 * ntile;
+    PH_HIP(ph::launch_pool_bucket(member_of, active, n, K, p.b, ctx->stream));
+    PH_HIP(ph::launch_group_fwd(p, K, ctx->stream));
+  }
+  if (ctx->group_scripted[table])
+    PH_HIP(ph::launch_block_group_scripted(ctor_variant, obs, ctx->group_dev[table], member_of, active, actions, n, K, ctx->stream));
+  return 0;
+}
+}  // namespace
+
+int ph_block_scripted_actions(ph_ctx* ctx, int variant, int rule, const float* obs, const unsigned char* active, int* actions, int n) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_block_scripted_actions";
+  if (!ctx) return fail("null ctx");
+  if (!obs || !actions) return fail_who(who, ": null argument");
+  if (n <= 0) return fail_who(who, ": n must be positive");
+  if (check_block_rule(who, variant, rule)) return 1;
+  PH_HIP(ph::launch_block_scripted_actions(variant, rule, obs, active, actions, n, ctx->stream));
+  return 0;
+}
+
+int ph_block_scripted_actions_host(int variant, int rule, const float* obs, int* actions, int n) {
+  const char* who = "ph_block_scripted_actions_host";
+  if (!obs || !actions || n <= 0) return fail_who(who, ": bad arguments");
+  if (check_block_rule(who, variant, rule)) return 1;
+  const int D = ph::bw_alt_obs_len(variant), A = ph::bw_alt_act_len(variant);
+  for (int e = 0; e < n; ++e) {
+    int a[3];
+    ph::bw_scripted_move(variant, rule, obs + (size_t)e * D, a);
+    for (int j = 0; j < A; ++j) actions[(size_t)e * A + j] = a[j];
+  }
+  return 0;
+}
+
+int ph_block_group_forward(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* members, int n_members, const float* obs,
+                           const int* member_of, const unsigned char* active, unsigned long long counter, int* actions, int n) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_block_group_forward";
+  if (!ctx) return fail("null ctx");
+  if (!spec || !obs || !member_of || !active || !actions) return fail_who(who, ": null argument");
+  if (n <= 0) return fail_who(who, ": n must be positive");
+  int ctor_variant = -1;
+  const int table = group_table_of(spec, &ctor_variant);
+  if (table < 0) return 1;
+  if (group_members(ctx, who, table, ctor_variant, members, n_members)) return 1;
+  return group_forward(ctx, who, table, ctor_variant, spec, n_members, obs, member_of, active, counter, actions, n);
+}
+
+int ph_block_xplay_step(ph_ctx* ctx, const ph_block_xplay* xp, unsigned long long counter, int first) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_block_xplay_step";
+  if (!ctx || !xp) return fail_who(who, ": null argument");
+  const ph_block_xplay& s = *xp;
+  if (s.variant != 0 && s.variant != 1) return fail_who(who, ": variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (s.n <= 0) return fail_who(who, ": n must be positive");
+  if (!s.ego_spec || !s.alt_spec || !s.state || !s.pairs || !s.ego_id || !s.alt_id || !s.ego_actions || !s.alt_actions || !s.obs_ego ||
+      !s.obs_alt || !s.games || !s.playing || !s.tables_left || !s.ep_return || !s.ep_length || !s.returns || !s.lengths || !s.running)
+    return fail_who(who, ": incomplete description");
+  if ((uintptr_t)s.state % 16) return fail_who(who, ": state must be 16-byte aligned");
+  if (s.episodes_per_table < 1) return fail_who(who, ": episodes_per_table must be at least 1");
+  if (s.n_pairs < 1 || s.n_pairs > s.n) return fail_who(who, ": 1..n pairs (every pair needs a table)");
+  ph_layout le, la;
+  if (ph_layout_of(s.ego_spec, &le) || ph_layout_of(s.alt_spec, &la)) return 1;
+  if (le.D != ph::bw_ego_obs_len(s.variant) || le.A != 1 || le.L != ph::bw_tokens(s.variant) || block_constructor_variant(la) != s.variant)
+    return fail_who(who, ": the specs are not the variant's planner / constructor spaces");
+  if (s.n_planners < 1 || s.n_planners > PH_MAX_POOL || s.n_constructors < 1 || s.n_constructors > PH_MAX_POOL)
+    return fail_who(who, ": a seat holds 1..PH_MAX_POOL members");
+  for (int p = 0; p < s.n_pairs; ++p)
+    if (s.pairs[2 * p] < 0 || s.pairs[2 * p] >= s.n_planners || s.pairs[2 * p + 1] < 0 || s.pairs[2 * p + 1] >= s.n_constructors)
+      return fail("ph_block_xplay_step: pair " + std::to_string(p) + " names a member out of range");
+  if (group_members(ctx, "ph_block_xplay_step: planners", 0, -1, s.planners, s.n_planners) ||
+      group_members(ctx, "ph_block_xplay_step: constructors", 1, s.variant, s.constructors, s.n_constructors))
+    return 1;
+  if (first) {
+    PH_HIP(ph::launch_block_reset(s.variant, s.state, nullptr, s.world_seed, 0ull, ctx->rng_epoch, s.n, ctx->stream));
+    PH_HIP(ph::launch_block_obs(s.variant, s.state, 1, nullptr, s.obs_ego, s.n, ctx->stream));
+    return 0;
+  }
+  if (group_forward(ctx, who, 0, -1, s.ego_spec, s.n_planners, s.obs_ego, s.ego_id, s.playing, 2 * counter, s.ego_actions, s.n)) return 1;
+  PH_HIP(ph::launch_block_xp_after_ego(s, counter, ctx->rng_epoch, ctx->stream));
+  if (group_forward(ctx, who, 1, s.variant, s.alt_spec, s.n_constructors, s.obs_alt, s.alt_id, s.running, 2 * counter + 1, s.alt_actions,
+                    s.n))
+    return 1;
+  PH_HIP(ph::launch_block_xp_after_alt(s, ctx->stream));
   return 0;
 }
 

@@ -240,7 +240,77 @@ __host__ __device__ inline void bw_write_alt_obs(const BwTable& t, int variant, 
   else bw_write_blocks(t, false, o + 1);
 }
 
+// ---- the scripted constructors (envs/blockworld.py: DefaultConstructorAgent, SBWDefaultAgent, SBWEasyPartner) --------------------
+// One function of a constructor observation row o (bw_alt_obs_len floats) and a rule; a[] gets bw_alt_act_len ints (a[2] = 0 for
+// variant 0).  Integer rules, the reference's quirks included:
+//   variant 1, DEFAULT  token - 1 = 4 x + 2 orientation + colour; the first and the last token get (6, vertical, blue)
+//   variant 0, DEFAULT  tokens 1-7 / 8-14 name a grid row: the first still uncoloured block met along it (a cell covered twice
+//                       belongs to the later block) turns red / blue; a red-range token whose row is done looks at row token - 8,
+//                       counted from the bottom, for a block to turn blue; otherwise the pass move (0, colour of block 0)
+//   variant 0, EASY     tokens above 10 are halved; 1-5 turn block token - 1 red, 6-10 block token - 8 blue.  The host agent answers
+//                       the negative index -2 / -1 for tokens 6 / 7 (and 12-15), which the host game reads from the end of its
+//                       list; here the index is given modulo BW_BLOCKS (3 / 4): the move the host game makes, inside the action space
+constexpr int BW_RULE_DEFAULT = PH_BLOCK_RULE_DEFAULT, BW_RULE_EASY = PH_BLOCK_RULE_EASY;
+// SBWDefaultAgent.first_uncoloured: `row` as a Python index into the seven grid rows (negative: from the bottom)
+__host__ __device__ inline int bw_first_uncoloured(const float* o, int row) {
+  if (row < 0) row += BW_GRID;
+  for (int x = 0; x < BW_GRID; ++x) {
+    int owner = -1;
+#pragma unroll
+    for (int i = 0; i < BW_BLOCKS; ++i) {
+      const int v = (int)o[1 + 4 * i], y = (int)o[2 + 4 * i], bx = (int)o[3 + 4 * i];
+      const bool covers = (y == row && bx == x) || (v ? (y + 1 == row && bx == x) : (y == row && bx + 1 == x));
+      owner = covers ? i : owner;
+    }
+    if (owner < 0) continue;
+    int colour = 0;
+#pragma unroll
+    for (int i = 0; i < BW_BLOCKS; ++i) colour = (i == owner) ? (int)o[4 + 4 * i] : colour;
+    if (colour == 0) return owner;
+  }
+  return -1;
+}
+__host__ __device__ inline void bw_scripted_move(int variant, int rule, const float* o, int* a) {
+  int token = (int)o[0];
+  a[2] = 0;
+  if (variant) {
+    if (token <= 0 || token >= bw_tokens(1) - 1) {
+      a[0] = BW_GRID - 1; a[1] = 1; a[2] = 0;
+      return;
+    }
+    const int t = token - 1;
+    a[0] = t / 4; a[1] = (t / 2) % 2; a[2] = t % 2;
+    return;
+  }
+  a[0] = 0;
+  a[1] = (int)o[4];   // the pass move: block 0 keeps its colour
+  if (rule == BW_RULE_EASY) {
+    if (token > 10) token /= 2;
+    if (token >= 1 && token <= 5) { a[0] = token - 1; a[1] = 2; }
+    else if (token >= 6 && token <= 10) { a[0] = (token - 8 + BW_BLOCKS) % BW_BLOCKS; a[1] = 1; }
+    return;
+  }
+  if (token <= 0) return;
+  if (token <= 7) {
+    const int i = bw_first_uncoloured(o, token - 1);
+    if (i >= 0) { a[0] = i; a[1] = 2; return; }
+  }
+  if (token <= 14) {
+    const int i = bw_first_uncoloured(o, token - 8);
+    if (i >= 0) { a[0] = i; a[1] = 1; }
+  }
+}
+
 // ---- launchers (ph_block.hip) ----------------------------------------------------------------------------------------------------
+hipError_t launch_block_scripted_actions(int variant, int rule, const float* obs, const unsigned char* active, int* actions, int n,
+                                         hipStream_t s);
+// the scripted members' rows of a grouped forward: one lane per table, which reads its member from the device-side member table
+// (ph_pool.h; a scripted member's `rb_T` word holds its rule) and moves where the table is active and that member is scripted
+struct PoolMemberDev;
+hipError_t launch_block_group_scripted(int variant, const float* obs, const PoolMemberDev* members, const int* member_of,
+                                       const unsigned char* active, int* actions, int n, int K, hipStream_t s);
+hipError_t launch_block_xp_after_ego(const ph_block_xplay& s, unsigned long long counter, const unsigned long long* epoch, hipStream_t st);
+hipError_t launch_block_xp_after_alt(const ph_block_xplay& s, hipStream_t st);
 hipError_t launch_block_reset(int variant, int* state, const unsigned char* reset_mask, unsigned long long seed,
                               unsigned long long counter, const unsigned long long* epoch, int n, hipStream_t s);
 hipError_t launch_block_step(int variant, int* state, const int* actions, int is_ego, const unsigned char* active, float* obs_next,

@@ -1,8 +1,9 @@
-// The block worlds on the device (BlockEnv-v0 / BlockEnv-v1): the masked per-call kernels and the two book-keeping launches of
-// the vectorised self-play step.  One lane per table; the rules are ph_block.h's, the partner seat's ragged book-keeping is
+// The block worlds on the device (BlockEnv-v0 / BlockEnv-v1): the masked per-call kernels, the two book-keeping launches of
+// the vectorised self-play step, the scripted constructors and the two book-keeping launches of the cross-play step.  One lane per table; the rules are ph_block.h's, the partner seat's ragged book-keeping is
 // ph_liar.h's (liar_sp_credit / liar_sp_prepare / liar_sp_commit).
 #include "ph_block.h"
 #include "ph_liar.h"
+#include "ph_pool.h"
 
 namespace ph {
 
@@ -145,6 +146,109 @@ hipError_t launch_block_sp_after_ego(const ph_block_selfplay& s, float* ego_rew_
 }
 hipError_t launch_block_sp_after_alt(const ph_block_selfplay& s, hipStream_t st) {
   hipLaunchKernelGGL(block_sp_after_alt_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s);
+  return hipGetLastError();
+}
+
+// ---- the scripted constructors (ph_block.h: bw_scripted_move), one lane per table -------------------------------------------------
+__device__ __forceinline__ void bw_store_move(int variant, int* actions, int e, const int* a) {
+  const int A = bw_alt_act_len(variant);
+  actions[(size_t)e * A] = a[0];
+  actions[(size_t)e * A + 1] = a[1];
+  if (variant) actions[(size_t)e * A + 2] = a[2];
+}
+__global__ void block_scripted_actions_kernel(int variant, int rule, const float* __restrict__ obs,
+                                              const unsigned char* __restrict__ active, int* __restrict__ actions, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n || (active && !active[e])) return;
+  int a[3];
+  bw_scripted_move(variant, rule, obs + (size_t)e * bw_alt_obs_len(variant), a);
+  bw_store_move(variant, actions, e, a);
+}
+hipError_t launch_block_scripted_actions(int variant, int rule, const float* obs, const unsigned char* active, int* actions, int n,
+                                         hipStream_t s) {
+  hipLaunchKernelGGL(block_scripted_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, s, variant, rule, obs, active, actions, n);
+  return hipGetLastError();
+}
+// the scripted members' rows of a grouped forward: the member and its rule come from the member table in device memory
+__global__ void block_group_scripted_kernel(int variant, const float* __restrict__ obs, const PoolMemberDev* __restrict__ members,
+                                            const int* __restrict__ member_of, const unsigned char* __restrict__ active,
+                                            int* __restrict__ actions, int n, int K) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n || !active[e]) return;
+  const int k = member_of[e];
+  if (k < 0 || k >= K) return;
+  if (members[k].kind != PH_POOL_SCRIPTED) return;
+  int a[3];
+  bw_scripted_move(variant, members[k].rb_T, obs + (size_t)e * bw_alt_obs_len(variant), a);
+  bw_store_move(variant, actions, e, a);
+}
+hipError_t launch_block_group_scripted(int variant, const float* obs, const PoolMemberDev* members, const int* member_of,
+                                       const unsigned char* active, int* actions, int n, int K, hipStream_t s) {
+  hipLaunchKernelGGL(block_group_scripted_kernel, dim3((n + 255) / 256), dim3(256), 0, s, variant, obs, members, member_of, active,
+                     actions, n, K);
+  return hipGetLastError();
+}
+
+// ---- cross-play evaluation: grouped planner forward | after_ego | grouped constructor forward | after_alt ------------------------
+// after_ego of a playing table: the token is played and counted; the end token logs the game's return and length at [e, games[e]],
+// counts the game and either generates the next world (the step's counter) with its planner observation or -- budget spent --
+// retires the table (playing = running = 0, tables_left -= 1: it leaves every later launch, its state and logs stay as they are).
+// Where the game goes on the constructor's observation is written and the table is `running`.
+__global__ void block_xp_after_ego_kernel(ph_block_xplay s, uint64_t counter, const unsigned long long* __restrict__ epoch) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= s.n) return;
+  if (!s.playing[e]) return;
+  BwTable t;
+  bw_load(t, s.variant, s.state, e);
+  const BwOutcome o = bw_ego_step(t, s.variant, s.ego_actions[e]);
+  float ret = s.ep_return[e] + o.reward;
+  int len = s.ep_length[e] + 1;
+  bool running = !o.done;
+  if (o.done) {
+    const int G = s.episodes_per_table;
+    int g = s.games[e];
+    if (g >= 0 && g < G) {
+      s.returns[(size_t)e * G + g] = ret;
+      s.lengths[(size_t)e * G + g] = len;
+    }
+    g += 1;
+    s.games[e] = g;
+    ret = 0.f;
+    len = 0;
+    if (g >= G) {
+      s.playing[e] = 0;
+      atomicSub(s.tables_left, 1);
+    } else {
+      bw_reset(t, s.variant, s.world_seed, bw_counter(counter, epoch), (uint32_t)e, BW_MAX_DRAWS);
+      bw_write_ego_obs(t, s.variant, s.obs_ego + (size_t)e * bw_ego_obs_len(s.variant));
+    }
+  } else {
+    bw_write_alt_obs(t, s.variant, s.obs_alt + (size_t)e * bw_alt_obs_len(s.variant));
+  }
+  s.running[e] = running ? 1 : 0;
+  s.ep_return[e] = ret;
+  s.ep_length[e] = len;
+  bw_store(t, s.variant, s.state, e);
+}
+// after_alt: where the game goes on the constructor's move is played and the planner sees the result
+__global__ void block_xp_after_alt_kernel(ph_block_xplay s) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= s.n) return;
+  if (!s.running[e]) return;
+  BwTable t;
+  bw_load(t, s.variant, s.state, e);
+  const int A = bw_alt_act_len(s.variant);
+  int a[3] = {s.alt_actions[(size_t)e * A], s.alt_actions[(size_t)e * A + 1], s.variant ? s.alt_actions[(size_t)e * A + 2] : 0};
+  bw_alt_step(t, s.variant, a);
+  bw_store(t, s.variant, s.state, e);
+  bw_write_ego_obs(t, s.variant, s.obs_ego + (size_t)e * bw_ego_obs_len(s.variant));
+}
+hipError_t launch_block_xp_after_ego(const ph_block_xplay& s, unsigned long long counter, const unsigned long long* epoch, hipStream_t st) {
+  hipLaunchKernelGGL(block_xp_after_ego_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s, (uint64_t)counter, epoch);
+  return hipGetLastError();
+}
+hipError_t launch_block_xp_after_alt(const ph_block_xplay& s, hipStream_t st) {
+  hipLaunchKernelGGL(block_xp_after_alt_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s);
   return hipGetLastError();
 }
 

@@ -2125,6 +2125,62 @@ hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide,
   return hipSuccess;
 }
 
+// ---- the grouped forward for any categorical spec (the block worlds' cross-play: ph_block_group_forward) ---------------------------
+// One workgroup per tile of the bucket pass, the policy net only: a frozen member records nothing and nothing caches its value.  The
+// member's parameters and seed are uniform loads from the member table in DEVICE memory (ph_pool.h).  A tile runs the body that
+// launch_policy_fwd picks for the spec with gemm_mode 0, with the tile's tables as its rows, so table e's logits and its draw --
+// (member seed, counter, e) -- are ph_policy_forward's over all rows, bit for bit: group_fwd16h_kernel the 16-row one-hot body
+// (policy_fwd16h_body with MAP, as pool_fwd16h_kernel, whose text stays what it is), group_fwd32_kernel the general 32-row body, half
+// empty (policy_fwd_body<32, 32, false> with MAP, as pool_adap_kernel).  A scripted member's tile is nobody's here: its rows are
+// launch_block_group_scripted's (ph_block.hip).
+__global__ __launch_bounds__(256) void group_fwd16h_kernel(PoolFwd p) {
+  const int tile = blockIdx.x;
+  if (tile >= p.b.ntiles[0]) return;
+  const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1];
+  const int rows = p.b.tiles[3 * tile + 2] < POOL_TILE ? p.b.tiles[3 * tile + 2] : POOL_TILE;   // (device data: clamped once)
+  const PoolMemberDev& m = p.members[member];
+  if (m.kind != PH_POOL_FROZEN) return;
+  FwdArgs a = p.a;
+  a.params = m.params;
+  a.seed = m.seed;
+  policy_fwd16h_body<false, false, false, true>(a, 0, 0, 0, nullptr, 0, ResidentNet{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr,
+                                                p.b.order + first, rows);
+}
+// XStage whose rows come through the tile's map: policy_fwd_body has put the tables into rowphys, which is all XStage reads
+template <int R, int NT>
+struct MapXStage : XStage<R, NT> {
+  __device__ __forceinline__ void stage(const int*, int) {}
+};
+constexpr int GROUP32_ROWS = 32, GROUP32_NT = GROUP32_ROWS * 4;
+__global__ __launch_bounds__(GROUP32_NT) void group_fwd32_kernel(PoolFwd p) {
+  const int tile = blockIdx.x;
+  if (tile >= p.b.ntiles[0]) return;
+  const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1];
+  const int rows = p.b.tiles[3 * tile + 2] < POOL_TILE ? p.b.tiles[3 * tile + 2] : POOL_TILE;   // (device data: clamped once)
+  const PoolMemberDev& m = p.members[member];
+  if (m.kind != PH_POOL_FROZEN) return;
+  FwdArgs a = p.a;
+  a.params = m.params;
+  a.seed = m.seed;
+  policy_fwd_body<GROUP32_ROWS, 32, false, MapXStage<GROUP32_ROWS, GROUP32_NT>, true>(a, MapXStage<GROUP32_ROWS, GROUP32_NT>(),
+                                                                                      p.b.order + first, rows);
+}
+// what launch_policy_fwd would run on one of the two bodies above: categorical heads padded to 32 logits, n below the 64-row class,
+// not the 16-row dense class
+bool group_fwd_eligible(const NetDims& nd, int n) { return !nd.gauss && nd.Lp == 32 && n < 16384 && !fwd16_eligible(nd, n); }
+hipError_t launch_group_fwd(const PoolFwd& p, int K, hipStream_t s) {
+  if (!group_fwd_eligible(p.a.nd, p.a.n)) return hipErrorInvalidValue;
+  const dim3 grid(pool_max_tiles(p.a.n, K));
+  if (fwd16h_eligible(p.a.nd, p.a.n)) {
+    hipLaunchKernelGGL(group_fwd16h_kernel, grid, dim3(256), fwd16h_lds_bytes(), s, p);
+    return hipGetLastError();
+  }
+  const size_t lds = sizeof(float) * (size_t)fwd_lds_floats(GROUP32_ROWS, 32);
+  if (const hipError_t e = allow_dynamic_lds((const void*)group_fwd32_kernel, lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL(group_fwd32_kernel, grid, dim3(GROUP32_NT), lds, s, p);
+  return hipGetLastError();
+}
+
 template <int R, int LP, bool VALU>
 __global__ __launch_bounds__(R * 4) void policy_fwd_kernel(FwdArgs a) {
   policy_fwd_body<R, LP, VALU>(a);

@@ -155,6 +155,11 @@ hipError_t launch_pool_fwd(const PoolFwd& p, int K, hipStream_t s, bool no_wide 
 hipError_t launch_pool_tower(const PoolFwd& p, int K, size_t lds, hipStream_t s);
 bool pool_fwd_eligible(const NetDims& nd, int n);                     // ph_policy.hip
 bool pool_clone_eligible(const NetDims& nd, const ph_bc_layout& lay); // ph_policy.hip: the clone tile's shapes and LDS inside the grouped launch
+// ph_policy.hip: the grouped forward for any categorical spec of 32 padded logits (the block worlds' cross-play): the frozen members'
+// tiles, on the body launch_policy_fwd picks for the spec.  p.bc is not read; a scripted member's `rb_T` word holds its rule, for
+// launch_block_group_scripted (ph_block.h).
+bool group_fwd_eligible(const NetDims& nd, int n);
+hipError_t launch_group_fwd(const PoolFwd& p, int K, hipStream_t s);
 hipError_t launch_liar_default_actions(const float* obs, const unsigned char* active, int* actions, int n, hipStream_t s);
 
 }  // namespace ph

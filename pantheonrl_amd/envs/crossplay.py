@@ -6,6 +6,9 @@ for a whole population at once.
 `VecLiarDefaultPartner`)
 and plays a list of ordered pairs (i, j) -- member i at seat 0 (the ego), member j at seat 1 (the partner).  `crossplay_stats` is the
 host statement of the per-pair reduction `ph_xplay_stats` runs on the device.
+
+`VecBlockCrossPlay` is the same evaluation for the block worlds, whose seats have different spaces: a population of planners, a
+population of constructors (frozen policies and scripted constructors), a list of (planner, constructor) pairs.
 """
 from __future__ import annotations
 
@@ -254,3 +257,285 @@ class VecLiarCrossPlay(VecLiarStep):
         stats = self.compute_stats()
         return CrossPlayResult(self.M, self.pairs, self.pair_of_table, self.returns.cpu().numpy(), self.lengths.cpu().numpy(), stats,
                                self.steps_done)
+
+
+# ---- the block worlds: every planner with every constructor ----------------------------------------------------------------------
+BLOCK_STEPS_PER_GAME = 200     # default step cap per game of the budget: only the planner's last token ends a game, nothing bounds one
+
+
+def block_pairs(n_envs: int, n_planners: int, n_constructors: int, pairs: Optional[Sequence[Sequence[int]]]) -> np.ndarray:
+    """-> (P, 2) int32 of (planner, constructor).  None = all planner x constructor pairs, row major; more pairs than tables, an
+    empty list, or a member out of range is refused"""
+    for name, count in (("planners", n_planners), ("constructors", n_constructors)):
+        if not 1 <= int(count) <= nat.PH_MAX_POOL:
+            raise nat.NativeError(f"block cross-play: a seat holds 1..{nat.PH_MAX_POOL} {name}, not {count}")
+    every = [(i, j) for i in range(int(n_planners)) for j in range(int(n_constructors))]
+    arr = np.asarray(every if pairs is None else [tuple(p) for p in pairs], np.int64).reshape(-1, 2)
+    if len(arr) < 1:
+        raise nat.NativeError("block cross-play: the pair list is empty")
+    if len(arr) > int(n_envs):
+        raise nat.NativeError(f"block cross-play: {len(arr)} pairs need at least as many tables, not n_envs = {n_envs} (table e plays "
+                              "pairs[e % P])")
+    if arr.min() < 0 or arr[:, 0].max() >= int(n_planners) or arr[:, 1].max() >= int(n_constructors):
+        raise nat.NativeError(f"block cross-play: a pair names a member outside 0..{int(n_planners) - 1} x 0..{int(n_constructors) - 1}")
+    return arr.astype(np.int32)
+
+
+def check_block_member(member, variant: int, seat: int, who: str) -> None:
+    """a member of a block-world evaluation is a frozen 64-64 policy on that seat's spaces or -- at the constructor's seat -- a
+    scripted constructor of that variant; everything else is refused by name"""
+    from ..ppo import require_mlp_kernels
+    from ..vec import is_tower
+    from .vec import VecBlockScriptedPartner, VecBlockWorld
+    seat_name = ("planner", "constructor")[seat]
+    if isinstance(member, VecBlockScriptedPartner):
+        if seat == 0:
+            raise nat.NativeError(f"{who}: a scripted constructor does not sit at the planner's seat")
+        if member.variant != int(variant):
+            raise nat.NativeError(f"{who}: the scripted constructor is {VecBlockWorld.GAMES[member.variant]}'s, not "
+                                  f"{VecBlockWorld.GAMES[int(variant)]}'s")
+        return
+    if isinstance(member, VecLiarDefaultPartner):
+        raise nat.NativeError(f"{who}: VecLiarDefaultPartner is the Liar's Dice player; a block world's scripted constructor is "
+                              "VecBlockScriptedPartner(variant, rule)")
+    if isinstance(member, ClonedVecPartner):
+        raise nat.NativeError(f"{who}: a BC clone (ClonedVecPartner, FeedForward32Policy) does not sit in the block worlds' cross-play")
+    if isinstance(member, AdapFrozenVecPartner):
+        raise nat.NativeError(f"{who}: an ADAP checkpoint (AdapFrozenVecPartner) does not sit in the block worlds' cross-play")
+    if isinstance(member, TowerFrozenVecPartner) or (isinstance(member, FrozenVecPartner) and is_tower(member.policy)):
+        raise nat.NativeError(f"{who}: a net_arch tower (ArchActorCriticPolicy) does not sit in the block worlds' cross-play")
+    if not isinstance(member, FrozenVecPartner):
+        raise nat.NativeError(f"{who}: members are FrozenVecPartner / VecBlockScriptedPartner (learners train in VecBlockSelfPlay), "
+                              f"not {type(member).__name__}")
+    policy = member.policy
+    if policy.spec.act.kind == nat.PH_SPACE_BOX:
+        raise nat.NativeError(f"{who}: a policy with Box actions does not play a block world")
+    require_mlp_kernels(policy, who)
+    spaces = VecBlockWorld.seat_spaces(variant)[seat]
+    want = nat.layout_of(make_spec(spaces.observation_space, spaces.action_space))
+    lay = policy.layout
+    if (lay.D, lay.F, lay.A, lay.L) != (want.D, want.F, want.A, want.L):
+        raise nat.NativeError(f"{who}: the policy does not play on {VecBlockWorld.GAMES[int(variant)]}'s {seat_name} spaces")
+
+
+class BlockCrossPlayResult(CrossPlayResult):
+    """What `VecBlockCrossPlay.run` returns: CrossPlayResult with a planner x constructor matrix, the games each table logged and the
+    number of budgeted games that did not finish under the step cap."""
+
+    def __init__(self, n_planners, n_constructors, pairs, pair_of_table, returns, lengths, games, stats, steps):
+        super().__init__(n_planners, pairs, pair_of_table, returns, lengths, stats, steps)
+        self.n_planners, self.n_constructors = int(n_planners), int(n_constructors)
+        self.games = np.asarray(games)
+        self.unfinished = int(returns.shape[0] * returns.shape[1] - self.games.sum())
+
+    def matrix(self, name: str = "mean") -> np.ndarray:
+        """(planners, constructors): entry [i, j] = statistic `name` of the pair (planner i, constructor j); nan where the pair was
+        not played"""
+        out = np.full((self.n_planners, self.n_constructors), np.nan)
+        for (i, j), v in zip(self.pairs, getattr(self, name)):
+            out[i, j] = v
+        return out
+
+
+class VecBlockCrossPlay:
+    """tester.py:41-63 for a block world and two populations: n_envs tables of BlockEnv-v0 (variant 0) or BlockEnv-v1 (variant 1)
+    resident on the device, the planner's seat held by one of up to 8 frozen 64-64 policies (`FrozenVecPartner`), the constructor's
+    by one of up to 8 frozen policies or scripted constructors (`VecBlockScriptedPartner`).
+
+    * table e plays `pairs[e % P]` = (planner, constructor) for the whole evaluation; `pairs=None` is every planner x constructor
+      pair, row major; P > n_envs is refused;
+    * every table plays exactly `games` games and then goes idle: masked out of every launch, its state and logs frozen;
+    * one step c >= 1: the planners' forward (Philox counter 2c), the token; on the end token the game's return (f32 sum of ego
+      rewards) and length (planner tokens) are logged at [e, games[e]], the game counted, and the next world generated (world counter
+      c) or the table retired (`tables_left` -= 1); otherwise the constructors' forward (2c + 1) and their move.  The first worlds
+      use world counter 0.  A member draws under its own seed with row = table;
+    * a game ends only when the planner says its last token, so nothing bounds one: `run` stops at a step cap and reports the games
+      that did not finish; the statistics cover the logged games only.
+
+    native=True: one `ph_block_xplay_step` per step -- two bucket passes, two grouped forwards, two book-keeping launches and one more
+    when a constructor is scripted, whatever the number of members, no host synchronisation.  native=False: the readable walk --
+    `ph_policy_forward` per member over all rows, `ph_block_scripted_actions`, `ph_block_step` / `ph_block_reset` / `ph_block_obs`,
+    torch masks, the same counters; bitwise the native step."""
+
+    def __init__(self, variant: int, n_envs: int, planners, constructors, pairs=None, games: int = 1, seed: int = 0,
+                 native: bool = True):
+        from .vec import VecBlockScriptedPartner, VecBlockWorld
+        self.variant = int(variant)
+        if self.variant not in (0, 1):
+            raise nat.NativeError("VecBlockCrossPlay: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)")
+        self.planners, self.constructors = list(planners), list(constructors)
+        self.pairs = block_pairs(n_envs, len(self.planners), len(self.constructors), pairs)
+        if int(games) < 1:
+            raise nat.NativeError("VecBlockCrossPlay: games must be at least 1")
+        self.E, self.G, self.P, self.native = int(n_envs), int(games), len(self.pairs), bool(native)
+        self.seed = int(seed)
+        dev = None
+        for seat, members in enumerate((self.planners, self.constructors)):
+            for k, m in enumerate(members):
+                check_block_member(m, self.variant, seat, f"VecBlockCrossPlay: {('planner', 'constructor')[seat]} {k}")
+                if not isinstance(m, VecBlockScriptedPartner):
+                    dev = dev or m.policy.device
+        dev = dev or th.device("cuda", th.cuda.current_device())
+        self.dev = dev
+        self.ctx = nat.Context(dev.index or 0)
+        self.env = VecBlockWorld(self.variant, self.E, self.ctx, dev)
+        ego_spaces, alt_spaces = VecBlockWorld.seat_spaces(self.variant)
+        self.ego_spec = make_spec(ego_spaces.observation_space, ego_spaces.action_space)
+        self.alt_spec = make_spec(alt_spaces.observation_space, alt_spaces.action_space)
+        self.pair_of_table = pair_of_tables(self.E, self.P)
+        self._seat_members = [sorted(set(self.pairs[:, s].tolist())) for s in (0, 1)]
+        E, G = self.E, self.G
+        A = len(alt_spaces.action_space.nvec)
+        self.ego_id = th.as_tensor(self.pairs[self.pair_of_table, 0].copy()).to(dev)
+        self.alt_id = th.as_tensor(self.pairs[self.pair_of_table, 1].copy()).to(dev)
+        self.ego_actions = th.zeros(E, dtype=th.int32, device=dev)
+        self.alt_actions = th.zeros((E, A), dtype=th.int32, device=dev)
+        self.obs_ego = th.zeros((E, self.env.D_ego), dtype=th.float32, device=dev)
+        self.obs_alt = th.zeros((E, self.env.D_alt), dtype=th.float32, device=dev)
+        self.games = th.zeros(E, dtype=th.int32, device=dev)
+        self.playing = th.ones(E, dtype=th.uint8, device=dev)
+        self.running = th.zeros(E, dtype=th.uint8, device=dev)
+        self.tables_left = th.full((1,), E, dtype=th.int32, device=dev)
+        self.ep_return = th.zeros(E, dtype=th.float32, device=dev)
+        self.ep_length = th.zeros(E, dtype=th.int32, device=dev)
+        self.returns = th.zeros((E, G), dtype=th.float32, device=dev)
+        self.lengths = th.zeros((E, G), dtype=th.int32, device=dev)
+        self._stats = th.zeros((self.P, nat.XPLAY_NSTAT), dtype=th.float64, device=dev)
+        self.steps_done = 0
+        self._ctxs = [self.ctx] + [m.policy.ctx for m in self.planners + self.constructors if isinstance(m, FrozenVecPartner)]
+        self._bind()
+        if self.native:
+            self._build_native()
+            nat.check(self.ctx.lib.ph_block_xplay_step(self.ctx.handle, C.byref(self._desc), 0, 1))
+        else:
+            self.env.reset(self.seed, 0)
+            self.env.observe(True, self.obs_ego)
+
+    @property
+    def state(self) -> th.Tensor:
+        """(E, 12) int32 packed tables"""
+        return self.env.state
+
+    def _bind(self):
+        stream = th.cuda.current_stream(self.dev).cuda_stream
+        for ctx in self._ctxs:
+            ctx.set_stream(stream)
+
+    # -- the engine-side step ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _member_array(members):
+        arr = (nat.PhPoolMember * len(members))()
+        for c, m in zip(arr, members):
+            c.kind = m.kind
+            if m.kind == nat.PH_POOL_SCRIPTED:
+                c.seed = m.rule                   # (a scripted member's `seed` holds its rule)
+            else:
+                c.params, c.seed = m.policy.params.data_ptr(), m.policy._seed
+        return arr
+
+    def _build_native(self) -> None:
+        self._pairs_arr = (C.c_int * (2 * self.P))(*[int(v) for v in self.pairs.reshape(-1)])
+        self._planner_arr, self._constructor_arr = self._member_array(self.planners), self._member_array(self.constructors)
+        s = nat.PhBlockXplay()
+        s.n, s.variant = self.E, self.variant
+        s.ego_spec, s.alt_spec = C.pointer(self.ego_spec), C.pointer(self.alt_spec)
+        s.state, s.world_seed = self.env.state.data_ptr(), self.seed
+        s.planners, s.n_planners = self._planner_arr, len(self.planners)
+        s.constructors, s.n_constructors = self._constructor_arr, len(self.constructors)
+        s.pairs, s.n_pairs, s.episodes_per_table = self._pairs_arr, self.P, self.G
+        for name in ("ego_id", "alt_id", "ego_actions", "alt_actions", "obs_ego", "obs_alt", "games", "playing", "tables_left",
+                     "ep_return", "ep_length", "returns", "lengths", "running"):
+            setattr(s, name, getattr(self, name).data_ptr())
+        self._desc = s
+
+    # -- the walk: the per-call entry points with torch masks ------------------------------------------------------------------------
+    def _seat_act(self, seat: int, obs: th.Tensor, mask: th.Tensor, counter: int) -> None:
+        """the forward of every member that can sit at `seat` over all rows, Philox counter `counter`; member k's move lands in the
+        tables of `mask` it holds that seat of"""
+        from .vec import VecBlockScriptedPartner
+        members, ids, out = ((self.planners, self.ego_id, self.ego_actions) if seat == 0 else
+                             (self.constructors, self.alt_id, self.alt_actions))
+        for k in self._seat_members[seat]:
+            m = members[k]
+            mk = (mask.bool() & (ids == k)).to(th.uint8)
+            if isinstance(m, VecBlockScriptedPartner):
+                m.get_action(obs, mk, out, self.ctx)
+                continue
+            m.policy._counter = counter - 1
+            a = m.get_action(obs, mk)
+            if seat == 0:
+                out.copy_(th.where(mk.bool(), a[:, 0], out))
+            else:
+                out.copy_(th.where(mk.bool()[:, None], a, out))
+
+    def _walk(self, c: int) -> None:
+        env, G = self.env, self.G
+        playing = self.playing.clone()
+        pb = playing.bool()
+        self._seat_act(0, self.obs_ego, playing, 2 * c)
+        obs_alt, rew, done = env.player_step(self.ego_actions, True, playing)
+        d = done.bool() & pb                                       # (rows of idle tables are stale)
+        # the token counts; the end token logs the game, counts it, and spends the budget or starts the next world
+        self.ep_return.copy_(th.where(pb, self.ep_return + rew[:, 0], self.ep_return))
+        self.ep_length.add_(pb.to(th.int32))
+        slot = self.games.clamp(max=G - 1).long()[:, None]
+        self.returns.scatter_(1, slot, th.where(d, self.ep_return, self.returns.gather(1, slot)[:, 0])[:, None])
+        self.lengths.scatter_(1, slot, th.where(d, self.ep_length, self.lengths.gather(1, slot)[:, 0])[:, None])
+        self.games.add_(d.to(th.int32))
+        self.ep_return.copy_(th.where(d, th.zeros_like(self.ep_return), self.ep_return))
+        self.ep_length.copy_(th.where(d, th.zeros_like(self.ep_length), self.ep_length))
+        spent = d & (self.games >= G)
+        self.playing.copy_((pb & ~spent).to(th.uint8))
+        self.tables_left.sub_(spent.sum().to(th.int32))
+        again = (d & ~spent).to(th.uint8)
+        env.reset(self.seed, c, again)
+        env.observe(True, self.obs_ego, again)
+        # the constructor moves where the game goes on
+        rb = pb & ~d
+        running = rb.to(th.uint8)
+        self.running.copy_(th.where(pb, running, self.running))
+        self.obs_alt.copy_(th.where(rb[:, None], obs_alt, self.obs_alt))
+        self._seat_act(1, self.obs_alt, running, 2 * c + 1)
+        obs_ego, _, _ = env.player_step(self.alt_actions, False, running)
+        self.obs_ego.copy_(th.where(rb[:, None], obs_ego, self.obs_ego))
+
+    # -- one vectorised MultiAgentEnv.step of the playing tables -------------------------------------------------------------------
+    def step(self) -> None:
+        self.steps_done += 1
+        self._bind()
+        if self.native:
+            nat.check(self.ctx.lib.ph_block_xplay_step(self.ctx.handle, C.byref(self._desc), self.steps_done, 0))
+        else:
+            self._walk(self.steps_done)
+
+    def left(self) -> int:
+        """tables with budget left (synchronises)"""
+        return int(self.tables_left.item())
+
+    def compute_stats(self) -> np.ndarray:
+        """`ph_xplay_stats` over the logs so far -> (P, 4) float64: count, sum, sum of squares, sum of lengths"""
+        self._bind()
+        nat.check(self.ctx.lib.ph_xplay_stats(self.ctx.handle, self.returns.data_ptr(), self.lengths.data_ptr(), self.games.data_ptr(),
+                                              self.E, self.G, self.P, self._stats.data_ptr()))
+        return self._stats.cpu().numpy()
+
+    def result(self) -> BlockCrossPlayResult:
+        stats = self.compute_stats()
+        return BlockCrossPlayResult(len(self.planners), len(self.constructors), self.pairs, self.pair_of_table,
+                                    self.returns.cpu().numpy(), self.lengths.cpu().numpy(), self.games.cpu().numpy(), stats,
+                                    self.steps_done)
+
+    def stats(self) -> dict:
+        """per pair: count, mean, population standard deviation and mean length of the logged games; `unfinished`: budgeted games
+        that have not finished"""
+        res = self.result()
+        return dict(count=res.count, mean=res.mean, std=res.std, mean_length=res.mean_length, unfinished=res.unfinished)
+
+    def run(self, max_steps: Optional[int] = None, chunk: int = 8) -> BlockCrossPlayResult:
+        """play the budgets out, `chunk` steps at a time with nothing on the host in between, then one read of `tables_left`; stops
+        after `max_steps` steps in all (default 200 per game of the budget) and reports what did not finish"""
+        limit = BLOCK_STEPS_PER_GAME * self.G if max_steps is None else int(max_steps)
+        while self.steps_done < limit and self.left() > 0:
+            for _ in range(min(int(chunk), limit - self.steps_done)):
+                self.step()
+        return self.result()

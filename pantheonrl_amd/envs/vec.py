@@ -1429,6 +1429,37 @@ class VecBlockWorld:
         return out
 
 
+class VecBlockScriptedPartner:
+    """A scripted constructor for E tables, integer-exact (`ph_block_scripted_actions`): variant 1 with rule "DEFAULT" is
+    DefaultConstructorAgent, variant 0 with "DEFAULT" SBWDefaultAgent and with "EASY" SBWEasyPartner (envs/blockworld.py).  Where
+    SBWEasyPartner answers a negative block index the rule gives it modulo 5 -- the block the host game colours."""
+    kind = nat.PH_POOL_SCRIPTED
+
+    def __init__(self, variant: int, rule="DEFAULT"):
+        self.variant = int(variant)
+        if self.variant not in (0, 1):
+            raise nat.NativeError("VecBlockScriptedPartner: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)")
+        if isinstance(rule, str):
+            if rule not in nat.BLOCK_RULES:
+                raise nat.NativeError(f"VecBlockScriptedPartner: unknown rule {rule!r} (DEFAULT or EASY)")
+            rule = nat.BLOCK_RULES[rule]
+        self.rule = int(rule)
+        if self.rule not in (nat.PH_BLOCK_RULE_DEFAULT, nat.PH_BLOCK_RULE_EASY):
+            raise nat.NativeError(f"VecBlockScriptedPartner: unknown rule {rule!r} (DEFAULT or EASY)")
+        if self.rule == nat.PH_BLOCK_RULE_EASY and self.variant != 0:
+            raise nat.NativeError("VecBlockScriptedPartner: EASY (SBWEasyPartner) exists for BlockEnv-v0 only, not BlockEnv-v1")
+
+    def get_action(self, obs: th.Tensor, rec_mask: th.Tensor, out: th.Tensor, ctx: nat.Context) -> th.Tensor:
+        """writes the rule's move into `out` (E, 3 | 2) int32 where rec_mask is set (None: everywhere); the other rows keep what
+        they hold"""
+        nat.check(ctx.lib.ph_block_scripted_actions(ctx.handle, self.variant, self.rule, obs.data_ptr(), nat.ptr(rec_mask),
+                                                    out.data_ptr(), int(obs.shape[0])))
+        return out
+
+    def update(self, reward, done, mask=None) -> None:
+        return None
+
+
 class VecBlockSelfPlay:
     """`trainer.py BlockEnv-v0|v1 PPO PPO` with n_envs tables resident on the device.
 
