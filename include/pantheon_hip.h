@@ -45,7 +45,8 @@ extern "C" {
                                  still 7: + ph_block_reset / _step / _obs, ph_block_selfplay_step, ph_block_replay_host (additions only)
                                  still 7: + ph_bc_train_path (addition only)
                                  still 7: + ph_adap_rows, ph_adap_context_draw, ph_adap_vec_host, ph_liar_selfplay_step_adap (additions only)
-                                 still 7: + ph_block_scripted_actions / _host, ph_block_group_forward, ph_block_xplay_step (additions only) */
+                                 still 7: + ph_block_scripted_actions / _host, ph_block_group_forward, ph_block_xplay_step (additions only)
+                                 still 7: + ph_block_pool_forward, ph_block_pool_step (additions only) */
 #define PH_HIDDEN 64     /* SB3 MlpPolicy default net_arch pi=[64,64], vf=[64,64] (modular/policies.py:112-114) */
 #define PH_MAX_COMP 256  /* max MultiDiscrete components per space */
 #define PH_MAX_LOGITS 64 /* max total policy logits L */
@@ -881,6 +882,61 @@ typedef struct ph_block_xplay {
  * played -- every table gets its first world (world counter 0) and its planner observation; the caller has set games = 0,
  * playing = 1, tables_left = n and cleared ep_return / ep_length. */
 int ph_block_xplay_step(ph_ctx *ctx, const ph_block_xplay *xp, unsigned long long counter, int first);
+
+/* ---- the block worlds against a pool of constructors (additions, PH_ABI_VERSION unchanged): ph_block_selfplay with the partner
+ * block replaced by the pool, as ph_liar_pool is ph_liar_selfplay's.  Seat 1 of table e is held by member partnerid[e] of 1..PH_MAX_POOL
+ * members -- PH_POOL_LEARNER (its own (T, n) ragged buffer and per-table book, as the partner block of ph_block_selfplay), PH_POOL_FROZEN
+ * or PH_POOL_SCRIPTED (`seed` holds the PH_BLOCK_RULE_*) -- resampled where the table's game ends.
+ *
+ * The grouped constructor forward on its own: ph_block_group_forward's bucket pass and launches for a table that may hold learners.
+ * A learner (rb with E = n, pos, boundary, term, open, values, log_probs) records row e at pos[e] where active[e] != 0 and the column
+ * has room: episode_start_in[e] goes into the row, the value is cached for recorded rows only, pos is not advanced.  Row e of a learner
+ * is bitwise what ph_policy_forward_ragged(spec, member params, obs, seed, counter, ..., rb, pos, active, episode_start_in) leaves for
+ * that row -- action, cached value and log-prob, every recorded plane; a frozen member's row is ph_policy_forward's, a scripted
+ * member's ph_block_scripted_actions'.  When the table holds a learner ONE launch of grid (tiles, 2) runs the learners' and the frozen
+ * members' tiles; otherwise the launches are ph_block_group_forward's.  Learner tiles exist on the 16-row one-hot body only: a table
+ * with a learner whose spec is not in that class is refused before anything is launched, as are a PH_POOL_CLONE member and a learner
+ * without episode_start_in. */
+int ph_block_pool_forward(ph_ctx *ctx, const ph_spec *spec, const ph_pool_member *members, int n_members, const float *obs,
+                          const int *member_of, const unsigned char *active, unsigned long long counter, int *actions,
+                          const float *episode_start_in, int n);
+typedef struct ph_block_pool {
+  int n, variant;
+  const ph_spec *ego_spec, *alt_spec;        /* planner / constructor spaces of the variant */
+  int *state;                                /* (n, PH_BLOCK_STATE_WORDS) */
+  unsigned long long world_seed;
+  /* ego: rectangular rollout buffer */
+  const float *ego_params;
+  const ph_rollout *ego_rb;
+  int *ego_actions;                          /* (n) */
+  float *ego_values, *ego_log_probs;         /* (n) */
+  float *ego_episode_start;                  /* (n) in: flags of the previous step; out: this step's done */
+  unsigned long long ego_seed;
+  /* the pool at the constructor's seat */
+  const ph_pool_member *members;             /* host array [n_members] */
+  int n_members;
+  int *partnerid;                            /* (n) member of every table */
+  int resample;                              /* PH_POOL_ROBIN / PH_POOL_RANDOM */
+  unsigned long long pool_seed;
+  int *alt_actions;                          /* (n,3) | (n,2) shared by the members */
+  unsigned char *alt_acted;                  /* (n) the table's member has moved in the current game */
+  float *obs_ego, *obs_alt;                  /* planner / constructor observation of every table */
+  unsigned long long *episodes;              /* finished games */
+  /* scratch */
+  float *es_alt;                             /* (n) */
+  unsigned char *running, *can, *done;       /* (n); done = tables whose game ended in this step */
+} ph_block_pool;
+/* One vectorised step: the ego's forward, recorded at ego_pos -> after_ego (token played, the member that has acted in this game
+ * credited, ego reward / episode flag / episode count; a finished table: its next world, alt_acted cleared, partnerid resampled, the
+ * planner's observation; a running one: the constructor's observation and what its member's forward records) -> a bucket pass by
+ * partnerid over `running` -> the grouped forward -> the scripted members' rows, only when the table holds one -> after_alt (commit,
+ * the move, the planner's observation).  Five launches, six with a scripted member, whatever the number of members; no host
+ * synchronisation; capturable once it ran outside capture (the member table is uploaded only when it changed, never inside capture).
+ * RNG counters of step c: the ego's forward c, a member's forward c under its own seed, worlds c, the resample c (with the context's
+ * epoch word, as the worlds): ph_block_selfplay_step's, so a pool of one learner is that step bit for bit.  first != 0: nothing is
+ * played -- every table gets world counter 0, a resample under counter 0 (PH_POOL_ROBIN from 0: 1 % n_members) and its planner
+ * observation; the caller has zeroed partnerid. */
+int ph_block_pool_step(ph_ctx *ctx, const ph_block_pool *pool, int ego_pos, unsigned long long counter, int first);
 
 /* n_steps vectorised agent steps against a SCRIPTED environment -- observations, rewards and dones of every step already
  * resident on the device (the synthetic rollout driver of SURVEY.md 8d; a recorded trajectory being replayed) -- in ONE launch:

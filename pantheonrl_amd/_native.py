@@ -291,6 +291,20 @@ class PhBlockXplay(C.Structure):
                 ("running", C.c_void_p)]
 
 
+class PhBlockPool(C.Structure):
+    """ph_block_pool: ph_block_selfplay with the partner block replaced by a pool of constructors"""
+    _fields_ = [("n", C.c_int), ("variant", C.c_int), ("ego_spec", C.POINTER(PhSpec)), ("alt_spec", C.POINTER(PhSpec)),
+                ("state", C.c_void_p), ("world_seed", C.c_ulonglong),
+                ("ego_params", C.c_void_p), ("ego_rb", C.POINTER(PhRollout)), ("ego_actions", C.c_void_p),
+                ("ego_values", C.c_void_p), ("ego_log_probs", C.c_void_p), ("ego_episode_start", C.c_void_p),
+                ("ego_seed", C.c_ulonglong),
+                ("members", C.POINTER(PhPoolMember)), ("n_members", C.c_int), ("partnerid", C.c_void_p),
+                ("resample", C.c_int), ("pool_seed", C.c_ulonglong),
+                ("alt_actions", C.c_void_p), ("alt_acted", C.c_void_p),
+                ("obs_ego", C.c_void_p), ("obs_alt", C.c_void_p), ("episodes", C.c_void_p),
+                ("es_alt", C.c_void_p), ("running", C.c_void_p), ("can", C.c_void_p), ("done", C.c_void_p)]
+
+
 class PhLiarRecord(C.Structure):
     """ph_liar_record: the device-resident move log of the vectorised Liar's Dice step (rows [obs 30 | action 2 | flag])"""
     _fields_ = [("n", C.c_int), ("cap", C.c_int), ("rows", C.c_void_p), ("member", C.c_void_p),
@@ -380,6 +394,8 @@ SIGNATURES = {
     "ph_block_scripted_actions_host": [_i, _i, _vp, _vp, _i],
     "ph_block_group_forward": [_vp, C.POINTER(PhSpec), C.POINTER(PhPoolMember), _i, _vp, _vp, _vp, _ull, _vp, _i],
     "ph_block_xplay_step": [_vp, C.POINTER(PhBlockXplay), _ull, _i],
+    "ph_block_pool_forward": [_vp, C.POINTER(PhSpec), C.POINTER(PhPoolMember), _i, _vp, _vp, _vp, _ull, _vp, _vp, _i],
+    "ph_block_pool_step": [_vp, C.POINTER(PhBlockPool), _i, _ull, _i],
     "ph_framestack_push": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "ph_scripted_rollout": [_vp, C.POINTER(PhSpec), _vp, _vp, _vp, _vp, _i, _i, _vp, _ull, _ull, _vp, _vp, _vp,
                             C.POINTER(PhRollout), _i, _i],

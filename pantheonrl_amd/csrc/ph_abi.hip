@@ -201,6 +201,7 @@ struct ph_ctx {
   int group_count[2] = {0, 0};
   bool group_scripted[2] = {false, false};  // ... of which one is scripted (launch_block_group_scripted has rows to write)
   bool group_frozen[2] = {false, false};    // ... of which one is frozen (launch_group_fwd has a tile to run)
+  bool group_learner[2] = {false, false};   // ... of which one is a learner (launch_group_learn runs the tiles; the block pool only)
   long long* prof = nullptr;               // caller-owned debug stamp buffer
   double* ep_partial = nullptr;             // ph_episode_stats: [workgroups][PH_MAX_POOL][PH_EPISODE_NSTAT] partial sums of one scan
   size_t ep_partial_cap = 0;
@@ -2585,21 +2586,23 @@ int block_constructor_variant(const ph_layout& l) {
 }
 // validate the members of one seat and bring that seat's device-side table up to date (pool_members' manner: uploaded only when it
 // changed, never inside graph capture).  ctor_variant: the variant whose constructor the spec is, -1: scripted members are refused.
-int group_members(ph_ctx* ctx, const char* who, int table, int ctor_variant, const ph_pool_member* members, int K) {
+// learner_n: 0 -- an evaluation: learners are refused; n > 0 -- the block worlds' partner pool: a learner brings a buffer of E = n
+// and its per-table book (pool_members' checks).
+int group_members(ph_ctx* ctx, const char* who, int table, int ctor_variant, const ph_pool_member* members, int K, int learner_n = 0) {
   const std::string w(who);
   if (!members) return fail(w + ": null member array");
   if (K < 1 || K > PH_MAX_POOL) return fail(w + ": a seat holds 1..PH_MAX_POOL members");
   ph::PoolMemberDev tab[PH_MAX_POOL];
   const size_t used = sizeof(ph::PoolMemberDev) * (size_t)K;
   std::memset(tab, 0, used);
-  bool scripted = false, frozen = false;
+  bool scripted = false, frozen = false, learner = false;
   for (int k = 0; k < K; ++k) {
     const ph_pool_member& m = members[k];
     ph::PoolMemberDev& d = tab[k];
     const std::string wk = w + ": member " + std::to_string(k);
-    if (m.kind == PH_POOL_LEARNER) return fail(wk + " is a PH_POOL_LEARNER: an evaluation seats frozen and scripted members only");
+    if (m.kind == PH_POOL_LEARNER && !learner_n) return fail(wk + " is a PH_POOL_LEARNER: an evaluation seats frozen and scripted members only");
     if (m.kind == PH_POOL_CLONE) return fail(wk + " is a PH_POOL_CLONE: a BC clone does not sit in the block worlds' grouped forward");
-    if (m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED) return fail(wk + ": unknown kind");
+    if (m.kind != PH_POOL_FROZEN && m.kind != PH_POOL_SCRIPTED && m.kind != PH_POOL_LEARNER) return fail(wk + ": unknown kind");
     d.kind = d.fwd = m.kind;
     if (m.kind == PH_POOL_SCRIPTED) {
       if (ctor_variant < 0) return fail(wk + ": a scripted member needs a block-world constructor spec");
@@ -2612,7 +2615,29 @@ int group_members(ph_ctx* ctx, const char* who, int table, int ctor_variant, con
     if ((uintptr_t)m.params % 16 != 0) return fail(wk + ": params must be 16-byte aligned");
     d.params = m.params;
     d.seed = m.seed;
-    frozen = true;
+    if (m.kind == PH_POOL_FROZEN) {
+      frozen = true;
+      continue;
+    }
+    if (!m.rb) return fail(wk + ": a learner needs its rollout buffer");
+    if (check_rb(m.rb)) return 1;
+    if (m.rb->E != learner_n) return fail(wk + ": the learner's buffer must have E = n");
+    if (!m.pos || !m.boundary || !m.term || !m.open || !m.values || !m.log_probs)
+      return fail(wk + ": a learner needs pos / boundary / term / open / values / log_probs");
+    d.values = m.values;
+    d.log_probs = m.log_probs;
+    d.rb_T = m.rb->T;
+    d.rb_obs = m.rb->observations;
+    d.rb_act = m.rb->actions;
+    d.rb_rew = m.rb->rewards;
+    d.rb_es = m.rb->episode_starts;
+    d.rb_val = m.rb->values;
+    d.rb_logp = m.rb->log_probs;
+    d.pos = m.pos;
+    d.boundary = m.boundary;
+    d.term = m.term;
+    d.open = m.open;
+    learner = true;
   }
   if (ctx->group_count[table] != K || std::memcmp(ctx->group_host[table], tab, used) != 0) {
     if (ctx->capturing) return fail(w + ": the member table changed inside graph capture: run the same call once outside capture first");
@@ -2625,6 +2650,7 @@ int group_members(ph_ctx* ctx, const char* who, int table, int ctor_variant, con
     ctx->group_count[table] = K;
     ctx->group_scripted[table] = scripted;
     ctx->group_frozen[table] = frozen;
+    ctx->group_learner[table] = learner;
   }
   return 0;
 }
@@ -2635,16 +2661,26 @@ int group_table_of(const ph_spec* spec, int* ctor_variant) {
   *ctor_variant = block_constructor_variant(lay);
   return *ctor_variant >= 0 ? 1 : 0;
 }
-// bucket pass + the frozen members' tiles + the scripted members' rows over the tables with active[e] != 0
+// bucket pass + the frozen members' tiles + the scripted members' rows over the tables with active[e] != 0.  A table that holds a
+// learner (the partner pool): its learners' and frozen members' tiles in launch_group_learn's ONE launch instead, the learners' rows
+// recorded where rec_mask[e] != 0 with es_in[e].
 int group_forward(ph_ctx* ctx, const char* who, int table, int ctor_variant, const ph_spec* spec, int K, const float* obs,
-                  const int* member_of, const unsigned char* active, unsigned long long counter, int* actions, int n) {
+                  const int* member_of, const unsigned char* active, unsigned long long counter, int* actions, int n,
+                  const unsigned char* rec_mask = nullptr, const float* es_in = nullptr) {
   ph::PoolFwd p;
   std::memset(&p, 0, sizeof(p));
   if (fwd_args(p.a, ctx, spec, false, nullptr, obs, n, 0, counter, actions, nullptr, nullptr)) return 1;
   if (!ph::group_fwd_eligible(p.a.nd, n))
     return fail_who(who, ": the spec is not in the grouped forward's class (categorical heads of at most 32 logits, n < 16384, not the "
                          "16-row dense class of one Discrete head of <= 8 logits over one feature chunk)");
-  if (ctx->group_frozen[table]) {
+  const bool learner = ctx->group_learner[table];
+  if (learner && !ph::group_learn_eligible(p.a.nd, n))
+    return fail_who(who, ": the member table holds a PH_POOL_LEARNER, whose tiles exist on the 16-row one-hot forward only (one-hot "
+                         "observations of at most 64 components, PH_FWD16H not 0): the spec is not in that class");
+  if (learner && (!rec_mask || !es_in)) return fail_who(who, ": learners need a record mask and episode_start_in");
+  p.a.rec_mask = learner ? rec_mask : nullptr;
+  p.a.es_in = learner ? es_in : nullptr;
+  if (ctx->group_frozen[table] || learner) {
     if (ensure(ctx, ctx->pool_order, ctx->pool_order_cap, (size_t)n)) return 1;
     const size_t ntile = (size_t)ph::pool_max_tiles(n, PH_MAX_POOL);
     if (ensure(ctx, ctx->pool_tiles, ctx->pool_tiles_cap, 3 * (ntile + 1))) return 1;
@@ -2653,7 +2689,7 @@ int group_forward(ph_ctx* ctx, const char* who, int table, int ctor_variant, con
     p.b.tiles = ctx->pool_tiles;
     p.b.ntiles = ctx->pool_tiles + 3 * ntile;
     PH_HIP(ph::launch_pool_bucket(member_of, active, n, K, p.b, ctx->stream));
-    PH_HIP(ph::launch_group_fwd(p, K, ctx->stream));
+    PH_HIP(learner ? ph::launch_group_learn(p, K, ctx->stream) : ph::launch_group_fwd(p, K, ctx->stream));
   }
   if (ctx->group_scripted[table])
     PH_HIP(ph::launch_block_group_scripted(ctor_variant, obs, ctx->group_dev[table], member_of, active, actions, n, K, ctx->stream));
@@ -2735,6 +2771,73 @@ int ph_block_xplay_step(ph_ctx* ctx, const ph_block_xplay* xp, unsigned long lon
                     s.n))
     return 1;
   PH_HIP(ph::launch_block_xp_after_alt(s, ctx->stream));
+  return 0;
+}
+
+// ---- the block worlds against a pool of constructors: the grouped forward with learners, the step ----
+int ph_block_pool_forward(ph_ctx* ctx, const ph_spec* spec, const ph_pool_member* members, int n_members, const float* obs,
+                          const int* member_of, const unsigned char* active, unsigned long long counter, int* actions,
+                          const float* episode_start_in, int n) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_block_pool_forward";
+  if (!ctx) return fail("null ctx");
+  if (!spec || !obs || !member_of || !active || !actions) return fail_who(who, ": null argument");
+  if (n <= 0) return fail_who(who, ": n must be positive");
+  int ctor_variant = -1;
+  const int table = group_table_of(spec, &ctor_variant);
+  if (table < 0) return 1;
+  if (members && n_members >= 1 && n_members <= PH_MAX_POOL)
+    for (int k = 0; k < n_members; ++k)
+      if (members[k].kind == PH_POOL_LEARNER && !episode_start_in) return fail_who(who, ": learners need episode_start_in");
+  if (group_members(ctx, who, table, ctor_variant, members, n_members, n)) return 1;
+  return group_forward(ctx, who, table, ctor_variant, spec, n_members, obs, member_of, active, counter, actions, n, active,
+                       episode_start_in);
+}
+
+int ph_block_pool_step(ph_ctx* ctx, const ph_block_pool* pool, int ego_pos, unsigned long long counter, int first) {
+  DevGuard dev_guard(ctx);
+  const char* who = "ph_block_pool_step";
+  if (!ctx || !pool) return fail_who(who, ": null argument");
+  const ph_block_pool& s = *pool;
+  if (s.variant != 0 && s.variant != 1) return fail_who(who, ": variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)");
+  if (s.n <= 0) return fail_who(who, ": n must be positive");
+  if (!s.ego_spec || !s.alt_spec || !s.state || !s.ego_params || !s.ego_rb || !s.ego_actions || !s.ego_episode_start || !s.partnerid ||
+      !s.alt_actions || !s.alt_acted || !s.obs_ego || !s.obs_alt || !s.episodes || !s.es_alt || !s.running || !s.can || !s.done)
+    return fail_who(who, ": incomplete description");
+  if (s.resample != PH_POOL_ROBIN && s.resample != PH_POOL_RANDOM) return fail_who(who, ": unknown resample rule");
+  if (check_rb(s.ego_rb)) return 1;
+  if (s.ego_rb->E != s.n) return fail_who(who, ": buffers must have E = n");
+  if ((uintptr_t)s.state % 16) return fail_who(who, ": state must be 16-byte aligned");
+  if ((uintptr_t)s.ego_params % 16) return fail_who(who, ": params must be 16-byte aligned");
+  if (!first && (ego_pos < 0 || ego_pos >= s.ego_rb->T)) return fail_who(who, ": ego_pos out of range (buffer full?)");
+  // the specs must be the variant's: the book-keeping kernels write rows of these lengths
+  ph_layout le, la;
+  if (ph_layout_of(s.ego_spec, &le) || ph_layout_of(s.alt_spec, &la)) return 1;
+  if (le.D != ph::bw_ego_obs_len(s.variant) || le.A != 1 || le.L != ph::bw_tokens(s.variant) || block_constructor_variant(la) != s.variant)
+    return fail_who(who, ": the specs are not the variant's planner / constructor spaces");
+  if (group_members(ctx, "ph_block_pool_step", 1, s.variant, s.members, s.n_members, s.n)) return 1;
+  {   // what the grouped forward would refuse, in front of the first launch
+    ph::NetDims nd;
+    if (resolve(ctx, s.alt_spec, &nd)) return 1;
+    if (!ph::group_fwd_eligible(nd, s.n) || (ctx->group_learner[1] && !ph::group_learn_eligible(nd, s.n)))
+      return fail_who(who, ": the constructor spec is not in the grouped forward's class -- a PH_POOL_LEARNER's tiles exist on the 16-row "
+                           "one-hot forward only (PH_FWD16H not 0)");
+  }
+  const ph::PoolBook book{s.n, s.n_members, s.resample, s.pool_seed, ctx->group_dev[1], s.partnerid, s.alt_acted, s.can, s.es_alt};
+  if (first) {
+    PH_HIP(ph::launch_block_pool_after_ego(s, book, nullptr, 0ull, ctx->rng_epoch, 1, ctx->stream));
+    return 0;
+  }
+  // the planner moves in every table
+  if (seat_forward(ctx, s.ego_spec, nullptr, s.ego_params, s.obs_ego, s.n, s.ego_seed, counter, s.ego_actions, s.ego_values,
+                   s.ego_log_probs, s.ego_rb, ego_pos, s.ego_episode_start))
+    return 1;
+  PH_HIP(ph::launch_block_pool_after_ego(s, book, s.ego_rb->rewards + (size_t)ego_pos * s.n, counter, ctx->rng_epoch, 0, ctx->stream));
+  // every running table's member replies: one bucket pass, one grouped launch, the scripted rows
+  if (group_forward(ctx, who, 1, s.variant, s.alt_spec, s.n_members, s.obs_alt, s.partnerid, s.running, counter, s.alt_actions, s.n, s.can,
+                    s.es_alt))
+    return 1;
+  PH_HIP(ph::launch_block_pool_after_alt(s, book, ctx->stream));
   return 0;
 }
 

@@ -311,6 +311,11 @@ hipError_t launch_block_group_scripted(int variant, const float* obs, const Pool
                                        const unsigned char* active, int* actions, int n, int K, hipStream_t s);
 hipError_t launch_block_xp_after_ego(const ph_block_xplay& s, unsigned long long counter, const unsigned long long* epoch, hipStream_t st);
 hipError_t launch_block_xp_after_alt(const ph_block_xplay& s, hipStream_t st);
+// the partner-pool step's two book-keeping launches (ph_pool.h: PoolBook is seat 1's book; first: the constructor's call, no token)
+struct PoolBook;
+hipError_t launch_block_pool_after_ego(const ph_block_pool& s, const PoolBook& book, float* ego_rew_row, unsigned long long counter,
+                                       const unsigned long long* epoch, int first, hipStream_t st);
+hipError_t launch_block_pool_after_alt(const ph_block_pool& s, const PoolBook& book, hipStream_t st);
 hipError_t launch_block_reset(int variant, int* state, const unsigned char* reset_mask, unsigned long long seed,
                               unsigned long long counter, const unsigned long long* epoch, int n, hipStream_t s);
 hipError_t launch_block_step(int variant, int* state, const int* actions, int is_ego, const unsigned char* active, float* obs_next,

@@ -1,5 +1,5 @@
 // The block worlds on the device (BlockEnv-v0 / BlockEnv-v1): the masked per-call kernels, the two book-keeping launches of
-// the vectorised self-play step, the scripted constructors and the two book-keeping launches of the cross-play step.  One lane per table; the rules are ph_block.h's, the partner seat's ragged book-keeping is
+// the vectorised self-play step, the scripted constructors and the two book-keeping launches of the cross-play step and of the partner-pool step.  One lane per table; the rules are ph_block.h's, the partner seat's ragged book-keeping is
 // ph_liar.h's (liar_sp_credit / liar_sp_prepare / liar_sp_commit).
 #include "ph_block.h"
 #include "ph_liar.h"
@@ -249,6 +249,73 @@ hipError_t launch_block_xp_after_ego(const ph_block_xplay& s, unsigned long long
 }
 hipError_t launch_block_xp_after_alt(const ph_block_xplay& s, hipStream_t st) {
   hipLaunchKernelGGL(block_xp_after_alt_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s);
+  return hipGetLastError();
+}
+
+// ---- the partner pool: ego forward | after_ego | bucket pass + grouped constructor forward (+ scripted rows) | after_alt ---------
+// The self-play kernels' lane logic with PoolBook (ph_pool.h) in place of the single learner's seat: the member that holds the
+// constructor's seat of table e is partnerid[e], resampled where the table's game ends -- under the counter of the table's next
+// world, epoch word included, so that ph_episode_stats replays it.  One lane per table; a pass loads each flag once at its top
+// (ph_liar_step.h) -- the book's cursor behind a deal is the NEW member's, a second load by necessity.
+//
+// after_ego: the token is played, the member that has acted in this game is credited, the ego's reward row / episode flag / the
+// episode count follow; a finished table gets its next world, PoolBook::on_deal (alt_acted cleared, the next member bound) and its
+// planner observation, a running one the constructor's observation.  prepare states what the seat's forward records: nothing in a
+// finished table.  first != 0 (the constructor's call): nothing is played -- world counter 0, a resample under counter 0, the
+// planner's observation.
+__global__ void block_pool_after_ego_kernel(ph_block_pool s, PoolBook book, float* ego_rew_row, uint64_t counter,
+                                            const unsigned long long* __restrict__ epoch, int first) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= s.n) return;
+  PoolBook::Lane b = book.load(e);
+  BwTable t;
+  bool done = true;
+  if (!first) {
+    bw_load(t, s.variant, s.state, e);
+    const BwOutcome o = bw_ego_step(t, s.variant, s.ego_actions[e]);
+    done = o.done;
+    book.credit(b, e, o.reward, o.done, book.acted(b));
+    liar_add_f32(ego_rew_row + e, o.reward);
+    s.ego_episode_start[e] = o.done ? 1.f : 0.f;
+    if (o.done) atomicAdd(s.episodes, 1ull);
+  }
+  s.done[e] = (done && !first) ? 1 : 0;
+  s.running[e] = done ? 0 : 1;
+  if (done) {
+    const uint64_t c = bw_counter(first ? 0ull : counter, epoch);
+    bw_reset(t, s.variant, s.world_seed, c, (uint32_t)e, BW_MAX_DRAWS);
+    book.on_deal(b, e, c);
+    bw_write_ego_obs(t, s.variant, s.obs_ego + (size_t)e * bw_ego_obs_len(s.variant));
+  } else {
+    bw_write_alt_obs(t, s.variant, s.obs_alt + (size_t)e * bw_alt_obs_len(s.variant));
+  }
+  bw_store(t, s.variant, s.state, e);
+  book.prepare(b, e, !done);
+}
+// after_alt: where the game goes on the member's forward is committed (a non-learner only marks alt_acted), its move is played and
+// the planner sees the result
+__global__ void block_pool_after_alt_kernel(ph_block_pool s, PoolBook book) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= s.n) return;
+  if (!s.running[e]) return;
+  PoolBook::Lane b = book.load(e);
+  BwTable t;
+  bw_load(t, s.variant, s.state, e);
+  book.commit(b, e);
+  const int A = bw_alt_act_len(s.variant);
+  int a[3] = {s.alt_actions[(size_t)e * A], s.alt_actions[(size_t)e * A + 1], s.variant ? s.alt_actions[(size_t)e * A + 2] : 0};
+  bw_alt_step(t, s.variant, a);
+  bw_store(t, s.variant, s.state, e);
+  bw_write_ego_obs(t, s.variant, s.obs_ego + (size_t)e * bw_ego_obs_len(s.variant));
+}
+hipError_t launch_block_pool_after_ego(const ph_block_pool& s, const PoolBook& book, float* ego_rew_row, unsigned long long counter,
+                                       const unsigned long long* epoch, int first, hipStream_t st) {
+  hipLaunchKernelGGL(block_pool_after_ego_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s, book, ego_rew_row, (uint64_t)counter,
+                     epoch, first);
+  return hipGetLastError();
+}
+hipError_t launch_block_pool_after_alt(const ph_block_pool& s, const PoolBook& book, hipStream_t st) {
+  hipLaunchKernelGGL(block_pool_after_alt_kernel, dim3((s.n + 255) / 256), dim3(256), 0, st, s, book);
   return hipGetLastError();
 }
 

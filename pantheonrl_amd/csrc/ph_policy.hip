@@ -2181,6 +2181,66 @@ hipError_t launch_group_fwd(const PoolFwd& p, int K, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- the grouped constructor forward of a table that holds a learner (the block worlds' partner pool: ph_block_pool_forward) -----
+// One workgroup per (tile of the bucket pass, net), pool_fwd16h_kernel's grid: y = 0 the policy net, y = 1 the value net.  The tile's
+// member comes from the member table in DEVICE memory; a learner's parameters, seed, caches and ragged-buffer bases are patched into
+// the workgroup's copy of the launch record, and the 16-row one-hot body records table e at pos[e] where rec_mask[e] is set and the
+// column has room (es_in[e] goes into the row, the value is cached for recorded rows only): row e is ph_policy_forward_ragged's, bit
+// for bit.  A frozen member's tile is group_fwd16h_kernel's -- actions only, its value workgroup returns -- so a table with a learner
+// needs this launch alone; a table without one keeps group_fwd16h_kernel, whose text and registers stay what they are.  A scripted
+// member's tile is nobody's here (launch_block_group_scripted).
+__global__ __launch_bounds__(256) void group_learn16h_kernel(PoolFwd p) {
+  const int tile = blockIdx.x;
+  if (tile >= p.b.ntiles[0]) return;
+  const int member = p.b.tiles[3 * tile], first = p.b.tiles[3 * tile + 1];
+  const int rows = p.b.tiles[3 * tile + 2] < POOL_TILE ? p.b.tiles[3 * tile + 2] : POOL_TILE;   // (device data: clamped once)
+  const PoolMemberDev& m = p.members[member];
+  const int kind = m.kind;
+  if (kind != PH_POOL_LEARNER && kind != PH_POOL_FROZEN) return;
+  const bool learner = kind == PH_POOL_LEARNER;
+  FwdArgs a = p.a;
+  a.params = m.params;
+  a.seed = m.seed;
+  if (learner) {
+    a.pos_env = m.pos;
+    a.rb_T = m.rb_T;
+  } else {
+    a.pos_env = nullptr;
+    a.rec_mask = nullptr;
+    a.es_in = nullptr;
+  }
+  const int* map = p.b.order + first;
+  const ResidentNet none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  // A workgroup patches in what ITS net writes and calls the body from its own branch: the policy net the action planes and the
+  // log-prob cache, the value net the value, reward, episode-start and observation planes and the value cache.  The other net's
+  // fields stay the shared record's nulls, which the body never reads on this side.  (Patched in all at once, the twelve pointers
+  // loaded from the member table are live across the whole body in both nets, and the kernel then holds sixteen scalar registers
+  // in the lanes of a vector register: tests/test_block_pool_resources.py.)
+  if (blockIdx.y == 0) {
+    if (learner) {
+      a.logp = m.log_probs;
+      a.rb_act = m.rb_act;
+      a.rb_logp = m.rb_logp;
+    }
+    policy_fwd16h_body<false, false, false, true>(a, 0, 0, 0, nullptr, 0, none, nullptr, map, rows);
+  } else {
+    if (!learner) return;
+    a.values = m.values;
+    a.rb_obs = m.rb_obs;
+    a.rb_rew = m.rb_rew;
+    a.rb_es = m.rb_es;
+    a.rb_val = m.rb_val;
+    policy_fwd16h_body<false, false, false, true>(a, 0, 0, 0, nullptr, 0, none, nullptr, map, rows);
+  }
+}
+// learner tiles exist on the 16-row one-hot body only (both constructor specs are in its class: D = 21 and D = 50, 32 padded logits)
+bool group_learn_eligible(const NetDims& nd, int n) { return group_fwd_eligible(nd, n) && fwd16h_eligible(nd, n); }
+hipError_t launch_group_learn(const PoolFwd& p, int K, hipStream_t s) {
+  if (!group_learn_eligible(p.a.nd, p.a.n)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(group_learn16h_kernel, dim3(pool_max_tiles(p.a.n, K), 2), dim3(256), fwd16h_lds_bytes(), s, p);
+  return hipGetLastError();
+}
+
 template <int R, int LP, bool VALU>
 __global__ __launch_bounds__(R * 4) void policy_fwd_kernel(FwdArgs a) {
   policy_fwd_body<R, LP, VALU>(a);

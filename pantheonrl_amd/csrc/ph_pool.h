@@ -160,6 +160,11 @@ bool pool_clone_eligible(const NetDims& nd, const ph_bc_layout& lay); // ph_poli
 // launch_block_group_scripted (ph_block.h).
 bool group_fwd_eligible(const NetDims& nd, int n);
 hipError_t launch_group_fwd(const PoolFwd& p, int K, hipStream_t s);
+// ph_policy.hip: the same launch for a constructor table that holds a learner (the block worlds' partner pool): grid (tiles, 2), the
+// learners' tiles recorded through p.a.rec_mask / p.a.es_in into their ragged buffers, the frozen members' tiles as above.  On the
+// 16-row one-hot body only.
+bool group_learn_eligible(const NetDims& nd, int n);
+hipError_t launch_group_learn(const PoolFwd& p, int K, hipStream_t s);
 hipError_t launch_liar_default_actions(const float* obs, const unsigned char* active, int* actions, int n, hipStream_t s);
 
 }  // namespace ph

@@ -1583,3 +1583,278 @@ class VecBlockSelfPlay:
         self.ego.learn_from_buffer()
         if self.alt.full():
             self.alt.learn_from_buffer()
+
+
+def check_block_pool_seat(agent, variant: int, seat: int, who: str) -> None:
+    """the ego (seat 0: a VecOnPolicyAgent on the planner spaces) or a member (seat 1: RaggedVecOnPolicyAgent, FrozenVecPartner or
+    VecBlockScriptedPartner on the constructor spaces) of the block worlds' partner pool runs on the pool step's kernels: the 64-64
+    MlpPolicy on the variant's spaces, or the variant's scripted rule.  Everything else is refused by name, before a device is
+    touched."""
+    from ..adap import AdapPolicy
+    from ..spaces import make_spec
+    game = VecBlockWorld.GAMES[int(variant)]
+    if isinstance(agent, VecBlockScriptedPartner):
+        if seat == 0:
+            raise nat.NativeError(f"{who}: a scripted constructor does not sit at the planner's seat")
+        if agent.variant != int(variant):
+            raise nat.NativeError(f"{who}: the scripted constructor is {VecBlockWorld.GAMES[agent.variant]}'s, not {game}'s")
+        return
+    if isinstance(agent, VecLiarDefaultPartner):
+        raise nat.NativeError(f"{who}: VecLiarDefaultPartner is the Liar's Dice player; a block world's scripted constructor is "
+                              "VecBlockScriptedPartner(variant, rule)")
+    if isinstance(agent, ClonedVecPartner):
+        raise nat.NativeError(f"{who}: a BC clone (ClonedVecPartner, FeedForward32Policy) does not sit in the block worlds' partner pool")
+    if isinstance(agent, (AdapFrozenVecPartner, AdapSeat)):
+        raise nat.NativeError(f"{who}: ADAP (a learner, an ego or an AdapFrozenVecPartner checkpoint) does not sit in the block worlds' "
+                              "partner pool")
+    if seat == 0:
+        if not isinstance(agent, VecOnPolicyAgent):
+            raise nat.NativeError(f"{who}: the ego is a VecOnPolicyAgent on {game}'s planner spaces, not {type(agent).__name__}")
+        policy = agent.model.policy
+    elif isinstance(agent, RaggedVecOnPolicyAgent):
+        policy = agent.model.policy
+    elif isinstance(agent, FrozenVecPartner):
+        policy = agent.policy
+    else:
+        raise nat.NativeError(f"{who}: members are RaggedVecOnPolicyAgent (a learner), FrozenVecPartner or VecBlockScriptedPartner, "
+                              f"not {type(agent).__name__}")
+    if isinstance(policy, AdapPolicy) or is_adap(policy):
+        raise nat.NativeError(f"{who}: ADAP (an AdapPolicy) does not sit in the block worlds' partner pool")
+    if is_tower(policy):
+        raise nat.NativeError(f"{who}: a net_arch tower (ArchActorCriticPolicy) does not sit in the block worlds' partner pool")
+    if isinstance(policy, FeedForward32Policy):
+        raise nat.NativeError(f"{who}: a FeedForward32Policy (a BC clone) does not sit in the block worlds' partner pool")
+    if policy.spec.act.kind == nat.PH_SPACE_BOX:
+        raise nat.NativeError(f"{who}: a policy with Box actions does not play a block world")
+    require_mlp_kernels(policy, who)
+    spaces = VecBlockWorld.seat_spaces(variant)[seat]
+    want = nat.layout_of(make_spec(spaces.observation_space, spaces.action_space))
+    lay = policy.layout
+    if (lay.D, lay.F, lay.A, lay.L) != (want.D, want.F, want.A, want.L):
+        raise nat.NativeError(f"{who}: the policy does not play on {game}'s {('planner', 'constructor')[seat]} spaces")
+
+
+class VecBlockPartnerPool:
+    """`trainer.py BlockEnv-v0|v1 PPO <alt>+ --partner-pool --n-envs E`: n_envs block-world tables resident on the device, the
+    constructor's seat of every table held by one of K <= 8 pool members -- learners (RaggedVecOnPolicyAgent), frozen policies
+    (FrozenVecPartner) or scripted constructors (VecBlockScriptedPartner).  `partnerid[e]` names table e's member; it is resampled
+    where the table's game ends (`pool_resample`), the first world included: under "robin" every table starts at 1 % K.
+
+    Per table the callbacks are VecBlockSelfPlay's, with every partner-side mask ANDed with `partnerid == k`: credit goes to the
+    member that has acted in this game (`alt_acted`, cleared with the next world), and a member's `boundary` flag of a table
+    survives the games it sits out.  RNG counters of step c: the ego's forward c, a member's forward c under its own seed, the
+    worlds of the games that start in it c, the resample c (the first worlds and the first resample: 0) -- VecBlockSelfPlay's, so
+    a pool of one learner is that class bit for bit.  `rollout_and_learn` trains the ego, then every learner whose `full()`
+    holds; a learner's `min_full` becomes max(1, E // K) unless the caller lowered it already.  It carries what EpisodeStats
+    reads of a pool (`partnerid`, `K`, `resample`, `pool_seed`, `row0_counter`, `steps_done`).
+
+    native=True: one `ph_block_pool_step` per vectorised step -- five launches, six with a scripted member, whatever K is, no
+    host synchronisation.  native=False: the readable walk -- K per-member get_action / update calls with torch masks, the
+    per-call entry points only, the same counters; bitwise the native step."""
+
+    def __init__(self, variant: int, n_envs: int, ego: VecOnPolicyAgent, members, seed: int = 0, resample: str = "robin",
+                 native: bool = True):
+        self.variant = int(variant)
+        if self.variant not in (0, 1):
+            raise nat.NativeError("VecBlockPartnerPool: variant must be 0 (BlockEnv-v0) or 1 (BlockEnv-v1)")
+        members = list(members)
+        if not 1 <= len(members) <= nat.PH_MAX_POOL:
+            raise nat.NativeError(f"VecBlockPartnerPool: the pool holds 1..{nat.PH_MAX_POOL} members, not {len(members)}")
+        if resample not in nat.POOL_RESAMPLE:
+            raise nat.NativeError(f"VecBlockPartnerPool: resample must be one of {sorted(nat.POOL_RESAMPLE)}, not {resample!r}")
+        check_block_pool_seat(ego, self.variant, 0, "VecBlockPartnerPool: the ego")
+        for k, m in enumerate(members):
+            check_block_pool_seat(m, self.variant, 1, f"VecBlockPartnerPool: member {k}")
+        self.E, self.ego, self.members, self.native = int(n_envs), ego, members, bool(native)
+        self.resample, self.K = resample, len(members)
+        self.learners = [m for m in members if isinstance(m, RaggedVecOnPolicyAgent)]
+        if ego.E != self.E:
+            raise nat.NativeError("VecBlockPartnerPool: the ego's rollout buffer must have n_envs columns")
+        for m in self.learners:
+            if m.E != self.E:
+                raise nat.NativeError("VecBlockPartnerPool: a learner's rollout buffer must have n_envs columns")
+            if m.min_full >= m.E:
+                m.min_full = max(1, self.E // self.K)
+        pol = ego.model.policy
+        self.dev = pol.device
+        self.env = VecBlockWorld(self.variant, self.E, pol.ctx, self.dev)
+        self.seed = int(seed)
+        self.pool_seed = (self.seed ^ POOL_SEED_SALT) & 0x7FFFFFFFFFFFFFFF
+        E, dev = self.E, self.dev
+        u8 = lambda v=0: th.full((E,), v, dtype=th.uint8, device=dev)  # noqa: E731
+        A = len(self.env.partner_action_space.nvec)
+        self.obs_ego = th.zeros((E, self.env.D_ego), dtype=th.float32, device=dev)
+        self.obs_alt = th.zeros((E, self.env.D_alt), dtype=th.float32, device=dev)
+        self.partnerid = th.zeros(E, dtype=th.int32, device=dev)
+        self.alt_actions = th.zeros((E, A), dtype=th.int32, device=dev)
+        self.alt_acted = u8()
+        self._done, self._running, self._can = u8(), u8(), u8()
+        self._es_alt = th.zeros(E, dtype=th.float32, device=dev)
+        self._episodes_dev = th.zeros(1, dtype=th.int64, device=dev)
+        self._rows = np.arange(E)
+        self.steps_done = 0
+        self.row0_counter = 1      # the step counter of row 0 of the ego's buffer: what EpisodeStats replays the resamples from
+        self._ctxs = tuple(dict.fromkeys([self.env.ctx] + [p.ctx for p in map(self._policy_of, [ego] + members) if p is not None]))
+        self._bind()
+        if self.native:
+            self._build_native()
+            self._native_call(0, first=True)
+        else:
+            self.env.reset(self.seed, 0)
+            self.partnerid.copy_(self._resampled(0).to(th.int32))
+            self.env.observe(True, self.obs_ego)
+
+    @staticmethod
+    def _policy_of(agent):
+        """the policy a seat plays with (None: a scripted constructor)"""
+        if isinstance(agent, VecBlockScriptedPartner):
+            return None
+        return agent.policy if isinstance(agent, FrozenVecPartner) else agent.model.policy
+
+    @property
+    def episodes(self) -> int:
+        return int(self._episodes_dev.item())
+
+    def _bind(self):
+        stream = th.cuda.current_stream(self.dev).cuda_stream
+        for ctx in self._ctxs:
+            ctx.set_stream(stream)
+
+    # -- the engine-side step ------------------------------------------------------------------------------------------------------
+    def _member_array(self):
+        """the PhPoolMember array (kept alive with the learners' buffer records); a scripted member's `seed` holds its rule"""
+        self._member_rbc = []
+        arr = (nat.PhPoolMember * self.K)()
+        for c, m in zip(arr, self.members):
+            learner = isinstance(m, RaggedVecOnPolicyAgent)
+            c.kind = nat.PH_POOL_LEARNER if learner else m.kind
+            if isinstance(m, VecBlockScriptedPartner):
+                c.seed = m.rule
+                continue
+            p = self._policy_of(m)
+            c.params, c.seed = p.params.data_ptr(), p._seed
+            if learner:
+                rbc = m.model.rollout_buffer.c_struct()
+                self._member_rbc.append(rbc)
+                c.rb = C.pointer(rbc)
+                c.pos, c.boundary, c.term, c.open = (t.data_ptr() for t in (m.pos, m.boundary, m.term, m.open))
+                c.values, c.log_probs = m.values.data_ptr(), m.log_probs.data_ptr()
+        self._member_arr = arr
+        return arr
+
+    def _build_native(self) -> None:
+        from ..spaces import make_spec
+        ego, pe = self.ego, self.ego.model.policy
+        ego._last_episode_starts = ego._last_episode_starts.clone()    # updated in place by the step from here on
+        alt_spaces = VecBlockWorld.seat_spaces(self.variant)[1]
+        self._alt_spec = make_spec(alt_spaces.observation_space, alt_spaces.action_space)
+        s = nat.PhBlockPool()
+        s.n, s.variant = self.E, self.variant
+        s.ego_spec, s.alt_spec = C.pointer(pe.spec), C.pointer(self._alt_spec)
+        s.state, s.world_seed = self.env.state.data_ptr(), self.seed
+        self._ego_rbc = ego.model.rollout_buffer.c_struct()
+        s.ego_params, s.ego_rb, s.ego_actions = pe.params.data_ptr(), C.pointer(self._ego_rbc), ego.actions.data_ptr()
+        s.ego_values, s.ego_log_probs = ego.values.data_ptr(), ego.log_probs.data_ptr()
+        s.ego_episode_start, s.ego_seed = ego._last_episode_starts.data_ptr(), pe._seed
+        s.members, s.n_members, s.partnerid = self._member_array(), self.K, self.partnerid.data_ptr()
+        s.resample, s.pool_seed = nat.POOL_RESAMPLE[self.resample], self.pool_seed
+        s.alt_actions, s.alt_acted = self.alt_actions.data_ptr(), self.alt_acted.data_ptr()
+        s.obs_ego, s.obs_alt, s.episodes = self.obs_ego.data_ptr(), self.obs_alt.data_ptr(), self._episodes_dev.data_ptr()
+        s.es_alt, s.running, s.can, s.done = (t.data_ptr() for t in (self._es_alt, self._running, self._can, self._done))
+        self._desc = s
+
+    def _native_call(self, counter: int, ego_pos: int = -1, first: bool = False) -> None:
+        self._bind()
+        ctx, rb = self.env.ctx, self.ego.model.rollout_buffer
+        pos = int(rb.pos if ego_pos < 0 else ego_pos)
+        nat.check(ctx.lib.ph_block_pool_step(ctx.handle, C.byref(self._desc), pos, int(counter), int(first)))
+
+    # -- the walk: the per-call entry points with torch masks ------------------------------------------------------------------------
+    def _resampled(self, c: int) -> th.Tensor:
+        if self.resample == "robin":
+            return (self.partnerid + 1) % self.K
+        words = philox_word0(self.pool_seed, c, self._rows, POOL_RESAMPLE_BLOCK).astype(np.uint64)
+        ids = (words * np.uint64(self.K)) >> np.uint64(32)
+        return th.as_tensor(ids.astype(np.int32)).to(self.dev)
+
+    def _credit(self, reward: th.Tensor, done: th.Tensor, mask: th.Tensor) -> None:
+        for k, m in enumerate(self.members):
+            if isinstance(m, RaggedVecOnPolicyAgent):
+                mine = self.partnerid == k
+                m.update(reward, (done.bool() & mine).to(th.uint8), (mask.bool() & mine).to(th.uint8))
+
+    def _members_act(self, obs: th.Tensor, mask: th.Tensor, counter: int) -> th.Tensor:
+        """the forward of every member over all rows with Philox counter `counter`; member k's move lands in the tables of `mask`
+        where partnerid == k"""
+        out = self.alt_actions
+        for k, m in enumerate(self.members):
+            mk = (mask.bool() & (self.partnerid == k)).to(th.uint8)
+            if isinstance(m, VecBlockScriptedPartner):
+                m.get_action(obs, mk, out, self.env.ctx)
+                continue
+            self._policy_of(m)._counter = counter - 1
+            a = m.get_action(obs, mk)
+            out.copy_(th.where(mk.bool()[:, None], a, out))
+        return out
+
+    def _walk(self, c: int) -> th.Tensor:
+        ego, env = self.ego, self.env
+        self._bind()
+        ego.model.policy._counter = c - 1
+        tokens = ego.get_action(self.obs_ego)                                  # every table is at the planner's turn
+        obs_alt, rew, done = env.player_step(tokens, True)
+        done8 = done.clone()
+        d = done8.bool()
+        # the member that already moved in this game is credited this transition (multiagentenv.py:167-173)
+        self._credit(rew[:, 1].contiguous(), done8, self.alt_acted)
+        ego.update(rew[:, 0].contiguous(), done8.to(th.float32))
+        ego.flush_rewards()
+        self._episodes_dev += done8.sum()
+        running = (~d).to(th.uint8)
+        self.obs_alt.copy_(th.where(~d[:, None], obs_alt, self.obs_alt))
+        # finished tables: the next world, nobody has acted in it, the member that sits at it, the planner's first observation
+        env.reset(self.seed, c, done8)
+        self.alt_acted.copy_(th.where(d, th.zeros_like(self.alt_acted), self.alt_acted))
+        self.partnerid.copy_(th.where(d, self._resampled(c).to(th.int32), self.partnerid))
+        env.observe(True, self.obs_ego, done8)
+        # every running table's member moves
+        moves = self._members_act(self.obs_alt, running, c)
+        self.alt_acted.copy_((self.alt_acted.bool() | ~d).to(th.uint8))
+        obs_ego, _, _ = env.player_step(moves, False, running)
+        self.obs_ego.copy_(th.where(~d[:, None], obs_ego, self.obs_ego))
+        return done8
+
+    # -- one vectorised MultiAgentEnv.step -------------------------------------------------------------------------------------
+    def step(self):
+        """-> (E,) uint8 device tensor: tables whose game ended in this step"""
+        ego = self.ego
+        self.steps_done += 1
+        c = self.steps_done
+        model, rb = ego.model, ego.model.rollout_buffer
+        row0 = rb.pos == 0 or ego.n_steps >= model.n_steps       # this step fills row 0 (behind the roll-over, where one is due)
+        if not self.native:
+            done = self._walk(c)
+            if row0:
+                self.row0_counter = c
+            return done
+        if ego.n_steps >= model.n_steps:
+            ego.learn_from_buffer()
+        if row0:
+            self.row0_counter = c                                # behind the roll-over: its scan replayed the rollout before
+        self._native_call(c)
+        rb.pos += 1
+        rb.full = rb.pos == rb.buffer_size
+        ego.n_steps += 1
+        ego.num_timesteps += self.E
+        for m in self.learners:
+            m.num_timesteps += self.E
+        return self._done
+
+    def rollout_and_learn(self, n_steps: int) -> None:
+        """n_steps vectorised steps, the planner's update, then the update of every learner whose full() holds"""
+        for _ in range(n_steps):
+            self.step()
+        self.ego.learn_from_buffer()
+        for m in self.learners:
+            if m.full():
+                m.learn_from_buffer()

@@ -223,6 +223,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--n-envs", type=int, default=1,
                    help="(extension) >1: E copies of the game resident on the device, PPO-vs-PPO self-play without the "
                         "host in the step loop")
+    # (no attribute unless given: the completed arguments of every other command line stay the reference's, plus n_envs)
+    p.add_argument("--partner-pool", action="store_true", default=argparse.SUPPRESS,
+                   help="(extension) with --n-envs: BlockEnv-v0|v1 PPO <alt>+ trains the planner against a device-resident pool "
+                        "of constructors, each alt one of PPO / FIXED / DEFAULT (LiarsDice-v0 has its pool without the flag)")
     return p
 
 
@@ -269,15 +273,20 @@ class EpisodeLog:
 def pool_plan(args):
     """`LiarsDice-v0 PPO <alt>+ --n-envs E` with anything but exactly one PPO partner: the members of the device-resident partner
     pool as (kind, config) pairs, the resample rule and what remains of --env-config for the game -- checked before a device is
-    touched.  None when the arguments are the single-learner self-play pairing (that path stays as it is)."""
+    touched.  None when the arguments are the single-learner self-play pairing (that path stays as it is).  With --partner-pool
+    the same for `BlockEnv-v0|v1 PPO <alt>+`: the members of the pool of constructors (`block_member_config`), `block_variant` set;
+    without the flag the block worlds' argument lists are refused as before."""
     alts = list(args.alt)
     if alts == ["PPO"]:
         return None
     if args.ego != "PPO" or not all(kind in POOL_KINDS for kind in alts):
         raise EnvException(f"--n-envs supports a PPO ego against PPO self-play or a pool of {list(POOL_KINDS)} partners")
-    if args.env != "LiarsDice-v0":
+    block_variant = BLOCK_VARIANTS.get(args.env)
+    if args.env != "LiarsDice-v0" and not (block_variant is not None and getattr(args, "partner_pool", False)):
         raise EnvException(f"the device-resident partner pool exists for LiarsDice-v0, not {args.env}: with --n-envs the other "
-                           "games take exactly one PPO partner")
+                           "games take exactly one PPO partner"
+                           + (" (the block worlds' pool of constructors is asked for with --partner-pool)"
+                              if block_variant is not None else ""))
     from . import _native as nat
     if len(alts) > nat.PH_MAX_POOL:
         raise EnvException(f"the partner pool holds at most {nat.PH_MAX_POOL} members")
@@ -287,8 +296,13 @@ def pool_plan(args):
     if resample not in nat.POOL_RESAMPLE:
         raise EnvException(f"--env-config resample must be one of {sorted(nat.POOL_RESAMPLE)}")
     members = []
+    if block_variant is not None:
+        block_member_config(args.env, block_variant, "PPO", dict(args.ego_config))      # (the ego: a tower is refused here too)
     for kind, config in zip(alts, args.alt_config):
         config = dict(config)
+        if block_variant is not None:
+            members.append((kind, block_member_config(args.env, block_variant, kind, config)))
+            continue
         if kind == "FIXED":
             if "type" not in config or "location" not in config:
                 raise EnvException("a FIXED partner needs 'type' and 'location' in its --alt-config")
@@ -301,7 +315,48 @@ def pool_plan(args):
         elif kind == "DEFAULT" and config:
             raise EnvException("No config possible for this default agent")
         members.append((kind, config))
-    return dict(members=members, resample=resample, env_config=env_config, log_interval=log_interval)
+    return dict(members=members, resample=resample, env_config=env_config, log_interval=log_interval, block_variant=block_variant)
+
+
+BLOCK_VARIANTS = {"BlockEnv-v0": 0, "BlockEnv-v1": 1}
+
+
+def block_member_config(env_name: str, variant: int, kind: str, config: dict) -> dict:
+    """one member of the block worlds' pool of constructors, checked before a device is touched: PPO (a learner; its config goes to
+    the PPO constructor), FIXED (a PPO checkpoint on the variant's constructor spaces) or DEFAULT (the variant's scripted
+    constructor; on BlockEnv-v0 `{"rule": "EASY"}` seats SBWEasyPartner)"""
+    if kind == "PPO":
+        if (config.get("policy_kwargs") or {}).get("net_arch") is not None:
+            raise EnvException(f"a net_arch tower (policy_kwargs net_arch) does not sit in the {env_name} partner pool: the ego and "
+                               "the learners play PPO's 64-64 MlpPolicy")
+    elif kind == "FIXED":
+        if "type" not in config or "location" not in config:
+            raise EnvException("a FIXED partner needs 'type' and 'location' in its --alt-config")
+        if config["type"] != "PPO":
+            raise EnvException(f"a FIXED member of the {env_name} pool is a PPO checkpoint (the 64-64 MlpPolicy on the constructor's "
+                               f"spaces), not {config['type']}: BC clones and ADAP checkpoints do not sit in the block worlds' pool")
+    elif kind == "DEFAULT":
+        rule = config.pop("rule", "DEFAULT")
+        if config:
+            raise EnvException("the block worlds' default agent takes no config but 'rule'")
+        if rule not in ("DEFAULT", "EASY"):
+            raise EnvException(f"--alt-config rule must be DEFAULT or EASY, not {rule!r}")
+        if rule == "EASY" and variant != 0:
+            raise EnvException(f"EASY (SBWEasyPartner) exists for BlockEnv-v0 only, not {env_name}")
+        config = dict(rule=rule)
+    return config
+
+
+def partner_pool_check(args) -> None:
+    """--partner-pool: an extension beside --n-envs; it asks for the block worlds' pool of constructors, changes nothing for
+    LiarsDice-v0 (whose pool needs no flag) and is refused for a game without a pool"""
+    if not getattr(args, "partner_pool", False):
+        return
+    if args.n_envs <= 1:
+        raise EnvException("--partner-pool belongs to the device-resident trainers: give --n-envs E with E > 1")
+    if args.env != "LiarsDice-v0" and args.env not in BLOCK_VARIANTS:
+        raise EnvException(f"--partner-pool: no device-resident partner pool exists for {args.env} (LiarsDice-v0, BlockEnv-v0 and "
+                           "BlockEnv-v1 have one)")
 
 
 def check_adap_latent(latent, what: str):
@@ -440,6 +495,69 @@ def run_pool(args, plan):
     return ego_model, members, env
 
 
+def run_block_pool(args, plan):
+    """`BlockEnv-v0|v1 PPO <alt>+ --partner-pool --n-envs E`: the planner, one constructor per partner argument,
+    `VecBlockPartnerPool.rollout_and_learn` per iteration.  Learners are saved to `--alt-save DIR/i` whenever the pool has more
+    than one member, as the host path does."""
+    import random as _random
+
+    import torch as th
+
+    from . import _native as nat
+    from .envs.vec import (FrozenVecPartner, RaggedVecOnPolicyAgent, VecBlockPartnerPool, VecBlockScriptedPartner, VecBlockWorld,
+                           check_block_pool_seat)
+    from .vec import VecOnPolicyAgent
+    E, variant = int(args.n_envs), plan["block_variant"]
+    seat_spaces = VecBlockWorld.seat_spaces(variant)
+
+    def learner(config, seat, offset):
+        config = dict(config)
+        config.setdefault("n_steps", 128)
+        config.setdefault("batch_size", max(64, E * config["n_steps"] // 4))
+        config.update(env=seat_spaces[seat], device=args.device, n_envs=E)
+        if args.seed is not None:
+            config["seed"] = args.seed + offset
+        model = PPO(policy="MlpPolicy", **config)
+        model.device_permutations = True
+        return model
+
+    ego_model = learner(args.ego_config, 0, 0)
+    ego = VecOnPolicyAgent(ego_model)
+    members = []
+    try:
+        for i, (kind, config) in enumerate(plan["members"]):
+            if kind == "PPO":
+                members.append(RaggedVecOnPolicyAgent(learner(config, 1, i + 1)))
+            elif kind == "FIXED":
+                members.append(FrozenVecPartner(gen_load(config, config["type"], config["location"]).policy))
+                check_block_pool_seat(members[-1], variant, 1, f"FIXED member {i} ({config['location']})")
+            else:
+                members.append(VecBlockScriptedPartner(variant, config["rule"]))
+            print(f"Partner {i}: {members[-1]}")
+        base = args.seed if args.seed is not None else _random.SystemRandom().randrange(2 ** 31)
+        world_seed = ((base * 0x9E3779B97F4A7C15) ^ 0xB10CB10CB10C) & 0x7FFFFFFFFFFFFFFF      # a Philox key of the worlds' own
+        env = VecBlockPartnerPool(variant, E, ego, members, seed=world_seed, resample=plan["resample"], **plan["env_config"])
+    except nat.NativeError as e:
+        raise EnvException(str(e)) from e
+    n_steps = ego_model.n_steps
+    iterations = max(1, -(-args.total_timesteps // (E * n_steps)))
+    log = EpisodeLog(args, ego_model, ego, env, plan["log_interval"])
+    for it in range(1, iterations + 1):
+        env.rollout_and_learn(n_steps)
+        log.after(it, it == iterations)
+    th.cuda.synchronize()
+    updates = [m.iteration for m in env.learners]
+    print(f"vectorised pool play: {iterations} iterations x {E} envs x {n_steps} steps against {len(members)} constructors; "
+          f"ego updates {ego.iteration}, learner updates {updates}")
+    if args.ego_save:
+        ego_model.save(args.ego_save)
+    if args.alt_save:
+        for i, (kind, _) in enumerate(plan["members"]):
+            if kind == "PPO":       # FIXED / DEFAULT members have nothing to save (trainer.py:423-432)
+                members[i].model.save(f"{args.alt_save}/{i}" if len(members) > 1 else args.alt_save)
+    return ego_model, members, env
+
+
 def run_vectorised(args):
     """`<env> PPO PPO --n-envs E`: the reference's object graph with every table on the device.
     total_timesteps counts ego transitions over all tables, as SB3 does for a VecEnv.  `LiarsDice-v0 PPO <alt>+` with any other
@@ -449,14 +567,15 @@ def run_vectorised(args):
     from .envs.vec import VecLiarsDice, VecLiarSelfPlay, VecRPS, ragged_agent_for, selfplay_iteration
     from .vec import vec_agent_for
     vectorised_record_check(args)
+    partner_pool_check(args)
     aplan = adap_plan(args)                    # an ADAP learner in either seat of the single-partner pairing
     plan = pool_plan(args) if aplan is None else None
     if plan is not None:
-        return run_pool(args, plan)
+        return run_block_pool(args, plan) if plan["block_variant"] is not None else run_pool(args, plan)
     log_interval, env_config = vectorised_plan(args)
     if args.ego != "PPO" and aplan is None:
         raise EnvException("--n-envs supports the PPO-vs-PPO self-play pairing")
-    block_variant = {"BlockEnv-v0": 0, "BlockEnv-v1": 1}.get(args.env)
+    block_variant = BLOCK_VARIANTS.get(args.env)
     game = {"RPS-v0": VecRPS, "LiarsDice-v0": VecLiarsDice}.get(args.env)
     if game is None and block_variant is None:
         raise EnvException(f"no device-resident form of {args.env}")
@@ -555,6 +674,7 @@ def run(argv=None):
     print(f"Arguments: {args}")
     if args.n_envs > 1:
         return run_vectorised(args)
+    partner_pool_check(args)
     env, altenv = generate_env(args)
     print(f"Environment: {env}; Partner env: {altenv}")
     ego = generate_ego(env, args)
